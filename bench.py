@@ -78,6 +78,25 @@ LAUNCHES_PER_STEP = 16             # a step = 16 launches of `--frames` frames a
 EQ_KERNEL_NAMES = {0: "eq_views_kernel<3>", 1: "eq_staged_kernel", 2: "eq_srcmajor_kernel"}
 
 
+DUMP_SAMPLE = 1 << 20              # --dump-outputs: seeded sample of every output byte of the last step (+ frame 0's views whole)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, ctx, np, d_out, nf):
+    """What the last timed step computed, for output-by-output comparison of two builds: frame 0's six views whole
+    (views_frame0.npy, float32 (6, 800, 800, 3)) and a fixed, seeded sample of all nf x 6 views (sample_index.npy: float64 flat
+    indices into the (nf, 6, 800, 800, 3) output, sorted; sample_values.npy: float32 values there).  ~59 MB in all."""
+    out_dir = pathlib.Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    ctx.sync(-1)
+    allv = np.stack([ctx.download(d_out[k], (SIZE, SIZE, C)) for k in range(nf * N_VIEWS)]).reshape(nf, N_VIEWS, SIZE, SIZE, C)
+    idx = np.random.default_rng(DUMP_SEED).choice(allv.size, size=min(DUMP_SAMPLE, allv.size), replace=False)
+    idx.sort()
+    np.save(out_dir / "views_frame0.npy", allv[0].astype(np.float32))
+    np.save(out_dir / "sample_index.npy", idx.astype(np.float64))
+    np.save(out_dir / "sample_values.npy", allv.reshape(-1)[idx].astype(np.float32))
+
+
 def memsys_probe(dev):
     """The memory-system probe of profiles/tools/membench.hip (built as lib/libgs360probe.so -- measurement aid, not product) run IN-PROCESS on
     the GPU the bench just used, right after the timed region: bare loads of the headline's 784-byte row pieces, and the same with one stored byte per
@@ -436,12 +455,16 @@ def main():
     ap.add_argument("--job-size", type=int, default=1600, help="--mode job: view size (full360coverage: 1600)")
     ap.add_argument("--stream-frames", type=int, default=600, help="--mode stream: total frames of the job (all ranks)")
     ap.add_argument("--stream-size", type=int, default=1600, help="--mode stream: view size (full360coverage: 1600)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/*.npy (resident mode only; see dump_outputs)")
     ap.add_argument("--stride-pad", type=int, default=0, help="experiments only: extra bytes per source row")
     ap.add_argument("--src-width", type=int, default=7680, help="experiments only: equirect width (height = width/2); "
                     "any value other than 7680 is NOT the BASELINE workload and is labelled as such")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.dump_outputs is not None and args.mode != "resident":
+        ap.error("--dump-outputs applies to --mode resident (the headline workload)")
     if args.src_width != W:
         globals()["W"], globals()["H"] = args.src_width, args.src_width // 2
 
@@ -610,6 +633,8 @@ def main():
     if n_launches == 0:
         step()                                                       # leave a full batch in d_out for the check below
         ctx.sync(-1)
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, ctx, np, d_out, nf)
 
     # correctness spot-check of what was timed (rank 0): frame 0 against the oracle, plus the CPU baseline
     cpu = None

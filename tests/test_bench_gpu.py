@@ -110,3 +110,24 @@ def test_bench_stream_mode_strong_scaling_two_ranks():
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["steps"] == 7
     assert d["config"]["frames_rank0"] == 4 and d["config"]["parity_vs_oracle"] is True
     assert d["value"] > 0 and d["config"]["frames_per_s"] > 0
+
+
+def test_bench_dump_outputs_are_what_the_timed_step_computed(tmp_path, orc):
+    """--dump-outputs: frame 0's views whole and a seeded sample of every view of the last timed step, float32, under 64 MB,
+    equal to the oracle on the same seeded input; --steps sets the timed steps and ms_per_step is per step"""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    d = _run(["--steps", "2", "--warmup", "1", "--frames", "4", "--no-cpu-baseline", "--no-secondary", "--no-memsys",
+              "--dump-outputs", str(tmp_path / "out")])
+    assert d["steps"] == 2 and d["config"]["frames_rank0"] == 2 * 16 * 4 and d["ms_per_step"] > 0
+    files = {p.name: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert set(files) == {"views_frame0.npy", "sample_index.npy", "sample_values.npy"}
+    assert sum(p.stat().st_size for p in (tmp_path / "out").glob("*.npy")) <= 64 * 2 ** 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    want = orc.equirect_views_u8(bench.synth_frame(np, 0), [orc.make_view(*v) for v in bench.view_table()], threads=0)
+    assert np.array_equal(files["views_frame0.npy"], np.stack(want).astype(np.float32))
+    idx = files["sample_index.npy"].astype(np.int64)
+    assert idx.size == 1 << 20 and np.all(np.diff(idx) > 0) and idx[-1] < 4 * 6 * 800 * 800 * 3
+    frame0 = idx < 6 * 800 * 800 * 3
+    assert np.array_equal(files["sample_values.npy"][frame0], files["views_frame0.npy"].reshape(-1)[idx[frame0]])
