@@ -193,9 +193,9 @@ struct MaskPack {
     int64_t stride;              // bytes per row of the byte masks
 };
 hipError_t launch_mask_pack(const MaskPack& P, hipStream_t s);
-hipError_t launch_equirect(const EqLaunch& L, int C, hipStream_t s);
-hipError_t launch_equirect_staged(const EqLaunch& L, hipStream_t s);   // bilinear RGB u8, every view with blocked == 2 (LDS-staged 16x16 wavefront tiles)
-hipError_t launch_equirect_cubic(const EqLaunch& L, int C, hipStream_t s);
+// equirect -> views: 8-bit (esize 1) or 16-bit (esize 2), bilinear or cubic; `staged`: bilinear RGB u8, every view with blocked == 2
+// (LDS-staged 16x16 wavefront tiles)
+hipError_t launch_equirect(const EqLaunch& L, int C, int esize, bool cubic, bool staged, hipStream_t s);
 // source-major kernel (gs360_srcmajor.hip): one launch = one level yaw ring that fills its circle
 struct SmTile { int32_t x0, y0, nrows, wch, eoff, nq, pad0, pad1; };   // box of a plan tile: first byte (in the period) / row, rows, 16-byte chunks per row; entries
 struct SmPlan;
@@ -235,7 +235,6 @@ void sm_release(SmCache& cache, SmPlan* plan);
 void build_cubic_table(int16_t* out);      // host: OpenCV initInterTab2D(INTER_CUBIC, fixpt) restated, 32*32*16
 void build_lanczos4_table(int16_t* out);   // host: initInterTab2D(INTER_LANCZOS4, fixpt) restated, 32*32*64
 void build_coef1d(float* out);             // host: the float32 1-D phase tables (linear, cubic, lanczos4) of the CV_16U samplers, 448
-hipError_t launch_equirect_u16(const EqLaunch& L, int C, bool cubic, hipStream_t s);                       // gs360_u16.hip
 hipError_t launch_bswap16(uint16_t* buf, size_t n, hipStream_t s);            // gs360_u16.hip: in-place byte swap of 16-bit samples
 hipError_t launch_arith_selftest(uint32_t seed, int blocks, int iters, unsigned long long* d_bad, hipStream_t s);
 hipError_t launch_table_u16_batch(TableBatch& B, int C, const float* coef, const uint16_t cval[4], hipStream_t s);   // all jobs share interp

@@ -1557,33 +1557,6 @@ static unsigned eq_grid_blocks(const EqLaunch& L) {
     return (unsigned)((L.total_tiles + per - 1) / per * per);
 }
 
-hipError_t launch_equirect_staged(const EqLaunch& L, hipStream_t s) {
-    dim3 grid(eq_grid_blocks(L)), block(64 * kWaves);
-    if (L.mask[0] != nullptr) hipLaunchKernelGGL((eq_staged_kernel<true>), grid, block, 0, s, L);
-    else hipLaunchKernelGGL((eq_staged_kernel<false>), grid, block, 0, s, L);
-    return hipGetLastError();
-}
-
-hipError_t launch_equirect(const EqLaunch& L, int C, hipStream_t s) {
-    dim3 grid(eq_grid_blocks(L)), block(64 * kWaves);
-    const bool masked = L.mask[0] != nullptr;             // all frames or none (checked by the C ABI)
-    bool rows_only = kEqRowsKernel != 0;
-    for (int k = 0; k < L.n_views; ++k) rows_only = rows_only && !L.view[k].blocked;
-    switch (C) {
-        case 1: if (masked) hipLaunchKernelGGL((eq_views_kernel<1, false, true>), grid, block, 0, s, L);
-                else hipLaunchKernelGGL((eq_views_kernel<1, false, false>), grid, block, 0, s, L); break;
-        case 3: if (rows_only) {
-                    if (masked) hipLaunchKernelGGL((eq_views_kernel<3, false, true, 1, true>), grid, block, 0, s, L);
-                    else hipLaunchKernelGGL((eq_views_kernel<3, false, false, 1, true>), grid, block, 0, s, L);
-                } else if (masked) hipLaunchKernelGGL((eq_views_kernel<3, false, true>), grid, block, 0, s, L);
-                else hipLaunchKernelGGL((eq_views_kernel<3, false, false>), grid, block, 0, s, L); break;
-        case 4: if (masked) hipLaunchKernelGGL((eq_views_kernel<4, false, true>), grid, block, 0, s, L);
-                else hipLaunchKernelGGL((eq_views_kernel<4, false, false>), grid, block, 0, s, L); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 // persistent grid of the cubic variants: at most `persist_blocks` workgroups (rounded to the XCD count) walk the tile order
 static EqLaunch eq_persistent(const EqLaunch& L0, dim3& grid) {
     EqLaunch L = L0;
@@ -1592,41 +1565,42 @@ static EqLaunch eq_persistent(const EqLaunch& L0, dim3& grid) {
     return L;
 }
 
-hipError_t launch_equirect_cubic(const EqLaunch& L0, int C, hipStream_t s) {
-    dim3 grid(eq_grid_blocks(L0)), block(64 * kWaves);
-    const EqLaunch L = eq_persistent(L0, grid);
-    const bool masked = L.mask[0] != nullptr;
-    // (a rows-only instantiation like the bilinear kernel's halves the SGPR spills -- 61 -> 33 -- and changes nothing measurable:
-    // profiles/r04/cubic_split_ab.txt)
-    switch (C) {
-        case 1: if (masked) hipLaunchKernelGGL((eq_views_kernel<1, true, true>), grid, block, 0, s, L);
-                else hipLaunchKernelGGL((eq_views_kernel<1, true, false>), grid, block, 0, s, L); break;
-        case 3: if (masked) hipLaunchKernelGGL((eq_views_kernel<3, true, true>), grid, block, 0, s, L);
-                else hipLaunchKernelGGL((eq_views_kernel<3, true, false>), grid, block, 0, s, L); break;
-        case 4: if (masked) hipLaunchKernelGGL((eq_views_kernel<4, true, true>), grid, block, 0, s, L);
-                else hipLaunchKernelGGL((eq_views_kernel<4, true, false>), grid, block, 0, s, L); break;
-        default: return hipErrorInvalidValue;
+// The gather kernels of one channel count: bilinear and cubic 8-bit, each masked or not (bilinear RGB also in the rows-only form,
+// ROWS), and 16-bit bilinear and cubic without a mask.  (A rows-only cubic instantiation like the bilinear one halves the SGPR
+// spills -- 61 -> 33 -- and changes nothing measurable: profiles/r04/cubic_split_ab.txt.)
+template <int C, bool ROWS = false>
+static void eq_launch_gather(const EqLaunch& L, int esize, bool cubic, bool masked, dim3 grid, hipStream_t s) {
+    const dim3 block(64 * kWaves);
+    if (esize == 2) {
+        if (cubic) hipLaunchKernelGGL((eq_views_kernel<C, true, false, 2>), grid, block, 0, s, L);
+        else hipLaunchKernelGGL((eq_views_kernel<C, false, false, 2>), grid, block, 0, s, L);
+    } else if (cubic) {
+        if (masked) hipLaunchKernelGGL((eq_views_kernel<C, true, true>), grid, block, 0, s, L);
+        else hipLaunchKernelGGL((eq_views_kernel<C, true, false>), grid, block, 0, s, L);
+    } else if (masked) {
+        hipLaunchKernelGGL((eq_views_kernel<C, false, true, 1, ROWS>), grid, block, 0, s, L);
+    } else {
+        hipLaunchKernelGGL((eq_views_kernel<C, false, false, 1, ROWS>), grid, block, 0, s, L);
     }
-    return hipGetLastError();
 }
 
-hipError_t launch_equirect_u16(const EqLaunch& L0, int C, bool cubic, hipStream_t s) {
-    dim3 grid(eq_grid_blocks(L0)), block(64 * kWaves);
+hipError_t launch_equirect(const EqLaunch& L0, int C, int esize, bool cubic, bool staged, hipStream_t s) {
+    dim3 grid(eq_grid_blocks(L0));
     const EqLaunch L = cubic ? eq_persistent(L0, grid) : L0;
-    if (cubic) {
-        switch (C) {
-            case 1: hipLaunchKernelGGL((eq_views_kernel<1, true, false, 2>), grid, block, 0, s, L); break;
-            case 3: hipLaunchKernelGGL((eq_views_kernel<3, true, false, 2>), grid, block, 0, s, L); break;
-            case 4: hipLaunchKernelGGL((eq_views_kernel<4, true, false, 2>), grid, block, 0, s, L); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (C) {
-            case 1: hipLaunchKernelGGL((eq_views_kernel<1, false, false, 2>), grid, block, 0, s, L); break;
-            case 3: hipLaunchKernelGGL((eq_views_kernel<3, false, false, 2>), grid, block, 0, s, L); break;
-            case 4: hipLaunchKernelGGL((eq_views_kernel<4, false, false, 2>), grid, block, 0, s, L); break;
-            default: return hipErrorInvalidValue;
-        }
+    const bool masked = L.mask[0] != nullptr;             // all frames or none (checked by the C ABI)
+    if (staged && esize == 1 && !cubic) {
+        if (masked) hipLaunchKernelGGL((eq_staged_kernel<true>), grid, dim3(64 * kWaves), 0, s, L);
+        else hipLaunchKernelGGL((eq_staged_kernel<false>), grid, dim3(64 * kWaves), 0, s, L);
+        return hipGetLastError();
+    }
+    bool rows_only = kEqRowsKernel != 0;
+    for (int k = 0; k < L.n_views; ++k) rows_only = rows_only && !L.view[k].blocked;
+    switch (C) {
+        case 1: eq_launch_gather<1>(L, esize, cubic, masked, grid, s); break;
+        case 3: if (rows_only) eq_launch_gather<3, true>(L, esize, cubic, masked, grid, s);
+                else eq_launch_gather<3>(L, esize, cubic, masked, grid, s); break;
+        case 4: eq_launch_gather<4>(L, esize, cubic, masked, grid, s); break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

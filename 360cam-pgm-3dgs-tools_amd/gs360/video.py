@@ -180,7 +180,7 @@ class SharedBudget:
 
 
 # View jobs take the frames of a video in WINDOWS of this many (one batched launch per window and device: ring families -- the
-# `full360coverage` preset, PC:616-680 -- reach the source-major kernel from four frames per call, csrc/gs360_capi.hip); frames are dealt to
+# `full360coverage` preset, PC:616-680 -- reach the source-major kernel from four frames per call, csrc/gs360_capi_equirect.hip); frames are dealt to
 # the devices in blocks of a window, so that a window's frames sit on one device.  GS360_VIDEO_WINDOW=1: one frame per launch (A/B).
 _WINDOW = max(1, min(16, int(os.environ.get("GS360_VIDEO_WINDOW", "4"))))
 _WINDOW_WAIT_S = 0.05                             # longest a view job waits for the frames behind the first one of its window
