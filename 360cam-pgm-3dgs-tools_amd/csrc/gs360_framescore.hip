@@ -1,0 +1,263 @@
+// gs360_framescore.hip -- the FrameSelector's per-pixel scoring pass on the GPU (include/gs360.h, "frame sharpness statistics").
+//
+// Reference: score_one_file, cli_tools/gs360_FrameSelector.py:902-1044 with lapvar32 / tenengrad32 (FS:720-739) and the INTER_AREA
+// input of fft_energy_fast (FS:742-786).  FS-SPEC v1 restates all of it for 8-bit sources as integer arithmetic: the gray
+// values, the Laplacian and the Sobel responses are small integers, so their sums are exact and this kernel reproduces the
+// double accumulators of cv2.meanStdDev / cv2.mean bit for bit, whatever the order in which workgroups finish.
+//
+// fs_stats_kernel: one 256-thread workgroup per strip of kFsRows frame rows, walking the frame width in tiles of kFsTileW columns.
+// A tile's rows (plus one halo row above and below, plus one halo column each side, reflect-101 at x = 0 / W-1) are staged as raw
+// bytes in LDS with dword loads, converted to gray in LDS, and every lane then walks one column down the strip: full-frame counts
+// for every row, the 3x3 Laplacian / Sobel for rows inside the band.  The band is an image of its own (cv2 receives a NumPy view),
+// so the row above the band's first row is its second row (reflect-101), and the same at its last row; those rows always lie
+// inside the staged window.  Sums go lane -> wavefront (cross-lane adds) -> workgroup (LDS) -> one 64-bit atomic per field.
+//
+// fs_small_kernel: the band resized with INTER_AREA (OpenCV's per-axis area tables, computed per output pixel in double exactly as
+// computeResizeAreaTab does, float32 accumulation in ResizeArea_Invoker's order), and the gray at the INTER_NEAREST sample that the
+// host turns into the resized valid mask.  A second, small launch over the band: its 2-D cells read every band pixel once more
+// (the stats pass keeps to one streaming read of the frame), and it runs only for the fft / hybrid metrics.
+#include "gs360_kernels.h"
+
+namespace gs360 {
+
+namespace {
+
+constexpr int kFsThreads = 256;
+constexpr int kFsRows = 16;                    // frame rows per strip
+constexpr int kFsTileW = 256;                  // columns per tile: one per lane
+constexpr int kFsLdsRows = kFsRows + 2;        // + halo above and below
+constexpr int kFsRawDw = 260;                  // dwords of one staged row: (kFsTileW + 2) * 4 bytes + 3 of alignment
+constexpr int kFsGrayPitch = 260;
+constexpr int kFsFields = 13;                  // int64 fields of gs360_frame_stats
+static_assert(sizeof(gs360_frame_stats) == kFsFields * 8, "gs360_frame_stats layout");
+
+struct FsLds {
+    uint32_t raw[kFsLdsRows][kFsRawDw];
+    int32_t gray[kFsLdsRows][kFsGrayPitch];
+    long long red[kFsThreads / 64][kFsFields];
+};
+
+__device__ __forceinline__ int reflect101(int i, int n) {   // one step outside [0, n) at most (cv::borderInterpolate, BORDER_REFLECT_101)
+    if (n == 1) return 0;
+    return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
+}
+
+template <int C>
+__device__ __forceinline__ int gray_of(const uint8_t* p, int red) {
+    if constexpr (C == 1) {
+        return p[0];
+    } else {
+        const int r = p[red], g = p[1], b = p[2 - red];
+        return (r * 4899 + g * 9617 + b * 1868 + 8192) >> 14;    // cv2 COLOR_BGR2GRAY on 8U (yuv_shift 14)
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int C>
+__global__ void __launch_bounds__(kFsThreads) fs_stats_kernel(const FsLaunch L) {
+    __shared__ FsLds S;
+    const int b = blockIdx.x;
+    const int t = (b & 7) * L.chunk + (b >> 3);             // XCD-aware order: an XCD walks neighbouring strips (shared halo rows)
+    if (t >= L.total) return;
+    const int f = t / L.strips;
+    const int ys = (t - f * L.strips) * kFsRows;
+    const int H = L.H, W = L.W, y0 = L.y0, y1 = L.y1;
+    const int ye = min(ys + kFsRows, H);
+    const uint8_t* const src = L.src[f];
+    const int tid = threadIdx.x;
+    // circle: (2x - (W-1))^2 + (2y - (H-1))^2 <= 4 r^2, r = max(1, min(W, H) / 2)
+    const int64_t mwh = min(W, H);
+    const int64_t r4 = max((int64_t)4, mwh * mwh);
+
+    int cnt_c = 0, cnt_h = 0, cnt_hc = 0;
+    int n_a = 0, g_a = 0, l_a = 0, n_v = 0, g_v = 0, l_v = 0;
+    int64_t l2_a = 0, m2_a = 0, l2_v = 0, m2_v = 0;
+
+    for (int x0 = 0; x0 < W; x0 += kFsTileW) {
+        const int nx = min(kFsTileW, W - x0);
+        const int xa = max(x0 - 1, 0), xb = min(x0 + nx, W - 1);    // staged pixel columns (the reflected halo lies inside)
+        // 1. raw bytes of rows ys-1 .. ye (those the counts or a band stencil need) -> LDS, dword loads
+        uint32_t v[kFsLdsRows][2];
+#pragma unroll
+        for (int r = 0; r < kFsLdsRows; ++r) {
+            const int y = ys - 1 + r;
+            const bool need = y >= 0 && y < H && ((y >= ys && y < ye) || (y >= y0 && y < y1 && y <= ye));
+            const uintptr_t a = (uintptr_t)(src + (int64_t)y * L.stride + xa * C);
+            const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
+            const int ndw = need ? ((int)(a & 3) + (xb - xa + 1) * C + 3) >> 2 : 0;
+            v[r][0] = tid < ndw ? __builtin_nontemporal_load(q + tid) : 0u;
+            v[r][1] = tid + kFsThreads < ndw ? __builtin_nontemporal_load(q + tid + kFsThreads) : 0u;
+        }
+#pragma unroll
+        for (int r = 0; r < kFsLdsRows; ++r) {
+            S.raw[r][tid] = v[r][0];
+            if (tid < kFsRawDw - kFsThreads) S.raw[r][tid + kFsThreads] = v[r][1];
+        }
+        __syncthreads();
+        // 2. gray of columns x0-1 .. x0+nx (reflect-101 at the frame's left and right edges)
+        for (int i = tid; i < kFsLdsRows * (kFsTileW + 2); i += kFsThreads) {
+            const int r = i / (kFsTileW + 2), c = i - r * (kFsTileW + 2);
+            if (c > nx + 1) continue;
+            const int xs = reflect101(x0 - 1 + c, W);
+            const int off = (int)((uintptr_t)(src + (int64_t)(ys - 1 + r) * L.stride + xa * C) & 3);   // as staged in step 1
+            const uint8_t* p = (const uint8_t*)S.raw[r] + off + (xs - xa) * C;
+            S.gray[r][c] = gray_of<C>(p, L.red);
+        }
+        __syncthreads();
+        // 3. one column per lane down the strip
+        if (tid < nx) {
+            const int c = tid + 1;
+            const int x = x0 + tid;
+            const int64_t dx = 2 * x - (W - 1);
+            const int64_t dx2 = dx * dx;
+            uint32_t tl2_a = 0, tm2_a = 0, tl2_v = 0, tm2_v = 0;   // <= kFsRows * 2040^2 < 2^32 per tile
+            int wu[3], wm[3], wd[3];
+            int pm = -2, pd = -2;                                   // band rows held in wm / wd
+            for (int y = ys; y < ye; ++y) {
+                const int64_t dy = 2 * y - (H - 1);
+                const bool circ = dx2 + dy * dy <= r4;
+                int g;
+                const bool inband = y >= y0 && y < y1;
+                if (inband) {
+                    const int up = y > y0 ? y - 1 : (y1 - y0 > 1 ? y0 + 1 : y0);
+                    const int dn = y < y1 - 1 ? y + 1 : (y1 - y0 > 1 ? y1 - 2 : y);
+                    const int* Rd = S.gray[dn - ys + 1] + c;
+                    if (up == pm && y == pd) {
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) { wu[k] = wm[k]; wm[k] = wd[k]; }
+                    } else {
+                        const int* Ru = S.gray[up - ys + 1] + c;
+                        const int* Rm = S.gray[y - ys + 1] + c;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) { wu[k] = Ru[k - 1]; wm[k] = Rm[k - 1]; }
+                    }
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) wd[k] = Rd[k - 1];
+                    pm = y; pd = dn;
+                    g = wm[1];
+                } else {
+                    g = S.gray[y - ys + 1][c];
+                }
+                const bool hl = g >= 243;
+                cnt_c += circ;
+                cnt_h += hl;
+                cnt_hc += hl && circ;
+                if (inband) {
+                    const int lap = 2 * (wu[0] + wu[2] + wd[0] + wd[2]) - 8 * wm[1];
+                    const int gx = (wu[2] + 2 * wm[2] + wd[2]) - (wu[0] + 2 * wm[0] + wd[0]);
+                    const int gy = (wd[0] + 2 * wd[1] + wd[2]) - (wu[0] + 2 * wu[1] + wu[2]);
+                    const uint32_t l2 = (uint32_t)(lap * lap), m2 = (uint32_t)(gx * gx + gy * gy);
+                    n_a += 1; g_a += g; l_a += lap; tl2_a += l2; tm2_a += m2;
+                    const bool valid = (!L.circle || circ) && (!L.highlights || !hl);
+                    if (valid) { n_v += 1; g_v += g; l_v += lap; tl2_v += l2; tm2_v += m2; }
+                }
+            }
+            l2_a += tl2_a; m2_a += tm2_a; l2_v += tl2_v; m2_v += tm2_v;
+        }
+        __syncthreads();
+    }
+    // lane -> wavefront -> workgroup -> one atomic per field
+    long long acc[kFsFields] = {wave_sum(cnt_c), wave_sum(cnt_h), wave_sum(cnt_hc),
+                                wave_sum(n_a), wave_sum(g_a), wave_sum(l_a), wave_sum((long long)l2_a), wave_sum((long long)m2_a),
+                                wave_sum(n_v), wave_sum(g_v), wave_sum(l_v), wave_sum((long long)l2_v), wave_sum((long long)m2_v)};
+    const int wave = tid >> 6;
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kFsFields; ++k) S.red[wave][k] = acc[k];
+    }
+    __syncthreads();
+    if (tid < kFsFields) {
+        long long s = 0;
+#pragma unroll
+        for (int w = 0; w < kFsThreads / 64; ++w) s += S.red[w][tid];
+        if (s != 0) atomicAdd((unsigned long long*)&L.stats[f] + tid, (unsigned long long)s);
+    }
+}
+
+// One axis of cv::computeResizeAreaTab for output index d: source cells [i1, i2) of weight `mid`, plus a leading cell i1-1 of
+// weight `head` and a trailing cell i2 of weight `tail` when those flags are set.
+struct AreaSpan {
+    int i1, i2;
+    bool has_head, has_tail;
+    float head, mid, tail;
+};
+__device__ __forceinline__ AreaSpan area_span(int d, int ssize, double scale) {
+    const double f1 = d * scale, f2 = f1 + scale;
+    const double cell = fmin(scale, ssize - f1);
+    int s2 = (int)floor(f2), s1 = (int)ceil(f1);
+    s2 = min(s2, ssize - 1);
+    s1 = min(s1, s2);
+    AreaSpan a;
+    a.i1 = s1;
+    a.i2 = s2;
+    a.has_head = s1 - f1 > 1e-3;
+    a.head = (float)((s1 - f1) / cell);
+    a.mid = (float)(1.0 / cell);
+    a.has_tail = f2 - s2 > 1e-3;
+    a.tail = (float)(fmin(fmin(f2 - s2, 1.0), cell) / cell);
+    return a;
+}
+
+template <int C>
+__device__ __forceinline__ float area_row(const uint8_t* row, const AreaSpan& ax, int red) {
+    float buf = 0.0f;                                        // buf[dx] += S[sx] * alpha, xtab order
+    if (ax.has_head) buf += (float)gray_of<C>(row + (ax.i1 - 1) * C, red) * ax.head;
+    for (int sx = ax.i1; sx < ax.i2; ++sx) buf += (float)gray_of<C>(row + sx * C, red) * ax.mid;
+    if (ax.has_tail) buf += (float)gray_of<C>(row + ax.i2 * C, red) * ax.tail;
+    return buf;
+}
+
+template <int C>
+__global__ void __launch_bounds__(kFsThreads) fs_small_kernel(const FsLaunch L) {
+    const int dx = blockIdx.x * kFsThreads + threadIdx.x;
+    const int dy = blockIdx.y;
+    const int f = blockIdx.z;
+    if (dx >= L.small_w) return;
+    const int bh = L.y1 - L.y0;
+    const uint8_t* const band = L.src[f] + (int64_t)L.y0 * L.stride;
+    const AreaSpan ax = area_span(dx, L.W, L.scale_x);
+    const AreaSpan ay = area_span(dy, bh, L.scale_y);
+    float sum = 0.0f;                                        // sum[dx] += beta * buf[dx], ytab order
+    if (ay.has_head) sum += ay.head * area_row<C>(band + (int64_t)(ay.i1 - 1) * L.stride, ax, L.red);
+    for (int sy = ay.i1; sy < ay.i2; ++sy) sum += ay.mid * area_row<C>(band + (int64_t)sy * L.stride, ax, L.red);
+    if (ay.has_tail) sum += ay.tail * area_row<C>(band + (int64_t)ay.i2 * L.stride, ax, L.red);
+    // INTER_NEAREST (resizeNN): floor(d * (1 / (dsize / ssize))), clamped to the last source index
+    const int nx = min((int)floor(dx * L.scale_x), L.W - 1);
+    const int ny = min((int)floor(dy * L.scale_y), bh - 1);
+    float* out = L.small[f];
+    const int64_t plane = (int64_t)L.small_w * L.small_h;
+    out[(int64_t)dy * L.small_w + dx] = sum;
+    out[plane + (int64_t)dy * L.small_w + dx] = (float)gray_of<C>(band + (int64_t)ny * L.stride + nx * C, L.red);
+}
+
+template <int C>
+hipError_t launch_fs(FsLaunch& L, hipStream_t s) {
+    L.strips = (L.H + kFsRows - 1) / kFsRows;
+    L.total = L.strips * L.n_frames;
+    L.chunk = (L.total + 7) / 8;
+    hipLaunchKernelGGL(fs_stats_kernel<C>, dim3((unsigned)(L.chunk * 8)), dim3(kFsThreads), 0, s, L);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !L.small[0]) return e;
+    hipLaunchKernelGGL(fs_small_kernel<C>, dim3((unsigned)((L.small_w + kFsThreads - 1) / kFsThreads), (unsigned)L.small_h,
+                                                (unsigned)L.n_frames), dim3(kFsThreads), 0, s, L);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_frame_stats(FsLaunch& L, hipStream_t s) {
+    switch (L.C) {
+        case 1: return launch_fs<1>(L, s);
+        case 3: return launch_fs<3>(L, s);
+        case 4: return launch_fs<4>(L, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace gs360

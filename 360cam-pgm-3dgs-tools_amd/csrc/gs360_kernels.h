@@ -288,4 +288,19 @@ hipError_t ts_launch(const TsLaunch& L, int n_cu, size_t lds_per_cu, hipStream_t
 hipError_t launch_table_batch(TableBatch& B, int C, hipStream_t s);   // all jobs share C and interp (job[0].interp)
 hipError_t launch_fisheye(const FeLaunch& L, int C, hipStream_t s);
 
+// Frame sharpness statistics (gs360_framescore.hip, FS-SPEC v1 in DESIGN.md): one batch of up to GS360_MAX_FRAMES frames of one size.
+struct FsLaunch {
+    const uint8_t* src[GS360_MAX_FRAMES];
+    float* small[GS360_MAX_FRAMES];      // 2 x small_h x small_w each (INTER_AREA plane, nearest-sample gray plane), or all null
+    gs360_frame_stats* stats;            // n_frames records, cleared by the caller
+    int64_t stride;
+    int32_t H, W, C, red;
+    int32_t y0, y1;                      // band rows [y0, y1)
+    int32_t circle, highlights;          // GS360_FS_CIRCLE / GS360_FS_HIGHLIGHTS
+    int32_t n_frames, strips, total, chunk;   // strips per frame, strip workgroups in all, ceil(total / 8) (XCD order)
+    int32_t small_w, small_h;
+    double scale_x, scale_y;             // cv2.resize's 1 / (small_w / W), 1 / (small_h / band height)
+};
+hipError_t launch_frame_stats(FsLaunch& L, hipStream_t s);
+
 }  // namespace gs360

@@ -32,7 +32,10 @@ EXPORTS = (
     "gs360_equirect_views_u16", "gs360_remap_table_u16", "gs360_remap_tables_u16", "gs360_equirect_views_u16_host", "gs360_remap_table_u16_host",
     "gs360_png_unfilter", "gs360_event_sync", "gs360_stream_wait_event",
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
+    "gs360_frame_stats_u8",
 )
+FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
+FS_HIGHLIGHTS = 0x2   # ignore_highlights
 
 
 class Gs360Error(RuntimeError):
@@ -67,6 +70,13 @@ class RemapJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("src_stride", C.c_size_t),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p), ("valid", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32),
                 ("fill_value", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_size_t)]
+
+
+class FrameStats(C.Structure):
+    """gs360_frame_stats: full-frame mask counts and the band's exact sums (all band pixels, then the valid ones)."""
+    _fields_ = [(n, C.c_int64) for n in (
+        "n_circle", "n_highlight", "n_highlight_in_circle", "n", "sum_gray", "sum_lap", "sum_lap2", "sum_mag2",
+        "n_valid", "sum_gray_valid", "sum_lap_valid", "sum_lap2_valid", "sum_mag2_valid")]
 
 
 ABI_VERSION = 2          # GS360_ABI_VERSION of include/gs360.h this binding was written against
@@ -145,6 +155,7 @@ def load_library(path=None):
         L.gs360_color_apply_u16.argtypes = [vp, vp, vp, i, i, i, sz, i, vp, sz, i]
         L.gs360_event_sync.argtypes = [vp, i, i]
         L.gs360_stream_wait_event.argtypes = [vp, i, i, i]
+        L.gs360_frame_stats_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, u32, vp, pvp, i, i, i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -483,6 +494,17 @@ class Context:
         """Apply a colour plan to a device-resident H x W x C image (in place when dst is None)."""
         _check(self.L.gs360_color_apply_u8(self.handle, plan, src.ptr, H, W, Cn, src_stride, red_index,
                                            (dst or src).ptr, dst_stride, slot), self.L)
+
+    # -- frame sharpness statistics (gs360/framescore.py) -------------------------------------
+    def frame_stats_dev(self, frames, H, W, Cn, band, stats, flags=0, smalls=None, small_w=0, small_h=0, red_index=0, stride=0, slot=0):
+        """gs360_frame_stats_u8 on device frames (list of DeviceBuffer, H x W x C uint8): stats = DeviceBuffer of len(frames)
+        FrameStats records; smalls = None or one DeviceBuffer of 2 x small_h x small_w float32 per frame.  band = (y0, y1).
+        Asynchronous on `slot`."""
+        nf = len(frames)
+        fp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in frames])
+        sp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in smalls]) if smalls is not None else None
+        _check(self.L.gs360_frame_stats_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(band[0]),
+                                           int(band[1]), int(flags), stats.ptr, sp, int(small_w), int(small_h), slot), self.L)
 
     # -- hot path, host buffers (synchronous) -----------------------------------------------
     def equirect_views(self, src, views, slot=0, interp=INTERP_LINEAR, flags=0):

@@ -1,0 +1,378 @@
+"""Frame sharpness scoring on the GPU: the per-frame pass of the FrameSelector tool (FS-SPEC v1).
+
+Drop-in seams of cli_tools/gs360_FrameSelector.py:
+  score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none")   FS:902-1044
+  score_one_record(record, metric, crop_ratio, max_long, augment_motion, ignore_highlights, score_backend) FS:458-517
+both return the reference's 9-tuple (sharp, p0, p255, brightness_mean, brightness_weight, lap_feature, ten_feature, fft_feature,
+motion_factor).  The per-pixel work (gray, masks, Laplacian, Sobel, the INTER_AREA downscale of fft_energy_fast) runs in
+gs360_frame_stats_u8; what is left here is the reference's branch logic on exact integer sums, in double, and the FFT of the
+<= 512-pixel image (NumPy, the reference's own code, FS:742-786).  score_arrays / score_files batch frames GS360_MAX_FRAMES per
+launch; hybrid_scores is the main flow's per-run normalisation of the hybrid features (FS:2363-2392).
+
+8-bit sources only: 16-bit and float images raise Gs360Error (GS360_ERR_UNSUPPORTED), as does max_long > 0.
+"""
+import collections
+import concurrent.futures
+import math
+import os
+import threading
+
+import numpy as np
+
+from . import capi, imageio
+
+HYBRID_LAPVAR_WEIGHT = 0.6        # FS:311-315 (the code's weights; the docstring's 0.2 is not what runs)
+HYBRID_TENENGRAD_WEIGHT = 0.3
+HYBRID_FFT_WEIGHT = 0.1
+HYBRID_MOTION_REFERENCE = 5000.0
+HYBRID_MOTION_PENALTY_WEIGHT = 0.4
+HYBRID_DARK_THRESHOLD = 0.35      # FS:330-331
+HYBRID_DARK_PENALTY_WEIGHT = 0.5
+FFT_LONG_SIDE = 512               # fft_energy_fast's downscale target (FS:754)
+HIGHLIGHT_LEVEL = 243             # gray >= 0.95 * 255 = 242.25 on integer gray (FS:945)
+METRICS = ("lapvar", "tenengrad", "fft", "hybrid")
+FAILED = (None, 0.0, 0.0, 0.0, 1.0, None, None, None, 1.0)   # the reference's tuple for an unreadable image
+FIELDS = tuple(n for n, _ in capi.FrameStats._fields_)
+
+DeviceFrame = collections.namedtuple("DeviceFrame", "buf H W C stride")   # an H x W x C uint8 frame already in device memory
+DeviceFrame.__new__.__defaults__ = (0,)
+
+
+def band_rows(H, crop_ratio):
+    """crop_by_ratio_gray_and_mask's band (FS:674-690) -> (y0, y1); ValueError outside (0, 1]."""
+    if crop_ratio is None or abs(crop_ratio - 1.0) < 1e-6:
+        return 0, H
+    if not (0.0 < crop_ratio <= 1.0):
+        raise ValueError("crop_ratio must be in (0, 1]")
+    nh = max(1, int(H * crop_ratio))
+    y0 = max(0, (H - nh) // 2)
+    return y0, min(H, y0 + nh)
+
+
+def fft_input_size(bw, bh):
+    """(width, height) of the image fft_energy_fast transforms for a bw x bh band (FS:754-760): the band itself up to 512."""
+    if max(bh, bw) > FFT_LONG_SIDE:
+        scale = float(FFT_LONG_SIDE) / float(max(bh, bw))
+        return max(1, int(bw * scale)), max(1, int(bh * scale))
+    return bw, bh
+
+
+def nearest_index(dsize, ssize):
+    """cv2.resize INTER_NEAREST's source index per destination index: min(floor(d * (1 / (dsize / ssize))), ssize - 1)."""
+    ifx = 1.0 / (float(dsize) / float(ssize))
+    return np.minimum(np.floor(np.arange(dsize) * ifx).astype(np.int64), ssize - 1)
+
+
+def circle_mask(H, W, ys, xs):
+    """build_circular_valid_mask (FS:693-705) at rows ys x columns xs of an H x W frame, in integers."""
+    r4 = max(4, min(W, H) ** 2)
+    dy = 2 * np.asarray(ys, np.int64)[:, None] - (H - 1)
+    dx = 2 * np.asarray(xs, np.int64)[None, :] - (W - 1)
+    return dx * dx + dy * dy <= r4
+
+
+def fft_energy(g, g_mask):
+    """fft_energy_fast after its resize (FS:762-786), on the float32 image g and the resized mask (or None)."""
+    f = np.fft.fft2(g.astype(np.float32))
+    fshift = np.fft.fftshift(f)
+    h, w = g.shape
+    cy, cx = h // 2, w // 2
+    r = max(1, min(h, w) // 8)
+    yy, xx = np.ogrid[:h, :w]
+    dist2 = (yy - cy) ** 2 + (xx - cx) ** 2
+    hf_abs = np.abs(fshift * (dist2 >= r * r).astype(np.float32))
+    if g_mask is not None and np.any(g_mask):
+        valid = (g_mask > 0).astype(np.float32)
+        total = np.sum(valid)
+        if total > 0:
+            return float(np.sum(hf_abs * valid) / total)
+    return float(np.mean(hf_abs))
+
+
+def _cv_mean(s, n):
+    return s * (1.0 / n)          # cv::mean: sum * (1. / count)
+
+
+def _cv_var(s, sq, n):
+    """std^2 of cv::meanStdDev: mean = s * (1/n), std = sqrt(max(sq * (1/n) - mean^2, 0))."""
+    scale = 1.0 / n
+    m = s * scale
+    std = math.sqrt(max(sq * scale - m * m, 0.0))
+    return std * std
+
+
+def mask_plan(st, H, W, ignore_highlights, mask_mode):
+    """-> (p255, masked): the reference's mask branches (FS:938-961) decided from the full-frame counts.  masked = the band
+    statistics come from the valid sums (a mask exists; the empty-mask fallback is the caller's)."""
+    circle = mask_mode == "fisheye_circle"
+    p255 = 0.0
+    masked = circle
+    if ignore_highlights:
+        if circle and st["n_circle"] > 0:
+            p255 = float(st["n_highlight_in_circle"] / float(st["n_circle"]))
+        else:
+            p255 = float(st["n_highlight"] / float(H * W))
+        if not circle:
+            masked = 0.0 < p255 < 1.0
+    return p255, masked
+
+
+def finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small=None):
+    """The 9-tuple of score_one_file from one frame's statistics.  st: mapping of the gs360_frame_stats fields; small: the two
+    planes of the fft input (INTER_AREA image, gray at the nearest sample) for metric fft / hybrid."""
+    if metric not in METRICS:
+        return FAILED                 # the reference's `sharp` is never bound: its except clause returns this
+    p255, masked = mask_plan(st, H, W, ignore_highlights, mask_mode)
+    use_valid = masked and st["n_valid"] > 0
+    sfx = "_valid" if use_valid else ""
+    n = st["n_valid"] if use_valid else st["n"]
+    if use_valid:
+        brightness_mean = float(_cv_mean(float(st["sum_gray_valid"]), n) / 255.0)
+    else:
+        brightness_mean = float(st["sum_gray"] / n / 255.0)   # exact sum / n (the reference's np.mean sums in float32)
+    brightness_weight = 1.0
+    lap_feature = ten_feature = fft_feature = None
+    motion_factor = 1.0
+    lap = _cv_var(float(st["sum_lap" + sfx]), float(st["sum_lap2" + sfx]), n) if metric in ("lapvar", "hybrid") else None
+    ten = _cv_mean(float(st["sum_mag2" + sfx]), n) if metric in ("tenengrad", "hybrid") else None
+    fft = None
+    if metric in ("fft", "hybrid"):
+        g, g_near = small
+        g_mask = None
+        if masked:
+            y0, y1 = band
+            ys = y0 + nearest_index(g.shape[0], y1 - y0)
+            xs = nearest_index(g.shape[1], W)
+            m = np.ones(g.shape, bool)
+            if mask_mode == "fisheye_circle":
+                m &= circle_mask(H, W, ys, xs)
+            if ignore_highlights:
+                m &= g_near < HIGHLIGHT_LEVEL
+            g_mask = m.astype(np.uint8)
+        fft = fft_energy(g, g_mask)
+    if metric == "lapvar":
+        sharp = lap
+        lap_feature = lap * lap
+    elif metric == "tenengrad":
+        sharp = ten_feature = ten
+    elif metric == "fft":
+        sharp = fft_feature = fft
+    else:
+        lap_feature, ten_feature, fft_feature = lap * lap, ten, fft
+        hybrid_raw = HYBRID_LAPVAR_WEIGHT * lap_feature + HYBRID_TENENGRAD_WEIGHT * ten + HYBRID_FFT_WEIGHT * fft
+        if augment_motion:
+            motion_ratio = max(0.0, min(1.0, ten / (ten + HYBRID_MOTION_REFERENCE)))
+            motion_factor = max(0.0, 1.0 - HYBRID_MOTION_PENALTY_WEIGHT * (1.0 - motion_ratio))
+        dark_ratio = brightness_mean / HYBRID_DARK_THRESHOLD if brightness_mean < HYBRID_DARK_THRESHOLD else 1.0
+        dark_ratio = max(0.0, min(1.0, dark_ratio))
+        brightness_weight = max(0.0, 1.0 - HYBRID_DARK_PENALTY_WEIGHT * (1.0 - dark_ratio))
+        sharp = hybrid_raw * motion_factor
+    return (sharp, 0.0, p255, brightness_mean, brightness_weight, lap_feature, ten_feature, fft_feature, motion_factor)
+
+
+def hybrid_scores(tuples):
+    """The main flow's hybrid normalisation (FS:2363-2392): each feature min-max normalised over the run, blended with the hybrid
+    weights and multiplied by the motion factor.  tuples: the run's 9-tuples; returns the final score column (a frame without a
+    Laplacian feature keeps its own sharp value)."""
+    lap_arr = [t[5] for t in tuples]
+    ten_arr = [t[6] for t in tuples]
+    fft_arr = [t[7] for t in tuples]
+    lap_values = [v for v in lap_arr if v is not None]
+    ten_values = [v for v in ten_arr if v is not None]
+    fft_values = [v for v in fft_arr if v is not None]
+
+    def _normalize(values, value):
+        if not values or value is None:
+            return 0.0
+        vmin, vmax = min(values), max(values)
+        if math.isclose(vmax, vmin):
+            return 0.0
+        return (value - vmin) / (vmax - vmin)
+
+    scores = [t[0] for t in tuples]
+    for i, t in enumerate(tuples):
+        if lap_arr[i] is None:
+            continue
+        combined = (HYBRID_LAPVAR_WEIGHT * _normalize(lap_values, lap_arr[i]) + HYBRID_TENENGRAD_WEIGHT * _normalize(ten_values, ten_arr[i])
+                    + HYBRID_FFT_WEIGHT * _normalize(fft_values, fft_arr[i]))
+        scores[i] = combined * t[8]
+    return scores
+
+
+def _mean_optional(values, default=None):
+    valid = [float(v) for v in values if v is not None and math.isfinite(float(v))]
+    if not valid:
+        return default
+    return float(sum(valid) / float(len(valid)))
+
+
+# ---- the GPU pass ------------------------------------------------------------------------------------------------------------
+_ctx = None
+_ctx_lock = threading.Lock()
+
+
+def default_context():
+    """One engine context per process (device 0), created on first use."""
+    global _ctx
+    with _ctx_lock:
+        if _ctx is None:
+            _ctx = capi.Context(device=0, n_slots=1)
+        return _ctx
+
+
+def _frame_shape(fr):
+    if isinstance(fr, DeviceFrame):
+        return fr.H, fr.W, fr.C
+    a = np.asarray(fr)
+    if a.dtype != np.uint8:
+        raise capi.Gs360Error(-4, f"frame scoring takes 8-bit images (got {a.dtype}); 16-bit and float sources are not implemented")
+    if a.ndim == 2:
+        return a.shape[0], a.shape[1], 1
+    if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
+        raise ValueError(f"frame of shape {a.shape}: want H x W or H x W x C with C in (1, 3, 4)")
+    return a.shape
+
+
+def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index):
+    H, W, Cn = shape
+    band = band_rows(H, crop_ratio)
+    n = len(frames)
+    want_small = metric in ("fft", "hybrid")
+    sw, sh = fft_input_size(W, band[1] - band[0])
+    flags = (capi.FS_CIRCLE if mask_mode == "fisheye_circle" else 0) | (capi.FS_HIGHLIGHTS if ignore_highlights else 0)
+    owned = []
+    try:
+        bufs, stride = [], 0
+        for fr in frames:
+            if isinstance(fr, DeviceFrame):
+                bufs.append(fr.buf)
+                stride = fr.stride
+            else:
+                b = ctx.to_device(np.ascontiguousarray(fr))
+                owned.append(b)
+                bufs.append(b)
+        stats = ctx.alloc(n * capi.C.sizeof(capi.FrameStats))
+        owned.append(stats)
+        smalls = None
+        if want_small:
+            smalls = [ctx.alloc(2 * sw * sh * 4) for _ in range(n)]
+            owned += smalls
+        with ctx.slot_locks[0]:
+            ctx.frame_stats_dev(bufs, H, W, Cn, band, stats, flags=flags, smalls=smalls, small_w=sw, small_h=sh, red_index=red_index,
+                                stride=stride, slot=0)
+            recs = ctx.download(stats, (n, len(FIELDS)), np.int64)
+            planes = [ctx.download(b, (2, sh, sw), np.float32) for b in smalls] if want_small else [None] * n
+    finally:
+        for b in owned:
+            ctx.free(b)
+    out = []
+    for k in range(n):
+        st = {f: int(v) for f, v in zip(FIELDS, recs[k])}
+        small = (planes[k][0], planes[k][1]) if want_small else None
+        out.append(finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small))
+    return out
+
+
+def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode="none", red_index=0):
+    """9-tuples for a sequence of frames: uint8 ndarrays (H x W or H x W x C, RGB(A) order unless red_index = 2) or DeviceFrames
+    already in device memory (decoded video frames, gs360/video.py).  Consecutive frames of one size share a launch of up to
+    GS360_MAX_FRAMES frames.  ctx None = the process's default context."""
+    frames = list(frames)
+    shapes = [_frame_shape(fr) for fr in frames]          # 16-bit / float sources and bad crops fail before any GPU work
+    for shape in set(shapes):
+        band_rows(shape[0], crop_ratio)
+    ctx = ctx or default_context()
+    out = []
+    i = 0
+    while i < len(frames):
+        j = i + 1
+        while j < len(frames) and j - i < capi.MAX_FRAMES and shapes[j] == shapes[i] \
+                and isinstance(frames[j], DeviceFrame) == isinstance(frames[i], DeviceFrame):
+            j += 1
+        out += _score_batch(ctx, frames[i:j], shapes[i], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index)
+        i = j
+    return out
+
+
+def _decode(fp):
+    try:
+        a = imageio.read_image(fp)
+    except (imageio.ImageIOError, OSError):
+        return None
+    _frame_shape(a)            # 16-bit -> Gs360Error
+    return a
+
+
+def _check_max_long(max_long):
+    if max_long and max_long > 0:
+        raise capi.Gs360Error(-4, "max_long > 0 is not implemented (the reference CLI runs with MAX_LONG = 0)")
+
+
+def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none", workers=None):
+    """score_one_file over many paths: decoding on a thread pool overlaps the GPU batches; unreadable files give the reference's
+    failure tuple.  Returns one tuple per path, in order."""
+    _check_max_long(max_long)
+    band_rows(1, crop_ratio)   # the reference's ValueError before any work
+    paths = list(paths)
+    ctx = default_context()
+    out = [None] * len(paths)
+    workers = workers or min(16, os.cpu_count() or 1)
+    window = 2 * capi.MAX_FRAMES
+    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as ex:
+        futs = collections.deque()
+        nxt = 0
+        pending = []                      # (index, image) decoded, not yet scored
+
+        def flush():
+            if pending:
+                res = score_arrays(ctx, [a for _, a in pending], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode)
+                for (k, _), r in zip(pending, res):
+                    out[k] = r
+                pending.clear()
+        while nxt < len(paths) or futs:
+            while nxt < len(paths) and len(futs) < window:
+                futs.append((nxt, ex.submit(_decode, paths[nxt])))
+                nxt += 1
+            k, fut = futs.popleft()
+            a = fut.result()
+            if a is None:
+                out[k] = FAILED
+                continue
+            if pending and _frame_shape(a) != _frame_shape(pending[0][1]):
+                flush()
+            pending.append((k, a))
+            if len(pending) == capi.MAX_FRAMES:
+                flush()
+        flush()
+    return out
+
+
+def score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none"):
+    """Drop-in for the reference's score_one_file (FS:902-1044) on the GPU."""
+    _check_max_long(max_long)
+    a = _decode(fp)
+    if a is None:
+        return FAILED
+    return score_arrays(None, [a], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode)[0]
+
+
+def score_one_record(record, metric, crop_ratio, max_long, augment_motion, ignore_highlights, score_backend="opencv"):
+    """Drop-in for the reference's score_one_record (FS:458-517): a single image, or an X / Y fisheye pair scored with the circle
+    mask and averaged field by field.  The ffmpeg backend is not implemented (pairs always take the OpenCV path, as there)."""
+    mask_mode = "fisheye_circle" if str(record.get("input_mode", "")).strip().lower() == "pair" else "none"
+    if score_backend == "ffmpeg" and mask_mode != "fisheye_circle":
+        raise capi.Gs360Error(-4, "the ffmpeg scoring backend is not implemented; use score_backend='opencv'")
+    paths = list(record.get("file_paths", []))
+    if not paths:
+        return FAILED
+    results = score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode, workers=len(paths))
+    sharp = _mean_optional([r[0] for r in results if r[0] is not None], default=None)
+    return (sharp,
+            _mean_optional([r[1] for r in results], default=0.0),
+            _mean_optional([r[2] for r in results], default=0.0),
+            _mean_optional([r[3] for r in results], default=0.0),
+            _mean_optional([r[4] for r in results], default=1.0),
+            _mean_optional([r[5] for r in results], default=None),
+            _mean_optional([r[6] for r in results], default=None),
+            _mean_optional([r[7] for r in results], default=None),
+            _mean_optional([r[8] for r in results], default=1.0))

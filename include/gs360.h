@@ -329,6 +329,36 @@ int gs360_color_plan16_destroy(gs360_ctx *ctx, gs360_color_plan16 *plan);
 int gs360_color_apply_u16(gs360_ctx *ctx, const gs360_color_plan16 *plan, const void *src, int H, int W, int C,
                           size_t src_stride, int red_index, void *dst, size_t dst_stride, int slot);
 
+/* ---- frame sharpness statistics (the FrameSelector's scoring pass) ----------------------------
+ * The per-pixel part of score_one_file in cli_tools/gs360_FrameSelector.py (FS:902-1044: gray conversion, fisheye-circle and
+ * highlight masks, central crop band) with lapvar32 / tenengrad32 (FS:720-739: cv2.Laplacian ksize 3 + meanStdDev, cv2.Sobel x / y +
+ * mean of gx^2 + gy^2) reduced to exact integer sums, and the INTER_AREA downscale fft_energy_fast feeds its FFT (FS:742-786).  The
+ * FFT, the masks' branch logic and the final score stay on the host (FS-SPEC v1; gs360/framescore.py).
+ *
+ * For every frame f < n_frames (H x W x C uint8, C in {1,3,4}, row stride `stride` bytes, 0 = tight; 4-byte aligned base):
+ *   gray      C = 1: the sample; else (R*4899 + G*9617 + B*1868 + 8192) >> 14 (cv2 BGR2GRAY on 8U), red at byte red_index (0 or 2)
+ *   circle    (2x - (W-1))^2 + (2y - (H-1))^2 <= max(4, min(W,H)^2)     highlight  gray >= 243 (the reference's gray >= 242.25)
+ *   band      rows [band_y0, band_y1): the Laplacian [[2,0,2],[0,-8,0],[2,0,2]] and the Sobel pair of the band as an image of its own
+ *             (BORDER_REFLECT_101 at its four edges); mag2 = gx^2 + gy^2
+ *   valid     (circle, with GS360_FS_CIRCLE) and (not highlight, with GS360_FS_HIGHLIGHTS); all ones without flags
+ * stats_dev[f] (device memory) receives the full-frame counts and, over the band, the sums of every band pixel and of its valid
+ * pixels.  The call clears the records first.  All sums are integers: the result does not depend on the order of the work.
+ * small_dev (NULL = not wanted) holds n_frames device pointers to 2 x small_h x small_w float32 each: plane 0 = the band resized
+ * to small_w x small_h with cv2.resize INTER_AREA (OpenCV's per-axis area weights, float32, its operation order), plane 1 = the
+ * band's gray at INTER_NEAREST's sample (min(floor(d * s/d_size), s - 1) per axis), from which the host forms the resized mask.
+ * small_w <= W and small_h <= band_y1 - band_y0 (equal sizes give the band itself).  n_frames may exceed GS360_MAX_FRAMES (split
+ * internally).  H, W <= 65535.  Asynchronous on `slot`. */
+#define GS360_FS_CIRCLE 0x1u      /* mask_mode "fisheye_circle" (the pair records, FS:451-455, 693-705) */
+#define GS360_FS_HIGHLIGHTS 0x2u  /* ignore_highlights (FS:944-961) */
+typedef struct gs360_frame_stats {
+    int64_t n_circle, n_highlight, n_highlight_in_circle;      /* whole frame */
+    int64_t n, sum_gray, sum_lap, sum_lap2, sum_mag2;          /* every band pixel */
+    int64_t n_valid, sum_gray_valid, sum_lap_valid, sum_lap2_valid, sum_mag2_valid;   /* band pixels where `valid` is set */
+} gs360_frame_stats;
+int gs360_frame_stats_u8(gs360_ctx *ctx, const void *const *frames, int n_frames, int H, int W, int C, size_t stride,
+                         int red_index, int band_y0, int band_y1, uint32_t flags, gs360_frame_stats *stats_dev,
+                         float *const *small_dev, int small_w, int small_h, int slot);
+
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
                                  const gs360_view *views, int n_views,
