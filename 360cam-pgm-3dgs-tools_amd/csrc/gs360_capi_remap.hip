@@ -83,6 +83,10 @@ void lanczos4_coef1d(float* c1) {   // OpenCV interpolateLanczos4: taps -3..+4, 
 }
 
 constexpr int kTsBoxBudget = 26 * 1024 - 64;     // largest tile box of the LDS-staged table kernel: two of them per workgroup, three workgroups per CU
+// its box loader splits chunk c into (c * magic) >> 21 rows, magic = ceil(2^21 / wch) (table_stage_plan_kernel): exact while chunks * wch <
+// 2^21, no 32-bit overflow while rows < 2^11 -- for boxes as wide as a map plan's widest source (wch <= 766) and up to the budget's chunks
+constexpr int kTsBoxChunks = kTsBoxBudget / 16, kTsMaxWch = ((((3 * (kMapPlanMaxDim - 1)) & ~3) + 12) + 15) >> 4;
+static_assert(kTsBoxChunks * kTsMaxWch < (1 << 21) && kTsBoxChunks < (1 << 11), "the box loader's row split needs a wider magic");
 
 uint8_t sat_u8(double v) {  // cv::saturate_cast<uchar>(double)
     long r = std::lrint(v);
@@ -186,6 +190,7 @@ int remap_batches(gs360_ctx* c, const gs360_remap_job* jobs, const gs360_map_pla
         cval16[k] = (uint16_t)(r < 0 ? 0 : (r > 65535 ? 65535 : r));
     }
     HIP_TRY(hipSetDevice(c->device));
+    int staged_jobs = 0, slow_tiles = 0;        // the whole call's, over all its launches (read-only options last_table_*)
     for (int j0 = 0; j0 < n_jobs; j0 += GS360_MAX_VIEWS) {
         TableBatch B;
         B.n_jobs = 0;
@@ -199,7 +204,6 @@ int remap_batches(gs360_ctx* c, const gs360_remap_job* jobs, const gs360_map_pla
         const int opt_stage = opt(c, kOptTableStage);
         S.R = opt(c, kOptTableStageRows);
         S.wg_per_cu = opt(c, kOptTableStageWgs);
-        int slow_tiles = 0;
         for (int j = j0; j < n_jobs && j < j0 + GS360_MAX_VIEWS; ++j) {
             if (esize == 1 && (jobs[j].h == 0 || jobs[j].w == 0)) continue;     // (8-bit: an empty job is skipped unchecked; 16-bit: checked first)
             const gs360_map_plan* plan = plans ? plans[j] : nullptr;
@@ -225,7 +229,10 @@ int remap_batches(gs360_ctx* c, const gs360_remap_job* jobs, const gs360_map_pla
         if (esize == 2) continue;
         if (S.n_jobs) HIP_TRY(ts_launch(S, c->prop.multiProcessorCount, 160 * 1024, c->stream[slot]));
         if (B.n_jobs) HIP_TRY(launch_table_batch(B, C, c->stream[slot]));
-        c->last_table_kernel.store(S.n_jobs, std::memory_order_relaxed);
+        staged_jobs += S.n_jobs;
+    }
+    if (esize == 1) {
+        c->last_table_kernel.store(staged_jobs, std::memory_order_relaxed);
         c->last_table_slow.store(slow_tiles, std::memory_order_relaxed);
     }
     return GS360_OK;

@@ -115,7 +115,10 @@ __global__ __launch_bounds__(256) void table_stage_plan_kernel(const uint32_t* _
             if (threadIdx.x == 0) atomicAdd(&stats[1], 1);
         } else {
             T.chunks = T.nrows * T.wch;                  // < 2^13 (the budget is < 128 KiB)
-            T.magic = ((1 << 20) + T.wch - 1) / T.wch;   // chunk c lies in box row (c * magic) >> 20: exact for c < 2^20 / wch
+            // chunk c lies in box row (c * magic) >> 21: with magic wch = 2^21 + e, 0 <= e < wch, that is c / wch + c e / (wch 2^21),
+            // exact while c e < 2^21, and c magic < nrows 2^21 + chunks fits 32 bits -- both for every box the budget admits
+            // (kTsBoxBudget, gs360_capi_remap.hip).  (A 20-bit magic was a row too far for wch = 756 and 762 with two rows.)
+            T.magic = ((1 << 21) + T.wch - 1) / T.wch;
             if (threadIdx.x == 0) atomicMax(&stats[0], T.chunks * 16);
         }
     }
@@ -227,7 +230,7 @@ __global__ __launch_bounds__(64 * NW) void table_staged_kernel(const TsArgs P) {
         const int H1 = J.H - 1, stride = J.src_stride;
         auto chunk = [&](const int k) {
             const int cc = max(min(64 * (wave + NW * k) + lane, T.chunks - 1), 0);      // (lanes past the box repeat its last chunk)
-            const int row = (int)(((uint32_t)cc * (uint32_t)T.magic) >> 20), col = cc - row * T.wch;
+            const int row = (int)(((uint32_t)cc * (uint32_t)T.magic) >> 21), col = cc - row * T.wch;
             const int yc = min(T.y0 + row, H1);          // (a bottom tap of weight zero: any readable row)
             return *reinterpret_cast<const uint4*>(__builtin_assume_aligned(src + (size_t)yc * (size_t)stride + (uint32_t)(T.x0b + col * 16), 4));
         };

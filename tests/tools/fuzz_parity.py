@@ -218,11 +218,24 @@ def fuzz_table(ctx, rng, case):
 def fuzz_tablestage(ctx, rng, case):
     """the LDS-staged table kernel (bilinear RGB through map plans, csrc/gs360_tablestage.hip): smooth maps of random scale / rotation /
     radial term that cross the source's borders, valid fills, 1-4 jobs per call on one source, tight outputs (any width with h w % 4 == 0)
-    and padded ones (rows of whole dwords), tiles of 8 / 16 / 32 rows; forced onto every job (option table_stage = 1)"""
-    W = 4 * int(rng.integers(2, 160))                    # rows of whole dwords: what the kernel's box loads need
-    H = int(rng.integers(2, 400))
-    src = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
-    d_src = ctx.to_device(src)
+    and padded ones (rows of whole dwords), tiles of 8 / 16 / 32 rows; forced onto every job (option table_stage = 1).  A quarter of the
+    calls take a wide, short source (up to 4079 texels, the widest a map plan addresses) through maps that minify strongly along x: boxes
+    of hundreds of 16-byte chunks.  Sources come with padded strides and at offsets into their buffer; those whose rows do not start on
+    dwords (stride or offset not a multiple of 4) keep the gather kernel."""
+    wide = rng.random() < 0.25
+    if wide:
+        W, H = int(rng.integers(1000, 4080)), int(rng.integers(2, 40))
+    else:
+        W = 4 * int(rng.integers(2, 160)) if rng.random() < 0.8 else int(rng.integers(8, 640))
+        H = int(rng.integers(2, 400))
+    stride = 3 * W + int(rng.choice([0, 0, 4, 64]))
+    if rng.random() < 0.85:
+        stride += -stride % 4                            # rows of whole dwords: what the kernel's box loads need
+    off = int(rng.choice([0, 0, 0, 4, 1]))               # 4: dword- but not 16-byte-aligned
+    eligible = stride % 4 == 0 and off % 4 == 0
+    raw = rng.integers(0, 256, off + H * stride, dtype=np.uint8)
+    src = raw[off:].reshape(H, stride)[:, :3 * W].reshape(H, W, 3)
+    d_src = ctx.to_device(raw)
     rows = int(rng.choice([8, 16, 32]))
     bv = tuple(float(v) for v in rng.integers(0, 256, 4))
     n_jobs = int(rng.integers(1, 5))
@@ -239,6 +252,10 @@ def fuzz_tablestage(ctx, rng, case):
         kk = 1.0 + k2 * (u * u + v * v)
         mx = (((u * np.cos(ang) - v * np.sin(ang)) * kk * sc + rng.uniform(0.2, 0.8)) * (W - 1)).astype(np.float32)
         my = (((u * np.sin(ang) + v * np.cos(ang)) * kk * sc + rng.uniform(0.2, 0.8)) * (H - 1)).astype(np.float32)
+        if wide:                                         # a 64-pixel tile row spans 128 texels .. the whole row, a few source rows
+            step = rng.uniform(2.0, max(2.0, (W - 1) / max(min(w, 64) - 1, 1)))
+            mx = (rng.uniform(-0.05, 0.5) * W + xx * step + yy * rng.uniform(-0.5, 0.5)).astype(np.float32)
+            my = (rng.uniform(-1.0, H) + yy * rng.uniform(0.0, 0.4) + xx * rng.uniform(-0.01, 0.01)).astype(np.float32)
         if rng.random() < 0.3:                           # exact grid points: weight-zero taps on the last column / row
             mx, my = np.rint(mx).astype(np.float32), np.rint(my).astype(np.float32)
         valid = (rng.random((h, w)) > 0.2) if rng.random() < 0.5 else None
@@ -248,12 +265,13 @@ def fuzz_tablestage(ctx, rng, case):
         for b in d:
             if b is not None:
                 ctx.free(b)
-        stride = w * 3 + pad
-        dst = ctx.alloc(h * stride)
+        stride_out = w * 3 + pad
+        dst = ctx.alloc(h * stride_out)
         ctx.memset(dst, 0xAB)
         bufs.append(dst)
-        strides.append(stride)
-        jobs.append(gs360.capi.RemapJob(d_src.ptr, H, W, 0, None, None, dst.ptr if valid is not None else None, h, w, fill, dst.ptr, stride))
+        strides.append(stride_out)
+        jobs.append(gs360.capi.RemapJob(d_src.ptr + off, H, W, stride, None, None, dst.ptr if valid is not None else None, h, w, fill, dst.ptr,
+                                        stride_out))
         want = orc.remap_u8(src, mx, my, interp=1, border_value=bv, threads=0)
         wants.append((orc.valid_fill(want.copy(), valid, fill) if valid is not None else want).reshape(h, w, 3))
     import ctypes as C
@@ -264,9 +282,9 @@ def fuzz_tablestage(ctx, rng, case):
         gs360.capi._check(ctx.L.gs360_remap_plans_u8(ctx.handle, arr, pl, n_jobs, 3, 1, cbv, 0), ctx.L)
         ctx.sync(0)
         staged = ctx.get_option("last_table_kernel")
-    ok = staged == n_jobs
+    ok = staged == (n_jobs if eligible else 0)
     if not ok:
-        print(f"[tablestage] case {case}: {staged} of {n_jobs} jobs took the staged kernel")
+        print(f"[tablestage] case {case}: {staged} of {n_jobs} jobs took the staged kernel (source stride {stride}, offset {off})")
     for k in range(n_jobs):
         h, w = wants[k].shape[:2]
         raw = ctx.download(bufs[k], (h, strides[k]))
@@ -274,7 +292,8 @@ def fuzz_tablestage(ctx, rng, case):
         if not np.array_equal(got, wants[k]):
             ok = False
             bad = np.argwhere(got != wants[k])
-            print(f"[tablestage] case {case}: job {k} src {W}x{H} map {w}x{h} rows={rows} stride={strides[k]}: {len(bad)} bytes differ, first at {bad[0].tolist()}")
+            print(f"[tablestage] case {case}: job {k} src {W}x{H} (stride {stride}, offset {off}) map {w}x{h} rows={rows} stride={strides[k]}: "
+                  f"{len(bad)} bytes differ, first at {bad[0].tolist()}")
         if strides[k] > w * 3 and not np.all(raw[:, w * 3:] == 0xAB):
             ok = False
             print(f"[tablestage] case {case}: job {k} wrote into the row padding")
