@@ -303,4 +303,22 @@ struct FsLaunch {
 };
 hipError_t launch_frame_stats(FsLaunch& L, hipStream_t s);
 
+// Frame FFT energy (gs360_framefft.hip, FS-FFT v1 in DESIGN.md): one batch of up to GS360_MAX_FRAMES fft inputs of one size.
+struct FfPartial {                       // one column-pass workgroup's share of a frame's record
+    double sum_hf, sum_hf_valid;
+    int64_t n_valid;
+};
+struct FfLaunch {
+    const float* small[GS360_MAX_FRAMES];   // 2 x h x w each: the INTER_AREA image, the gray at the nearest sample
+    float* x[GS360_MAX_FRAMES];             // 2 x h x K each (re, im): row-pass output, K = w/2 + 1
+    FfPartial* part;                        // n_frames x n_part
+    gs360_frame_fft* out;                   // n_frames records
+    int32_t n_frames, h, w, K, n_part;
+    int32_t H, W, y0, y1;                   // frame size and band rows [y0, y1)
+    int32_t circle, highlights;             // GS360_FS_CIRCLE / GS360_FS_HIGHLIGHTS
+    double scale_x, scale_y;                // INTER_NEAREST's 1 / (w / W), 1 / (h / band height)
+};
+hipError_t launch_frame_fft(FfLaunch& L, hipStream_t s);
+int frame_fft_partials(int h, int w);       // n_part: column-pass workgroups per frame
+
 }  // namespace gs360

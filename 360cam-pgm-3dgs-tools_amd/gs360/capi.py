@@ -32,10 +32,11 @@ EXPORTS = (
     "gs360_equirect_views_u16", "gs360_remap_table_u16", "gs360_remap_tables_u16", "gs360_equirect_views_u16_host", "gs360_remap_table_u16_host",
     "gs360_png_unfilter", "gs360_event_sync", "gs360_stream_wait_event",
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
-    "gs360_frame_stats_u8",
+    "gs360_frame_stats_u8", "gs360_frame_fft_energy",
 )
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
+FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
 
 
 class Gs360Error(RuntimeError):
@@ -77,6 +78,11 @@ class FrameStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "n_circle", "n_highlight", "n_highlight_in_circle", "n", "sum_gray", "sum_lap", "sum_lap2", "sum_mag2",
         "n_valid", "sum_gray_valid", "sum_lap_valid", "sum_lap2_valid", "sum_mag2_valid")]
+
+
+class FrameFft(C.Structure):
+    """gs360_frame_fft: sum of |fftshift(fft2(g))| over the donut, over the donut's valid positions, the valid count and h*w."""
+    _fields_ = [("sum_hf", C.c_double), ("sum_hf_valid", C.c_double), ("n_valid", C.c_int64), ("n", C.c_int64)]
 
 
 ABI_VERSION = 2          # GS360_ABI_VERSION of include/gs360.h this binding was written against
@@ -156,6 +162,7 @@ def load_library(path=None):
         L.gs360_event_sync.argtypes = [vp, i, i]
         L.gs360_stream_wait_event.argtypes = [vp, i, i, i]
         L.gs360_frame_stats_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, u32, vp, pvp, i, i, i]
+        L.gs360_frame_fft_energy.argtypes = [vp, pvp, i, i, i, i, i, i, i, u32, vp, i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -505,6 +512,14 @@ class Context:
         sp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in smalls]) if smalls is not None else None
         _check(self.L.gs360_frame_stats_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(band[0]),
                                            int(band[1]), int(flags), stats.ptr, sp, int(small_w), int(small_h), slot), self.L)
+
+    def frame_fft_energy_dev(self, smalls, small_w, small_h, H, W, band, out, flags=0, slot=0):
+        """gs360_frame_fft_energy on the fft inputs frame_stats_dev wrote (one DeviceBuffer of 2 x small_h x small_w float32 per
+        frame of H x W, band = (y0, y1)): out = DeviceBuffer of len(smalls) FrameFft records.  Asynchronous on `slot`."""
+        nf = len(smalls)
+        sp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in smalls])
+        _check(self.L.gs360_frame_fft_energy(self.handle, sp, nf, int(small_w), int(small_h), int(H), int(W), int(band[0]),
+                                             int(band[1]), int(flags), out.ptr, slot), self.L)
 
     # -- hot path, host buffers (synchronous) -----------------------------------------------
     def equirect_views(self, src, views, slot=0, interp=INTERP_LINEAR, flags=0):

@@ -6,8 +6,10 @@ Drop-in seams of cli_tools/gs360_FrameSelector.py:
 both return the reference's 9-tuple (sharp, p0, p255, brightness_mean, brightness_weight, lap_feature, ten_feature, fft_feature,
 motion_factor).  The per-pixel work (gray, masks, Laplacian, Sobel, the INTER_AREA downscale of fft_energy_fast) runs in
 gs360_frame_stats_u8; what is left here is the reference's branch logic on exact integer sums, in double, and the FFT of the
-<= 512-pixel image (NumPy, the reference's own code, FS:742-786).  score_arrays / score_files batch frames GS360_MAX_FRAMES per
-launch; hybrid_scores is the main flow's per-run normalisation of the hybrid features (FS:2363-2392).
+<= 512-pixel image (FS:742-786).  That FFT runs on the host (fft="host": NumPy, the reference's own code, on the downloaded
+planes) or on the device (fft="device": gs360_frame_fft_energy, FS-FFT v1, after the statistics on the same stream; only two small
+records per frame come back).  score_arrays / score_files batch frames GS360_MAX_FRAMES per launch; hybrid_scores is the main
+flow's per-run normalisation of the hybrid features (FS:2363-2392).
 
 8-bit sources only: 16-bit and float images raise Gs360Error (GS360_ERR_UNSUPPORTED), as does max_long > 0.
 """
@@ -33,6 +35,9 @@ HIGHLIGHT_LEVEL = 243             # gray >= 0.95 * 255 = 242.25 on integer gray 
 METRICS = ("lapvar", "tenengrad", "fft", "hybrid")
 FAILED = (None, 0.0, 0.0, 0.0, 1.0, None, None, None, 1.0)   # the reference's tuple for an unreadable image
 FIELDS = tuple(n for n, _ in capi.FrameStats._fields_)
+FFT_MODES = ("host", "device")
+DEFAULT_FFT = "host"              # where score_* compute the fft term when their `fft` keyword is None
+FFT_DTYPE = np.dtype([(n, np.float64 if t is capi.C.c_double else np.int64) for n, t in capi.FrameFft._fields_])
 
 DeviceFrame = collections.namedtuple("DeviceFrame", "buf H W C stride")   # an H x W x C uint8 frame already in device memory
 DeviceFrame.__new__.__defaults__ = (0,)
@@ -89,6 +94,22 @@ def fft_energy(g, g_mask):
     return float(np.mean(hf_abs))
 
 
+def fft_mode(fft):
+    """The `fft` keyword of the score_* functions: None -> DEFAULT_FFT; "host" or "device"; anything else is a ValueError."""
+    mode = DEFAULT_FFT if fft is None else fft
+    if mode not in FFT_MODES:
+        raise ValueError(f"fft must be one of {FFT_MODES} or None (got {fft!r})")
+    return mode
+
+
+def fft_energy_from_record(rec, masked):
+    """fft_energy's value from a gs360_frame_fft record (mapping of its fields), with the reference's branches (FS:779-786): the
+    valid mean when a mask exists and is not empty, else the mean over all h*w positions."""
+    if masked and rec["n_valid"] > 0:
+        return float(rec["sum_hf_valid"] / float(rec["n_valid"]))
+    return float(rec["sum_hf"] / float(rec["n"]))
+
+
 def _cv_mean(s, n):
     return s * (1.0 / n)          # cv::mean: sum * (1. / count)
 
@@ -117,9 +138,10 @@ def mask_plan(st, H, W, ignore_highlights, mask_mode):
     return p255, masked
 
 
-def finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small=None):
+def finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small=None, fft_rec=None):
     """The 9-tuple of score_one_file from one frame's statistics.  st: mapping of the gs360_frame_stats fields; small: the two
-    planes of the fft input (INTER_AREA image, gray at the nearest sample) for metric fft / hybrid."""
+    planes of the fft input (INTER_AREA image, gray at the nearest sample) for metric fft / hybrid; fft_rec: instead of small, the
+    frame's gs360_frame_fft record (mapping of its fields), computed with the flags of mask_mode and ignore_highlights."""
     if metric not in METRICS:
         return FAILED                 # the reference's `sharp` is never bound: its except clause returns this
     p255, masked = mask_plan(st, H, W, ignore_highlights, mask_mode)
@@ -136,7 +158,9 @@ def finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode,
     lap = _cv_var(float(st["sum_lap" + sfx]), float(st["sum_lap2" + sfx]), n) if metric in ("lapvar", "hybrid") else None
     ten = _cv_mean(float(st["sum_mag2" + sfx]), n) if metric in ("tenengrad", "hybrid") else None
     fft = None
-    if metric in ("fft", "hybrid"):
+    if metric in ("fft", "hybrid") and fft_rec is not None:
+        fft = fft_energy_from_record(fft_rec, masked)
+    elif metric in ("fft", "hybrid"):
         g, g_near = small
         g_mask = None
         if masked:
@@ -233,11 +257,12 @@ def _frame_shape(fr):
     return a.shape
 
 
-def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index):
+def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index, fft):
     H, W, Cn = shape
     band = band_rows(H, crop_ratio)
     n = len(frames)
     want_small = metric in ("fft", "hybrid")
+    on_device = want_small and fft == "device"
     sw, sh = fft_input_size(W, band[1] - band[0])
     flags = (capi.FS_CIRCLE if mask_mode == "fisheye_circle" else 0) | (capi.FS_HIGHLIGHTS if ignore_highlights else 0)
     owned = []
@@ -257,26 +282,35 @@ def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_
         if want_small:
             smalls = [ctx.alloc(2 * sw * sh * 4) for _ in range(n)]
             owned += smalls
+        if on_device:
+            ffts = ctx.alloc(n * FFT_DTYPE.itemsize)
+            owned.append(ffts)
         with ctx.slot_locks[0]:
             ctx.frame_stats_dev(bufs, H, W, Cn, band, stats, flags=flags, smalls=smalls, small_w=sw, small_h=sh, red_index=red_index,
                                 stride=stride, slot=0)
+            if on_device:
+                ctx.frame_fft_energy_dev(smalls, sw, sh, H, W, band, ffts, flags=flags, slot=0)
             recs = ctx.download(stats, (n, len(FIELDS)), np.int64)
-            planes = [ctx.download(b, (2, sh, sw), np.float32) for b in smalls] if want_small else [None] * n
+            frecs = ctx.download(ffts, (n,), FFT_DTYPE) if on_device else None
+            planes = [ctx.download(b, (2, sh, sw), np.float32) for b in smalls] if want_small and not on_device else [None] * n
     finally:
         for b in owned:
             ctx.free(b)
     out = []
     for k in range(n):
         st = {f: int(v) for f, v in zip(FIELDS, recs[k])}
-        small = (planes[k][0], planes[k][1]) if want_small else None
-        out.append(finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small))
+        small = (planes[k][0], planes[k][1]) if want_small and not on_device else None
+        fft_rec = {f: frecs[k][f].item() for f in FFT_DTYPE.names} if on_device else None
+        out.append(finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small, fft_rec=fft_rec))
     return out
 
 
-def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode="none", red_index=0):
+def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode="none", red_index=0, fft=None):
     """9-tuples for a sequence of frames: uint8 ndarrays (H x W or H x W x C, RGB(A) order unless red_index = 2) or DeviceFrames
     already in device memory (decoded video frames, gs360/video.py).  Consecutive frames of one size share a launch of up to
-    GS360_MAX_FRAMES frames.  ctx None = the process's default context."""
+    GS360_MAX_FRAMES frames.  ctx None = the process's default context.  fft: where the fft / hybrid metrics' FFT runs, "host" or
+    "device" (None = DEFAULT_FFT); with "device" no plane leaves the GPU."""
+    fft = fft_mode(fft)
     frames = list(frames)
     shapes = [_frame_shape(fr) for fr in frames]          # 16-bit / float sources and bad crops fail before any GPU work
     for shape in set(shapes):
@@ -289,7 +323,8 @@ def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlig
         while j < len(frames) and j - i < capi.MAX_FRAMES and shapes[j] == shapes[i] \
                 and isinstance(frames[j], DeviceFrame) == isinstance(frames[i], DeviceFrame):
             j += 1
-        out += _score_batch(ctx, frames[i:j], shapes[i], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index)
+        out += _score_batch(ctx, frames[i:j], shapes[i], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index,
+                            fft)
         i = j
     return out
 
@@ -308,9 +343,10 @@ def _check_max_long(max_long):
         raise capi.Gs360Error(-4, "max_long > 0 is not implemented (the reference CLI runs with MAX_LONG = 0)")
 
 
-def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none", workers=None):
+def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none", workers=None, fft=None):
     """score_one_file over many paths: decoding on a thread pool overlaps the GPU batches; unreadable files give the reference's
-    failure tuple.  Returns one tuple per path, in order."""
+    failure tuple.  Returns one tuple per path, in order.  fft: as score_arrays."""
+    fft = fft_mode(fft)
     _check_max_long(max_long)
     band_rows(1, crop_ratio)   # the reference's ValueError before any work
     paths = list(paths)
@@ -325,7 +361,8 @@ def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_high
 
         def flush():
             if pending:
-                res = score_arrays(ctx, [a for _, a in pending], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode)
+                res = score_arrays(ctx, [a for _, a in pending], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode,
+                                   fft=fft)
                 for (k, _), r in zip(pending, res):
                     out[k] = r
                 pending.clear()
@@ -347,25 +384,28 @@ def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_high
     return out
 
 
-def score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none"):
-    """Drop-in for the reference's score_one_file (FS:902-1044) on the GPU."""
+def score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none", fft=None):
+    """Drop-in for the reference's score_one_file (FS:902-1044) on the GPU.  fft: as score_arrays."""
+    fft = fft_mode(fft)
     _check_max_long(max_long)
     a = _decode(fp)
     if a is None:
         return FAILED
-    return score_arrays(None, [a], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode)[0]
+    return score_arrays(None, [a], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, fft=fft)[0]
 
 
-def score_one_record(record, metric, crop_ratio, max_long, augment_motion, ignore_highlights, score_backend="opencv"):
+def score_one_record(record, metric, crop_ratio, max_long, augment_motion, ignore_highlights, score_backend="opencv", fft=None):
     """Drop-in for the reference's score_one_record (FS:458-517): a single image, or an X / Y fisheye pair scored with the circle
-    mask and averaged field by field.  The ffmpeg backend is not implemented (pairs always take the OpenCV path, as there)."""
+    mask and averaged field by field.  The ffmpeg backend is not implemented (pairs always take the OpenCV path, as there).
+    fft: as score_arrays."""
+    fft = fft_mode(fft)
     mask_mode = "fisheye_circle" if str(record.get("input_mode", "")).strip().lower() == "pair" else "none"
     if score_backend == "ffmpeg" and mask_mode != "fisheye_circle":
         raise capi.Gs360Error(-4, "the ffmpeg scoring backend is not implemented; use score_backend='opencv'")
     paths = list(record.get("file_paths", []))
     if not paths:
         return FAILED
-    results = score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode, workers=len(paths))
+    results = score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode, workers=len(paths), fft=fft)
     sharp = _mean_optional([r[0] for r in results if r[0] is not None], default=None)
     return (sharp,
             _mean_optional([r[1] for r in results], default=0.0),

@@ -333,7 +333,8 @@ int gs360_color_apply_u16(gs360_ctx *ctx, const gs360_color_plan16 *plan, const 
  * The per-pixel part of score_one_file in cli_tools/gs360_FrameSelector.py (FS:902-1044: gray conversion, fisheye-circle and
  * highlight masks, central crop band) with lapvar32 / tenengrad32 (FS:720-739: cv2.Laplacian ksize 3 + meanStdDev, cv2.Sobel x / y +
  * mean of gx^2 + gy^2) reduced to exact integer sums, and the INTER_AREA downscale fft_energy_fast feeds its FFT (FS:742-786).  The
- * FFT, the masks' branch logic and the final score stay on the host (FS-SPEC v1; gs360/framescore.py).
+ * FFT runs on the host or in gs360_frame_fft_energy (below); the masks' branch logic and the final score stay on the host (FS-SPEC
+ * v1; gs360/framescore.py).
  *
  * For every frame f < n_frames (H x W x C uint8, C in {1,3,4}, row stride `stride` bytes, 0 = tight; 4-byte aligned base):
  *   gray      C = 1: the sample; else (R*4899 + G*9617 + B*1868 + 8192) >> 14 (cv2 BGR2GRAY on 8U), red at byte red_index (0 or 2)
@@ -358,6 +359,29 @@ typedef struct gs360_frame_stats {
 int gs360_frame_stats_u8(gs360_ctx *ctx, const void *const *frames, int n_frames, int H, int W, int C, size_t stride,
                          int red_index, int band_y0, int band_y1, uint32_t flags, gs360_frame_stats *stats_dev,
                          float *const *small_dev, int small_w, int small_h, int slot);
+
+/* ---- frame FFT energy (the fft / hybrid metrics' spectrum term) -------------------------------
+ * The FFT of fft_energy_fast in cli_tools/gs360_FrameSelector.py (FS:742-786), on the fft input gs360_frame_stats_u8 writes
+ * (FS-FFT v1), so that no plane leaves the device.  For every frame f < n_frames, small_dev[f] is that call's
+ * 2 x small_h x small_w float32 output for a frame of H x W with band rows [band_y0, band_y1): plane 0 = g (the INTER_AREA image),
+ * plane 1 = the gray at the nearest sample.  With h = small_h, w = small_w, S = fftshift(fft2(g)):
+ *   donut   shifted position (i, j) with (i - h/2)^2 + (j - w/2)^2 >= r^2, r = max(1, min(h, w)/8)
+ *   valid   at (i, j), the SPATIAL position (the reference multiplies the shifted spectrum by the resized mask): the circle of
+ *           gs360_frame_stats_u8 at (xs[j], ys[i]) with GS360_FS_CIRCLE, and plane1[i, j] < 243 with GS360_FS_HIGHLIGHTS;
+ *           xs = min(floor(j * W/w), W-1), ys = band_y0 + min(floor(i * bh/h), bh-1) (INTER_NEAREST, bh = band height)
+ * out_dev[f] (device memory) receives sum_hf = sum of |S| over the donut, sum_hf_valid = the same over valid positions,
+ * n_valid = the count of valid positions (donut or not) and n = h*w.  The host keeps the reference's branches: no mask or
+ * n_valid == 0 -> sum_hf / n, else sum_hf_valid / n_valid.  float32 DFT products, double sums, all in a fixed order: the records
+ * are bit-identical from call to call, and within 1e-5 relative + 1e-3 absolute of a float64 FFT.  Asynchronous
+ * on `slot`, stream-ordered after gs360_frame_stats_u8 on the same slot.  1 <= small_w <= min(W, GS360_FFT_MAX_SIDE),
+ * 1 <= small_h <= min(band height, GS360_FFT_MAX_SIDE); n_frames may exceed GS360_MAX_FRAMES (split internally). */
+#define GS360_FFT_MAX_SIDE 512
+typedef struct gs360_frame_fft {
+    double sum_hf, sum_hf_valid;
+    int64_t n_valid, n;     /* n = h*w */
+} gs360_frame_fft;
+int gs360_frame_fft_energy(gs360_ctx *ctx, const float *const *small_dev, int n_frames, int small_w, int small_h, int H, int W,
+                           int band_y0, int band_y1, uint32_t flags, gs360_frame_fft *out_dev, int slot);
 
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
