@@ -121,5 +121,11 @@ __device__ __forceinline__ int eq_lon_member(int base_norm, int x0i32, int W32) 
 __device__ __forceinline__ int eq_quant_lon(float r0, int K, const EqLaunch& L, const EqView& V) {
     return eq_lon_wrap(eq_lon_base(r0, K, L, V.x0f32), V.x0i32, 32 * L.W);
 }
+// quantised latitude (1/32 px) about the launch's row origin: a pixel's coordinate is L.y0i32 - q, that of its mirror image about
+// the horizon L.y0i32 + q (rint is odd).  The per-pixel sites write L.y0i32 - Kt * 8 * L.H - rint(...) out: the same integer, but
+// through this helper it compiles to a different instruction schedule.
+__device__ __forceinline__ int eq_quant_lat(float rt, int Kt, const EqLaunch& L) {
+    return Kt * 8 * L.H + (int)__builtin_rintf(rt * L.ky32);
+}
 
 }  // namespace gs360

@@ -30,14 +30,9 @@
 namespace gs360 {
 
 constexpr int kEqWaves = 5;     // wavefronts per SIMD of the bilinear equirect kernel (measured optimum, see the kernel comment)
-constexpr int kEqRowsKernel = 1;
 constexpr int kEqRowsWaves = 5;    // bilinear RGB kernel of launches without blocked views (pipelined member loop only)
 constexpr int kEqStagedWaves = 4;    // LDS-staged bilinear RGB kernel: 40 KiB of LDS per workgroup = four workgroups per CU
-constexpr int kStageEnable = 1; // 0: every pass of eq_staged_kernel takes the gather form (A/B of the lane map alone)
 constexpr int kEqCubicWaves = 4;    // wavefronts per SIMD of the cubic equirect kernel (124 registers; 40 KiB of LDS = four workgroups per CU)
-constexpr int kRingPark = 0;    // bilinear kernel: ring-shared coordinates that wait in LDS between members (0 none, 1 latitude, 3 all)
-constexpr int kRingParkCubic = 1;
-constexpr int kEqLean = 1;      // bilinear RGB row-per-slot views: the lean, software-pipelined member loop (0: the round-3 loop, A/B reference)
 
 
 // Store for the blocked lane map (RGB).  A wavefront holds a patch of 4 rows x (16 NS) columns in NS slots -- lane l of
@@ -584,42 +579,60 @@ __device__ __forceinline__ void eq_pass16(const EqSrc& L, const uint8_t* __restr
 template <int C, bool CUBIC, int ES, bool ROWS = false, bool MASKED = false>     // ROWS: instantiation for launches without blocked views
 struct EqLds {
     static constexpr bool kBlocked = !ROWS && (C == 3) && (ES == 1) && (kRowsPerWave == 4) && (kWaves == 4);   // blocked lane map available
-    static constexpr int kParkN = (CUBIC && ES == 2) ? 3 : (CUBIC ? kRingParkCubic : kRingPark);     // 0 none, 1 latitude only, 3 all three
+    // ring-shared coordinates parked between members of the generic loop: cubic 8-bit the latitude, cubic 16-bit all three
+    static constexpr int kParkN = (CUBIC && ES == 2) ? 3 : (CUBIC ? 1 : 0);
     static constexpr int kBlkDw = kBlocked ? kWaves * 256 : 0;
     static constexpr int kParkDw = kParkN * kRowsPerWave * 64 * kWaves;
-    // the pipelined bilinear member loop keeps ALL ring-shared coordinates in LDS (three 16-byte entries per thread)
     // lean member loop (bilinear RGB, row-per-slot map): six int4 entries per thread -- latitude, left / mirrored longitude, the two
     // tap rows' byte offsets and the vertical phase of the current pitch sign
-    static constexpr bool kLean = kEqLean && C == 3 && !CUBIC && ES == 1 && kRowsPerWave == 4;
+    static constexpr bool kLean = C == 3 && !CUBIC && ES == 1 && kRowsPerWave == 4;
     static constexpr int kPipeDw = kLean ? (MASKED ? 7 : 6) * kRowsPerWave * 64 * kWaves : 0;   // masked: + the keep-bit image's row offsets
     static constexpr int kDwords = kBlkDw + (kParkDw + kPipeDw ? kParkDw + kPipeDw : 4);
 };
 
-// One tile of a ring (all its members, both halves) -- the body of eq_views_kernel.  `b` is the workgroup's position in the
-// tile order (blockIdx.x, or the persistent walk of the cubic variants).
-template <int C, bool CUBIC, bool MASKED, int ES, bool ROWS = false>
-__device__ __forceinline__ void eq_views_tile(const EqLaunch& L, const int b, const int16_t* s_wtab, uint32_t* const s_lds) {
-    // XCD-aware tile order: XCD x (= b % 8) walks tiles [x*chunk, (x+1)*chunk), or -- when the launch mixes rings of
-    // different sizes, whose tiles differ in cost -- runs of 2^g consecutive tiles dealt round-robin to the XCDs
+// The launch's tile order: position b (blockIdx.x, or a step of the persistent walk) -> tile number, >= L.total_tiles past the last
+// tile.  XCD x (= b % 8) walks tiles [x*chunk, (x+1)*chunk), or -- when the launch mixes rings of different sizes, whose tiles differ
+// in cost -- runs of 2^g consecutive tiles dealt round-robin to the XCDs.
+__device__ __forceinline__ int eq_tile_order(const EqLaunch& L, const int b) {
     int t = (b & 7) * L.chunk + (b >> 3);
     if (L.xcd_group_log2 >= 0) {
         const int q = b >> 3, g = L.xcd_group_log2;
         t = ((((q >> g) << 3) + (b & 7)) << g) + (q & ((1 << g) - 1));
     }
+    return t;
+}
+// Tile t: its frame, its ring -- first view k0, whose geometry every member shares, and member count -- and its row / column of
+// tiles in the ring's views.  The caller takes the view as a reference into the kernel argument (L.view[k0]): a copy spills the
+// whole argument array to scratch memory (see fe_views_tile).
+struct EqTile { int f, k0, n_members, tile_y, tile_x; };
+__device__ __forceinline__ EqTile eq_tile_at(const EqLaunch& L, const int t) {
+    EqTile T;
+    T.f = t / L.tiles_per_frame;
+    int r = t - T.f * L.tiles_per_frame;
+    int g = 0;
+    while (g + 1 < L.n_rings && r >= L.view[L.ring_first[g + 1]].tile_base) ++g;
+    T.k0 = L.ring_first[g];
+    T.n_members = L.ring_count[g];
+    r -= L.view[T.k0].tile_base;
+    T.tile_y = r / L.view[T.k0].tiles_x;
+    T.tile_x = r - T.tile_y * L.view[T.k0].tiles_x;
+    return T;
+}
+
+// One tile of a ring (all its members, both halves) -- the body of eq_views_kernel.  `b` is the workgroup's position in the
+// tile order (blockIdx.x, or the persistent walk of the cubic variants).
+template <int C, bool CUBIC, bool MASKED, int ES, bool ROWS = false>
+__device__ __forceinline__ void eq_views_tile(const EqLaunch& L, const int b, const int16_t* s_wtab, uint32_t* const s_lds) {
+    const int t = eq_tile_order(L, b);
     if (t >= L.total_tiles) return;
     constexpr bool kBlocked = EqLds<C, CUBIC, ES, ROWS, MASKED>::kBlocked;
     constexpr int kParkN = EqLds<C, CUBIC, ES, ROWS, MASKED>::kParkN;
     constexpr int kBlkDw = EqLds<C, CUBIC, ES, ROWS, MASKED>::kBlkDw;
     uint32_t* const s_blk = s_lds;
     int* const s_park = reinterpret_cast<int*>(s_lds + kBlkDw);
-    int f = t / L.tiles_per_frame;
-    int r = t - f * L.tiles_per_frame;
-    int g = 0;
-    while (g + 1 < L.n_rings && r >= L.view[L.ring_first[g + 1]].tile_base) ++g;
-    const int k0 = L.ring_first[g], n_members = L.ring_count[g];
+    const EqTile T = eq_tile_at(L, t);
+    const int f = T.f, k0 = T.k0, n_members = T.n_members, tile_y = T.tile_y, tile_x = T.tile_x;
     const EqView& V = L.view[k0];          // the ring's geometry (every member has the same, up to x0i32 and the pitch sign)
-    r -= V.tile_base;
-    const int tile_y = r / V.tiles_x, tile_x = r - tile_y * V.tiles_x;
 
     // the wavefront index as a scalar: everything derived from it (row slots, patch origins) then lives in SGPRs
     // (the lane index behind an optimisation barrier in the persistent variants: nothing derived from it is hoisted out of the walk)
@@ -679,7 +692,7 @@ __device__ __forceinline__ void eq_views_tile(const EqLaunch& L, const int b, co
             const float rl = eq_atan2_red(xx, 1.0f, Kl);
             const float h = eq_sqrt(__builtin_fmaf(xx, xx, 1.0f));
             const float rt = eq_atan2_red<true>(cy, h, Kt);
-            const int q = Kt * 8 * L.H + (int)__builtin_rintf(rt * L.ky32);
+            const int q = eq_quant_lat(rt, Kt, L);
             sys[s] = L.y0i32 - q;
             sys[s + 2] = L.y0i32 + q;
             sxl[s] = sxl[s + 2] = eq_lon_base(rl, Kl, L, V.x0f32);
@@ -696,7 +709,7 @@ __device__ __forceinline__ void eq_views_tile(const EqLaunch& L, const int b, co
             const float cy = __builtin_fmaf(-V.cp, yv, V.sp);
             int Kt;
             const float rt = eq_atan2_red<true>(cy, h, Kt);
-            const int q = Kt * 8 * L.H + (int)__builtin_rintf(rt * L.ky32);
+            const int q = eq_quant_lat(rt, Kt, L);
             sys[s] = L.y0i32 - q;
             sys[s + kHalfRows] = L.y0i32 + q;
             sxl[s] = sxl[s + kHalfRows] = sx_left;
@@ -946,7 +959,7 @@ __device__ __forceinline__ void eq_views_tile(const EqLaunch& L, const int b, co
                 }
                 return;
             }
-            if (kShiftedStore && !(mirror && centre_dup) && ofs32_ok) {
+            if (!(mirror && centre_dup) && ofs32_ok) {
                 // Row segments that start off a dword boundary (widths that are not multiples of four: 5250-byte rows of a 1750-pixel
                 // view): the same two shuffles per slot, with the byte stream of the segment re-sliced at the row's own misalignment.
                 // Lanes 0..47 write the aligned dwords inside the segment, lanes 48..50 its 0-3 head bytes, lanes 52..54 its 0-3 tail
@@ -1157,21 +1170,11 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(kEq
     static_assert(kSliceBytes % 1024 == 0, "a slice is whole DMA rounds");
     __shared__ __attribute__((aligned(16))) uint32_t s_stage[kWaves * kSliceBytes / 4];
     __shared__ __attribute__((aligned(16))) int4 s_park[(MASKED ? 5 : 4) * 64 * kWaves];
-    const int b = blockIdx.x;
-    int t = (b & 7) * L.chunk + (b >> 3);
-    if (L.xcd_group_log2 >= 0) {
-        const int q = b >> 3, g = L.xcd_group_log2;
-        t = ((((q >> g) << 3) + (b & 7)) << g) + (q & ((1 << g) - 1));
-    }
+    const int t = eq_tile_order(L, blockIdx.x);
     if (t >= L.total_tiles) return;
-    const int f = t / L.tiles_per_frame;
-    int r = t - f * L.tiles_per_frame;
-    int g = 0;
-    while (g + 1 < L.n_rings && r >= L.view[L.ring_first[g + 1]].tile_base) ++g;
-    const int k0 = L.ring_first[g], n_members = L.ring_count[g];
+    const EqTile T = eq_tile_at(L, t);
+    const int f = T.f, k0 = T.k0, n_members = T.n_members, tile_y = T.tile_y, tile_x = T.tile_x;
     const EqView& V = L.view[k0];
-    r -= V.tile_base;
-    const int tile_y = r / V.tiles_x, tile_x = r - tile_y * V.tiles_x;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half_w = (V.out_w + 1) >> 1;
     const int x0 = tile_x * kTileW + 16 * wave;           // this wavefront's first column (left half of the view)
@@ -1225,7 +1228,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(kEq
     const int ny_max = ((symax - symin) >> 5) + 3;
     // (pitch <= stride: a box row that starts inside row y ends inside row y + 1 at the latest, and the last row a box may hold is
     // H - 2 -- the copy never leaves the frame)
-    const bool tile_fits = ny_max * pitch <= kSliceBytes && (stride & 3u) == 0 && (uint32_t)pitch <= stride && kStageEnable;
+    const bool tile_fits = ny_max * pitch <= kSliceBytes && (stride & 3u) == 0 && (uint32_t)pitch <= stride;
     const int nchp = pitch >> 4;                          // 16-byte chunks per box row
     // DMA lane map, fixed for the tile: round k moves chunks 64 k + lane; chunk c = (row c / nchp, piece c % nchp)
     uint32_t voff[kSliceRounds];
@@ -1593,7 +1596,7 @@ hipError_t launch_equirect(const EqLaunch& L0, int C, int esize, bool cubic, boo
         else hipLaunchKernelGGL((eq_staged_kernel<false>), grid, dim3(64 * kWaves), 0, s, L);
         return hipGetLastError();
     }
-    bool rows_only = kEqRowsKernel != 0;
+    bool rows_only = true;
     for (int k = 0; k < L.n_views; ++k) rows_only = rows_only && !L.view[k].blocked;
     switch (C) {
         case 1: eq_launch_gather<1>(L, esize, cubic, masked, grid, s); break;

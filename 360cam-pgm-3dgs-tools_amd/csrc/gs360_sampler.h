@@ -62,7 +62,6 @@ __device__ __forceinline__ uint2 ld_u64_via_aligned96(const uint8_t* p) {
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #define GS360_AB(o) (o)   // v_alignbyte_b32 shifts by S2[1:0] bytes: a byte offset's upper bits need not be masked off
-constexpr bool kShiftedStore = true;   // dword stores for row segments that start off a dword boundary (false: byte stores, the A/B reference)
 
 // The 8 tap bytes (two RGB pixels + 2) of rows y0 and y1 of one pixel, at byte offsets o0 / o1 from `src`.
 // Row-paired gathers: issued naively, one instruction reads row y0 of all 64 pixels and the next one row y1; where the
@@ -133,7 +132,7 @@ __device__ __forceinline__ void store_row(uint8_t* row, const uint32_t (&px)[4],
                 for (int k = 0; k < rem; ++k) row[4 * full + k] = (uint8_t)(dw >> (8 * k));
             return;
         }
-        if (SHIFTED && kShiftedStore && !skip_first) {
+        if (SHIFTED && !skip_first) {
             // a segment that starts off a dword boundary (widths that are not multiples of four): the same two shuffles, the segment's
             // byte stream re-sliced at its own misalignment -- lanes 0..47 write the aligned dwords inside it, lanes 48..50 its 0-3 head
             // bytes, lanes 52..54 its 0-3 tail bytes (one dword store + one byte store instead of three byte stores per pixel)
