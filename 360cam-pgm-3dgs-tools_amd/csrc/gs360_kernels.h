@@ -321,4 +321,41 @@ struct FfLaunch {
 hipError_t launch_frame_fft(FfLaunch& L, hipStream_t s);
 int frame_fft_partials(int h, int w);       // n_part: column-pass workgroups per frame
 
+// Frame optical flow (gs360_frameflow.hip, FS-FLOW v1 in DESIGN.md).  A frame's state (level planes padded by 15, their Scharr
+// derivatives, its corners) lives in one of kFlSlots resident slots of the context's scratch; a batch of <= GS360_MAX_FRAMES
+// frames computes it through per-batch-entry work areas (mask, Sobel pairs, eigenvalues, candidate keys, counters).
+constexpr int kFlSlots = 2 * GS360_MAX_FRAMES;
+constexpr int kFlMaxPairs = 64;          // pairs per pair launch
+struct FlCounters {
+    int n_mask, n_cand;
+    unsigned max_key;                    // order-preserving bits of the masked maximum eigenvalue
+    int pad;
+};
+struct FlLaunch {
+    const uint8_t* src[GS360_MAX_FRAMES];
+    int32_t slot[GS360_MAX_FRAMES];      // resident slot of batch entry b
+    int32_t n_frames;
+    int64_t stride;
+    int32_t H, W, C, red, circle;
+    int32_t cx0, cy0, cw, ch, sw, sh;    // crop and small (level-0) size
+    int32_t mode, kx, ky;                // 0 no resize, 1 INTER_AREA integer factors kx x ky, 2 general INTER_AREA
+    double scale_x, scale_y;             // cv2.resize's 1 / (sw / cw), 1 / (sh / ch)
+    int32_t levels;                      // pyramid levels (maxLevel + 1)
+    int32_t lw[3], lh[3], pitch[3];      // level sizes; pitch = lw + 30 (padded rows: lh + 30)
+    uint8_t* state;                      // kFlSlots x state_bytes
+    size_t state_bytes, img_off[3], der_off[3], corner_off, ncorner_off;
+    uint8_t* work;                       // GS360_MAX_FRAMES x work_bytes
+    size_t work_bytes, mask_off, sob_off, eig_off, cnt_off, key_off;
+    int32_t key_cap;                     // keys per work area: a power of two >= 2048 and >= the candidate count
+};
+struct FlPairs {
+    int32_t prev[kFlMaxPairs], curr[kFlMaxPairs], out_index[kFlMaxPairs];   // resident slots; index into out / user_points
+    int32_t n_pairs;
+    gs360_flow_point* points;            // kFlMaxPairs x GS360_FLOW_MAX_CORNERS scratch
+    gs360_flow_point* user_points;       // optional caller copy, indexed by out_index
+    gs360_frame_flow* out;
+};
+hipError_t launch_frame_flow_frames(const FlLaunch& L, hipStream_t s);
+hipError_t launch_frame_flow_pairs(const FlLaunch& L, const FlPairs& Q, hipStream_t s);
+
 }  // namespace gs360

@@ -32,11 +32,13 @@ EXPORTS = (
     "gs360_equirect_views_u16", "gs360_remap_table_u16", "gs360_remap_tables_u16", "gs360_equirect_views_u16_host", "gs360_remap_table_u16_host",
     "gs360_png_unfilter", "gs360_event_sync", "gs360_stream_wait_event",
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
-    "gs360_frame_stats_u8", "gs360_frame_fft_energy",
+    "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8",
 )
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
+FLOW_MAX_SIDE = 320   # GS360_FLOW_MAX_SIDE: gs360_frame_flow_u8's largest small image side (FLOW_DOWNSCALE)
+FLOW_MAX_CORNERS = 1000   # GS360_FLOW_MAX_CORNERS: goodFeaturesToTrack's maxCorners
 
 
 class Gs360Error(RuntimeError):
@@ -83,6 +85,16 @@ class FrameStats(C.Structure):
 class FrameFft(C.Structure):
     """gs360_frame_fft: sum of |fftshift(fft2(g))| over the donut, over the donut's valid positions, the valid count and h*w."""
     _fields_ = [("sum_hf", C.c_double), ("sum_hf_valid", C.c_double), ("n_valid", C.c_int64), ("n", C.c_int64)]
+
+
+class FrameFlow(C.Structure):
+    """gs360_frame_flow: the prev frame's corner count, the tracked (status 1) count and the double sum of their |p1 - p0|."""
+    _fields_ = [("n_corners", C.c_int64), ("n_tracked", C.c_int64), ("sum_mag", C.c_double)]
+
+
+class FlowPoint(C.Structure):
+    """gs360_flow_point: one corner, its tracked end point (level-0 pixels) and its status."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
 ABI_VERSION = 2          # GS360_ABI_VERSION of include/gs360.h this binding was written against
@@ -163,6 +175,7 @@ def load_library(path=None):
         L.gs360_stream_wait_event.argtypes = [vp, i, i, i]
         L.gs360_frame_stats_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, u32, vp, pvp, i, i, i]
         L.gs360_frame_fft_energy.argtypes = [vp, pvp, i, i, i, i, i, i, i, u32, vp, i]
+        L.gs360_frame_flow_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, i, i, i, i, u32, C.POINTER(C.c_int), i, vp, vp, i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -520,6 +533,18 @@ class Context:
         sp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in smalls])
         _check(self.L.gs360_frame_fft_energy(self.handle, sp, nf, int(small_w), int(small_h), int(H), int(W), int(band[0]),
                                              int(band[1]), int(flags), out.ptr, slot), self.L)
+
+    def frame_flow_dev(self, frames, H, W, Cn, crop, small_w, small_h, pairs, out, flags=0, points=None, red_index=0, stride=0, slot=0):
+        """gs360_frame_flow_u8 on device frames (list of DeviceBuffer, H x W x C uint8): crop = (x0, y0, w, h), pairs = sequence of
+        (prev, curr) indices into frames; out = DeviceBuffer of len(pairs) FrameFlow records; points = None or a DeviceBuffer of
+        len(pairs) x FLOW_MAX_CORNERS FlowPoint records.  Asynchronous on `slot`."""
+        nf = len(frames)
+        fp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in frames])
+        flat = [int(v) for pr in pairs for v in pr]
+        pa = (C.c_int * max(len(flat), 1))(*flat)
+        _check(self.L.gs360_frame_flow_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(crop[0]),
+                                          int(crop[1]), int(crop[2]), int(crop[3]), int(small_w), int(small_h), int(flags), pa,
+                                          len(pairs), out.ptr, points.ptr if points is not None else None, slot), self.L)
 
     # -- hot path, host buffers (synchronous) -----------------------------------------------
     def equirect_views(self, src, views, slot=0, interp=INTERP_LINEAR, flags=0):

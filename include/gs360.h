@@ -383,6 +383,36 @@ typedef struct gs360_frame_fft {
 int gs360_frame_fft_energy(gs360_ctx *ctx, const float *const *small_dev, int n_frames, int small_w, int small_h, int H, int W,
                            int band_y0, int band_y1, uint32_t flags, gs360_frame_fft *out_dev, int slot);
 
+/* ---- frame optical flow (the FrameSelector's motion pass) -------------------------------------
+ * The Lucas-Kanade motion value of _compute_pair_flow_magnitude in cli_tools/gs360_FrameSelector.py (FS:1245-1337, FLOW_METHOD
+ * "lucas_kanade"; it replaces _load_flow_gray, cv2.goodFeaturesToTrack and cv2.calcOpticalFlowPyrLK), restated as FS-FLOW v1
+ * (DESIGN.md section 10).  frames[f], f < n_frames: H x W x C uint8 (C in {1,3,4}, row stride `stride` bytes, 0 = tight), gray
+ * as gs360_frame_stats_u8 (red at byte red_index, 0 or 2).  Each frame that a pair names is, once per call:
+ *   cropped   to [crop_x0, crop_x0 + crop_w) x [crop_y0, crop_y0 + crop_h) (the host's copy of FS:1254-1262)
+ *   resized   to small_w x small_h <= GS360_FLOW_MAX_SIDE with cv2.resize INTER_AREA on 8U (equal sizes: no resize)
+ *   masked    with GS360_FS_CIRCLE: the full-frame circle of gs360_frame_stats_u8 at INTER_NEAREST's sample; used when not empty
+ *   cornered  goodFeaturesToTrack(maxCorners 1000, quality 0.01, minDistance 5, blockSize 7, that mask)
+ * and pairs[2k], pairs[2k+1] (frame indices, prev then curr) are tracked with calcOpticalFlowPyrLK(winSize 15, maxLevel 2,
+ * (EPS|COUNT, 10, 0.03)).  out_dev[k] (device memory) receives the prev frame's corner count, the count of points with status 1
+ * and the double sum, in point order, of their float32 |p1 - p0|: the reference's value is sum_mag / n_tracked, None when either
+ * count is 0.  points_dev (NULL = not wanted): n_pairs x GS360_FLOW_MAX_CORNERS records, of which the first n_corners of pair k
+ * are written.  Every sum runs in a fixed order: records are bit-identical from call to call and do not depend on the other
+ * frames or pairs of the call.  n_frames and n_pairs are not limited (frames are computed GS360_MAX_FRAMES per launch and stay
+ * resident while later pairs need them).  H, W <= 65535.  Asynchronous on `slot`. */
+#define GS360_FLOW_MAX_SIDE 320
+#define GS360_FLOW_MAX_CORNERS 1000
+typedef struct gs360_frame_flow {
+    int64_t n_corners, n_tracked;
+    double sum_mag;
+} gs360_frame_flow;
+typedef struct gs360_flow_point {
+    float x0, y0, x1, y1;   /* corner and tracked end point, level-0 pixels */
+    int32_t status, pad;
+} gs360_flow_point;
+int gs360_frame_flow_u8(gs360_ctx *ctx, const void *const *frames, int n_frames, int H, int W, int C, size_t stride,
+                        int red_index, int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags,
+                        const int *pairs, int n_pairs, gs360_frame_flow *out_dev, gs360_flow_point *points_dev, int slot);
+
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
                                  const gs360_view *views, int n_views,
