@@ -4,6 +4,48 @@
 
 using namespace gs360;
 
+namespace {
+
+int check_frame_size(int H, int W) {
+    if (H <= 0 || W <= 0) return fail(GS360_ERR_ARG, "bad size %d x %d", W, H);
+    if (H > 65535 || W > 65535) return fail(GS360_ERR_UNSUPPORTED, "frame %d x %d above 65535 on a side", W, H);
+    return 0;
+}
+
+// An 8-bit source frame: channels, channel order and size, then the row stride (0 = packed rows, filled in here)
+int check_frame_layout(int H, int W, int C, int red_index, size_t* stride) {
+    if (int rc = check_channels(C)) return rc;
+    if (red_index != 0 && red_index != 2) return fail(GS360_ERR_ARG, "red_index must be 0 (RGB) or 2 (BGR)");
+    if (int rc = check_frame_size(H, W)) return rc;
+    if (*stride == 0) *stride = (size_t)W * C;
+    if (*stride < (size_t)W * C) return fail(GS360_ERR_ARG, "stride smaller than a row");
+    return 0;
+}
+
+int check_band(int band_y0, int band_y1, int H) {
+    if (band_y0 < 0 || band_y1 > H || band_y0 >= band_y1) return fail(GS360_ERR_ARG, "band [%d,%d) outside [0,%d) or empty", band_y0, band_y1, H);
+    return 0;
+}
+
+// cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale (both INTER_AREA's tables and INTER_NEAREST's index)
+double cv_resize_scale(int dsize, int ssize) { return 1.0 / ((double)dsize / ssize); }
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// FS-FLOW's resize path: 0 none, 1 INTER_AREA integer factors (cv::resize's is_area_fast), 2 the general area tables
+int flow_resize_mode(int cw, int ch, int sw, int sh, int* kx, int* ky) {
+    if (sw == cw && sh == ch) return 0;
+    const double sx = cv_resize_scale(sw, cw), sy = cv_resize_scale(sh, ch);
+    const int ix = (int)std::nearbyint(sx), iy = (int)std::nearbyint(sy);
+    if (std::fabs(sx - ix) < 2.220446049250313e-16 && std::fabs(sy - iy) < 2.220446049250313e-16 && sw * ix == cw && sh * iy == ch) {
+        *kx = ix; *ky = iy;
+        return 1;
+    }
+    return 2;
+}
+
+}  // namespace
+
 int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
                          int band_y0, int band_y1, uint32_t flags, gs360_frame_stats* stats_dev, float* const* small_dev, int small_w,
                          int small_h, int slot) {
@@ -11,13 +53,8 @@ int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, 
     if (n_frames < 0) return fail(GS360_ERR_ARG, "n_frames < 0");
     if (n_frames == 0) return GS360_OK;
     if (!frames || !stats_dev) return fail(GS360_ERR_ARG, "NULL argument");
-    if (int rc = check_channels(C)) return rc;
-    if (red_index != 0 && red_index != 2) return fail(GS360_ERR_ARG, "red_index must be 0 (RGB) or 2 (BGR)");
-    if (H <= 0 || W <= 0) return fail(GS360_ERR_ARG, "bad size %d x %d", W, H);
-    if (H > 65535 || W > 65535) return fail(GS360_ERR_UNSUPPORTED, "frame %d x %d above 65535 on a side", W, H);
-    if (stride == 0) stride = (size_t)W * C;
-    if (stride < (size_t)W * C) return fail(GS360_ERR_ARG, "stride smaller than a row");
-    if (band_y0 < 0 || band_y1 > H || band_y0 >= band_y1) return fail(GS360_ERR_ARG, "band [%d,%d) outside [0,%d) or empty", band_y0, band_y1, H);
+    if (int rc = check_frame_layout(H, W, C, red_index, &stride)) return rc;
+    if (int rc = check_band(band_y0, band_y1, H)) return rc;
     if (flags & ~(GS360_FS_CIRCLE | GS360_FS_HIGHLIGHTS)) return fail(GS360_ERR_ARG, "unknown flags 0x%x", flags);
     for (int f = 0; f < n_frames; ++f) {
         if (!frames[f]) return fail(GS360_ERR_ARG, "frames[%d] is NULL", f);
@@ -36,10 +73,10 @@ int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, 
     L.y0 = band_y0; L.y1 = band_y1;
     L.circle = (flags & GS360_FS_CIRCLE) ? 1 : 0;
     L.highlights = (flags & GS360_FS_HIGHLIGHTS) ? 1 : 0;
-    if (small_dev) {   // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale (both INTER_AREA's tables and INTER_NEAREST's index)
+    if (small_dev) {
         L.small_w = small_w; L.small_h = small_h;
-        L.scale_x = 1.0 / ((double)small_w / W);
-        L.scale_y = 1.0 / ((double)small_h / (band_y1 - band_y0));
+        L.scale_x = cv_resize_scale(small_w, W);
+        L.scale_y = cv_resize_scale(small_h, band_y1 - band_y0);
     }
     for (int f0 = 0; f0 < n_frames; f0 += GS360_MAX_FRAMES) {
         L.n_frames = std::min(GS360_MAX_FRAMES, n_frames - f0);
@@ -59,9 +96,8 @@ int gs360_frame_fft_energy(gs360_ctx* c, const float* const* small_dev, int n_fr
     if (n_frames < 0) return fail(GS360_ERR_ARG, "n_frames < 0");
     if (n_frames == 0) return GS360_OK;
     if (!small_dev || !out_dev) return fail(GS360_ERR_ARG, "NULL argument");
-    if (H <= 0 || W <= 0) return fail(GS360_ERR_ARG, "bad size %d x %d", W, H);
-    if (H > 65535 || W > 65535) return fail(GS360_ERR_UNSUPPORTED, "frame %d x %d above 65535 on a side", W, H);
-    if (band_y0 < 0 || band_y1 > H || band_y0 >= band_y1) return fail(GS360_ERR_ARG, "band [%d,%d) outside [0,%d) or empty", band_y0, band_y1, H);
+    if (int rc = check_frame_size(H, W)) return rc;
+    if (int rc = check_band(band_y0, band_y1, H)) return rc;
     if (flags & ~(GS360_FS_CIRCLE | GS360_FS_HIGHLIGHTS)) return fail(GS360_ERR_ARG, "unknown flags 0x%x", flags);
     const int bh = band_y1 - band_y0;
     if (small_w < 1 || small_w > std::min(W, GS360_FFT_MAX_SIDE) || small_h < 1 || small_h > std::min(bh, GS360_FFT_MAX_SIDE))
@@ -78,8 +114,8 @@ int gs360_frame_fft_energy(gs360_ctx* c, const float* const* small_dev, int n_fr
     L.H = H; L.W = W; L.y0 = band_y0; L.y1 = band_y1;
     L.circle = (flags & GS360_FS_CIRCLE) ? 1 : 0;
     L.highlights = (flags & GS360_FS_HIGHLIGHTS) ? 1 : 0;
-    L.scale_x = 1.0 / ((double)small_w / W);      // cv::resize INTER_NEAREST, as gs360_frame_stats_u8's nearest plane
-    L.scale_y = 1.0 / ((double)small_h / bh);
+    L.scale_x = cv_resize_scale(small_w, W);      // INTER_NEAREST, as gs360_frame_stats_u8's nearest plane
+    L.scale_y = cv_resize_scale(small_h, bh);
     // per-slot workspace for one launch: the partials, then each frame's row-pass spectrum (2 x h x K float32)
     const size_t part_bytes = (size_t)GS360_MAX_FRAMES * L.n_part * sizeof(FfPartial);
     const size_t x_bytes = (size_t)2 * L.h * L.K * sizeof(float);
@@ -96,24 +132,6 @@ int gs360_frame_fft_energy(gs360_ctx* c, const float* const* small_dev, int n_fr
     return GS360_OK;
 }
 
-namespace {
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// FS-FLOW's resize path: 0 none, 1 INTER_AREA integer factors (cv::resize's is_area_fast), 2 the general area tables
-int flow_resize_mode(int cw, int ch, int sw, int sh, int* kx, int* ky) {
-    if (sw == cw && sh == ch) return 0;
-    const double sx = 1.0 / ((double)sw / cw), sy = 1.0 / ((double)sh / ch);
-    const int ix = (int)std::nearbyint(sx), iy = (int)std::nearbyint(sy);
-    if (std::fabs(sx - ix) < 2.220446049250313e-16 && std::fabs(sy - iy) < 2.220446049250313e-16 && sw * ix == cw && sh * iy == ch) {
-        *kx = ix; *ky = iy;
-        return 1;
-    }
-    return 2;
-}
-
-}  // namespace
-
 int gs360_frame_flow_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
                         int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags, const int* pairs,
                         int n_pairs, gs360_frame_flow* out_dev, gs360_flow_point* points_dev, int slot) {
@@ -121,12 +139,7 @@ int gs360_frame_flow_u8(gs360_ctx* c, const void* const* frames, int n_frames, i
     if (n_pairs < 0 || n_frames < 0) return fail(GS360_ERR_ARG, "n_frames or n_pairs < 0");
     if (n_pairs == 0) return GS360_OK;
     if (!frames || !pairs || !out_dev) return fail(GS360_ERR_ARG, "NULL argument");
-    if (int rc = check_channels(C)) return rc;
-    if (red_index != 0 && red_index != 2) return fail(GS360_ERR_ARG, "red_index must be 0 (RGB) or 2 (BGR)");
-    if (H <= 0 || W <= 0) return fail(GS360_ERR_ARG, "bad size %d x %d", W, H);
-    if (H > 65535 || W > 65535) return fail(GS360_ERR_UNSUPPORTED, "frame %d x %d above 65535 on a side", W, H);
-    if (stride == 0) stride = (size_t)W * C;
-    if (stride < (size_t)W * C) return fail(GS360_ERR_ARG, "stride smaller than a row");
+    if (int rc = check_frame_layout(H, W, C, red_index, &stride)) return rc;
     if (crop_w < 1 || crop_h < 1 || crop_x0 < 0 || crop_y0 < 0 || crop_x0 + crop_w > W || crop_y0 + crop_h > H)
         return fail(GS360_ERR_ARG, "crop %d x %d at (%d, %d) outside the %d x %d frame", crop_w, crop_h, crop_x0, crop_y0, W, H);
     if (small_w < 1 || small_h < 1 || small_w > std::min(crop_w, GS360_FLOW_MAX_SIDE) || small_h > std::min(crop_h, GS360_FLOW_MAX_SIDE))
@@ -147,8 +160,8 @@ int gs360_frame_flow_u8(gs360_ctx* c, const void* const* frames, int n_frames, i
     L.circle = (flags & GS360_FS_CIRCLE) ? 1 : 0;
     L.cx0 = crop_x0; L.cy0 = crop_y0; L.cw = crop_w; L.ch = crop_h; L.sw = small_w; L.sh = small_h;
     L.mode = flow_resize_mode(crop_w, crop_h, small_w, small_h, &L.kx, &L.ky);
-    L.scale_x = 1.0 / ((double)small_w / crop_w);   // cv::resize: INTER_AREA's tables and INTER_NEAREST's index
-    L.scale_y = 1.0 / ((double)small_h / crop_h);
+    L.scale_x = cv_resize_scale(small_w, crop_w);
+    L.scale_y = cv_resize_scale(small_h, crop_h);
     // buildOpticalFlowPyramid(winSize 15, maxLevel 2): the next level's ((w+1)/2, (h+1)/2) must exceed 15 on both sides
     int w = small_w, h = small_h;
     L.levels = 0;

@@ -18,7 +18,7 @@
 // Both passes are LDS-tiled float32 GEMMs on the vector ALUs: 64 x 64 outputs per 256-thread workgroup, 4 x 4 per thread, the inner
 // dimension in chunks of kFfKc.  Twiddle tiles are built in LDS from a per-workgroup table of cos / sin(2 pi m/N) (double sincospi,
 // rounded to float), indexed by (j*k) mod N, which each thread advances by (kFfKc*k) mod N per chunk.
-#include "gs360_kernels.h"
+#include "gs360_framepx.h"
 
 namespace gs360 {
 
@@ -35,13 +35,6 @@ __device__ __forceinline__ void build_table(float2* tab, int N) {
         sincospi(2.0 * m / N, &s, &c);
         tab[m] = make_float2((float)c, (float)s);
     }
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // Row pass: X = (g - row mean) . [C_w | -S_w], column 0 = the row sums.  Grid (k tiles, row tiles, frames).
@@ -200,8 +193,7 @@ __global__ void __launch_bounds__(kFfThreads) ff_cols_kernel(const FfLaunch L) {
     // epilogue: credit every computed bin, and its mirror, at its fftshift position (i, j)
     const int hc = h / 2, wc = w / 2;
     const int rd = max(1, min(h, w) / 8);
-    const int64_t mwh = min(L.W, L.H);
-    const int64_t r4 = max((int64_t)4, mwh * mwh);
+    const int64_t r4 = circle_r4(L.W, L.H);
     const int bh = L.y1 - L.y0;
     const float* const near = L.small[f] + (int64_t)h * w;
     double s_hf = 0.0, s_hfv = 0.0;
@@ -212,8 +204,8 @@ __global__ void __launch_bounds__(kFfThreads) ff_cols_kernel(const FfLaunch L) {
         const bool donut = (i - hc) * (i - hc) + (j - wc) * (j - wc) >= rd * rd;
         bool valid = true;
         if (L.circle) {   // the full-frame circle at INTER_NEAREST's sample (xs[j], ys[i])
-            const int64_t x = min((int)floor(j * L.scale_x), L.W - 1);
-            const int64_t y = L.y0 + min((int)floor(i * L.scale_y), bh - 1);
+            const int64_t x = nearest_index(j, L.scale_x, L.W);
+            const int64_t y = L.y0 + nearest_index(i, L.scale_y, bh);
             const int64_t dx = 2 * x - (L.W - 1), dy = 2 * y - (L.H - 1);
             valid = dx * dx + dy * dy <= r4;
         }

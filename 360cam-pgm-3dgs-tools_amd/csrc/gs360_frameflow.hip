@@ -17,7 +17,7 @@
 // Per pair (fl_lk, fl_pair): one wavefront per corner runs the pyramid LK; one wavefront per pair sums the magnitudes in point
 // order.  Frame state lives in the context's per-slot scratch (resident slots, so a frame in two pairs is computed once); the
 // only atomics are integer counts and an integer maximum.
-#include "gs360_kernels.h"
+#include "gs360_framepx.h"
 
 namespace gs360 {
 
@@ -34,49 +34,9 @@ __device__ __forceinline__ int bint(int p, int n) {   // cv::borderInterpolate, 
     return p;
 }
 
-template <int C>
-__device__ __forceinline__ int gray_at(const uint8_t* p, int red) {
-    if constexpr (C == 1) {
-        return p[0];
-    } else {
-        return (p[red] * 4899 + p[1] * 9617 + p[2 - red] * 1868 + 8192) >> 14;   // FS-SPEC gray
-    }
-}
-
 __device__ __forceinline__ uint8_t sat_u8(float v) {   // saturate_cast<uchar>(float): round half to even, clamp
     const int i = (int)__builtin_rintf(v);
     return (uint8_t)min(max(i, 0), 255);
-}
-
-struct Span {
-    int i1, i2;
-    bool has_head, has_tail;
-    float head, mid, tail;
-};
-__device__ __forceinline__ Span area_tab(int d, int ssize, double scale) {   // cv::computeResizeAreaTab for one destination index
-    const double f1 = d * scale, f2 = f1 + scale;
-    const double cell = fmin(scale, ssize - f1);
-    int s2 = (int)floor(f2), s1 = (int)ceil(f1);
-    s2 = min(s2, ssize - 1);
-    s1 = min(s1, s2);
-    Span a;
-    a.i1 = s1;
-    a.i2 = s2;
-    a.has_head = s1 - f1 > 1e-3;
-    a.head = (float)((s1 - f1) / cell);
-    a.mid = (float)(1.0 / cell);
-    a.has_tail = f2 - s2 > 1e-3;
-    a.tail = (float)(fmin(fmin(f2 - s2, 1.0), cell) / cell);
-    return a;
-}
-
-template <int C>
-__device__ __forceinline__ float area_row(const uint8_t* row, const Span& ax, int red) {
-    float buf = 0.0f;
-    if (ax.has_head) buf += (float)gray_at<C>(row + (ax.i1 - 1) * C, red) * ax.head;
-    for (int sx = ax.i1; sx < ax.i2; ++sx) buf += (float)gray_at<C>(row + sx * C, red) * ax.mid;
-    if (ax.has_tail) buf += (float)gray_at<C>(row + ax.i2 * C, red) * ax.tail;
-    return buf;
 }
 
 __device__ __forceinline__ uint8_t* plane(const FlLaunch& L, int slot, int lev) { return L.state + (size_t)slot * L.state_bytes + L.img_off[lev]; }
@@ -101,16 +61,16 @@ __global__ void __launch_bounds__(kT) fl_small(const FlLaunch L) {
         const uint8_t* crop = L.src[b] + (int64_t)L.cy0 * L.stride + (int64_t)L.cx0 * C;
         int v;
         if (L.mode == 0) {                 // no resize: the crop itself
-            v = gray_at<C>(crop + (int64_t)dy * L.stride + dx * C, L.red);
+            v = gray_of<C>(crop + (int64_t)dy * L.stride + dx * C, L.red);
         } else if (L.mode == 1) {          // integer factors kx x ky: int block sum * float32(1 / area)
             int s = 0;
             for (int yy = 0; yy < L.ky; ++yy) {
                 const uint8_t* r = crop + (int64_t)(dy * L.ky + yy) * L.stride + (int64_t)dx * L.kx * C;
-                for (int xx = 0; xx < L.kx; ++xx) s += gray_at<C>(r + xx * C, L.red);
+                for (int xx = 0; xx < L.kx; ++xx) s += gray_of<C>(r + xx * C, L.red);
             }
             v = sat_u8((float)s * (1.0f / (float)(L.kx * L.ky)));
         } else {                           // general float32 tables, ResizeArea_Invoker's order
-            const Span ax = area_tab(dx, L.cw, L.scale_x), ay = area_tab(dy, L.ch, L.scale_y);
+            const AreaSpan ax = area_span(dx, L.cw, L.scale_x), ay = area_span(dy, L.ch, L.scale_y);
             float sum = 0.0f;
             if (ay.has_head) sum += ay.head * area_row<C>(crop + (int64_t)(ay.i1 - 1) * L.stride, ax, L.red);
             for (int sy = ay.i1; sy < ay.i2; ++sy) sum += ay.mid * area_row<C>(crop + (int64_t)sy * L.stride, ax, L.red);
@@ -119,10 +79,10 @@ __global__ void __launch_bounds__(kT) fl_small(const FlLaunch L) {
         }
         plane(L, L.slot[b], 0)[(int64_t)(dy + kPad) * L.pitch[0] + dx + kPad] = (uint8_t)v;
         if (L.circle) {   // INTER_NEAREST of the full-frame circle, cropped
-            const int nx = L.cx0 + min((int)floor(dx * L.scale_x), L.cw - 1);
-            const int ny = L.cy0 + min((int)floor(dy * L.scale_y), L.ch - 1);
+            const int nx = L.cx0 + nearest_index(dx, L.scale_x, L.cw);
+            const int ny = L.cy0 + nearest_index(dy, L.scale_y, L.ch);
             const int64_t ex = 2 * (int64_t)nx - (L.W - 1), ey = 2 * (int64_t)ny - (L.H - 1);
-            const int64_t mwh = min(L.W, L.H);
+            const int64_t mwh = min(L.W, L.H);       // circle_r4 written out: the helper changes this kernel's schedule
             inmask = ex * ex + ey * ey <= max((int64_t)4, mwh * mwh);
         }
         work(L, b)[L.mask_off + (int64_t)dy * L.sw + dx] = (uint8_t)inmask;
@@ -343,13 +303,6 @@ __global__ void __launch_bounds__(64) fl_select(const FlLaunch L) {
 }
 
 // 8. pyramid Lucas-Kanade: one wavefront per corner; the 15 x 15 window as lane + 64 k, k < 4 (225 pixels)
-template <typename T>
-__device__ __forceinline__ T wsum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ int descale(int v, int n) { return (v + (1 << (n - 1))) >> n; }
 
 struct Wts { int w00, w01, w10, w11; };
@@ -407,7 +360,7 @@ __global__ void __launch_bounds__(kT) fl_lk(const FlLaunch L, const FlPairs Q) {
                 a22 += (long long)iyv[k] * iyv[k];
             }
         }
-        const float A11 = (float)(double)wsum(a11) * FS, A12 = (float)(double)wsum(a12) * FS, A22 = (float)(double)wsum(a22) * FS;
+        const float A11 = (float)(double)wave_sum(a11) * FS, A12 = (float)(double)wave_sum(a12) * FS, A22 = (float)(double)wave_sum(a22) * FS;
         float Dt = A11 * A22 - A12 * A12;
         const float minEig = ((A22 + A11) - sqrtf((A11 - A22) * (A11 - A22) + (4.f * A12) * A12)) / (float)(2 * kWin * kWin);
         if (minEig < 1e-4f || Dt < 1.1920929e-07f) {
@@ -436,7 +389,7 @@ __global__ void __launch_bounds__(kT) fl_lk(const FlLaunch L, const FlPairs Q) {
                     b2 += (long long)diff * iyv[k];
                 }
             }
-            const float B1 = (float)(double)wsum(b1) * FS, B2 = (float)(double)wsum(b2) * FS;
+            const float B1 = (float)(double)wave_sum(b1) * FS, B2 = (float)(double)wave_sum(b2) * FS;
             const float dx = (A12 * B2 - A22 * B1) * Dt, dy = (A12 * B1 - A11 * B2) * Dt;
             cx += dx; cy += dy;
             nx = cx + hw; ny = cy + hw;

@@ -16,7 +16,7 @@
 // computeResizeAreaTab does, float32 accumulation in ResizeArea_Invoker's order), and the gray at the INTER_NEAREST sample that the
 // host turns into the resized valid mask.  A second, small launch over the band: its 2-D cells read every band pixel once more
 // (the stats pass keeps to one streaming read of the frame), and it runs only for the fft / hybrid metrics.
-#include "gs360_kernels.h"
+#include "gs360_framepx.h"
 
 namespace gs360 {
 
@@ -43,23 +43,6 @@ __device__ __forceinline__ int reflect101(int i, int n) {   // one step outside 
 }
 
 template <int C>
-__device__ __forceinline__ int gray_of(const uint8_t* p, int red) {
-    if constexpr (C == 1) {
-        return p[0];
-    } else {
-        const int r = p[red], g = p[1], b = p[2 - red];
-        return (r * 4899 + g * 9617 + b * 1868 + 8192) >> 14;    // cv2 COLOR_BGR2GRAY on 8U (yuv_shift 14)
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <int C>
 __global__ void __launch_bounds__(kFsThreads) fs_stats_kernel(const FsLaunch L) {
     __shared__ FsLds S;
     const int b = blockIdx.x;
@@ -71,9 +54,7 @@ __global__ void __launch_bounds__(kFsThreads) fs_stats_kernel(const FsLaunch L) 
     const int ye = min(ys + kFsRows, H);
     const uint8_t* const src = L.src[f];
     const int tid = threadIdx.x;
-    // circle: (2x - (W-1))^2 + (2y - (H-1))^2 <= 4 r^2, r = max(1, min(W, H) / 2)
-    const int64_t mwh = min(W, H);
-    const int64_t r4 = max((int64_t)4, mwh * mwh);
+    const int64_t r4 = circle_r4(W, H);
 
     int cnt_c = 0, cnt_h = 0, cnt_hc = 0;
     int n_a = 0, g_a = 0, l_a = 0, n_v = 0, g_v = 0, l_v = 0;
@@ -180,39 +161,6 @@ __global__ void __launch_bounds__(kFsThreads) fs_stats_kernel(const FsLaunch L) 
     }
 }
 
-// One axis of cv::computeResizeAreaTab for output index d: source cells [i1, i2) of weight `mid`, plus a leading cell i1-1 of
-// weight `head` and a trailing cell i2 of weight `tail` when those flags are set.
-struct AreaSpan {
-    int i1, i2;
-    bool has_head, has_tail;
-    float head, mid, tail;
-};
-__device__ __forceinline__ AreaSpan area_span(int d, int ssize, double scale) {
-    const double f1 = d * scale, f2 = f1 + scale;
-    const double cell = fmin(scale, ssize - f1);
-    int s2 = (int)floor(f2), s1 = (int)ceil(f1);
-    s2 = min(s2, ssize - 1);
-    s1 = min(s1, s2);
-    AreaSpan a;
-    a.i1 = s1;
-    a.i2 = s2;
-    a.has_head = s1 - f1 > 1e-3;
-    a.head = (float)((s1 - f1) / cell);
-    a.mid = (float)(1.0 / cell);
-    a.has_tail = f2 - s2 > 1e-3;
-    a.tail = (float)(fmin(fmin(f2 - s2, 1.0), cell) / cell);
-    return a;
-}
-
-template <int C>
-__device__ __forceinline__ float area_row(const uint8_t* row, const AreaSpan& ax, int red) {
-    float buf = 0.0f;                                        // buf[dx] += S[sx] * alpha, xtab order
-    if (ax.has_head) buf += (float)gray_of<C>(row + (ax.i1 - 1) * C, red) * ax.head;
-    for (int sx = ax.i1; sx < ax.i2; ++sx) buf += (float)gray_of<C>(row + sx * C, red) * ax.mid;
-    if (ax.has_tail) buf += (float)gray_of<C>(row + ax.i2 * C, red) * ax.tail;
-    return buf;
-}
-
 template <int C>
 __global__ void __launch_bounds__(kFsThreads) fs_small_kernel(const FsLaunch L) {
     const int dx = blockIdx.x * kFsThreads + threadIdx.x;
@@ -227,9 +175,8 @@ __global__ void __launch_bounds__(kFsThreads) fs_small_kernel(const FsLaunch L) 
     if (ay.has_head) sum += ay.head * area_row<C>(band + (int64_t)(ay.i1 - 1) * L.stride, ax, L.red);
     for (int sy = ay.i1; sy < ay.i2; ++sy) sum += ay.mid * area_row<C>(band + (int64_t)sy * L.stride, ax, L.red);
     if (ay.has_tail) sum += ay.tail * area_row<C>(band + (int64_t)ay.i2 * L.stride, ax, L.red);
-    // INTER_NEAREST (resizeNN): floor(d * (1 / (dsize / ssize))), clamped to the last source index
-    const int nx = min((int)floor(dx * L.scale_x), L.W - 1);
-    const int ny = min((int)floor(dy * L.scale_y), bh - 1);
+    const int nx = nearest_index(dx, L.scale_x, L.W);
+    const int ny = nearest_index(dy, L.scale_y, bh);
     float* out = L.small[f];
     const int64_t plane = (int64_t)L.small_w * L.small_h;
     out[(int64_t)dy * L.small_w + dx] = sum;

@@ -97,6 +97,16 @@ class FlowPoint(C.Structure):
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+_NP_OF_C = {C.c_double: np.float64, C.c_int64: np.int64, C.c_int32: np.int32, C.c_float: np.float32}
+
+
+def record_dtype(struct):
+    """The NumPy dtype of a ctypes record of c_double / c_int64 / c_int32 / c_float fields, with the same field names and bytes."""
+    dt = np.dtype([(n, _NP_OF_C[t]) for n, t in struct._fields_])
+    assert dt.itemsize == C.sizeof(struct), struct.__name__
+    return dt
+
+
 ABI_VERSION = 2          # GS360_ABI_VERSION of include/gs360.h this binding was written against
 _lib = None
 _lib_lock = threading.Lock()

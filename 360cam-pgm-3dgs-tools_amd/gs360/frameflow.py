@@ -26,11 +26,12 @@ FLOW_DOWNSCALE = 320              # FS:317
 FLOW_MISSING_HIGH_VALUE = 9999.0  # FS:322
 FLOW_CROP_RATIO = 0.6             # FS:323 (the main flow forces 1.0 for pair inputs, FS:2158-2163)
 PROGRESS_INTERVAL = 5             # FS:332
-RECORD_DTYPE = np.dtype([(n, np.float64 if t is capi.C.c_double else np.int64) for n, t in capi.FrameFlow._fields_])
-POINT_DTYPE = np.dtype([(n, np.int32 if t is capi.C.c_int32 else np.float32) for n, t in capi.FlowPoint._fields_])
+RECORD_DTYPE = capi.record_dtype(capi.FrameFlow)
+POINT_DTYPE = capi.record_dtype(capi.FlowPoint)
 CHUNK_PAIRS = 32                  # record pairs per device call of _compute_flow_magnitudes
 
 cancel_event = threading.Event()  # the reference's module-level cancel flag (FS:63)
+_decode = framescore.decode       # the path-based seams' decode, looked up at call time so that tests can replace it
 
 
 def flow_geometry(H, W, crop_ratio):
@@ -89,7 +90,7 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
     for a, b in pairs:
         if not (0 <= a < len(frames) and 0 <= b < len(frames)):
             raise IndexError(f"pair ({a}, {b}) outside the {len(frames)} frames")
-    shapes = [framescore._frame_shape(fr) for fr in frames]   # 16-bit / float sources fail before any GPU work
+    shapes = [framescore.frame_shape(fr) for fr in frames]   # 16-bit / float sources fail before any GPU work
     recs = np.zeros(len(pairs), RECORD_DTYPE)
     pts = np.zeros((len(pairs), capi.FLOW_MAX_CORNERS), POINT_DTYPE) if with_points else None
     ctx = ctx or framescore.default_context()
@@ -110,38 +111,20 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
             gray.setdefault(f, _host_gray(frames[f], red_index))
         groups.setdefault(shapes[a][:2] + (1, False, "gray"), []).append(k)
     for key, ks in groups.items():
-        H, W, Cn, on_dev = key[:4]
+        H, W, Cn = key[:3]
         use_gray = len(key) == 5
         idx = sorted({f for k in ks for f in pairs[k]})
         local = {f: i for i, f in enumerate(idx)}
         x0, y0, cw, ch, sw, sh = flow_geometry(H, W, crop_ratio)
-        owned = []
-        try:
-            bufs, stride = [], 0
-            for f in idx:
-                fr = frames[f]
-                if on_dev:
-                    bufs.append(fr.buf)
-                    stride = fr.stride
-                else:
-                    b = ctx.to_device(np.ascontiguousarray(gray[f] if use_gray else fr))
-                    owned.append(b)
-                    bufs.append(b)
-            out = ctx.alloc(len(ks) * RECORD_DTYPE.itemsize)
-            owned.append(out)
-            pbuf = None
-            if with_points:
-                pbuf = ctx.alloc(len(ks) * capi.FLOW_MAX_CORNERS * POINT_DTYPE.itemsize)
-                owned.append(pbuf)
+        with framescore.device_frames(ctx, [gray[f] if use_gray else frames[f] for f in idx]) as (bufs, stride, alloc):
+            out = alloc(len(ks) * RECORD_DTYPE.itemsize)
+            pbuf = alloc(len(ks) * capi.FLOW_MAX_CORNERS * POINT_DTYPE.itemsize) if with_points else None
             with ctx.slot_locks[0]:
                 ctx.frame_flow_dev(bufs, H, W, Cn, (x0, y0, cw, ch), sw, sh, [(local[pairs[k][0]], local[pairs[k][1]]) for k in ks], out,
                                    flags=flags, points=pbuf, red_index=0 if use_gray else red_index, stride=stride, slot=0)
                 got = ctx.download(out, (len(ks),), RECORD_DTYPE)
                 if with_points:
                     gp = ctx.download(pbuf, (len(ks), capi.FLOW_MAX_CORNERS), POINT_DTYPE)
-        finally:
-            for b in owned:
-                ctx.free(b)
         recs[ks] = got
         if with_points:
             pts[ks] = gp
@@ -156,10 +139,6 @@ def flow_arrays(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0):
     return [value_of(r) for r in recs]
 
 
-def _decode(fp):
-    return framescore._decode(fp)   # None when unreadable; 16-bit -> Gs360Error
-
-
 def _compute_pair_flow_magnitude(prev_path, curr_path, crop_ratio, mask_mode="none"):
     """Drop-in for the reference's _compute_pair_flow_magnitude (FS:1283-1337, Lucas-Kanade) on the GPU."""
     a = _decode(prev_path)
@@ -171,20 +150,9 @@ def _compute_pair_flow_magnitude(prev_path, curr_path, crop_ratio, mask_mode="no
     return flow_arrays(None, [a, b], [(0, 1)], crop_ratio, mask_mode)[0]
 
 
-def _record_mask_mode(record):
-    return "fisheye_circle" if str(record.get("input_mode", "")).strip().lower() == "pair" else "none"
-
-
 def _record_exists(record):
     paths = record.get("file_paths", [])
     return bool(paths) and all(os.path.isfile(p) for p in paths)
-
-
-def _mean_of(values):
-    vals = [float(v) for v in values if v is not None and math.isfinite(v)]
-    if not vals:
-        return None
-    return float(sum(vals) / float(len(vals)))
 
 
 def _compute_record_flow_magnitude(prev_record, curr_record, crop_ratio):
@@ -194,8 +162,9 @@ def _compute_record_flow_magnitude(prev_record, curr_record, crop_ratio):
     curr_paths = list(curr_record.get("file_paths", []))
     if not prev_paths or not curr_paths or len(prev_paths) != len(curr_paths):
         return None
-    mask_mode = _record_mask_mode(curr_record)
-    return _mean_of([_compute_pair_flow_magnitude(p, c, crop_ratio, mask_mode=mask_mode) for p, c in zip(prev_paths, curr_paths)])
+    mask_mode = framescore.record_mask_mode(curr_record)
+    return framescore.mean_finite([_compute_pair_flow_magnitude(p, c, crop_ratio, mask_mode=mask_mode)
+                                   for p, c in zip(prev_paths, curr_paths)])
 
 
 def update_progress(label, completed, total, last_pct):
@@ -221,7 +190,7 @@ def _chunk_values(ctx, records, chunk, images):
         ok.append(good)
         if not good:
             continue
-        mode = _record_mask_mode(records[r])
+        mode = framescore.record_mask_mode(records[r])
         frames, where, prs, dest = jobs.setdefault(mode, ([], {}, [], []))
         for j, (a, b) in enumerate(zip(lp, rp)):
             if a is None or b is None:
@@ -293,7 +262,7 @@ def _compute_flow_magnitudes(records, flow_mag_arr, flow_crop_ratio, workers, la
                 for (pos, j), v in zip(dest, flow_arrays(ctx, frames, prs, flow_crop_ratio, mode)):
                     per[pos][j] = v
             for pos, (l, r) in enumerate(chunk):
-                mean_mag = _mean_of(per[pos]) if ok[pos] else None
+                mean_mag = framescore.mean_finite(per[pos]) if ok[pos] else None
                 if mean_mag is None or not math.isfinite(mean_mag):
                     mean_mag = FLOW_MISSING_HIGH_VALUE
                 flow_mag_arr[r] = max(flow_mag_arr[r], mean_mag)

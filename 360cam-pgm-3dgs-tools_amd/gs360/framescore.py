@@ -15,6 +15,7 @@ flow's per-run normalisation of the hybrid features (FS:2363-2392).
 """
 import collections
 import concurrent.futures
+import contextlib
 import math
 import os
 import threading
@@ -37,7 +38,7 @@ FAILED = (None, 0.0, 0.0, 0.0, 1.0, None, None, None, 1.0)   # the reference's t
 FIELDS = tuple(n for n, _ in capi.FrameStats._fields_)
 FFT_MODES = ("host", "device")
 DEFAULT_FFT = "host"              # where score_* compute the fft term when their `fft` keyword is None
-FFT_DTYPE = np.dtype([(n, np.float64 if t is capi.C.c_double else np.int64) for n, t in capi.FrameFft._fields_])
+FFT_DTYPE = capi.record_dtype(capi.FrameFft)
 
 DeviceFrame = collections.namedtuple("DeviceFrame", "buf H W C stride")   # an H x W x C uint8 frame already in device memory
 DeviceFrame.__new__.__defaults__ = (0,)
@@ -223,7 +224,8 @@ def hybrid_scores(tuples):
     return scores
 
 
-def _mean_optional(values, default=None):
+def mean_finite(values, default=None):
+    """The mean of the values that are not None and finite; default when there is none."""
     valid = [float(v) for v in values if v is not None and math.isfinite(float(v))]
     if not valid:
         return default
@@ -244,7 +246,9 @@ def default_context():
         return _ctx
 
 
-def _frame_shape(fr):
+def frame_shape(fr):
+    """(H, W, C) of a DeviceFrame or a uint8 ndarray; Gs360Error (GS360_ERR_UNSUPPORTED) for other dtypes, ValueError for other
+    shapes."""
     if isinstance(fr, DeviceFrame):
         return fr.H, fr.W, fr.C
     a = np.asarray(fr)
@@ -257,6 +261,31 @@ def _frame_shape(fr):
     return a.shape
 
 
+@contextlib.contextmanager
+def device_frames(ctx, frames):
+    """Device buffers of one launch's frames: a DeviceFrame's own buffer, a host frame uploaded.  Yields (bufs, stride, alloc):
+    stride is the DeviceFrames' row stride (0 = packed rows), alloc(nbytes) allocates an output buffer.  Whatever was uploaded or
+    allocated is freed on exit."""
+    owned = []
+
+    def alloc(nbytes):
+        owned.append(ctx.alloc(nbytes))
+        return owned[-1]
+    try:
+        bufs, stride = [], 0
+        for fr in frames:
+            if isinstance(fr, DeviceFrame):
+                bufs.append(fr.buf)
+                stride = fr.stride
+            else:
+                owned.append(ctx.to_device(np.ascontiguousarray(fr)))
+                bufs.append(owned[-1])
+        yield bufs, stride, alloc
+    finally:
+        for b in owned:
+            ctx.free(b)
+
+
 def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index, fft):
     H, W, Cn = shape
     band = band_rows(H, crop_ratio)
@@ -265,26 +294,10 @@ def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_
     on_device = want_small and fft == "device"
     sw, sh = fft_input_size(W, band[1] - band[0])
     flags = (capi.FS_CIRCLE if mask_mode == "fisheye_circle" else 0) | (capi.FS_HIGHLIGHTS if ignore_highlights else 0)
-    owned = []
-    try:
-        bufs, stride = [], 0
-        for fr in frames:
-            if isinstance(fr, DeviceFrame):
-                bufs.append(fr.buf)
-                stride = fr.stride
-            else:
-                b = ctx.to_device(np.ascontiguousarray(fr))
-                owned.append(b)
-                bufs.append(b)
-        stats = ctx.alloc(n * capi.C.sizeof(capi.FrameStats))
-        owned.append(stats)
-        smalls = None
-        if want_small:
-            smalls = [ctx.alloc(2 * sw * sh * 4) for _ in range(n)]
-            owned += smalls
-        if on_device:
-            ffts = ctx.alloc(n * FFT_DTYPE.itemsize)
-            owned.append(ffts)
+    with device_frames(ctx, frames) as (bufs, stride, alloc):
+        stats = alloc(n * capi.C.sizeof(capi.FrameStats))
+        smalls = [alloc(2 * sw * sh * 4) for _ in range(n)] if want_small else None
+        ffts = alloc(n * FFT_DTYPE.itemsize) if on_device else None
         with ctx.slot_locks[0]:
             ctx.frame_stats_dev(bufs, H, W, Cn, band, stats, flags=flags, smalls=smalls, small_w=sw, small_h=sh, red_index=red_index,
                                 stride=stride, slot=0)
@@ -293,9 +306,6 @@ def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_
             recs = ctx.download(stats, (n, len(FIELDS)), np.int64)
             frecs = ctx.download(ffts, (n,), FFT_DTYPE) if on_device else None
             planes = [ctx.download(b, (2, sh, sw), np.float32) for b in smalls] if want_small and not on_device else [None] * n
-    finally:
-        for b in owned:
-            ctx.free(b)
     out = []
     for k in range(n):
         st = {f: int(v) for f, v in zip(FIELDS, recs[k])}
@@ -312,7 +322,7 @@ def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlig
     "device" (None = DEFAULT_FFT); with "device" no plane leaves the GPU."""
     fft = fft_mode(fft)
     frames = list(frames)
-    shapes = [_frame_shape(fr) for fr in frames]          # 16-bit / float sources and bad crops fail before any GPU work
+    shapes = [frame_shape(fr) for fr in frames]          # 16-bit / float sources and bad crops fail before any GPU work
     for shape in set(shapes):
         band_rows(shape[0], crop_ratio)
     ctx = ctx or default_context()
@@ -329,12 +339,13 @@ def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlig
     return out
 
 
-def _decode(fp):
+def decode(fp):
+    """The image at fp as a uint8 ndarray, None when it cannot be read; Gs360Error for a 16-bit image."""
     try:
         a = imageio.read_image(fp)
     except (imageio.ImageIOError, OSError):
         return None
-    _frame_shape(a)            # 16-bit -> Gs360Error
+    frame_shape(a)
     return a
 
 
@@ -368,14 +379,14 @@ def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_high
                 pending.clear()
         while nxt < len(paths) or futs:
             while nxt < len(paths) and len(futs) < window:
-                futs.append((nxt, ex.submit(_decode, paths[nxt])))
+                futs.append((nxt, ex.submit(decode, paths[nxt])))
                 nxt += 1
             k, fut = futs.popleft()
             a = fut.result()
             if a is None:
                 out[k] = FAILED
                 continue
-            if pending and _frame_shape(a) != _frame_shape(pending[0][1]):
+            if pending and frame_shape(a) != frame_shape(pending[0][1]):
                 flush()
             pending.append((k, a))
             if len(pending) == capi.MAX_FRAMES:
@@ -388,10 +399,15 @@ def score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_high
     """Drop-in for the reference's score_one_file (FS:902-1044) on the GPU.  fft: as score_arrays."""
     fft = fft_mode(fft)
     _check_max_long(max_long)
-    a = _decode(fp)
+    a = decode(fp)
     if a is None:
         return FAILED
     return score_arrays(None, [a], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, fft=fft)[0]
+
+
+def record_mask_mode(record):
+    """The mask of a record's frames: the circle for an X / Y fisheye pair record (FS:458-517, FS:1340-1361), else none."""
+    return "fisheye_circle" if str(record.get("input_mode", "")).strip().lower() == "pair" else "none"
 
 
 def score_one_record(record, metric, crop_ratio, max_long, augment_motion, ignore_highlights, score_backend="opencv", fft=None):
@@ -399,20 +415,20 @@ def score_one_record(record, metric, crop_ratio, max_long, augment_motion, ignor
     mask and averaged field by field.  The ffmpeg backend is not implemented (pairs always take the OpenCV path, as there).
     fft: as score_arrays."""
     fft = fft_mode(fft)
-    mask_mode = "fisheye_circle" if str(record.get("input_mode", "")).strip().lower() == "pair" else "none"
+    mask_mode = record_mask_mode(record)
     if score_backend == "ffmpeg" and mask_mode != "fisheye_circle":
         raise capi.Gs360Error(-4, "the ffmpeg scoring backend is not implemented; use score_backend='opencv'")
     paths = list(record.get("file_paths", []))
     if not paths:
         return FAILED
     results = score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode, workers=len(paths), fft=fft)
-    sharp = _mean_optional([r[0] for r in results if r[0] is not None], default=None)
+    sharp = mean_finite([r[0] for r in results if r[0] is not None], default=None)
     return (sharp,
-            _mean_optional([r[1] for r in results], default=0.0),
-            _mean_optional([r[2] for r in results], default=0.0),
-            _mean_optional([r[3] for r in results], default=0.0),
-            _mean_optional([r[4] for r in results], default=1.0),
-            _mean_optional([r[5] for r in results], default=None),
-            _mean_optional([r[6] for r in results], default=None),
-            _mean_optional([r[7] for r in results], default=None),
-            _mean_optional([r[8] for r in results], default=1.0))
+            mean_finite([r[1] for r in results], default=0.0),
+            mean_finite([r[2] for r in results], default=0.0),
+            mean_finite([r[3] for r in results], default=0.0),
+            mean_finite([r[4] for r in results], default=1.0),
+            mean_finite([r[5] for r in results], default=None),
+            mean_finite([r[6] for r in results], default=None),
+            mean_finite([r[7] for r in results], default=None),
+            mean_finite([r[8] for r in results], default=1.0))

@@ -34,28 +34,10 @@ def _rint_u8(v):
     return np.clip(np.rint(v), 0, 255).astype(np.uint8)       # saturate_cast<uchar>(float): round half to even
 
 
-def _area_tab(d, ssize, scale):
-    """computeResizeAreaTab for destination index d -> [(source index, float32 weight)] in table order."""
-    f1 = d * scale
-    f2 = f1 + scale
-    cell = min(scale, ssize - f1)
-    s1, s2 = int(np.ceil(f1)), int(np.floor(f2))
-    s2 = min(s2, ssize - 1)
-    s1 = min(s1, s2)
-    out = []
-    if s1 - f1 > 1e-3:
-        out.append((s1 - 1, F32((s1 - f1) / cell)))
-    out += [(s, F32(1.0 / cell)) for s in range(s1, s2)]
-    if f2 - s2 > 1e-3:
-        out.append((s2, F32(min(min(f2 - s2, 1.0), cell) / cell)))
-    return out
-
-
 def area_general(g, dw, dh):
     """INTER_AREA's general 8U path: float32 row buffers then rows, in the tables' order, saturate_cast at the end."""
     sh, sw = g.shape
-    sx, sy = 1.0 / (dw / sw), 1.0 / (dh / sh)
-    xt = [_area_tab(d, sw, sx) for d in range(dw)]
+    xt = fnp.area_tab(sw, dw)
     kx = max(len(t) for t in xt)
     gf = g.astype(F32)
     buf = np.zeros((sh, dw), F32)
@@ -64,9 +46,9 @@ def area_general(g, dw, dh):
         al = np.array([t[k][1] if k < len(t) else 0 for t in xt], F32)
         buf = buf + gf[:, si] * al
     out = np.zeros((dh, dw), F32)
-    for d in range(dh):
+    for d, yt in enumerate(fnp.area_tab(sh, dh)):
         s = F32(0)
-        for si, beta in _area_tab(d, sh, sy):
+        for si, beta in yt:
             s = s + beta * buf[si]
         out[d] = s
     return _rint_u8(out)
