@@ -1,4 +1,4 @@
-// gs360_capi_framescore.hip -- C-ABI glue of the frame sharpness statistics, the frame FFT energy and the frame optical flow
+// gs360_capi_framescore.hip -- C-ABI glue of the frame sharpness statistics, edge score, FFT energy and optical flow
 // (include/gs360.h; kernels in gs360_framescore.hip, gs360_framefft.hip and gs360_frameflow.hip).
 #include "gs360_capi_internal.h"
 
@@ -24,6 +24,15 @@ int check_frame_layout(int H, int W, int C, int red_index, size_t* stride) {
 
 int check_band(int band_y0, int band_y1, int H) {
     if (band_y0 < 0 || band_y1 > H || band_y0 >= band_y1) return fail(GS360_ERR_ARG, "band [%d,%d) outside [0,%d) or empty", band_y0, band_y1, H);
+    return 0;
+}
+
+// The frame pointers of a call: none NULL, each 4-byte aligned (the kernels stage rows with dword loads)
+int check_frame_pointers(const void* const* frames, int n_frames) {
+    for (int f = 0; f < n_frames; ++f) {
+        if (!frames[f]) return fail(GS360_ERR_ARG, "frames[%d] is NULL", f);
+        if ((uintptr_t)frames[f] & 3) return fail(GS360_ERR_ARG, "frames[%d] is not 4-byte aligned", f);
+    }
     return 0;
 }
 
@@ -56,11 +65,9 @@ int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, 
     if (int rc = check_frame_layout(H, W, C, red_index, &stride)) return rc;
     if (int rc = check_band(band_y0, band_y1, H)) return rc;
     if (flags & ~(GS360_FS_CIRCLE | GS360_FS_HIGHLIGHTS)) return fail(GS360_ERR_ARG, "unknown flags 0x%x", flags);
-    for (int f = 0; f < n_frames; ++f) {
-        if (!frames[f]) return fail(GS360_ERR_ARG, "frames[%d] is NULL", f);
-        if ((uintptr_t)frames[f] & 3) return fail(GS360_ERR_ARG, "frames[%d] is not 4-byte aligned", f);   // dword row loads
-        if (small_dev && !small_dev[f]) return fail(GS360_ERR_ARG, "small_dev[%d] is NULL", f);
-    }
+    if (int rc = check_frame_pointers(frames, n_frames)) return rc;
+    for (int f = 0; small_dev && f < n_frames; ++f)
+        if (!small_dev[f]) return fail(GS360_ERR_ARG, "small_dev[%d] is NULL", f);
     if (small_dev && (small_w < 1 || small_w > W || small_h < 1 || small_h > band_y1 - band_y0))
         return fail(GS360_ERR_ARG, "small image %d x %d outside [1,%d] x [1,%d]", small_w, small_h, W, band_y1 - band_y0);
     HIP_TRY(hipSetDevice(c->device));
@@ -86,6 +93,32 @@ int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, 
         }
         L.stats = stats_dev + f0;
         HIP_TRY(launch_frame_stats(L, s));
+    }
+    return GS360_OK;
+}
+
+int gs360_frame_edge_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
+                        int band_y0, int band_y1, gs360_frame_edge* out_dev, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (n_frames < 0) return fail(GS360_ERR_ARG, "n_frames < 0");
+    if (n_frames == 0) return GS360_OK;
+    if (!frames || !out_dev) return fail(GS360_ERR_ARG, "NULL argument");
+    if (int rc = check_frame_layout(H, W, C, red_index, &stride)) return rc;
+    if (int rc = check_band(band_y0, band_y1, H)) return rc;
+    if (int rc = check_frame_pointers(frames, n_frames)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream[slot];
+    HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)n_frames * sizeof(gs360_frame_edge), s));
+    FsLaunch L;
+    std::memset(&L, 0, sizeof(L));
+    L.stride = (int64_t)stride;
+    L.H = H; L.W = W; L.C = C; L.red = red_index;
+    L.y0 = band_y0; L.y1 = band_y1;
+    for (int f0 = 0; f0 < n_frames; f0 += GS360_MAX_FRAMES) {
+        L.n_frames = std::min(GS360_MAX_FRAMES, n_frames - f0);
+        for (int k = 0; k < L.n_frames; ++k) L.src[k] = (const uint8_t*)frames[f0 + k];
+        L.edge = out_dev + f0;
+        HIP_TRY(launch_frame_edge(L, s));
     }
     return GS360_OK;
 }

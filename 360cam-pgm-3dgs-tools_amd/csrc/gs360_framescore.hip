@@ -5,12 +5,18 @@
 // values, the Laplacian and the Sobel responses are small integers, so their sums are exact and this kernel reproduces the
 // double accumulators of cv2.meanStdDev / cv2.mean bit for bit, whatever the order in which workgroups finish.
 //
-// fs_stats_kernel: one 256-thread workgroup per strip of kFsRows frame rows, walking the frame width in tiles of kFsTileW columns.
+// fs_strip_kernel<C, false>, the statistics pass: one 256-thread workgroup per strip of kFsRows frame rows, walking the frame width
+// in tiles of kFsTileW columns.
 // A tile's rows (plus one halo row above and below, plus one halo column each side, reflect-101 at x = 0 / W-1) are staged as raw
 // bytes in LDS with dword loads, converted to gray in LDS, and every lane then walks one column down the strip: full-frame counts
 // for every row, the 3x3 Laplacian / Sobel for rows inside the band.  The band is an image of its own (cv2 receives a NumPy view),
 // so the row above the band's first row is its second row (reflect-101), and the same at its last row; those rows always lie
 // inside the staged window.  Sums go lane -> wavefront (cross-lane adds) -> workgroup (LDS) -> one 64-bit atomic per field.
+//
+// The same kernel with kEdge set is the edge pass (FS-EDGE v1): the default backend's score, the filter graph `format=gray,
+// crop, signalstats, sobel, signalstats` of score_one_file_ffmpeg (FS:789-899).  Its strips cover the band only, the staging is the
+// same code with libavfilter's mirror (one past the last row / column is the last one itself) in place of reflect-101, and every
+// lane sums the gray and the clipped Sobel magnitude of its column into a gs360_frame_edge record.
 //
 // fs_small_kernel: the band resized with INTER_AREA (OpenCV's per-axis area tables, computed per output pixel in double exactly as
 // computeResizeAreaTab does, float32 accumulation in ResizeArea_Invoker's order), and the gray at the INTER_NEAREST sample that the
@@ -42,16 +48,30 @@ __device__ __forceinline__ int reflect101(int i, int n) {   // one step outside 
     return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
 }
 
-template <int C>
-__global__ void __launch_bounds__(kFsThreads) fs_stats_kernel(const FsLaunch L) {
+// libavfilter's 3x3 set-up, as FS-EDGE v1 restates it: |i| inside, else 2n - 1 - |i| (-1 -> 1, n -> n - 1; n = 1 -> 0)
+__device__ __forceinline__ int mirror_av(int i, int n) {
+    const int a = abs(i);
+    return a < n ? a : 2 * n - 1 - a;
+}
+
+// floor(sqrt(s)) for 0 <= s < 2^24 (exact in float): the hardware square root is a candidate, integer compares settle it
+__device__ __forceinline__ int isqrt24(int s) {
+    int r = (int)__builtin_amdgcn_sqrtf((float)s);
+    r -= r * r > s;
+    r += (r + 1) * (r + 1) <= s;
+    return r;
+}
+
+template <int C, bool kEdge>
+__global__ void __launch_bounds__(kFsThreads) fs_strip_kernel(const FsLaunch L) {
     __shared__ FsLds S;
     const int b = blockIdx.x;
     const int t = (b & 7) * L.chunk + (b >> 3);             // XCD-aware order: an XCD walks neighbouring strips (shared halo rows)
     if (t >= L.total) return;
     const int f = t / L.strips;
-    const int ys = (t - f * L.strips) * kFsRows;
     const int H = L.H, W = L.W, y0 = L.y0, y1 = L.y1;
-    const int ye = min(ys + kFsRows, H);
+    const int ys = (kEdge ? y0 : 0) + (t - f * L.strips) * kFsRows;     // the edge pass walks the band's strips only
+    const int ye = min(ys + kFsRows, kEdge ? y1 : H);
     const uint8_t* const src = L.src[f];
     const int tid = threadIdx.x;
     const int64_t r4 = circle_r4(W, H);
@@ -59,6 +79,7 @@ __global__ void __launch_bounds__(kFsThreads) fs_stats_kernel(const FsLaunch L) 
     int cnt_c = 0, cnt_h = 0, cnt_hc = 0;
     int n_a = 0, g_a = 0, l_a = 0, n_v = 0, g_v = 0, l_v = 0;
     int64_t l2_a = 0, m2_a = 0, l2_v = 0, m2_v = 0;
+    int e_a = 0;                                            // edge pass: sum of e, next to n_a and g_a (<= 256 tiles x kFsRows x 255)
 
     for (int x0 = 0; x0 < W; x0 += kFsTileW) {
         const int nx = min(kFsTileW, W - x0);
@@ -81,18 +102,40 @@ __global__ void __launch_bounds__(kFsThreads) fs_stats_kernel(const FsLaunch L) 
             if (tid < kFsRawDw - kFsThreads) S.raw[r][tid + kFsThreads] = v[r][1];
         }
         __syncthreads();
-        // 2. gray of columns x0-1 .. x0+nx (reflect-101 at the frame's left and right edges)
+        // 2. gray of columns x0-1 .. x0+nx (reflect-101, or the edge pass's mirror, at the frame's left and right edges)
         for (int i = tid; i < kFsLdsRows * (kFsTileW + 2); i += kFsThreads) {
             const int r = i / (kFsTileW + 2), c = i - r * (kFsTileW + 2);
             if (c > nx + 1) continue;
-            const int xs = reflect101(x0 - 1 + c, W);
+            const int xs = kEdge ? mirror_av(x0 - 1 + c, W) : reflect101(x0 - 1 + c, W);
             const int off = (int)((uintptr_t)(src + (int64_t)(ys - 1 + r) * L.stride + xa * C) & 3);   // as staged in step 1
             const uint8_t* p = (const uint8_t*)S.raw[r] + off + (xs - xa) * C;
             S.gray[r][c] = gray_of<C>(p, L.red);
         }
         __syncthreads();
         // 3. one column per lane down the strip
-        if (tid < nx) {
+        if constexpr (kEdge) {
+            if (tid < nx) {
+                // taps t[row][col] = wu / wm / wd; the band's row -1 is its row 1 (row 0 when it has one row), its row bh is row bh-1
+                const int c = tid + 1;
+                int wu[3], wm[3], wd[3];
+                const int* Ru = S.gray[ys > y0 ? 0 : (y1 - y0 > 1 ? 2 : 1)] + c;
+                const int* Rm = S.gray[1] + c;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { wu[k] = Ru[k - 1]; wm[k] = Rm[k - 1]; }
+                for (int y = ys; y < ye; ++y) {
+                    const int* Rd = S.gray[min(y + 1, y1 - 1) - ys + 1] + c;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) wd[k] = Rd[k - 1];
+                    const int ga = (wd[0] + 2 * wd[1] + wd[2]) - (wu[0] + 2 * wu[1] + wu[2]);
+                    const int gb = (wu[2] + 2 * wm[2] + wd[2]) - (wu[0] + 2 * wm[0] + wd[0]);
+                    n_a += 1;
+                    g_a += wm[1];
+                    e_a += isqrt24(min(ga * ga + gb * gb, 255 * 255));            // min(255, floor(sqrt(.)))
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) { wu[k] = wm[k]; wm[k] = wd[k]; }
+                }
+            }
+        } else if (tid < nx) {
             const int c = tid + 1;
             const int x = x0 + tid;
             const int64_t dx = 2 * x - (W - 1);
@@ -143,21 +186,31 @@ __global__ void __launch_bounds__(kFsThreads) fs_stats_kernel(const FsLaunch L) 
         }
         __syncthreads();
     }
-    // lane -> wavefront -> workgroup -> one atomic per field
-    long long acc[kFsFields] = {wave_sum(cnt_c), wave_sum(cnt_h), wave_sum(cnt_hc),
-                                wave_sum(n_a), wave_sum(g_a), wave_sum(l_a), wave_sum((long long)l2_a), wave_sum((long long)m2_a),
-                                wave_sum(n_v), wave_sum(g_v), wave_sum(l_v), wave_sum((long long)l2_v), wave_sum((long long)m2_v)};
+    // lane -> wavefront -> workgroup -> one atomic per field of the frame's record
+    constexpr int kN = kEdge ? 3 : kFsFields;
+    static_assert(sizeof(gs360_frame_edge) == 3 * 8, "gs360_frame_edge layout");
+    long long acc[kN];
+    if constexpr (kEdge) {
+        acc[0] = wave_sum(n_a); acc[1] = wave_sum(g_a); acc[2] = wave_sum(e_a);
+    } else {
+        const long long all[kFsFields] = {wave_sum(cnt_c), wave_sum(cnt_h), wave_sum(cnt_hc),
+                                          wave_sum(n_a), wave_sum(g_a), wave_sum(l_a), wave_sum((long long)l2_a), wave_sum((long long)m2_a),
+                                          wave_sum(n_v), wave_sum(g_v), wave_sum(l_v), wave_sum((long long)l2_v), wave_sum((long long)m2_v)};
+#pragma unroll
+        for (int k = 0; k < kFsFields; ++k) acc[k] = all[k];
+    }
+    unsigned long long* const rec = kEdge ? (unsigned long long*)&L.edge[f] : (unsigned long long*)&L.stats[f];
     const int wave = tid >> 6;
     if ((tid & 63) == 0) {
 #pragma unroll
-        for (int k = 0; k < kFsFields; ++k) S.red[wave][k] = acc[k];
+        for (int k = 0; k < kN; ++k) S.red[wave][k] = acc[k];
     }
     __syncthreads();
-    if (tid < kFsFields) {
+    if (tid < kN) {
         long long s = 0;
 #pragma unroll
         for (int w = 0; w < kFsThreads / 64; ++w) s += S.red[w][tid];
-        if (s != 0) atomicAdd((unsigned long long*)&L.stats[f] + tid, (unsigned long long)s);
+        if (s != 0) atomicAdd(rec + tid, (unsigned long long)s);
     }
 }
 
@@ -188,11 +241,20 @@ hipError_t launch_fs(FsLaunch& L, hipStream_t s) {
     L.strips = (L.H + kFsRows - 1) / kFsRows;
     L.total = L.strips * L.n_frames;
     L.chunk = (L.total + 7) / 8;
-    hipLaunchKernelGGL(fs_stats_kernel<C>, dim3((unsigned)(L.chunk * 8)), dim3(kFsThreads), 0, s, L);
+    hipLaunchKernelGGL((fs_strip_kernel<C, false>), dim3((unsigned)(L.chunk * 8)), dim3(kFsThreads), 0, s, L);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !L.small[0]) return e;
     hipLaunchKernelGGL(fs_small_kernel<C>, dim3((unsigned)((L.small_w + kFsThreads - 1) / kFsThreads), (unsigned)L.small_h,
                                                 (unsigned)L.n_frames), dim3(kFsThreads), 0, s, L);
+    return hipGetLastError();
+}
+
+template <int C>
+hipError_t launch_fe(FsLaunch& L, hipStream_t s) {
+    L.strips = (L.y1 - L.y0 + kFsRows - 1) / kFsRows;
+    L.total = L.strips * L.n_frames;
+    L.chunk = (L.total + 7) / 8;
+    hipLaunchKernelGGL((fs_strip_kernel<C, true>), dim3((unsigned)(L.chunk * 8)), dim3(kFsThreads), 0, s, L);
     return hipGetLastError();
 }
 
@@ -203,6 +265,15 @@ hipError_t launch_frame_stats(FsLaunch& L, hipStream_t s) {
         case 1: return launch_fs<1>(L, s);
         case 3: return launch_fs<3>(L, s);
         case 4: return launch_fs<4>(L, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_frame_edge(FsLaunch& L, hipStream_t s) {
+    switch (L.C) {
+        case 1: return launch_fe<1>(L, s);
+        case 3: return launch_fe<3>(L, s);
+        case 4: return launch_fe<4>(L, s);
         default: return hipErrorInvalidValue;
     }
 }

@@ -300,8 +300,11 @@ struct FsLaunch {
     int32_t n_frames, strips, total, chunk;   // strips per frame, strip workgroups in all, ceil(total / 8) (XCD order)
     int32_t small_w, small_h;
     double scale_x, scale_y;             // cv2.resize's 1 / (small_w / W), 1 / (small_h / band height)
+    gs360_frame_edge* edge;              // launch_frame_edge: n_frames records, cleared by the caller
 };
 hipError_t launch_frame_stats(FsLaunch& L, hipStream_t s);
+// Frame edge score (FS-EDGE v1 in DESIGN.md): src, stride, H, W, C, red, y0, y1, n_frames and edge of L
+hipError_t launch_frame_edge(FsLaunch& L, hipStream_t s);
 
 // Frame FFT energy (gs360_framefft.hip, FS-FFT v1 in DESIGN.md): one batch of up to GS360_MAX_FRAMES fft inputs of one size.
 struct FfPartial {                       // one column-pass workgroup's share of a frame's record

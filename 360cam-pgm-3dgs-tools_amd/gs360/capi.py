@@ -32,7 +32,7 @@ EXPORTS = (
     "gs360_equirect_views_u16", "gs360_remap_table_u16", "gs360_remap_tables_u16", "gs360_equirect_views_u16_host", "gs360_remap_table_u16_host",
     "gs360_png_unfilter", "gs360_event_sync", "gs360_stream_wait_event",
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
-    "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8",
+    "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
 )
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
@@ -80,6 +80,11 @@ class FrameStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "n_circle", "n_highlight", "n_highlight_in_circle", "n", "sum_gray", "sum_lap", "sum_lap2", "sum_mag2",
         "n_valid", "sum_gray_valid", "sum_lap_valid", "sum_lap2_valid", "sum_mag2_valid")]
+
+
+class FrameEdge(C.Structure):
+    """gs360_frame_edge: the band's pixel count and its exact sums of gray and of the clipped Sobel magnitude (FS-EDGE v1)."""
+    _fields_ = [("n", C.c_int64), ("sum_gray", C.c_int64), ("sum_edge", C.c_int64)]
 
 
 class FrameFft(C.Structure):
@@ -184,6 +189,7 @@ def load_library(path=None):
         L.gs360_event_sync.argtypes = [vp, i, i]
         L.gs360_stream_wait_event.argtypes = [vp, i, i, i]
         L.gs360_frame_stats_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, u32, vp, pvp, i, i, i]
+        L.gs360_frame_edge_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, vp, i]
         L.gs360_frame_fft_energy.argtypes = [vp, pvp, i, i, i, i, i, i, i, u32, vp, i]
         L.gs360_frame_flow_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, i, i, i, i, u32, C.POINTER(C.c_int), i, vp, vp, i]
         for name in EXPORTS:
@@ -535,6 +541,14 @@ class Context:
         sp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in smalls]) if smalls is not None else None
         _check(self.L.gs360_frame_stats_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(band[0]),
                                            int(band[1]), int(flags), stats.ptr, sp, int(small_w), int(small_h), slot), self.L)
+
+    def frame_edge_dev(self, frames, H, W, Cn, band, out, red_index=0, stride=0, slot=0):
+        """gs360_frame_edge_u8 on device frames (list of DeviceBuffer, H x W x C uint8): out = DeviceBuffer of len(frames) FrameEdge
+        records.  band = (y0, y1).  Asynchronous on `slot`."""
+        nf = len(frames)
+        fp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in frames])
+        _check(self.L.gs360_frame_edge_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(band[0]),
+                                          int(band[1]), out.ptr, slot), self.L)
 
     def frame_fft_energy_dev(self, smalls, small_w, small_h, H, W, band, out, flags=0, slot=0):
         """gs360_frame_fft_energy on the fft inputs frame_stats_dev wrote (one DeviceBuffer of 2 x small_h x small_w float32 per

@@ -3,12 +3,15 @@
 Drop-in seams of cli_tools/gs360_FrameSelector.py:
   score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none")   FS:902-1044
   score_one_record(record, metric, crop_ratio, max_long, augment_motion, ignore_highlights, score_backend) FS:458-517
-both return the reference's 9-tuple (sharp, p0, p255, brightness_mean, brightness_weight, lap_feature, ten_feature, fft_feature,
+  score_one_file_ffmpeg(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none") FS:826-899
+all return the reference's 9-tuple (sharp, p0, p255, brightness_mean, brightness_weight, lap_feature, ten_feature, fft_feature,
 motion_factor).  The per-pixel work (gray, masks, Laplacian, Sobel, the INTER_AREA downscale of fft_energy_fast) runs in
 gs360_frame_stats_u8; what is left here is the reference's branch logic on exact integer sums, in double, and the FFT of the
 <= 512-pixel image (FS:742-786).  That FFT runs on the host (fft="host": NumPy, the reference's own code, on the downloaded
 planes) or on the device (fft="device": gs360_frame_fft_energy, FS-FFT v1, after the statistics on the same stream; only two small
-records per frame come back).  score_arrays / score_files batch frames GS360_MAX_FRAMES per launch; hybrid_scores is the main
+records per frame come back).  The reference's default backend ("ffmpeg": a filter graph's two YAVG values, whatever the metric)
+is gs360_frame_edge_u8 (FS-EDGE v1) with the branch logic of FS:875-896 here; no ffmpeg is spawned.  score_arrays / edge_arrays /
+score_files batch frames GS360_MAX_FRAMES per launch; hybrid_scores is the main
 flow's per-run normalisation of the hybrid features (FS:2363-2392).
 
 8-bit sources only: 16-bit and float images raise Gs360Error (GS360_ERR_UNSUPPORTED), as does max_long > 0.
@@ -39,6 +42,7 @@ FIELDS = tuple(n for n, _ in capi.FrameStats._fields_)
 FFT_MODES = ("host", "device")
 DEFAULT_FFT = "host"              # where score_* compute the fft term when their `fft` keyword is None
 FFT_DTYPE = capi.record_dtype(capi.FrameFft)
+EDGE_FIELDS = tuple(n for n, _ in capi.FrameEdge._fields_)
 
 DeviceFrame = collections.namedtuple("DeviceFrame", "buf H W C stride")   # an H x W x C uint8 frame already in device memory
 DeviceFrame.__new__.__defaults__ = (0,)
@@ -53,6 +57,31 @@ def band_rows(H, crop_ratio):
     nh = max(1, int(H * crop_ratio))
     y0 = max(0, (H - nh) // 2)
     return y0, min(H, y0 + nh)
+
+
+def edge_band_rows(H, crop_ratio):
+    """The filter graph's crop (FS:796-800) -> (y0, y1): only when crop_ratio < 1.0, height max(1, trunc(H * crop_ratio)) at
+    trunc((H - height) / 2)."""
+    if crop_ratio is None or not crop_ratio < 1.0:
+        return 0, H
+    bh = max(1, math.trunc(H * crop_ratio))
+    y0 = math.trunc((H - bh) / 2)
+    return y0, y0 + bh
+
+
+def yavg(total, n):
+    """signalstats' YAVG as the reference reads it (FS:813-823): the mean printed with %g, six significant digits, parsed back."""
+    return float("%g" % (total / n))
+
+
+def finish_edge(rec):
+    """The 9-tuple of score_one_file_ffmpeg (FS:875-896) from one frame's gs360_frame_edge record (mapping of its fields)."""
+    brightness_mean = max(0.0, min(1.0, yavg(rec["sum_gray"], rec["n"]) / 255.0))
+    sharp = max(0.0, min(1.0, yavg(rec["sum_edge"], rec["n"]) / 255.0))
+    dark_ratio = brightness_mean / HYBRID_DARK_THRESHOLD if brightness_mean < HYBRID_DARK_THRESHOLD else 1.0
+    dark_ratio = max(0.0, min(1.0, dark_ratio))
+    brightness_weight = max(0.0, 1.0 - HYBRID_DARK_PENALTY_WEIGHT * (1.0 - dark_ratio))
+    return (sharp, 0.0, 0.0, brightness_mean, brightness_weight, None, None, None, 1.0)
 
 
 def fft_input_size(bw, bh):
@@ -286,6 +315,18 @@ def device_frames(ctx, frames):
             ctx.free(b)
 
 
+def _batches(frames, shapes):
+    """(i, j) index ranges of one launch each: consecutive frames of one size and one kind, GS360_MAX_FRAMES at most."""
+    i = 0
+    while i < len(frames):
+        j = i + 1
+        while j < len(frames) and j - i < capi.MAX_FRAMES and shapes[j] == shapes[i] \
+                and isinstance(frames[j], DeviceFrame) == isinstance(frames[i], DeviceFrame):
+            j += 1
+        yield i, j
+        i = j
+
+
 def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index, fft):
     H, W, Cn = shape
     band = band_rows(H, crop_ratio)
@@ -327,15 +368,32 @@ def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlig
         band_rows(shape[0], crop_ratio)
     ctx = ctx or default_context()
     out = []
-    i = 0
-    while i < len(frames):
-        j = i + 1
-        while j < len(frames) and j - i < capi.MAX_FRAMES and shapes[j] == shapes[i] \
-                and isinstance(frames[j], DeviceFrame) == isinstance(frames[i], DeviceFrame):
-            j += 1
+    for i, j in _batches(frames, shapes):
         out += _score_batch(ctx, frames[i:j], shapes[i], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, red_index,
                             fft)
-        i = j
+    return out
+
+
+def _edge_batch(ctx, frames, shape, crop_ratio, red_index):
+    H, W, Cn = shape
+    n = len(frames)
+    with device_frames(ctx, frames) as (bufs, stride, alloc):
+        recs = alloc(n * capi.C.sizeof(capi.FrameEdge))
+        with ctx.slot_locks[0]:
+            ctx.frame_edge_dev(bufs, H, W, Cn, edge_band_rows(H, crop_ratio), recs, red_index=red_index, stride=stride, slot=0)
+            recs = ctx.download(recs, (n, len(EDGE_FIELDS)), np.int64)
+    return [finish_edge({f: int(v) for f, v in zip(EDGE_FIELDS, r)}) for r in recs]
+
+
+def edge_arrays(ctx, frames, crop_ratio, red_index=0):
+    """9-tuples of the default ("ffmpeg") backend for a sequence of frames, batched and typed as score_arrays' (FS-EDGE v1; the
+    backend ignores the metric, the highlights and the motion augmentation, FS:826-899)."""
+    frames = list(frames)
+    shapes = [frame_shape(fr) for fr in frames]
+    ctx = ctx or default_context()
+    out = []
+    for i, j in _batches(frames, shapes):
+        out += _edge_batch(ctx, frames[i:j], shapes[i], crop_ratio, red_index)
     return out
 
 
@@ -354,12 +412,23 @@ def _check_max_long(max_long):
         raise capi.Gs360Error(-4, "max_long > 0 is not implemented (the reference CLI runs with MAX_LONG = 0)")
 
 
-def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none", workers=None, fft=None):
-    """score_one_file over many paths: decoding on a thread pool overlaps the GPU batches; unreadable files give the reference's
-    failure tuple.  Returns one tuple per path, in order.  fft: as score_arrays."""
+def _edge_backend(backend, mask_mode):
+    """Does a file take the edge pass: the "ffmpeg" backend, except under the circle mask; any other name is the OpenCV path, as in
+    the reference (FS:480-483, FS:836-845)."""
+    return backend == "ffmpeg" and mask_mode != "fisheye_circle"
+
+
+def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none", workers=None, fft=None,
+                backend="opencv", progress=None):
+    """score_one_file (backend "opencv") or score_one_file_ffmpeg (backend "ffmpeg") over many paths: decoding on a thread pool
+    overlaps the GPU batches; unreadable files give the reference's failure tuple.  Returns one tuple per path, in order.
+    fft: as score_arrays.  progress(k), when given, is called as the number k of finished paths grows; what it raises ends the
+    run."""
     fft = fft_mode(fft)
+    edge = _edge_backend(backend, mask_mode)
     _check_max_long(max_long)
-    band_rows(1, crop_ratio)   # the reference's ValueError before any work
+    if not edge:
+        band_rows(1, crop_ratio)   # the reference's ValueError before any work
     paths = list(paths)
     ctx = default_context()
     out = [None] * len(paths)
@@ -369,13 +438,21 @@ def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_high
         futs = collections.deque()
         nxt = 0
         pending = []                      # (index, image) decoded, not yet scored
+        done = [0]
+
+        def finished(count):
+            done[0] += count
+            if progress:
+                progress(done[0])
 
         def flush():
             if pending:
-                res = score_arrays(ctx, [a for _, a in pending], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode,
-                                   fft=fft)
+                imgs = [a for _, a in pending]
+                res = edge_arrays(ctx, imgs, crop_ratio) if edge else \
+                    score_arrays(ctx, imgs, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, fft=fft)
                 for (k, _), r in zip(pending, res):
                     out[k] = r
+                finished(len(pending))
                 pending.clear()
         while nxt < len(paths) or futs:
             while nxt < len(paths) and len(futs) < window:
@@ -385,6 +462,7 @@ def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_high
             a = fut.result()
             if a is None:
                 out[k] = FAILED
+                finished(1)
                 continue
             if pending and frame_shape(a) != frame_shape(pending[0][1]):
                 flush()
@@ -405,6 +483,18 @@ def score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_high
     return score_arrays(None, [a], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, fft=fft)[0]
 
 
+def score_one_file_ffmpeg(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none"):
+    """Drop-in for the reference's score_one_file_ffmpeg (FS:826-899) on the GPU: the circle mask goes to score_one_file, as
+    there; anything else is the edge pass, whatever the metric."""
+    if mask_mode == "fisheye_circle":
+        return score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode=mask_mode)
+    _check_max_long(max_long)
+    a = decode(fp)
+    if a is None:
+        return FAILED
+    return edge_arrays(None, [a], crop_ratio)[0]
+
+
 def record_mask_mode(record):
     """The mask of a record's frames: the circle for an X / Y fisheye pair record (FS:458-517, FS:1340-1361), else none."""
     return "fisheye_circle" if str(record.get("input_mode", "")).strip().lower() == "pair" else "none"
@@ -412,23 +502,50 @@ def record_mask_mode(record):
 
 def score_one_record(record, metric, crop_ratio, max_long, augment_motion, ignore_highlights, score_backend="opencv", fft=None):
     """Drop-in for the reference's score_one_record (FS:458-517): a single image, or an X / Y fisheye pair scored with the circle
-    mask and averaged field by field.  The ffmpeg backend is not implemented (pairs always take the OpenCV path, as there).
-    fft: as score_arrays."""
+    mask and averaged field by field.  score_backend "ffmpeg" scores a single image with the edge pass (pairs always take the
+    OpenCV path, as there).  fft: as score_arrays."""
     fft = fft_mode(fft)
     mask_mode = record_mask_mode(record)
-    if score_backend == "ffmpeg" and mask_mode != "fisheye_circle":
-        raise capi.Gs360Error(-4, "the ffmpeg scoring backend is not implemented; use score_backend='opencv'")
     paths = list(record.get("file_paths", []))
-    if not paths:
+    results = score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode, workers=len(paths), fft=fft,
+                          backend=score_backend)
+    return average_tuples(results)
+
+
+def average_tuples(results):
+    """One record's 9-tuple from its files' (FS:502-517): every field the mean of its finite values, else the field's default."""
+    if not results:
         return FAILED
-    results = score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode, workers=len(paths), fft=fft)
-    sharp = mean_finite([r[0] for r in results if r[0] is not None], default=None)
-    return (sharp,
-            mean_finite([r[1] for r in results], default=0.0),
-            mean_finite([r[2] for r in results], default=0.0),
-            mean_finite([r[3] for r in results], default=0.0),
-            mean_finite([r[4] for r in results], default=1.0),
-            mean_finite([r[5] for r in results], default=None),
-            mean_finite([r[6] for r in results], default=None),
-            mean_finite([r[7] for r in results], default=None),
-            mean_finite([r[8] for r in results], default=1.0))
+    return tuple(mean_finite([r[k] for r in results], default=d) for k, d in enumerate(FAILED))
+
+
+def score_records(records, metric, crop_ratio, max_long, augment_motion, ignore_highlights, score_backend="opencv", workers=None,
+                  fft=None, progress=None):
+    """score_one_record over a run's records, batched: the records of one mask mode go through one score_files call (so that
+    decoding overlaps GS360_MAX_FRAMES-frame launches) and are averaged per record.  Returns one 9-tuple per record, in order.
+    progress(k), when given, is called as the number k of finished records grows; what it raises ends the run."""
+    out = [FAILED] * len(records)
+    by_mode = {}
+    for k, rec in enumerate(records):
+        by_mode.setdefault(record_mask_mode(rec), []).append(k)
+    base = 0
+    for mask_mode, members in by_mode.items():
+        paths, owner = [], []
+        for k in members:
+            for fp in records[k].get("file_paths", []):
+                paths.append(fp)
+                owner.append(k)
+
+        def tick(count, base=base, n_paths=len(paths), n_recs=len(members)):
+            progress(base + count * n_recs // max(1, n_paths))
+        res = score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode, workers=workers, fft=fft,
+                          backend=score_backend, progress=tick if progress else None)
+        per = {k: [] for k in members}
+        for k, r in zip(owner, res):
+            per[k].append(r)
+        for k in members:
+            out[k] = average_tuples(per[k])
+        base += len(members)
+    if progress:
+        progress(len(records))
+    return out

@@ -360,6 +360,26 @@ int gs360_frame_stats_u8(gs360_ctx *ctx, const void *const *frames, int n_frames
                          int red_index, int band_y0, int band_y1, uint32_t flags, gs360_frame_stats *stats_dev,
                          float *const *small_dev, int small_w, int small_h, int slot);
 
+/* ---- frame edge score (the FrameSelector's default scoring backend) ---------------------------
+ * The score of score_one_file_ffmpeg in cli_tools/gs360_FrameSelector.py (FS:789-899: the ffmpeg filter graph format=gray, crop,
+ * signalstats, sobel, signalstats, of which the reference reads the two YAVG values), restated as FS-EDGE v1
+ * on FS-SPEC's gray.  Frames as gs360_frame_stats_u8 (H x W x C uint8, C in {1,3,4}, `stride` 0 = tight, 4-byte aligned base,
+ * red at byte red_index, H, W <= 65535).  For every frame f < n_frames:
+ *   band      rows [band_y0, band_y1), full width, an image of its own (the crop filter runs before the edge filter):
+ *             n = W * (band_y1 - band_y0), sum_gray = the sum of gray over it
+ *   taps      t[row][col], the 3x3 neighbourhood read at mirrored band coordinates m(i, len) = |i| if |i| < len else
+ *             2*len - 1 - |i| on both axes (-1 -> 1, len -> len - 1, len = 1 -> 0: not BORDER_REFLECT_101)
+ *   edge      ga = -t00 - 2*t01 - t02 + t20 + 2*t21 + t22, gb = -t00 + t02 - 2*t10 + 2*t12 - t20 + t22,
+ *             e = min(255, floor(sqrt(ga*ga + gb*gb))) with an exact integer square root; sum_edge = the sum of e over the band
+ * out_dev[f] (device memory) receives the three integer sums; the call clears the records first, and the result does not depend
+ * on the order of the work.  The host forms the two YAVG values as sum / n (gs360/framescore.py).  n_frames may exceed
+ * GS360_MAX_FRAMES (split internally).  Asynchronous on `slot`. */
+typedef struct gs360_frame_edge {
+    int64_t n, sum_gray, sum_edge;
+} gs360_frame_edge;
+int gs360_frame_edge_u8(gs360_ctx *ctx, const void *const *frames, int n_frames, int H, int W, int C, size_t stride,
+                        int red_index, int band_y0, int band_y1, gs360_frame_edge *out_dev, int slot);
+
 /* ---- frame FFT energy (the fft / hybrid metrics' spectrum term) -------------------------------
  * The FFT of fft_energy_fast in cli_tools/gs360_FrameSelector.py (FS:742-786), on the fft input gs360_frame_stats_u8 writes
  * (FS-FFT v1), so that no plane leaves the device.  For every frame f < n_frames, small_dev[f] is that call's
