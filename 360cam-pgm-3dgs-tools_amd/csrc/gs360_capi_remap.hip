@@ -4,7 +4,7 @@
 
 using namespace gs360;
 
-struct gs360_map_plan {         // float maps packed once (gs360_kernels.hip, map plans)
+struct gs360_map_plan {         // float maps packed once (gs360_table.hip, map plans)
     int device = 0;
     int h = 0, w = 0;
     int nearest = 0;
@@ -416,16 +416,17 @@ int gs360_fisheye_views_u8(gs360_ctx* c, const void* const* src_lens, const gs36
     for (int v0 = 0; v0 < n_views; v0 += GS360_MAX_VIEWS) {
         int nv = n_views - v0 < GS360_MAX_VIEWS ? n_views - v0 : GS360_MAX_VIEWS;
         // one launch per group of equal-width sensors keeps a single src_stride in the parameter block
-        FeLaunch L;
-        std::memset(&L, 0, sizeof(L));
+        FeBatch B;
+        std::memset(&B, 0, sizeof(B));
+        FeCommon& L = B.common;
         int base = 0;
         for (int k = 0; k < nv; ++k) {
-            make_fe_view(calibs[v0 + k], views[v0 + k], lens_fov_deg, &L.view[k]);
-            L.view[k].src = (const uint8_t*)src_lens[v0 + k];
-            L.view[k].dst = (uint8_t*)dst[v0 + k];
-            L.view[k].valid_out = valid_out ? valid_out[v0 + k] : nullptr;
-            L.view[k].tile_base = base;
-            base += L.view[k].tiles_x * L.view[k].tiles_y;
+            make_fe_view(calibs[v0 + k], views[v0 + k], lens_fov_deg, &B.view[k]);
+            B.view[k].src = (const uint8_t*)src_lens[v0 + k];
+            B.view[k].dst = (uint8_t*)dst[v0 + k];
+            B.view[k].valid_out = valid_out ? valid_out[v0 + k] : nullptr;
+            B.view[k].tile_base = base;
+            base += B.view[k].tiles_x * B.view[k].tiles_y;
             if (calibs[v0 + k].width != calibs[v0].width)
                 return fail(GS360_ERR_UNSUPPORTED, "views of one call must share the sensor width");
         }
@@ -441,9 +442,9 @@ int gs360_fisheye_views_u8(gs360_ctx* c, const void* const* src_lens, const gs36
         for (int k = 0; k < nv; ++k)
             if (calibs[v0 + k].width < 8 || (uint64_t)L.src_stride * (uint64_t)calibs[v0 + k].height >= ((uint64_t)1 << 32)) L.pipelined = 0;
         if ((uint64_t)L.src_stride >= ((uint64_t)1 << 24)) L.pipelined = 0;
-        L.persist_blocks = c->prop.multiProcessorCount * 8;
-        if (const int v = opt(c, kOptTablePersist); v >= 0) L.persist_blocks = v;
-        HIP_TRY(launch_fisheye(L, C, c->stream[slot]));
+        int persist_blocks = c->prop.multiProcessorCount * 8;
+        if (const int v = opt(c, kOptTablePersist); v >= 0) persist_blocks = v;
+        HIP_TRY(launch_fisheye(B, persist_blocks, C, c->stream[slot]));
     }
     return GS360_OK;
 }

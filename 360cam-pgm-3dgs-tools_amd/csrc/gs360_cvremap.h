@@ -1,5 +1,6 @@
-// gs360_cvremap.h -- cv2.remap's coordinate conversion and its straight-line bilinear sampler (BORDER_CONSTANT), shared by the table
-// kernels (gs360_table.hip) and the LDS-staged table kernel (gs360_tablestage.hip).  DF:2001-2008 / DF:1198-1205 are the call sites.
+// gs360_cvremap.h -- what the cv2.remap family shares: the coordinate conversion, the tile order of a batched launch, the straight-line
+// bilinear sampler (BORDER_CONSTANT) and the launchers' dispatch.  Used by the table and fused-fisheye kernels (gs360_table.hip), the
+// LDS-staged table kernel (gs360_tablestage.hip) and the 16-bit table kernel (gs360_u16.hip).  DF:2001-2008 / DF:1198-1205 are the call sites.
 #pragma once
 #include "gs360_sampler.h"
 
@@ -10,6 +11,27 @@ __device__ __forceinline__ int cv_round(float v) {  // SSE cvtss2si: half-to-eve
     return (int)__builtin_rintf(v);
 }
 __device__ __forceinline__ int sat_s16(int v) { return min(max(v, -32768), 32767); }
+
+// The tile order of a batched launch (table jobs or fisheye views): position b (blockIdx.x, or a step of the persistent walk) -> tile
+// number, >= total_tiles past the last tile.  XCD x (= b % 8) walks tiles [x chunk, (x + 1) chunk).
+__device__ __forceinline__ int table_tile_order(const int chunk, const int b) { return (b & 7) * chunk + (b >> 3); }
+// Tile t < total_tiles: its job / view and its row / column of tiles there.  The job comes back as a pointer into the kernel argument:
+// a copy spills the argument array to scratch memory (see fe_views_tile), and an index that the caller looks up again is a second
+// address computation.
+template <typename Item>
+struct TableTile { const Item* item; int tile_y, tile_x; };
+template <typename Item>
+__device__ __forceinline__ TableTile<Item> table_tile_at(const Item (&item)[GS360_MAX_VIEWS], const int n, int t) {
+    int j = 0;
+    while (j + 1 < n && t >= item[j + 1].tile_base) ++j;
+    TableTile<Item> T;
+    T.item = &item[j];
+    t -= T.item->tile_base;
+    const int tiles_x = T.item->tiles_x;
+    T.tile_y = t / tiles_x;
+    T.tile_x = t - T.tile_y * tiles_x;
+    return T;
+}
 
 template <int C>
 __device__ __forceinline__ void cv_sample_linear(const uint8_t* __restrict__ src, int64_t stride, int W, int H,
@@ -51,6 +73,28 @@ __device__ __forceinline__ void cv_sample_linear(const uint8_t* __restrict__ src
         uint32_t v = blend(in00 ? s00[c] : cv, in01 ? s01[c] : cv, in10 ? s10[c] : cv, in11 ? s11[c] : cv,
                            w00, w01, w10, w11);
         out[c] = outside ? cv : v;
+    }
+}
+
+// Host: the family's kernels are instantiated per channel count and interpolation -- launch(c, interp) is called with the pair as
+// std::integral_constant values (decltype(c)::value is the template argument).
+template <typename Launch>
+hipError_t launch_c_interp(const int C, const int interp, Launch launch) {
+    const auto with_c = [&](auto c) {
+        switch (interp) {
+            case GS360_INTERP_NEAREST: launch(c, std::integral_constant<int, GS360_INTERP_NEAREST>()); break;
+            case GS360_INTERP_LINEAR: launch(c, std::integral_constant<int, GS360_INTERP_LINEAR>()); break;
+            case GS360_INTERP_CUBIC: launch(c, std::integral_constant<int, GS360_INTERP_CUBIC>()); break;
+            case GS360_INTERP_LANCZOS4: launch(c, std::integral_constant<int, GS360_INTERP_LANCZOS4>()); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    };
+    switch (C) {
+        case 1: return with_c(std::integral_constant<int, 1>());
+        case 3: return with_c(std::integral_constant<int, 3>());
+        case 4: return with_c(std::integral_constant<int, 4>());
+        default: return hipErrorInvalidValue;
     }
 }
 

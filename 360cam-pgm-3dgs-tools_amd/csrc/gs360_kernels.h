@@ -90,7 +90,7 @@ struct TableLaunch {
     uint8_t cval[4];
     const int16_t* cubic_tab;
     int32_t pipelined;   // W >= 8 and 32-bit tap offsets: split fetch/blend path allowed
-    int32_t tiles_x;     // filled by launch_table_batch
+    int32_t tiles_x;     // filled by the launcher (table_batch_tiling)
     int32_t tile_base;   // first tile of this job inside the batched launch
     // Lanczos-4, RGB: the 1-D phase table (32 x 8 float32, the floats the 2-D table was built from) and, per 2-D phase, the weight
     // pairs (taps 4, 5) of window rows 4 and 5 of the 2-D table as two dwords -- the block its sum fix-up patches.  With both
@@ -122,7 +122,7 @@ struct FeView {
     int32_t tiles_x, tiles_y, tile_base;
 };
 
-struct FeCommon {          // per-launch constants of fe_views_kernel
+struct FeCommon {          // per-launch constants of fe_views_kernel; the caller fills all but grid_total (tile_base of the views too)
     int32_t total_tiles, chunk, n_views;
     int32_t interp, mask_outside, mask_value;
     int64_t src_stride, dst_stride;
@@ -135,17 +135,6 @@ struct FeCommon {          // per-launch constants of fe_views_kernel
 struct FeBatch {           // kernel argument: all views of one launch + the common block
     FeView view[GS360_MAX_VIEWS];
     FeCommon common;
-};
-
-struct FeLaunch {          // host-side batch description
-    FeView view[GS360_MAX_VIEWS];
-    int32_t n_views, total_tiles, chunk;
-    int32_t interp, mask_outside, mask_value;
-    int64_t src_stride, dst_stride;
-    uint8_t cval[4];
-    const int16_t* cubic_tab;
-    int32_t pipelined;
-    int32_t persist_blocks;  // grid cap of the persistent bicubic RGB variant (0: one tile per workgroup)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -241,7 +230,7 @@ hipError_t launch_table_u16_batch(TableBatch& B, int C, const float* coef, const
 hipError_t launch_table(const TableLaunch& L, int C, hipStream_t s);
 // map plan: float maps (+ valid) -> the packed form; `nearest` packs cvRound(map) instead of the 1/32-pixel fixed point
 constexpr int kMapPlanMaxDim = 4079;     // x + 8, y + 8 of any position that still touches the image fit 12 bits
-// a packed position back as the floats k / 32 (or the integer position for nearest): what the samplers' own cvRound(. * 32) maps to k again
+// (map plans: gs360_table.hip, map_pack_kernel) a packed position back as the floats k / 32 (or the integer position for nearest): what the samplers' own cvRound(. * 32) maps to k again
 __device__ __forceinline__ void planned_coords(const uint32_t P, const uint32_t hb, const bool nearest, float& mx, float& my) {
     const int ix = (int)(P & 0xfffu) - 8, iy = (int)((P >> 12) & 0xfffu) - 8;
     if (nearest) {
@@ -285,8 +274,10 @@ struct TsLaunch {
     uint8_t cval[4];
 };
 hipError_t ts_launch(const TsLaunch& L, int n_cu, size_t lds_per_cu, hipStream_t s);
+void table_batch_tiling(TableBatch& B);                               // tiles_x / tile_base of the jobs, total_tiles, chunk (both launchers)
 hipError_t launch_table_batch(TableBatch& B, int C, hipStream_t s);   // all jobs share C and interp (job[0].interp)
-hipError_t launch_fisheye(const FeLaunch& L, int C, hipStream_t s);
+// persist_blocks: grid cap of the persistent bicubic RGB variant (0: one tile per workgroup)
+hipError_t launch_fisheye(FeBatch& B, int persist_blocks, int C, hipStream_t s);
 
 // Frame sharpness statistics (gs360_framescore.hip, FS-SPEC v1 in DESIGN.md): one batch of up to GS360_MAX_FRAMES frames of one size.
 struct FsLaunch {

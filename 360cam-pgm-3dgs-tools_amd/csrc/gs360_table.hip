@@ -1,9 +1,10 @@
 // gs360_table.hip -- cv2.remap semantics on gfx950: table_remap_kernel (cv2.remap(INTER_NEAREST|LINEAR|CUBIC|LANCZOS4, BORDER_CONSTANT) +
 // valid fill, cli_tools/gs360_DualFisheyeDistortionCalibration.py:2001-2014 / :2031-2043 / :1198-1212), map plans (map_pack_kernel) and the
-// fused dual-fisheye kernel fe_views_kernel (FE-SPEC v1, DF:1759-1823 in-kernel).  Split out of gs360_kernels.hip in round 5; the tiling,
-// lane maps and store paths are described there and in DESIGN.md section 5.
+// fused dual-fisheye kernel fe_views_kernel (FE-SPEC v1, DF:1759-1823 in-kernel).  The tile order, coordinate conversion and launch
+// dispatch the family shares (with gs360_u16.hip and gs360_tablestage.hip) are in gs360_cvremap.h, the gathers and row stores in
+// gs360_sampler.h / gs360_rowstore.h; the tiling, lane maps and store paths are described in DESIGN.md section 5.
 //
-// Compile with -ffp-contract=off (see gs360_kernels.hip).
+// Compile with -ffp-contract=off (see the Makefile).
 #include "gs360_sampler.h"
 #include "gs360_cvremap.h"
 
@@ -356,14 +357,11 @@ __device__ __forceinline__ void cv_cubic_slots_rgb(const uint8_t* __restrict__ s
 // occupancy) of the bilinear path.
 template <int C, int INTERP>
 __device__ __forceinline__ void table_remap_tile(const TableBatch& B, const int b, const int16_t* s_wtab) {
-    int t = (b & 7) * B.chunk + (b >> 3);
+    const int t = table_tile_order(B.chunk, b);
     if (t >= B.total_tiles) return;
-    int j = 0;
-    while (j + 1 < B.n_jobs && t >= B.job[j + 1].tile_base) ++j;
-    const TableLaunch& L = B.job[j];          // wave-uniform: fields are read from the kernel argument on demand
-    t -= L.tile_base;
-    const int tiles_x = L.tiles_x;
-    int tile_y = t / tiles_x, tile_x = t - tile_y * tiles_x;
+    const TableTile<TableLaunch> T = table_tile_at(B.job, B.n_jobs, t);
+    const TableLaunch& L = *T.item;           // wave-uniform: fields are read from the kernel argument on demand
+    const int tile_y = T.tile_y, tile_x = T.tile_x;
     // (behind an optimisation barrier: in the persistent variant the lane-derived constants would otherwise be hoisted out of the
     // tile loop and cost the kernel its fourth wavefront per SIMD)
     const int lane = lane_here(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -395,6 +393,8 @@ __device__ __forceinline__ void table_remap_tile(const TableBatch& B, const int 
         const int ybase = tile_y * kTileH + wave * kRowsPerWave;
         float mxs[kRowsPerWave], mys[kRowsPerWave];
         bool inval[kRowsPerWave];
+        // (this load and the pipelined bilinear sequence below stay written out here, in fe_views_tile and in gs360_u16.hip: as shared
+        // functions over the slot arrays they reschedule every bilinear and nearest instantiation)
         // the twelve map / valid reads of the four row slots go out together: behind a run-time `if (L.valid)` the compiler waits
         // for each valid byte (and with it for the slot's map reads) before it issues the next slot's -- four serial round trips
         // per tile.  Without a valid map the byte is read from the map itself (h * w readable bytes) and ignored.
@@ -540,6 +540,7 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_kernel(const TableBat
     constexpr bool kFastCubic = (INTERP == GS360_INTERP_CUBIC) && (C == 3);
     constexpr bool kLanczosRgb = (INTERP == GS360_INTERP_LANCZOS4) && (C == 3);   // 256 floats + 2048 dwords (cv_lanczos4_rgb_rebuilt)
     __shared__ __attribute__((aligned(16))) int16_t s_wtab[kFastCubic ? 32 * 32 * 16 : (kLanczosRgb ? (256 + 2048) * 2 : 8)];
+    // (fill + walk written out here and in fe_views_kernel: behind one wrapper with a tile callable the persistent kernels schedule differently)
     if constexpr (kFastCubic) {
         if (B.job[0].cubic_tab) {             // (the context's table: the same pointer in every job)
             cubic_lds_fill(s_wtab, B.job[0].cubic_tab, 64 * kWaves);
@@ -571,13 +572,11 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_kernel(const TableBat
 template <int C, int INTERP>
 __device__ __forceinline__ void fe_views_tile(const FeBatch& B, const int b, const int16_t* s_wtab) {
     const FeCommon& L = B.common;
-    int t = (b & 7) * L.chunk + (b >> 3);
+    const int t = table_tile_order(L.chunk, b);
     if (t >= L.total_tiles) return;
-    int j = 0;
-    while (j + 1 < L.n_views && t >= B.view[j + 1].tile_base) ++j;
-    const FeView& V = B.view[j];              // a reference: fields are fetched from the kernel argument on demand
-    t -= V.tile_base;
-    int tile_y = t / V.tiles_x, tile_x = t - tile_y * V.tiles_x;
+    const TableTile<FeView> T = table_tile_at(B.view, L.n_views, t);
+    const FeView& V = *T.item;                // a reference: fields are fetched from the kernel argument on demand
+    const int tile_y = T.tile_y, tile_x = T.tile_x;
     constexpr bool kFastCubic = (INTERP == GS360_INTERP_CUBIC) && (C == 3);
     // (persistent variant: lane-derived constants stay inside the tile, see table_remap_tile)
     const int lane = kFastCubic ? lane_here() : (int)(threadIdx.x & 63), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -694,31 +693,8 @@ void fe_views_kernel(const FeBatch B) {
     }
 }
 
-namespace {
-
-template <int C>
-void launch_table_c(const TableBatch& B, dim3 grid, dim3 block, hipStream_t s) {
-    switch (B.job[0].interp) {
-        case GS360_INTERP_LINEAR: hipLaunchKernelGGL((table_remap_kernel<C, GS360_INTERP_LINEAR>), grid, block, 0, s, B); break;
-        case GS360_INTERP_CUBIC: hipLaunchKernelGGL((table_remap_kernel<C, GS360_INTERP_CUBIC>), grid, block, 0, s, B); break;
-        case GS360_INTERP_LANCZOS4: hipLaunchKernelGGL((table_remap_kernel<C, GS360_INTERP_LANCZOS4>), grid, block, 0, s, B); break;
-        default: hipLaunchKernelGGL((table_remap_kernel<C, GS360_INTERP_NEAREST>), grid, block, 0, s, B); break;
-    }
-}
-
-template <int C>
-void launch_fisheye_c(const FeBatch& B, dim3 grid, dim3 block, hipStream_t s) {
-    switch (B.common.interp) {
-        case GS360_INTERP_LINEAR: hipLaunchKernelGGL((fe_views_kernel<C, GS360_INTERP_LINEAR>), grid, block, 0, s, B); break;
-        case GS360_INTERP_CUBIC: hipLaunchKernelGGL((fe_views_kernel<C, GS360_INTERP_CUBIC>), grid, block, 0, s, B); break;
-        case GS360_INTERP_LANCZOS4: hipLaunchKernelGGL((fe_views_kernel<C, GS360_INTERP_LANCZOS4>), grid, block, 0, s, B); break;
-        default: hipLaunchKernelGGL((fe_views_kernel<C, GS360_INTERP_NEAREST>), grid, block, 0, s, B); break;
-    }
-}
-
-}  // namespace
-
-hipError_t launch_table_batch(TableBatch& B, int C, hipStream_t s) {
+// Tiles of a batch's jobs in launch order: tiles_x / tile_base per job, total_tiles and chunk = ceil(total_tiles / 8) (XCD order).
+void table_batch_tiling(TableBatch& B) {
     int base = 0;
     for (int j = 0; j < B.n_jobs; ++j) {
         TableLaunch& L = B.job[j];
@@ -728,19 +704,19 @@ hipError_t launch_table_batch(TableBatch& B, int C, hipStream_t s) {
     }
     B.total_tiles = base;
     B.chunk = (base + 7) / 8;
-    if (base == 0) return hipSuccess;
+}
+
+hipError_t launch_table_batch(TableBatch& B, int C, hipStream_t s) {
+    table_batch_tiling(B);
+    if (B.total_tiles == 0) return hipSuccess;
     dim3 grid((unsigned)(B.chunk * 8)), block(64 * kWaves);
     // persistent workgroups for the kernel with a per-workgroup LDS table (see table_remap_kernel)
     if (C == 3 && (B.job[0].interp == GS360_INTERP_CUBIC || B.job[0].interp == GS360_INTERP_LANCZOS4) && B.persist_blocks > 0 &&
         (unsigned)B.persist_blocks < grid.x)
         grid.x = (unsigned)(B.persist_blocks + 7) & ~7u;
-    switch (C) {
-        case 1: launch_table_c<1>(B, grid, block, s); break;
-        case 3: launch_table_c<3>(B, grid, block, s); break;
-        case 4: launch_table_c<4>(B, grid, block, s); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_c_interp(C, B.job[0].interp, [&](auto c, auto interp) {
+        hipLaunchKernelGGL((table_remap_kernel<decltype(c)::value, decltype(interp)::value>), grid, block, 0, s, B);
+    });
 }
 
 hipError_t launch_map_pack(const float* map_x, const float* map_y, const uint8_t* valid, int64_t n, int nearest,
@@ -758,35 +734,16 @@ hipError_t launch_table(const TableLaunch& L, int C, hipStream_t s) {
     return launch_table_batch(B, C, s);
 }
 
-hipError_t launch_fisheye(const FeLaunch& L, int C, hipStream_t s) {
-    FeBatch B;
-    int base = 0;
-    for (int k = 0; k < L.n_views; ++k) {
-        B.view[k] = L.view[k];
-        B.view[k].tile_base = base;
-        base += L.view[k].tiles_x * L.view[k].tiles_y;
-    }
+hipError_t launch_fisheye(FeBatch& B, int persist_blocks, int C, hipStream_t s) {
     FeCommon& K = B.common;
-    K.n_views = L.n_views;
-    K.total_tiles = base;
-    K.chunk = (base + 7) / 8;
-    K.interp = L.interp; K.mask_outside = L.mask_outside; K.mask_value = L.mask_value;
-    K.src_stride = L.src_stride; K.dst_stride = L.dst_stride;
-    for (int i = 0; i < 4; ++i) K.cval[i] = L.cval[i];
-    K.cubic_tab = L.cubic_tab;
-    K.pipelined = L.pipelined;
-    if (base == 0) return hipSuccess;
+    if (K.total_tiles == 0) return hipSuccess;
     dim3 grid((unsigned)(K.chunk * 8)), block(64 * kWaves);
     K.grid_total = (int32_t)grid.x;
-    if (C == 3 && L.interp == GS360_INTERP_CUBIC && L.persist_blocks > 0 && (unsigned)L.persist_blocks < grid.x)
-        grid.x = (unsigned)(L.persist_blocks + 7) & ~7u;
-    switch (C) {
-        case 1: launch_fisheye_c<1>(B, grid, block, s); break;
-        case 3: launch_fisheye_c<3>(B, grid, block, s); break;
-        case 4: launch_fisheye_c<4>(B, grid, block, s); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (C == 3 && K.interp == GS360_INTERP_CUBIC && persist_blocks > 0 && (unsigned)persist_blocks < grid.x)
+        grid.x = (unsigned)(persist_blocks + 7) & ~7u;
+    return launch_c_interp(C, K.interp, [&](auto c, auto interp) {
+        hipLaunchKernelGGL((fe_views_kernel<decltype(c)::value, decltype(interp)::value>), grid, block, 0, s, B);
+    });
 }
 
 }  // namespace gs360

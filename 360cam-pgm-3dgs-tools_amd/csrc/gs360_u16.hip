@@ -1,5 +1,6 @@
 // gs360_u16.hip -- cv2.remap on CV_16U sources and the arithmetic self-test.
 // (The 16-bit EQUIRECT sampler lives in gs360_kernels.hip: eq_views_kernel<..., ES = 2>, the 8-bit kernel's skeleton on 2-byte samples.)
+// cvRound / the int16 saturation, the launch's tiling and the C x interpolation dispatch are the cv2.remap family's (gs360_cvremap.h).
 //
 //   table_remap_u16_kernel   cv2.remap on CV_16U sources (DF:735 keeps 16-bit inputs at native depth; DF:2001-2014):
 //                            OpenCV routes ushort to its FLOAT-weight samplers -- 2-D weight = cy[k1] * cx[k2] in float32
@@ -16,6 +17,7 @@
 // whole dwords (gs360_rowstore.h).
 #include "gs360_eqspec.h"
 #include "gs360_rowstore.h"
+#include "gs360_cvremap.h"
 
 namespace gs360 {
 
@@ -23,12 +25,17 @@ namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int cv_round_u16(float v) {
-    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return (int)0x80000000;
-    return (int)__builtin_rintf(v);
+__device__ __forceinline__ uint16_t sat_u16(float v) { return (uint16_t)min(max(cv_round(v), 0), 65535); }
+
+// N halfwords, as floats, that start o bytes into the dword-aligned row read r (N / 2 + 1 dwords): shifted into place, then split.
+template <int N>
+__device__ __forceinline__ void row_halfwords(const uint32_t (&r)[N / 2 + 1], const uint32_t o, float (&v)[N]) {
+    uint32_t d[N / 2];
+#pragma unroll
+    for (int t = 0; t < N / 2; ++t) d[t] = __builtin_amdgcn_alignbyte(r[t + 1], r[t], o);
+#pragma unroll
+    for (int t = 0; t < N; ++t) v[t] = (float)((t & 1) ? (d[t >> 1] >> 16) : (d[t >> 1] & 0xffffu));
 }
-__device__ __forceinline__ int sat_s16_u16(int v) { return min(max(v, -32768), 32767); }
-__device__ __forceinline__ uint16_t sat_u16(float v) { return (uint16_t)min(max(cv_round_u16(v), 0), 65535); }
 
 // cv2.remap(CV_16U) -- see the file header.  coef: 32 phases x (2 + 4 + 8) float32 1-D coefficients (linear, cubic, lanczos4).
 // All jobs of a call (the views of a dual-fisheye pair) in ONE launch, tiles dealt to the XCDs in contiguous chunks like the
@@ -36,6 +43,8 @@ __device__ __forceinline__ uint16_t sat_u16(float v) { return (uint16_t)min(max(
 template <int C, int INTERP>
 __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const TableBatch B, const float* __restrict__ coef, const uint16_t c0,
                                                                       const uint16_t c1, const uint16_t c2, const uint16_t c3) {
+    // (the tile lookup of table_tile_at, written out: through the shared step the compiler lays the plan / float-map branches out the other
+    // way round and every 16-bit instantiation is scheduled differently)
     int t = (blockIdx.x & 7) * B.chunk + (blockIdx.x >> 3);
     if (t >= B.total_tiles) return;
     int j = 0;
@@ -66,11 +75,11 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const Tabl
     float mxs[kRowsPerWave], mys[kRowsPerWave];
     bool inval[kRowsPerWave], done[kRowsPerWave];
     uint32_t px[kRowsPerWave][4];
-    // (branch-free: without a valid map the byte is read from the map itself and ignored -- see table_remap_kernel)
+    // (branch-free: without a valid map the byte is read from the map itself and ignored -- see table_remap_tile, gs360_table.hip)
     const uint8_t* __restrict__ vptr = vmask ? vmask : reinterpret_cast<const uint8_t*>(map_x);
     const bool has_valid = vmask != nullptr;
     uint8_t vbyte[kRowsPerWave];
-    if (T.packed) {                           // a map plan (wave-uniform): one dword and one byte per pixel, see gs360_kernels.hip
+    if (T.packed) {                           // a map plan (wave-uniform): one dword and one byte per pixel, see gs360_table.hip
         uint32_t pw[kRowsPerWave];
 #pragma unroll
         for (int s = 0; s < kRowsPerWave; ++s) {
@@ -107,8 +116,8 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const Tabl
             bool fast[kRowsPerWave];
 #pragma unroll
             for (int s = 0; s < kRowsPerWave; ++s) {
-                const int sx = cv_round_u16(mxs[s] * 32.0f), sy = cv_round_u16(mys[s] * 32.0f);
-                const int ix = sat_s16_u16(sx >> 5), iy = sat_s16_u16(sy >> 5);
+                const int sx = cv_round(mxs[s] * 32.0f), sy = cv_round(mys[s] * 32.0f);
+                const int ix = sat_s16(sx >> 5), iy = sat_s16(sy >> 5);
                 fast[s] = !inval[s] && ix >= 0 && iy >= 0 && ix + 3 <= W && iy + 2 <= H && ybase + s < th;
                 const int xa = min(max(ix, 0), W - 3), ya = min(max(iy, 0), H - 2);
                 const uint8_t* p0 = reinterpret_cast<const uint8_t*>(src) + (size_t)ya * (size_t)T.src_stride + (size_t)xa * 6;
@@ -126,20 +135,12 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const Tabl
 #pragma unroll
             for (int s = 0; s < kRowsPerWave; ++s) {
                 if (!fast[s]) continue;
-                const uint32_t o0 = sh[s] & 3u, o1 = sh[s] >> 2;
-                const uint32_t d[2][3] = {{__builtin_amdgcn_alignbyte(ra[s][1], ra[s][0], o0), __builtin_amdgcn_alignbyte(ra[s][2], ra[s][1], o0),
-                                           __builtin_amdgcn_alignbyte(ra[s][3], ra[s][2], o0)},
-                                          {__builtin_amdgcn_alignbyte(rb[s][1], rb[s][0], o1), __builtin_amdgcn_alignbyte(rb[s][2], rb[s][1], o1),
-                                           __builtin_amdgcn_alignbyte(rb[s][3], rb[s][2], o1)}};
-                float v[2][6];
-#pragma unroll
-                for (int ky = 0; ky < 2; ++ky) {
-                    v[ky][0] = (float)(d[ky][0] & 0xffffu); v[ky][1] = (float)(d[ky][0] >> 16); v[ky][2] = (float)(d[ky][1] & 0xffffu);
-                    v[ky][3] = (float)(d[ky][1] >> 16); v[ky][4] = (float)(d[ky][2] & 0xffffu); v[ky][5] = (float)(d[ky][2] >> 16);
-                }
+                float v0[6], v1[6];
+                row_halfwords<6>(ra[s], sh[s] & 3u, v0);
+                row_halfwords<6>(rb[s], sh[s] >> 2, v1);
                 const float w00 = cys[s].x * cxs[s].x, w01 = cys[s].x * cxs[s].y, w10 = cys[s].y * cxs[s].x, w11 = cys[s].y * cxs[s].y;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) px[s][c] = sat_u16(v[0][c] * w00 + v[0][3 + c] * w01 + v[1][c] * w10 + v[1][3 + c] * w11);
+                for (int c = 0; c < 3; ++c) px[s][c] = sat_u16(v0[c] * w00 + v0[3 + c] * w01 + v1[c] * w10 + v1[3 + c] * w11);
                 done[s] = true;
             }
         }
@@ -155,8 +156,8 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const Tabl
             int fxs[kRowsPerWave], fys[kRowsPerWave];
             bool fast[kRowsPerWave];
             auto issue = [&](int sl, uint32_t (&buf)[4][7]) {
-                const int sx = cv_round_u16(mxs[sl] * 32.0f), sy = cv_round_u16(mys[sl] * 32.0f);
-                const int x0 = sat_s16_u16(sx >> 5) - 1, y0 = sat_s16_u16(sy >> 5) - 1;
+                const int sx = cv_round(mxs[sl] * 32.0f), sy = cv_round(mys[sl] * 32.0f);
+                const int x0 = sat_s16(sx >> 5) - 1, y0 = sat_s16(sy >> 5) - 1;
                 fxs[sl] = sx & 31;
                 fys[sl] = sy & 31;
                 fast[sl] = !inval[sl] && x0 >= 0 && y0 >= 0 && x0 + 6 <= W && y0 + 4 <= H && ybase + sl < th;
@@ -180,21 +181,19 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const Tabl
                 float sum2 = 0.f;
 #pragma unroll
                 for (int ky = 0; ky < 4; ++ky) {
-                    uint32_t d[6];
-#pragma unroll
-                    for (int t = 0; t < 6; ++t) d[t] = __builtin_amdgcn_alignbyte(buf[ky][t + 1], buf[ky][t], sh[sl]);
+                    float v[12];
+                    row_halfwords<12>(buf[ky], sh[sl], v);
                     const float cyk = cy[ky];
                     f32x2 rs01 = {0.f, 0.f};
                     float rs2 = 0.f;
 #pragma unroll
                     for (int kx = 0; kx < 4; ++kx) {
                         const int e = kx * 3;                               // halfwords e, e + 1, e + 2 = the tap's three channels
-                        auto hw = [&](int h) { return (float)((h & 1) ? (d[h >> 1] >> 16) : (d[h >> 1] & 0xffffu)); };
                         const float w = cyk * cx[kx];
-                        const f32x2 v01 = {hw(e), hw(e + 1)};
+                        const f32x2 v01 = {v[e], v[e + 1]};
                         const f32x2 w01 = {w, w};
                         const f32x2 t01 = v01 * w01;
-                        const float t2 = hw(e + 2) * w;
+                        const float t2 = v[e + 2] * w;
                         rs01 = kx == 0 ? t01 : rs01 + t01;
                         rs2 = kx == 0 ? t2 : rs2 + t2;
                     }
@@ -226,15 +225,15 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const Tabl
             return;
         }
         if (interp == GS360_INTERP_NEAREST) {
-            const int ix = sat_s16_u16(cv_round_u16(mx)), iy = sat_s16_u16(cv_round_u16(my));
+            const int ix = sat_s16(cv_round(mx)), iy = sat_s16(cv_round(my));
             const bool in = (unsigned)ix < (unsigned)W && (unsigned)iy < (unsigned)H;
 #pragma unroll
             for (int c = 0; c < C; ++c) out[c] = in ? src[(size_t)iy * ss + (size_t)ix * C + c] : cval[c];
             return;
         }
-        const int sx = cv_round_u16(mx * 32.0f), sy = cv_round_u16(my * 32.0f);
+        const int sx = cv_round(mx * 32.0f), sy = cv_round(my * 32.0f);
         const int fx = sx & 31, fy = sy & 31;
-        const int ix = sat_s16_u16(sx >> 5), iy = sat_s16_u16(sy >> 5);
+        const int ix = sat_s16(sx >> 5), iy = sat_s16(sy >> 5);
         const int x0 = ix - (ks / 2 - 1), y0 = iy - (ks / 2 - 1);
         if (x0 >= W || x0 + ks <= 0 || y0 >= H || y0 + ks <= 0) {
 #pragma unroll
@@ -256,11 +255,8 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const Tabl
                         const uint16_t* pp = src + (size_t)(y0 + ky) * ss + (size_t)x0 * 3;
                         const uint32_t o = (uint32_t)reinterpret_cast<uintptr_t>(pp) & 3u;
                         const uint32_t* q = reinterpret_cast<const uint32_t*>(__builtin_assume_aligned(reinterpret_cast<const uint8_t*>(pp) - o, 4));
-                        const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-                        const uint32_t d0 = __builtin_amdgcn_alignbyte(q1, q0, o), d1 = __builtin_amdgcn_alignbyte(q2, q1, o),
-                                       d2 = __builtin_amdgcn_alignbyte(q3, q2, o);
-                        v[ky][0] = (float)(d0 & 0xffffu); v[ky][1] = (float)(d0 >> 16); v[ky][2] = (float)(d1 & 0xffffu);
-                        v[ky][3] = (float)(d1 >> 16); v[ky][4] = (float)(d2 & 0xffffu); v[ky][5] = (float)(d2 >> 16);
+                        const uint32_t r[4] = {q[0], q[1], q[2], q[3]};
+                        row_halfwords<6>(r, o, v[ky]);
                     }
                     const float w00 = cy[0] * cx[0], w01 = cy[0] * cx[1], w10 = cy[1] * cx[0], w11 = cy[1] * cx[1];
 #pragma unroll
@@ -281,7 +277,7 @@ __global__ __launch_bounds__(64 * kWaves) void table_remap_u16_kernel(const Tabl
                         const uint16_t* pp = src + (size_t)(y0 + ky) * ss + (size_t)x0 * 3;
                         const uint32_t o = (uint32_t)reinterpret_cast<uintptr_t>(pp) & 3u;
                         const uint32_t* q = reinterpret_cast<const uint32_t*>(__builtin_assume_aligned(reinterpret_cast<const uint8_t*>(pp) - o, 4));
-                        uint32_t r[ND + 1], d[ND];
+                        uint32_t r[ND + 1], d[ND];      // (row_halfwords, written out: its eager conversions reschedule the bicubic kernel)
 #pragma unroll
                         for (int t = 0; t < ND + 1; ++t) r[t] = q[t];
 #pragma unroll
@@ -437,36 +433,13 @@ hipError_t launch_arith_selftest(uint32_t seed, int blocks, int iters, unsigned 
 }
 
 hipError_t launch_table_u16_batch(TableBatch& B, int C, const float* coef, const uint16_t cval[4], hipStream_t s) {
-    int base = 0;
-    for (int j = 0; j < B.n_jobs; ++j) {
-        TableLaunch& L = B.job[j];
-        L.tiles_x = (L.w + kTileW - 1) / kTileW;
-        L.tile_base = base;
-        base += L.tiles_x * ((L.h + kTileH - 1) / kTileH);
-    }
-    B.total_tiles = base;
-    B.chunk = (base + 7) / 8;
-    if (base == 0) return hipSuccess;
+    table_batch_tiling(B);                    // (16-bit jobs never take the flat form)
+    if (B.total_tiles == 0) return hipSuccess;
     dim3 grid((unsigned)(B.chunk * 8)), block(64 * kWaves);
-    const int interp = B.job[0].interp;       // the same for every job of a call
-#define GS360_T16(CC, II) hipLaunchKernelGGL((table_remap_u16_kernel<CC, II>), grid, block, 0, s, B, coef, cval[0], cval[1], cval[2], cval[3])
-#define GS360_T16_C(CC)                                                             \
-    switch (interp) {                                                               \
-        case GS360_INTERP_NEAREST: GS360_T16(CC, GS360_INTERP_NEAREST); break;      \
-        case GS360_INTERP_LINEAR: GS360_T16(CC, GS360_INTERP_LINEAR); break;        \
-        case GS360_INTERP_CUBIC: GS360_T16(CC, GS360_INTERP_CUBIC); break;          \
-        case GS360_INTERP_LANCZOS4: GS360_T16(CC, GS360_INTERP_LANCZOS4); break;    \
-        default: return hipErrorInvalidValue;                                       \
-    }
-    switch (C) {
-        case 1: GS360_T16_C(1) break;
-        case 3: GS360_T16_C(3) break;
-        case 4: GS360_T16_C(4) break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GS360_T16_C
-#undef GS360_T16
-    return hipGetLastError();
+    return launch_c_interp(C, B.job[0].interp, [&](auto c, auto interp) {      // (the same interpolation for every job of a call)
+        hipLaunchKernelGGL((table_remap_u16_kernel<decltype(c)::value, decltype(interp)::value>), grid, block, 0, s, B, coef, cval[0], cval[1], cval[2],
+                           cval[3]);
+    });
 }
 
 }  // namespace gs360
