@@ -1,5 +1,6 @@
-// gs360_capi_codec.hip -- host-only image-codec helpers of libgs360hip.so (include/gs360.h): PNG scanline unfiltering and TIFF
-// LZW strip decoding for the Python-side codec (gs360/imageio.py).  No GPU involved.
+// gs360_capi_codec.hip -- image-codec entry points of libgs360hip.so (include/gs360.h): PNG scanline unfiltering and TIFF LZW strip
+// decoding for the Python-side codec (gs360/imageio.py; host only, no GPU involved), and the glue of the device JPEG scans
+// (gs360_jpeg.hip).
 #include "gs360_capi_internal.h"
 
 using namespace gs360;
@@ -101,5 +102,106 @@ int gs360_tiff_lzw_decode(const uint8_t* in, size_t in_len, uint8_t* out, size_t
         if (!more) break;
     }
     *out_len = op;
+    return GS360_OK;
+}
+
+// ---- baseline JPEG scans on the device (JPG-SPEC v1; kernels in gs360_jpeg.hip) ------------------------------------------
+namespace {
+
+int check_jpeg_geometry(int H, int W, int C, int restart_interval) {
+    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(GS360_ERR_ARG, "JPEG sides are 1..65535 (got %d x %d)", W, H);
+    if (C != 1 && C != 3) return fail(GS360_ERR_UNSUPPORTED, "the JPEG encoder takes C = 1 or 3 (got %d)", C);
+    if (restart_interval < 1 || restart_interval > 65535) return fail(GS360_ERR_ARG, "restart interval %d outside 1..65535", restart_interval);
+    return 0;
+}
+
+inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+}  // namespace
+
+int gs360_jpeg_scan_bound(int H, int W, int C, int restart_interval, size_t* bytes) {
+    if (!bytes) return fail(GS360_ERR_ARG, "NULL argument");
+    if (int rc = check_jpeg_geometry(H, W, C, restart_interval)) return rc;
+    // a block's 64 coefficients cost at most 26 bits each (a 16-bit code and 10 value bits): 208 bytes, twice that when every byte is
+    // stuffed; an interval adds at most its marker and one slack byte
+    const size_t mcus = (size_t)((H + 7) / 8) * (size_t)((W + 7) / 8);
+    const size_t intervals = (mcus + restart_interval - 1) / restart_interval;
+    *bytes = mcus * C * 416 + intervals * 3;
+    return GS360_OK;
+}
+
+int gs360_jpeg_scan_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval,
+                       uint64_t* lengths_dev, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
+    if (n_jobs == 0) return GS360_OK;
+    if (!jobs || !lengths_dev) return fail(GS360_ERR_ARG, "NULL argument");
+    if (quality < 1 || quality > 100) return fail(GS360_ERR_ARG, "quality %d outside 1..100", quality);
+    for (int k = 0; k < n_jobs; ++k) {
+        const gs360_jpeg_job& j = jobs[k];
+        if (int rc = check_jpeg_geometry(j.H, j.W, j.C, restart_interval)) return rc;
+        if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
+        if (j.src_stride && j.src_stride < (size_t)j.W * j.C) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream[slot];
+    Staging& st = c->stage[slot];
+    // scratch of a launch batch: coefficients, the quantiser table, the intervals' lengths and offsets.  Sized for the call's largest
+    // batch before the first launch (growing it later would free memory that queued kernels still use)
+    auto layout = [](int64_t blocks, int64_t intervals, size_t* quant_at, size_t* len_at, size_t* off_at) {
+        *quant_at = round_up((size_t)blocks * 128, 256);
+        *len_at = *quant_at + 128 * sizeof(JpQuant);
+        *off_at = *len_at + round_up((size_t)intervals * 4, 256);
+        return *off_at + (size_t)intervals * 8;
+    };
+    size_t need = 0;
+    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
+        int64_t blocks = 0, intervals = 0;
+        for (int k = k0; k < std::min(n_jobs, k0 + GS360_MAX_VIEWS); ++k) {
+            const int64_t mcus = (int64_t)((jobs[k].H + 7) / 8) * ((jobs[k].W + 7) / 8);
+            blocks += mcus * jobs[k].C;
+            intervals += (mcus + restart_interval - 1) / restart_interval;
+        }
+        size_t a, b, d;
+        need = std::max(need, layout(blocks, intervals, &a, &b, &d));
+    }
+    if (int rc = ensure(&st.d_jpeg, &st.jpeg_cap, need)) return rc;
+    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
+        JpLaunch L;
+        std::memset(&L, 0, sizeof(L));
+        L.n_jobs = std::min(GS360_MAX_VIEWS, n_jobs - k0);
+        L.quality = quality;
+        L.ri = restart_interval;
+        int64_t blocks = 0, tiles = 0, intervals = 0;
+        for (int k = 0; k < L.n_jobs; ++k) {
+            const gs360_jpeg_job& j = jobs[k0 + k];
+            JpJob& J = L.job[k];
+            J.src = (const uint8_t*)j.src;
+            J.out = (uint8_t*)j.out;
+            J.cap = j.out_capacity;
+            J.stride = (int64_t)(j.src_stride ? j.src_stride : (size_t)j.W * j.C);
+            J.H = j.H; J.W = j.W; J.C = j.C;
+            J.bw = (j.W + 7) / 8;
+            J.n_mcu = J.bw * ((j.H + 7) / 8);
+            J.n_int = (J.n_mcu + restart_interval - 1) / restart_interval;
+            J.tiles_x = (J.bw + 31) / 32;
+            J.coef_base = blocks; J.tile_base = (int32_t)tiles; J.int_base = (int32_t)intervals;
+            blocks += (int64_t)J.n_mcu * j.C;
+            tiles += (int64_t)J.tiles_x * ((j.H + 7) / 8);
+            intervals += J.n_int;
+        }
+        if (tiles > INT32_MAX || intervals > INT32_MAX) return fail(GS360_ERR_ARG, "JPEG batch too large");
+        L.total_tiles = (int32_t)tiles;
+        L.total_int = (int32_t)intervals;
+        size_t quant_at, len_at, off_at;
+        if (layout(blocks, intervals, &quant_at, &len_at, &off_at) > st.jpeg_cap) return fail(GS360_ERR_ARG, "JPEG scratch layout");
+        uint8_t* base = (uint8_t*)st.d_jpeg;
+        L.coef = (int16_t*)base;
+        L.quant = (JpQuant*)(base + quant_at);
+        L.int_len = (uint32_t*)(base + len_at);
+        L.int_off = (uint64_t*)(base + off_at);
+        L.lengths = lengths_dev + k0;
+        HIP_TRY(launch_jpeg_scan(L, s));
+    }
     return GS360_OK;
 }

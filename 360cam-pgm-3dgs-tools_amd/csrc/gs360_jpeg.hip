@@ -1,0 +1,380 @@
+// gs360_jpeg.hip -- baseline JPEG scans of 8-bit images resident on the device (JPG-SPEC v1).
+//
+// Reference: the image writer behind the views of cli_tools/gs360_360PerspCut.py:327-338 (ffmpeg's mjpeg encoder, `-q:v`), which the
+// host path leaves to Pillow.  Everything is integer arithmetic, so the scan is pinned byte for byte (tests/jpegenc_np.py).
+//
+//   set-up     the quantiser tables of `quality` (IJG's scaling of Annex K.1) as reciprocals, on the launch stream
+//   transform  one workgroup per strip of 8 rows x 256 columns: the rows' bytes -> LDS with dword loads; a lane per block row converts
+//              its 8 pixels to Y / Cb / Cr and runs the row product, a lane per block column the column product and the quantiser;
+//              the zig-zag int16 coefficients leave LDS as whole dwords, the blocks of an MCU side by side
+//   entropy    one wavefront per restart interval, one lane per zig-zag coefficient: the non-zero mask is a 64-bit ballot, a lane's zero
+//              run the gap to the next set bit below it, its bits (ZRLs, code, value) one word of <= 59 bits; a cross-lane prefix sum of
+//              the bit lengths places the words in an LDS bit buffer, and byte stuffing runs over the packed bytes (ballot + popcount)
+//   placement  size first: the entropy kernel runs once without stores for the intervals' lengths, one workgroup per image turns them
+//              into offsets (exclusive scan) and the scan's length, and the same kernel runs again writing at its final offsets.
+//              An image whose scan exceeds its capacity gets the length UINT64_MAX and is not written at all.
+// No float atomics; the LDS bit buffer is filled with integer ORs, so nothing depends on the order of the work.
+#include "gs360_kernels.h"
+
+namespace gs360 {
+namespace {
+
+constexpr int kJpThreads = 256;
+constexpr int kJpTileW = 256;                          // columns of one transform strip: 32 blocks
+constexpr int kJpTileBlocks = kJpTileW / 8;
+constexpr int kJpRawDw = 196;                          // dwords of one staged row: 256 * 3 bytes + 3 of alignment, rounded up
+
+// ITU-T T.81 Annex K.1, natural order
+__constant__ uint8_t kJpQBase[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+// zig-zag position of natural index n
+__constant__ uint8_t kJpZpos[64] = {0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53,
+                                    10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+
+// Annex K.3 as (code << 5) | length: per table 256 AC entries by (run << 4) | size, then 12 DC entries by size
+constexpr int kJpHuffN = 272;
+struct JpHuff { uint32_t e[2][kJpHuffN]; };
+constexpr uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+constexpr uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+constexpr uint8_t kAcVals[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+     0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+     0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+     0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+     0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa}};
+constexpr JpHuff jp_make_huff() {       // Annex C: codes in order of length, symbols in HUFFVAL order
+    JpHuff h{};
+    for (int t = 0; t < 2; ++t) {
+        uint32_t code = 0;
+        int k = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (int i = 0; i < kAcBits[t][len - 1]; ++i) h.e[t][kAcVals[t][k++]] = (code++ << 5) | (uint32_t)len;
+            code <<= 1;
+        }
+        code = 0;
+        k = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (int i = 0; i < kDcBits[t][len - 1]; ++i) h.e[t][256 + k++] = (code++ << 5) | (uint32_t)len;   // DC HUFFVAL is 0..11
+            code <<= 1;
+        }
+    }
+    return h;
+}
+constexpr JpHuff kJpHuffHost = jp_make_huff();
+static_assert(kJpHuffHost.e[0][0x00] == ((0xAu << 5) | 4) && kJpHuffHost.e[0][0xF0] == ((0x7F9u << 5) | 11), "Annex K.5: EOB 1010, ZRL 11111111001");
+static_assert(kJpHuffHost.e[1][0x00] == ((0x0u << 5) | 2) && kJpHuffHost.e[1][0xF0] == ((0x3FAu << 5) | 10), "Annex K.6: EOB 00, ZRL 1111111010");
+__constant__ JpHuff kJpHuff = kJpHuffHost;
+
+// ---- set-up: quantiser tables ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(128) jp_quant_kernel(JpQuant* q, int quality) {
+    const int t = threadIdx.x;            // table * 64 + natural index
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    const int v = min(max(((int)kJpQBase[t >> 6][t & 63] * s + 50) / 100, 1), 255);
+    JpQuant e;
+    e.recip = (1u << 24) / (uint32_t)v + 1u;
+    e.half = (uint16_t)(v >> 1);
+    e.zpos = kJpZpos[t & 63];
+    q[t] = e;
+}
+
+// ---- transform ------------------------------------------------------------------------------------------------------------------
+// out[u] = sum_x A[u][x] * s[x], A[u][x] = round(2^14 * k(u)/2 * cos((2x+1) u pi / 16)): the rows of A are even or odd about their
+// middle, so each output is four products of the sums or differences of mirrored inputs (the same integers, fewer multiplies)
+__device__ __forceinline__ void jp_dct8(const int (&s)[8], int (&o)[8]) {
+    constexpr int c1 = 8035, c2 = 7568, c3 = 6811, c4 = 5793, c5 = 4551, c6 = 3135, c7 = 1598;
+    const int e0 = s[0] + s[7], e1 = s[1] + s[6], e2 = s[2] + s[5], e3 = s[3] + s[4];
+    const int d0 = s[0] - s[7], d1 = s[1] - s[6], d2 = s[2] - s[5], d3 = s[3] - s[4];
+    o[0] = c4 * e0 + c4 * e1 + c4 * e2 + c4 * e3;
+    o[4] = c4 * e0 - c4 * e1 - c4 * e2 + c4 * e3;
+    o[2] = c2 * e0 + c6 * e1 - c6 * e2 - c2 * e3;
+    o[6] = c6 * e0 - c2 * e1 + c2 * e2 - c6 * e3;
+    o[1] = c1 * d0 + c3 * d1 + c5 * d2 + c7 * d3;
+    o[3] = c3 * d0 - c7 * d1 - c1 * d2 - c5 * d3;
+    o[5] = c5 * d0 - c1 * d1 + c7 * d2 + c3 * d3;
+    o[7] = c7 * d0 - c5 * d1 + c3 * d2 - c1 * d3;
+}
+
+struct JpLds {
+    uint32_t raw[8][kJpRawDw];
+    alignas(16) int16_t t1[3][8][kJpTileW];           // row products, [component][row][column]
+    alignas(16) int16_t zz[3 * kJpTileBlocks][64];    // [block * C + component][zig-zag position]
+    JpQuant quant[128];
+};
+
+template <int C>
+__device__ __forceinline__ void jp_transform_tile(JpLds& S, const JpLaunch& L, const JpJob& J, int t) {
+    const int tid = threadIdx.x;
+    const int by = t / J.tiles_x, tx = t - by * J.tiles_x;
+    const int bx0 = tx * kJpTileBlocks, nb = min(kJpTileBlocks, J.bw - bx0);
+    const int x0 = bx0 * 8, npx = min(kJpTileW, J.W - x0);
+    // 1. the strip's rows (the last row repeats below the image) -> LDS, dword loads
+    uint32_t v[8];
+    int off[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int y = min(by * 8 + r, J.H - 1);
+        const uintptr_t a = (uintptr_t)(J.src + (int64_t)y * J.stride + (int64_t)x0 * C);
+        const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
+        off[r] = (int)(a & 3);
+        const int ndw = (off[r] + npx * C + 3) >> 2;
+        v[r] = tid < ndw ? q[tid] : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+        if (tid < kJpRawDw) S.raw[r][tid] = v[r];
+    __syncthreads();
+    // 2. a lane per block row: colour, level shift, row product
+    {
+        const int b = tid & (kJpTileBlocks - 1), y = tid >> 5;
+        if (b < nb) {
+            int s[C][8];
+            int offy = 0;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) offy = r == y ? off[r] : offy;
+            const uint8_t* row = (const uint8_t*)S.raw[y] + offy;
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+                const uint8_t* p = row + min(b * 8 + x, npx - 1) * C;      // the last column repeats beside the image
+                if constexpr (C == 1) {
+                    s[0][x] = (int)p[0] - 128;
+                } else {
+                    const int R = p[0], G = p[1], B = p[2];
+                    s[0][x] = ((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128;
+                    s[1][x] = ((-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16) - 128;
+                    s[2][x] = ((32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16) - 128;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                int o[8];
+                jp_dct8(s[c], o);
+                union { int16_t h[8]; uint4 q; } w;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) w.h[u] = (int16_t)((o[u] + 1024) >> 11);
+                *(uint4*)&S.t1[c][y][b * 8] = w.q;
+            }
+        }
+    }
+    __syncthreads();
+    // 3. a lane per block column: column product, quantiser, zig-zag
+    {
+        const int b = tid >> 3, u = tid & 7;
+        if (b < nb) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                int s[8], o[8];
+#pragma unroll
+                for (int y = 0; y < 8; ++y) s[y] = S.t1[c][y][tid];
+                jp_dct8(s, o);
+#pragma unroll
+                for (int vv = 0; vv < 8; ++vv) {
+                    const int coef = (o[vv] + 65536) >> 17;
+                    const JpQuant e = S.quant[(c ? 64 : 0) + vv * 8 + u];
+                    const uint32_t n = (uint32_t)abs(coef) + e.half;
+                    const int q = (int)__umulhi(n << 8, e.recip);              // n / Q
+                    S.zz[b * C + c][e.zpos] = (int16_t)(coef < 0 ? -q : q);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // 4. the strip's coefficients, contiguous in the scratch
+    {
+        const int mcu0 = by * J.bw + bx0;
+        uint32_t* dst = (uint32_t*)(L.coef + (J.coef_base + (int64_t)mcu0 * C) * 64);
+        const uint32_t* srcw = (const uint32_t*)&S.zz[0][0];
+        const int ndw = nb * C * 32;
+        for (int i = tid; i < ndw; i += kJpThreads) dst[i] = srcw[i];
+    }
+}
+
+__global__ void __launch_bounds__(kJpThreads) jp_transform_kernel(const JpLaunch L) {
+    __shared__ JpLds S;
+    const int t = blockIdx.x;
+    int j = 0;
+    while (j + 1 < L.n_jobs && t >= L.job[j + 1].tile_base) ++j;
+    const JpJob J = L.job[j];
+    if (threadIdx.x < 128) S.quant[threadIdx.x] = L.quant[threadIdx.x];      // (visible after the tile's first barrier)
+    if (J.C == 3) jp_transform_tile<3>(S, L, J, t - J.tile_base);
+    else jp_transform_tile<1>(S, L, J, t - J.tile_base);
+}
+
+// ---- entropy --------------------------------------------------------------------------------------------------------------------
+// One wavefront, one restart interval.  kEmit = false counts the interval's bytes (stuffing and marker included) into int_len;
+// kEmit = true writes them at the image's out + int_off.
+template <bool kEmit>
+__global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
+    __shared__ uint32_t huff[2][kJpHuffN];
+    __shared__ uint32_t bitbuf[64];       // MSB-first: stream byte i is bits 31-8*(i&3) .. 24-8*(i&3) of word i >> 2
+    const int lane = threadIdx.x;
+    const int gi = blockIdx.x;
+    int j = 0;
+    while (j + 1 < L.n_jobs && gi >= L.job[j + 1].int_base) ++j;
+    const JpJob J = L.job[j];
+    if (kEmit && L.lengths[j] == UINT64_MAX) return;            // the scan does not fit: nothing of it is written
+    const int k = gi - J.int_base, C = J.C;
+    for (int i = lane; i < 2 * kJpHuffN; i += 64) (&huff[0][0])[i] = (&kJpHuff.e[0][0])[i];
+    bitbuf[lane] = 0;
+    __syncthreads();
+
+    const int m0 = k * L.ri, m1 = min(J.n_mcu, m0 + L.ri);
+    const int nblk = (m1 - m0) * C;
+    const int16_t* cf = L.coef + (J.coef_base + (int64_t)m0 * C) * 64 + lane;
+    uint8_t* dst = nullptr;
+    if constexpr (kEmit) dst = J.out + L.int_off[gi];
+    const uint64_t lower = (1ull << lane) - 1ull;
+    uint32_t carry = 0, nout = 0;         // bits waiting in bitbuf (< 8), bytes produced so far
+    int pred0 = 0, pred1 = 0, pred2 = 0, comp = 0;
+    int raw = cf[0];
+    for (int bi = 0; bi < nblk; ++bi) {
+        const int nxt = bi + 1 < nblk ? (int)cf[(int64_t)(bi + 1) * 64] : 0;     // the next block's load flies during this one
+        const int tab = comp ? 1 : 0;
+        const int dc = __shfl(raw, 0, 64);
+        const int pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
+        if (comp == 0) pred0 = dc; else if (comp == 1) pred1 = dc; else pred2 = dc;
+        const int v = lane == 0 ? raw - pred : raw;
+        const int size = 32 - __clz(abs(v));                                      // 0 for v == 0
+        const uint32_t vbits = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << size) - 1u);
+        const uint64_t mask = __ballot(v != 0) & ~1ull;                           // non-zero AC positions
+        const uint64_t below = mask & lower;
+        const int run = lane - (below ? 63 - __clzll(below) : 0) - 1;             // zeros since the previous non-zero (or the DC)
+        uint64_t str = 0;
+        int len = 0;
+        if (lane == 0) {
+            const uint32_t e = huff[tab][256 + size];
+            str = ((uint64_t)(e >> 5) << size) | vbits;
+            len = (int)(e & 31) + size;
+        } else if (v != 0) {
+            const uint32_t z = huff[tab][0xF0], e = huff[tab][((run & 15) << 4) | size];
+            const int zl = (int)(z & 31), nz = run >> 4;                          // up to three ZRLs in front of the code
+            if (nz > 0) { str = z >> 5; len = zl; }
+            if (nz > 1) { str = (str << zl) | (z >> 5); len += zl; }
+            if (nz > 2) { str = (str << zl) | (z >> 5); len += zl; }
+            const int cl = (int)(e & 31) + size;
+            str = (str << cl) | ((uint64_t)(e >> 5) << size) | vbits;
+            len += cl;
+        } else if (lane == 63) {                                                  // zeros trail: EOB
+            const uint32_t e = huff[tab][0x00];
+            str = e >> 5;
+            len = (int)(e & 31);
+        }
+        int incl = len;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += up;
+        }
+        const uint32_t total = carry + (uint32_t)__shfl(incl, 63, 64);            // <= 7 + 64 * 26 bits
+        if (len) {
+            const uint32_t at = carry + (uint32_t)(incl - len), w0 = at >> 5, sh = at & 31;
+            const uint64_t T = str << (64 - len), U = T >> sh;
+            const uint32_t a = (uint32_t)(U >> 32), b = (uint32_t)U, c = sh ? (uint32_t)((T << (64 - sh)) >> 32) : 0u;
+            if (a) atomicOr(&bitbuf[w0], a);
+            if (b) atomicOr(&bitbuf[w0 + 1], b);
+            if (c) atomicOr(&bitbuf[w0 + 2], c);
+        }
+        __syncthreads();
+        const uint32_t nbytes = total >> 3;                                       // whole bytes: <= 208
+        for (uint32_t base = 0; base < nbytes; base += 64) {
+            const uint32_t i = base + lane;
+            const bool act = i < nbytes;
+            const uint32_t byte = (bitbuf[(i >> 2) & 63] >> (24 - 8 * (i & 3))) & 255u;
+            const bool ff = act && byte == 255u;
+            const uint64_t fm = __ballot(ff);
+            if constexpr (kEmit) {
+                if (act) {
+                    uint8_t* p = dst + nout + lane + __popcll(fm & lower);
+                    p[0] = (uint8_t)byte;
+                    if (ff) p[1] = 0;
+                }
+            }
+            nout += min(64u, nbytes - base) + (uint32_t)__popcll(fm);
+        }
+        const uint32_t left = (bitbuf[nbytes >> 2] >> (24 - 8 * (nbytes & 3))) & 255u;   // the bits of the byte still open
+        __syncthreads();
+        bitbuf[lane] = lane == 0 ? left << 24 : 0u;
+        __syncthreads();
+        carry = total & 7;
+        raw = nxt;
+        comp = comp + 1 == C ? 0 : comp + 1;
+    }
+    if (carry) {                                                                  // pad with 1-bits; a 0xFF pad is stuffed like any byte
+        const uint32_t byte = (bitbuf[0] >> 24) | ((1u << (8 - carry)) - 1u);
+        if constexpr (kEmit) {
+            if (lane == 0) {
+                dst[nout] = (uint8_t)byte;
+                if (byte == 255u) dst[nout + 1] = 0;
+            }
+        }
+        nout += byte == 255u ? 2 : 1;
+    }
+    if (k + 1 < J.n_int) {
+        if constexpr (kEmit) {
+            if (lane == 0) {
+                dst[nout] = 0xFF;
+                dst[nout + 1] = (uint8_t)(0xD0 + (k & 7));
+            }
+        }
+        nout += 2;
+    }
+    if constexpr (!kEmit) {
+        if (lane == 0) L.int_len[gi] = nout;
+    }
+}
+
+// ---- placement: one workgroup per image, exclusive scan of its intervals' lengths -------------------------------------------------
+__global__ void __launch_bounds__(kJpThreads) jp_offsets_kernel(const JpLaunch L) {
+    __shared__ unsigned long long wsum[kJpThreads / 64];
+    const JpJob J = L.job[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long run = 0;
+    for (int i0 = 0; i0 < J.n_int; i0 += kJpThreads) {
+        const int i = i0 + tid;
+        const unsigned long long mine = i < J.n_int ? L.int_len[J.int_base + i] : 0ull;
+        unsigned long long incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        unsigned long long before = run, all = run;
+#pragma unroll
+        for (int w = 0; w < kJpThreads / 64; ++w) {
+            if (w < wave) before += wsum[w];
+            all += wsum[w];
+        }
+        if (i < J.n_int) L.int_off[J.int_base + i] = before + incl - mine;
+        run = all;
+        __syncthreads();
+    }
+    if (tid == 0) L.lengths[blockIdx.x] = run <= J.cap ? run : UINT64_MAX;
+}
+
+}  // namespace
+
+hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s) {
+    hipLaunchKernelGGL(jp_quant_kernel, dim3(1), dim3(128), 0, s, L.quant, L.quality);
+    hipLaunchKernelGGL(jp_transform_kernel, dim3(L.total_tiles), dim3(kJpThreads), 0, s, L);
+    hipLaunchKernelGGL(jp_entropy_kernel<false>, dim3(L.total_int), dim3(64), 0, s, L);
+    hipLaunchKernelGGL(jp_offsets_kernel, dim3(L.n_jobs), dim3(kJpThreads), 0, s, L);
+    hipLaunchKernelGGL(jp_entropy_kernel<true>, dim3(L.total_int), dim3(64), 0, s, L);
+    return hipGetLastError();
+}
+
+}  // namespace gs360

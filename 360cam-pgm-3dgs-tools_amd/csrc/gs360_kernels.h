@@ -352,4 +352,32 @@ struct FlPairs {
 hipError_t launch_frame_flow_frames(const FlLaunch& L, hipStream_t s);
 hipError_t launch_frame_flow_pairs(const FlLaunch& L, const FlPairs& Q, hipStream_t s);
 
+// Baseline JPEG scans (gs360_jpeg.hip, JPG-SPEC v1 in DESIGN.md): one batch of up to GS360_MAX_VIEWS images.  Scratch of the batch:
+// quantised zig-zag coefficients (64 int16 per 8x8 block, the blocks of an MCU side by side), the quantiser table the set-up kernel
+// derives from `quality`, and per restart interval its coded length and its offset in the image's scan.
+struct JpQuant {                         // one entry per (table, natural index)
+    uint32_t recip;                      // floor(2^24 / Q) + 1: n / Q == (n * recip) >> 24 for n < 65793
+    uint16_t half, zpos;                 // Q >> 1; the coefficient's zig-zag position
+};
+struct JpJob {
+    const uint8_t* src;
+    uint8_t* out;
+    uint64_t cap;
+    int64_t stride, coef_base;           // row stride in bytes; first block of the image in the coefficient scratch
+    int32_t H, W, C, bw;                 // bw: 8x8 blocks per row
+    int32_t n_mcu, n_int;                // MCUs (one block per component), restart intervals
+    int32_t tile_base, tiles_x;          // transform workgroups: strips of 8 rows x 256 columns
+    int32_t int_base, pad;               // first interval of the image in int_len / int_off
+};
+struct JpLaunch {
+    JpJob job[GS360_MAX_VIEWS];
+    int32_t n_jobs, quality, ri, total_tiles, total_int;
+    int16_t* coef;
+    JpQuant* quant;                      // 2 x 64
+    uint32_t* int_len;
+    uint64_t* int_off;
+    uint64_t* lengths;                   // n_jobs: the scans' lengths, UINT64_MAX where one exceeds its capacity
+};
+hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s);
+
 }  // namespace gs360

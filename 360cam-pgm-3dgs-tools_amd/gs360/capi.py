@@ -33,7 +33,9 @@ EXPORTS = (
     "gs360_png_unfilter", "gs360_event_sync", "gs360_stream_wait_event",
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
     "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
+    "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound",
 )
+JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
@@ -73,6 +75,12 @@ class RemapJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("src_stride", C.c_size_t),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p), ("valid", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32),
                 ("fill_value", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_size_t)]
+
+
+class JpegJob(C.Structure):
+    """gs360_jpeg_job: one image of a batched JPEG scan call (device pointers)."""
+    _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("src_stride", C.c_size_t),
+                ("out", C.c_void_p), ("out_capacity", C.c_size_t)]
 
 
 class FrameStats(C.Structure):
@@ -192,6 +200,8 @@ def load_library(path=None):
         L.gs360_frame_edge_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, vp, i]
         L.gs360_frame_fft_energy.argtypes = [vp, pvp, i, i, i, i, i, i, i, u32, vp, i]
         L.gs360_frame_flow_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, i, i, i, i, u32, C.POINTER(C.c_int), i, vp, vp, i]
+        L.gs360_jpeg_scan_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, vp, i]
+        L.gs360_jpeg_scan_bound.argtypes = [i, i, i, i, C.POINTER(C.c_size_t)]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -569,6 +579,17 @@ class Context:
         _check(self.L.gs360_frame_flow_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(crop[0]),
                                           int(crop[1]), int(crop[2]), int(crop[3]), int(small_w), int(small_h), int(flags), pa,
                                           len(pairs), out.ptr, points.ptr if points is not None else None, slot), self.L)
+
+    # -- JPEG scans of device images (gs360/jpegenc.py) ---------------------------------------
+    def jpeg_scan_dev(self, jobs, lengths, quality=100, restart=8, slot=0):
+        """gs360_jpeg_scan_u8: jobs = iterable of (src DeviceBuffer, H, W, C, src_stride, out DeviceBuffer, out_capacity); lengths =
+        DeviceBuffer of len(jobs) uint64 (JPEG_OVERFLOW where a scan exceeded its capacity).  Asynchronous on `slot`."""
+        arr = (JpegJob * max(len(jobs), 1))()
+        for k, (src, H, W, Cn, stride, out, cap) in enumerate(jobs):
+            if cap > out.nbytes:
+                raise ValueError("out_capacity larger than the output buffer")
+            arr[k] = JpegJob(src.ptr, int(H), int(W), int(Cn), int(stride), out.ptr, int(cap))
+        _check(self.L.gs360_jpeg_scan_u8(self.handle, arr, len(jobs), int(quality), int(restart), lengths.ptr, slot), self.L)
 
     # -- hot path, host buffers (synchronous) -----------------------------------------------
     def equirect_views(self, src, views, slot=0, interp=INTERP_LINEAR, flags=0):

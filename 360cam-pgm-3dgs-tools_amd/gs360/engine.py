@@ -12,16 +12,21 @@ frame becomes the batch leader, gets the frame resident, waits a short linger (G
 it leaves early once the announced number of views has arrived), then renders every view that joined in ONE batched
 launch, queues all device->pinned-host copies on the same stream and synchronises once.  Every job then encodes its
 own view in its own thread (the encoders are the end-to-end bound, scripts/bench_cli_e2e.py).
+
+GS360_JPEG_ENCODER=device moves that last step onto the GPU for 8-bit .jpg views: the batch's rendered views are entropy-coded where
+they are (gs360/jpegenc.py, one gs360_jpeg_scan_u8 call on the launch's stream), only the scans cross PCIe, and a job writes
+header + scan + EOI with a plain file write.  The default, `host`, is the path above, unchanged.
 """
 import collections
 import itertools
 import os
+import pathlib
 import threading
 import time
 
 import numpy as np
 
-from . import capi, hostmem, imageio, video
+from . import capi, hostmem, imageio, jpegenc, video
 from .jobspec import JobSpec
 
 _FRAME_CACHE_BYTES = int(os.environ.get("GS360_FRAME_CACHE_MB", "4096")) << 20
@@ -31,6 +36,31 @@ _PREFETCH_FRAMES = int(os.environ.get("GS360_PREFETCH_FRAMES", "8"))      # stil
 _PREFETCH_THREADS = int(os.environ.get("GS360_PREFETCH_THREADS", "4"))    # decoder threads of the read-ahead
 _STALE_RUN_S = float(os.environ.get("GS360_STALE_RUN_S", "30"))            # an earlier run's untouched sources are dropped by the next announce() after this long
 _RECENT_SOURCES = 512                   # sources whose device is remembered after their record is gone (bounded)
+_JPEG_RESTART = 8                       # MCUs per restart interval of the device JPEG encoder (JPG-SPEC v1's default)
+
+
+class _JpegScan:
+    """A view the device encoded (GS360_JPEG_ENCODER=device): the JFIF header and the scan, which aliases pinned host memory."""
+    __slots__ = ("header", "scan")
+
+    def __init__(self, header, scan):
+        self.header = header
+        self.scan = scan
+
+    def write(self, path):
+        path = pathlib.Path(path)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(self.header)
+            f.write(self.scan)
+            f.write(jpegenc.EOI)
+
+
+def _write_view(path, arr, jpeg_q):
+    if isinstance(arr, _JpegScan):
+        arr.write(path)
+    else:
+        imageio.write_image(path, arr, jpeg_q=jpeg_q)
 
 
 class _Batch:
@@ -300,10 +330,63 @@ class Engine:
             return capi.View.make(job.fnum("yaw"), job.fnum("pitch"), hfov, vfov, w, h), capi.EQ_FISHEYE_OUT
         return capi.View.make(job.fnum("yaw"), job.fnum("pitch"), job.fnum("h_fov"), job.fnum("v_fov"), job.width, job.height), 0
 
-    def _launch_batch(self, st: _DeviceState, buf, H, W, C, views, interp, flags, dtype=np.uint8):
+    @staticmethod
+    def _jpeg_mode(job: JobSpec, want_array=False):
+        """-> None (the host codecs write the view) or the device encoder's quality.  GS360_JPEG_ENCODER = host (default) | device, read
+        once per job; the device encoder takes the .jpg / .jpeg views nobody wants back as arrays."""
+        if want_array or os.environ.get("GS360_JPEG_ENCODER", "host") != "device":
+            return None
+        if pathlib.Path(str(job.dst)).suffix.lower() not in (".jpg", ".jpeg"):
+            return None
+        return jpegenc.quality_for(job.jpeg_q)
+
+    def _encode_views(self, st, ctx, slot, d_out, h_out, sizes, shapes, C, quality):
+        """(slot lock held, the views' launch queued on `slot`) one gs360_jpeg_scan_u8 call over the rendered views; only the scans'
+        bytes come back, into the views' pinned blocks.  A scan is given the view's raw size; one that needs more (noise at quality
+        100) is coded again into a buffer of the bound.  -> [_JpegScan]; h_out[i] is replaced where a larger block was needed."""
+        n = len(sizes)
+        d_scan = [st.take(st.dev_pool, nb, ctx.alloc) for nb in sizes]
+        d_len = st.take(st.dev_pool, 8 * capi.MAX_VIEWS * capi.MAX_FRAMES, ctx.alloc)
+        try:
+            if 8 * n > d_len.nbytes:
+                raise capi.Gs360Error(-1, "too many views in one batch for the device JPEG encoder")
+            jobs = [(d, h, w, C, 0, o, nb) for d, (h, w), o, nb in zip(d_out, shapes, d_scan, sizes)]
+            ctx.jpeg_scan_dev(jobs, d_len, quality=quality, restart=_JPEG_RESTART, slot=slot)
+            lengths = [int(v) for v in ctx.download(d_len, (n,), np.uint64, slot)]
+            for i, length in enumerate(lengths):
+                if length != capi.JPEG_OVERFLOW:
+                    continue
+                h, w = shapes[i]
+                bound = jpegenc.scan_bound(h, w, C, _JPEG_RESTART)
+                st.give(st.dev_pool, d_scan[i])
+                d_scan[i] = st.take(st.dev_pool, bound, ctx.alloc)
+                st.give(st.pin_pool, h_out[i])
+                h_out[i] = st.take(st.pin_pool, bound, ctx.pinned)
+                ctx.jpeg_scan_dev([(d_out[i], h, w, C, 0, d_scan[i], bound)], d_len, quality=quality, restart=_JPEG_RESTART, slot=slot)
+                lengths[i] = int(ctx.download(d_len, (1,), np.uint64, slot)[0])
+                if lengths[i] == capi.JPEG_OVERFLOW:
+                    raise capi.Gs360Error(-2, "a JPEG scan exceeded its bound")
+            L = ctx.L
+            for d, hb, length in zip(d_scan, h_out, lengths):
+                capi._check(L.gs360_download(ctx.handle, hb.ptr, d.ptr, length, slot), L)
+            ctx.sync(slot)
+        finally:
+            for d in d_scan + [d_len]:
+                st.give(st.dev_pool, d)
+        out = []
+        for hb, length, (h, w) in zip(h_out, lengths, shapes):
+            head = jpegenc.header(h, w, C, quality, _JPEG_RESTART)
+            out.append(_JpegScan(head, np.frombuffer(hb.view, dtype=np.uint8, count=length)))
+            with st.pool_lock:
+                st.stats["jpeg_device_images"] += 1
+                st.stats["jpeg_device_bytes"] += len(head) + length + len(jpegenc.EOI)
+        return out
+
+    def _launch_batch(self, st: _DeviceState, buf, H, W, C, views, interp, flags, dtype=np.uint8, jpeg=None):
         """One batched launch for `views` of one resident frame -- or of a WINDOW of resident frames (`buf` a list: the frames of a video
         the view jobs walk together, PC:746-749, PC:1049-1078; ring families reach the source-major kernel from four frames per call).
-        Returns [(array aliasing pinned memory, PinnedBuffer)] per view; for a window a list of those, one per frame."""
+        Returns [(array aliasing pinned memory, PinnedBuffer)] per view; for a window a list of those, one per frame.  With `jpeg` (a
+        quality) and an 8-bit gray or RGB frame the views are encoded where they are and the arrays are _JpegScan objects."""
         with st.lock:
             slot = next(st.slot_cycle)
         ctx, L = st.ctx, st.ctx.L
@@ -314,13 +397,18 @@ class Engine:
         sizes = [v.height * v.width * C * esz for v in views] * len(bufs)           # frame-major, as gs360_equirect_views_u8 writes them
         d_out = [st.take(st.dev_pool, n, ctx.alloc) for n in sizes]
         h_out = [st.take(st.pin_pool, n, ctx.pinned) for n in sizes]
+        encode = jpeg is not None and np.dtype(dtype) == np.uint8 and C in (1, 3)
+        scans = None
         t0 = time.perf_counter()
         try:
             with ctx.slot_locks[slot]:
                 ctx.equirect_views_dev(bufs, W, H, C, views, d_out, slot=slot, interp=interp, flags=flags, dtype=dtype)
-                for d, hb, n in zip(d_out, h_out, sizes):
-                    capi._check(L.gs360_download(ctx.handle, hb.ptr, d.ptr, n, slot), L)
-                ctx.sync(slot)
+                if encode:
+                    scans = self._encode_views(st, ctx, slot, d_out, h_out, sizes, [(v.height, v.width) for v in views] * len(bufs), C, jpeg)
+                else:
+                    for d, hb, n in zip(d_out, h_out, sizes):
+                        capi._check(L.gs360_download(ctx.handle, hb.ptr, d.ptr, n, slot), L)
+                    ctx.sync(slot)
         except BaseException:
             for hb in h_out:                      # nobody will ever hold these results: the pinned blocks go back to the pool
                 st.give(st.pin_pool, hb)
@@ -337,15 +425,19 @@ class Engine:
             if kname:
                 st.stats[kname] = st.stats.get(kname, 0) + 1
             st.stats["gpu_s"] += time.perf_counter() - t0
-        flat = [(np.frombuffer(hb.view, dtype=dtype, count=n // esz).reshape(v.height, v.width, C), hb)
-                for hb, n, v in zip(h_out, sizes, views * len(bufs))]
+        if scans is not None:
+            flat = list(zip(scans, h_out))
+        else:
+            flat = [(np.frombuffer(hb.view, dtype=dtype, count=n // esz).reshape(v.height, v.width, C), hb)
+                    for hb, n, v in zip(h_out, sizes, views * len(bufs))]
         return [flat[f * n_views:(f + 1) * n_views] for f in range(len(bufs))] if window else flat
 
-    def _render(self, st: _DeviceState, fkey, get_frame, view, interp, flags=0, expected=1, stop_event=None):
+    def _render(self, st: _DeviceState, fkey, get_frame, view, interp, flags=0, expected=1, stop_event=None, jpeg=None):
         """Render `view` of the frame identified by `fkey`, coalesced with the other views of that frame that arrive
         within the linger window.  get_frame() -> (DeviceBuffer, H, W, C, dtype) is called by the batch leader only.
-        Returns (array, release): the array aliases pinned host memory until release() is called."""
-        key = (fkey, interp, flags)
+        Returns (array, release): the array aliases pinned host memory until release() is called.  `jpeg`: the device encoder's
+        quality for this view (_jpeg_mode); views that differ in it do not share a batch."""
+        key = (fkey, interp, flags) if jpeg is None else (fkey, interp, flags, "jpeg", jpeg)
         with st.batch_cond:
             b = st.open_batches.get(key)
             leader = b is None
@@ -370,7 +462,7 @@ class Engine:
                 if buf is None:                   # (a video's window past its last frame)
                     res = [None] * len(views)
                 else:
-                    res = self._launch_batch(st, buf, H, W, C, views, interp, flags, dtype)
+                    res = self._launch_batch(st, buf, H, W, C, views, interp, flags, dtype, **({} if jpeg is None else {"jpeg": jpeg}))
                     if isinstance(buf, list):     # a window: per member the list of its view's frames
                         res = [[res[f][i] for f in range(len(buf))] for i in range(len(views))]
                 with st.batch_cond:
@@ -523,6 +615,7 @@ class Engine:
         of the view when want_array is set (the result itself lives in pooled pinned memory), else None."""
         view, flags = self._view_for(job)
         interp = self._interp_for(job)
+        jpeg = self._jpeg_mode(job, want_array)
         rec = self._job_touches(job.src)
         try:
             st = self.states[rec.dev]
@@ -534,12 +627,12 @@ class Engine:
                 return entry[0], entry[1], entry[2], entry[3], entry[5]
             try:
                 arr, release = self._render(st, self._frame_key(job.src), get_frame, view, interp, flags,
-                                            expected=rec.expected or capi.MAX_VIEWS, stop_event=stop_event)
+                                            expected=rec.expected or capi.MAX_VIEWS, stop_event=stop_event, **({} if jpeg is None else {"jpeg": jpeg}))
             finally:
                 for entry in held:
                     self.release_frame(st, entry)
             try:
-                imageio.write_image(job.dst, arr, jpeg_q=job.jpeg_q)
+                _write_view(job.dst, arr, job.jpeg_q)
                 return np.array(arr) if want_array else None
             finally:
                 release()
@@ -547,8 +640,9 @@ class Engine:
             self._job_leaves(job.src)
 
     def stats(self):
-        """Counters since start: batched launches, views, seconds the launch+copy sections held a stream."""
-        total = collections.Counter()
+        """Counters since start: batched launches, views, seconds the launch+copy sections held a stream; jpeg_device_images /
+        jpeg_device_bytes: views the device encoder wrote (GS360_JPEG_ENCODER=device) and their files' bytes."""
+        total = collections.Counter(jpeg_device_images=0, jpeg_device_bytes=0)
         for st in self.states:
             total.update(st.stats)
         return dict(total)
@@ -579,6 +673,7 @@ class Engine:
         """All frames of one view of a video; returns the number of frames written."""
         view, flags = self._view_for(job)
         interp = self._interp_for(job)
+        jpeg = self._jpeg_mode(job)
         sess, token = self._video_session(plan, stop_event, register_proc)
         written = 0
         try:
@@ -597,12 +692,13 @@ class Engine:
                     _st, bufs, H, W, fdtype = win
                     return bufs, H, W, 3, fdtype
                 outs, release = self._render(st, ("video", id(sess), k0), get_window, view, interp, flags,
-                                             expected=min(sess.active_jobs, expected_jobs or sess.active_jobs), stop_event=stop_event)
+                                             expected=min(sess.active_jobs, expected_jobs or sess.active_jobs), stop_event=stop_event,
+                                             **({} if jpeg is None else {"jpeg": jpeg}))
                 if outs is None:
                     break
                 try:
                     for out in outs:
-                        imageio.write_image(video.output_path(job, plan, written), out, jpeg_q=job.jpeg_q)
+                        _write_view(video.output_path(job, plan, written), out, job.jpeg_q)
                         written += 1
                 finally:
                     release()

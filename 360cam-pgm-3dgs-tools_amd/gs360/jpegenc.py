@@ -1,0 +1,126 @@
+"""Baseline JFIF files from images resident on the device (JPG-SPEC v1).
+
+The device writes the entropy-coded scan (gs360_jpeg_scan_u8: YCbCr 4:4:4 or gray, the Annex K Huffman tables, restart intervals);
+this module builds the header that describes it, appends EOI and offers the whole round trip for arrays and device buffers.  It
+stands in for the reference's image writer at PC:327-338 (ffmpeg's mjpeg encoder behind `-q:v`), which the host path leaves to Pillow.
+"""
+import ctypes as ct
+
+import numpy as np
+
+from . import capi
+
+EOI = b"\xff\xd9"
+
+_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+# ITU-T T.81 Annex K.1, natural order
+_Q_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+           18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_Q_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# Annex K.3: BITS then HUFFVAL.  The AC value lists are regular: every (run, size) symbol, ordered by code length.
+_DC_LUMA = bytes((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0)) + bytes(range(12))
+_DC_CHROMA = bytes((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0)) + bytes(range(12))
+_AC_LUMA = bytes((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d)) + bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f0243362728209"
+    "0a161718191a25262728292a3435363738393a434445464748494a535455565758595a636465"
+    "666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9"
+    "aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9ea"
+    "f1f2f3f4f5f6f7f8f9fa")
+_AC_CHROMA = bytes((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77)) + bytes.fromhex(
+    "0001020311040521310612415107617113223281081442"
+    "91a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445"
+    "464748494a535455565758595a636465666768696a737475767778797a82838485868788898a"
+    "92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3"
+    "d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+assert len(_AC_LUMA) == len(_AC_CHROMA) == 16 + 162
+
+
+def quality_for(jpeg_q):
+    """ffmpeg's -q:v -> the quality imageio.write_image gives Pillow: None or 1 -> 100, >= 2 -> 95"""
+    return 95 if (jpeg_q is not None and jpeg_q >= 2) else 100
+
+
+def quant_tables(quality):
+    """[luma, chroma] in natural order: IJG's scaling of the Annex K tables, forced to baseline (1..255)"""
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError("quality must be in 1..100")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return [[min(max((b * s + 50) // 100, 1), 255) for b in base] for base in (_Q_LUMA, _Q_CHROMA)]
+
+
+def _segment(marker, payload):
+    return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, "big") + payload
+
+
+def header(H, W, C, quality, restart):
+    """Everything in front of the scan: SOI, APP0 (JFIF 1.01, density 1:1), DQT per table, SOF0, DHT per table, DRI, SOS."""
+    H, W, C, restart = int(H), int(W), int(C), int(restart)
+    if C not in (1, 3):
+        raise ValueError("C must be 1 or 3")
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError("JPEG sides are 1..65535")
+    if not 1 <= restart <= 65535:
+        raise ValueError("restart interval must be in 1..65535")
+    qt = quant_tables(quality)
+    n_tab = 1 if C == 1 else 2
+    out = b"\xff\xd8" + _segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for t in range(n_tab):
+        out += _segment(0xDB, bytes((t,)) + bytes(qt[t][z] for z in _ZIGZAG))
+    sof = bytes((8,)) + H.to_bytes(2, "big") + W.to_bytes(2, "big") + bytes((C,))
+    sos = bytes((C,))
+    for c in range(C):
+        sof += bytes((c + 1, 0x11, min(c, 1)))
+        sos += bytes((c + 1, 0x11 * min(c, 1)))
+    out += _segment(0xC0, sof)
+    for ident, table in ((0x00, _DC_LUMA), (0x10, _AC_LUMA), (0x01, _DC_CHROMA), (0x11, _AC_CHROMA))[:2 * n_tab]:
+        out += _segment(0xC4, bytes((ident,)) + table)
+    out += _segment(0xDD, restart.to_bytes(2, "big"))
+    return out + _segment(0xDA, sos + b"\x00\x3f\x00")
+
+
+def scan_bound(H, W, C, restart=8):
+    """bytes that hold any scan of an H x W x C image (gs360_jpeg_scan_bound)"""
+    n = ct.c_size_t(0)
+    L = capi.load_library()
+    capi._check(L.gs360_jpeg_scan_bound(int(H), int(W), int(C), int(restart), ct.byref(n)), L)
+    return int(n.value)
+
+
+def encode_device(ctx, images, quality=100, restart=8, slot=0):
+    """images: uint8 ndarrays (H x W or H x W x C) or (DeviceBuffer, H, W, C) tuples of tight device images -> [bytes], one whole
+    JFIF file each.  One gs360_jpeg_scan_u8 call encodes them all; only the scans' bytes come back from the device."""
+    jobs, shapes, owned = [], [], []
+    try:
+        for im in images:
+            if isinstance(im, tuple):
+                buf, H, W, Cn = im
+            else:
+                a = np.ascontiguousarray(im, dtype=np.uint8)
+                H, W = a.shape[:2]
+                Cn = 1 if a.ndim == 2 else a.shape[2]
+                buf = ctx.to_device(a, slot)
+                owned.append(buf)
+            cap = scan_bound(H, W, Cn, restart)
+            out = ctx.alloc(cap)
+            owned.append(out)
+            jobs.append((buf, H, W, Cn, 0, out, cap))
+            shapes.append((H, W, Cn))
+        if not jobs:
+            return []
+        d_len = ctx.alloc(8 * len(jobs))
+        owned.append(d_len)
+        with ctx.slot_locks[slot]:
+            ctx.jpeg_scan_dev(jobs, d_len, quality=quality, restart=restart, slot=slot)
+            lengths = ctx.download(d_len, (len(jobs),), np.uint64, slot)
+            files = []
+            for (H, W, Cn), job, n in zip(shapes, jobs, lengths):
+                if int(n) > job[6]:
+                    raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
+                body = ctx.download(job[5], (int(n),), np.uint8, slot).tobytes()
+                files.append(header(H, W, Cn, quality, restart) + body + EOI)
+        return files
+    finally:
+        for b in owned:
+            ctx.free(b)

@@ -433,6 +433,29 @@ int gs360_frame_flow_u8(gs360_ctx *ctx, const void *const *frames, int n_frames,
                         int red_index, int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags,
                         const int *pairs, int n_pairs, gs360_frame_flow *out_dev, gs360_flow_point *points_dev, int slot);
 
+/* ---- baseline JPEG scans of device-resident images (JPG-SPEC v1) -------------------------
+ * The image writer behind every view of cli_tools/gs360_360PerspCut.py: the `-q:v` / `-huffman optimal` arguments of PC:327-338 and the
+ * mjpeg encoder ffmpeg runs for them (the host path hands the same pixels to Pillow, gs360/imageio.py).  For every job an H x W x C
+ * uint8 image (C = 1 gray, C = 3 RGB with red at byte 0, written as YCbCr 4:4:4; row stride src_stride bytes, 0 = tight; the buffer
+ * rules of the memory section apply) becomes the entropy-coded segment of a baseline sequential JPEG: the Annex K Huffman tables,
+ * IJG's scaling of the Annex K quantiser tables for `quality` in 1..100, one block per component in an MCU, restart markers RSTm
+ * every restart_interval MCUs (1..65535) and the last interval padded to a byte.  Integer arithmetic throughout: the bytes are a
+ * function of the pixels alone.  `out` receives the scan (no header, no EOI: gs360/jpegenc.py builds those), lengths_dev[k] (device
+ * memory) its length; a scan longer than out_capacity gets the length UINT64_MAX and none of it is written.  n_jobs may exceed
+ * GS360_MAX_VIEWS (split internally); the jobs of a call may differ in size and C.  Asynchronous on `slot`.
+ * Errors: GS360_ERR_ARG for sizes outside 1..65535, quality, restart_interval, NULL pointers; GS360_ERR_UNSUPPORTED for other C.
+ * gs360_jpeg_scan_bound: *bytes = a capacity no scan of such an image exceeds (416 bytes per block + 3 per restart interval). */
+typedef struct gs360_jpeg_job {
+    const void *src;       /* H x W x C uint8 */
+    int32_t H, W, C;
+    size_t src_stride;     /* 0 = tight */
+    void *out;             /* the scan */
+    size_t out_capacity;
+} gs360_jpeg_job;
+int gs360_jpeg_scan_u8(gs360_ctx *ctx, const gs360_jpeg_job *jobs, int n_jobs, int quality, int restart_interval,
+                       uint64_t *lengths_dev, int slot);
+int gs360_jpeg_scan_bound(int H, int W, int C, int restart_interval, size_t *bytes);
+
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
                                  const gs360_view *views, int n_views,
