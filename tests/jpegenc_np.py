@@ -1,5 +1,6 @@
 """JPG-SPEC v1 restated in NumPy and plain Python: planes, quantised coefficients, the bit writer with restart
-intervals, and the JFIF header.  Independent of gs360/jpegenc.py and of the HIP kernels: the tests compare both against this."""
+intervals, and the JFIF header.  Independent of gs360/jpegenc.py and of the HIP kernels: the tests compare both against this.
+decode_scan reads a scan back with nothing but the header's own DHT and DRI segments, so the bit writer is pinned as well."""
 import math
 
 import numpy as np
@@ -235,6 +236,154 @@ def encode(img, quality=100, restart=8):
     H, W = a.shape[:2]
     C = 1 if a.ndim == 2 else a.shape[2]
     return header(H, W, C, quality, restart) + scan(a, quality, restart) + b"\xff\xd9"
+
+
+# ---- an independent decoder: pins the restatement's own bit stream -----------------------------------------------------------------
+def _header_tables(header_bytes):
+    """-> ({(class, id): {code as a bit string: symbol}}, restart interval, [(dc id, ac id) per scan component]) from the DHT, DRI and SOS
+    segments of a header (T.81 B.2.4.2, B.2.4.4, B.2.3); the codes are generated from BITS and HUFFVAL as in Annex C"""
+    h = bytes(header_bytes)
+    assert h[:2] == b"\xff\xd8"
+    p, tables, restart, comps = 2, {}, 0, None
+    while comps is None:
+        assert h[p] == 0xFF, "marker expected"
+        marker, n = h[p + 1], int.from_bytes(h[p + 2:p + 4], "big")
+        body = h[p + 4:p + 2 + n]
+        p += 2 + n
+        if marker == 0xC4:
+            q = 0
+            while q < len(body):
+                tc_th, bits = body[q], body[q + 1:q + 17]
+                vals = body[q + 17:q + 17 + sum(bits)]
+                q += 17 + sum(bits)
+                lut, code, k = {}, 0, 0
+                for length in range(1, 17):
+                    for _ in range(bits[length - 1]):
+                        lut[f"{code:0{length}b}"] = vals[k]
+                        code += 1
+                        k += 1
+                    code <<= 1
+                tables[(tc_th >> 4, tc_th & 15)] = lut
+        elif marker == 0xDD:
+            restart = int.from_bytes(body, "big")
+        elif marker == 0xDA:
+            comps = [(body[2 + 2 * c] >> 4, body[2 + 2 * c] & 15) for c in range(body[0])]
+    assert p == len(h), "the header ends with SOS"
+    return tables, restart, comps
+
+
+class _BitReader:
+    """MSB-first bits of one restart interval's bytes, already unstuffed (kept as a string of 0s and 1s)"""
+
+    def __init__(self, data):
+        self.s, self.pos = "".join(f"{b:08b}" for b in data), 0
+
+    def bits(self, n):
+        if self.pos + n > len(self.s):
+            raise ValueError("the interval's bits ran out")
+        self.pos += n
+        return int(self.s[self.pos - n:self.pos], 2) if n else 0
+
+    def symbol(self, lut):
+        for length in range(1, 17):
+            v = lut.get(self.s[self.pos:self.pos + length])
+            if v is not None and self.pos + length <= len(self.s):
+                self.pos += length
+                return v
+        raise ValueError(f"no Huffman code matches at bit {self.pos}")
+
+    def value(self, size):
+        """EXTEND (F.2.2.1)"""
+        v = self.bits(size)
+        return v if size == 0 or v >> (size - 1) else v - (1 << size) + 1
+
+
+def decode_scan(header_bytes, scan_bytes, n_mcu, C):
+    """Baseline Huffman decoding (T.81 F.2.2) of an entropy-coded scan with the tables, restart interval and component selectors found
+    in `header_bytes` alone -> int [n_mcu][C][64] zig-zag coefficients.  Checks what a strict decoder checks: every 0xFF is followed by
+    0x00 or by the RSTm that is due, nothing follows the last MCU but 1-padding, no run passes coefficient 63.  ValueError otherwise."""
+    tables, restart, comps = _header_tables(header_bytes)
+    if len(comps) != C:
+        raise ValueError(f"the header's scan has {len(comps)} components, not {C}")
+    if restart < 1:
+        raise ValueError("no DRI segment")
+    data = bytes(scan_bytes)
+    n_int = (n_mcu + restart - 1) // restart
+    out = np.zeros((n_mcu, C, 64), np.int64)
+    p = 0
+    for k in range(n_int):
+        body = bytearray()
+        while p < len(data):                                      # this interval's bytes, unstuffed, up to its marker
+            b = data[p]
+            if b != 0xFF:
+                body.append(b)
+                p += 1
+                continue
+            if p + 1 >= len(data):
+                raise ValueError(f"interval {k}: 0xFF ends the scan")
+            if data[p + 1] == 0x00:
+                body.append(0xFF)
+                p += 2
+                continue
+            if k + 1 < n_int and data[p + 1] == 0xD0 + (k & 7):
+                p += 2
+                break
+            raise ValueError(f"interval {k}: unexpected marker 0xFF{data[p + 1]:02X} at byte {p}")
+        else:
+            if k + 1 < n_int:
+                raise ValueError(f"interval {k}: the scan ends before RST{k & 7}")
+        r = _BitReader(body)
+        pred = [0] * C
+        try:
+            for m in range(k * restart, min(n_mcu, (k + 1) * restart)):
+                for c, (td, ta) in enumerate(comps):
+                    pred[c] += r.value(r.symbol(tables[(0, td)]))
+                    out[m, c, 0] = pred[c]
+                    i = 1
+                    while i < 64:
+                        rs = r.symbol(tables[(1, ta)])
+                        run, size = rs >> 4, rs & 15
+                        if size == 0:
+                            if run == 15:
+                                i += 16
+                                if i > 63:
+                                    raise ValueError("a ZRL passes coefficient 63")
+                                continue
+                            if run:
+                                raise ValueError(f"symbol 0x{rs:02X} in a baseline scan")
+                            break
+                        i += run
+                        if i > 63:
+                            raise ValueError("a run passes coefficient 63")
+                        out[m, c, i] = r.value(size)
+                        i += 1
+        except ValueError as e:
+            raise ValueError(f"interval {k}: {e}") from None
+        rest = 8 * len(body) - r.pos
+        if rest >= 8 or r.bits(rest) != (1 << rest) - 1:
+            raise ValueError(f"interval {k}: {rest} bits follow its last MCU and are not 1-padding of the last byte")
+    if p != len(data):
+        raise ValueError(f"{len(data) - p} bytes follow the last interval")
+    return out
+
+
+def first_difference(header_bytes, got, want, n_mcu, C):
+    """a sentence on where two scans of the same image part: the first differing MCU, component, zig-zag index and interval of the
+    decoded coefficients, or the decoder's complaint about `got`"""
+    at = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+    where = f"{len(got)} bytes against {len(want)}, first differing byte {at}"
+    _t, restart, _c = _header_tables(header_bytes)
+    zw = decode_scan(header_bytes, want, n_mcu, C)
+    try:
+        zg = decode_scan(header_bytes, got, n_mcu, C)
+    except ValueError as e:
+        return f"{where}; the stream does not decode: {e}"
+    bad = np.argwhere(zg != zw)
+    if not len(bad):
+        return f"{where}; both decode to the same coefficients (padding, stuffing or markers differ)"
+    m, c, i = (int(v) for v in bad[0])
+    return (f"{where}; first differing coefficient: MCU {m} (interval {m // restart}), component {c}, zig-zag index {i}: "
+            f"{int(zg[m, c, i])} against {int(zw[m, c, i])}")
 
 
 # ---- the inputs the JPEG tests share ---------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import pytest
 
 from gs360 import jpegenc
 
+import jpegenc_cases as cases
 import jpegenc_np as ref
 
 
@@ -175,3 +176,102 @@ def test_the_device_tests_inputs_reach_the_cases_they_are_there_for():
     assert max(gaps) > 16                                                                 # a zero run over 15: ZRL
     assert np.abs(ref.coefficients(ref.checker_image(), 100)[..., 1:]).max() >= 512       # AC values of the largest size, 10 bits
     assert ref.scan(ref.noise_image(), 100, 1).count(b"\xff\xd7") >= 2                    # RST cycles past RST7
+
+
+# ---- the alphabet inputs (tests/jpegenc_cases.py): the decoder pins the restatement, the counts pin the inputs -----------------------
+GROUPS = cases.groups()
+GROUP_IDS = [f"{g} q{q} Ri{ri}" for g, q, ri, _ in GROUPS]
+
+
+@pytest.mark.parametrize("group", GROUPS, ids=GROUP_IDS)
+def test_the_independent_decoder_returns_the_restatements_coefficients(group):
+    """decode_scan builds its tables from the header's DHT and DRI bytes alone: the restatement's bit writer, Huffman codes, stuffing,
+    padding and markers must give back the coefficients they were fed, on every input the device is compared on"""
+    _g, quality, restart, images = group
+    for name, a in images:
+        H, W, C, n_mcu = cases.geometry(a)
+        got = ref.decode_scan(ref.header(H, W, C, quality, restart), ref.scan(a, quality, restart), n_mcu, C)
+        assert np.array_equal(got, ref.coefficients(a, quality).reshape(n_mcu, C, 64)), name
+
+
+def test_the_independent_decoder_refuses_damaged_streams():
+    a = ref.noise_image(16, 24, 3, seed=3)
+    head, scan = ref.header(16, 24, 3, 100, 2), ref.scan(a, 100, 2)
+    z = ref.coefficients(a, 100).reshape(6, 3, 64)
+    assert np.array_equal(ref.decode_scan(head, scan, 6, 3), z)
+    rst = scan.index(b"\xff\xd0")
+    damaged = {"a wrong restart index": scan[:rst] + b"\xff\xd1" + scan[rst + 2:], "a lost byte": scan[:5] + scan[6:],
+               "a lost marker": scan[:rst] + scan[rst + 2:], "a trailing byte": scan + b"\x00", "a truncated scan": scan[:-40],
+               "an unstuffed 0xFF": scan.replace(b"\xff\x00", b"\xff", 1)}
+    for what, data in damaged.items():
+        try:
+            same = np.array_equal(ref.decode_scan(head, data, 6, 3), z)
+        except ValueError:
+            continue
+        assert not same, what
+    # ... and first_difference names the place: the value bits of MCU 4's (interval 2's) first coefficient that is not +-1, inverted
+    z2 = z.copy()
+    m, c, i = next((m, c, i) for m in (4, 5) for c in range(3) for i in range(1, 64) if abs(z2[m, c, i]) > 1)
+    z2[m, c, i] = -z2[m, c, i]
+    other = ref.scan_from_coefficients(z2.reshape(2, 3, 3, 64), 2)
+    said = ref.first_difference(head, other, scan, 6, 3)
+    assert f"MCU {m} (interval 2), component {c}, zig-zag index {i}: {int(z2[m, c, i])} against {int(z[m, c, i])}" in said, said
+    assert "does not decode" in ref.first_difference(head, scan[:-40], scan, 6, 3)
+
+
+def test_pillow_decodes_the_alphabet_inputs():
+    """every new image, at the first quality and restart interval it is used with (100 or 97): Pillow opens the restatement's file with
+    the right shape and shows the picture, within the bound of test_pillow_decodes_the_restatements_files"""
+    seen = set()
+    for _g, quality, restart, images in GROUPS:
+        for name, a in images:
+            if name in seen:
+                continue
+            seen.add(name)
+            got = decode(ref.encode(a, quality, restart))
+            assert got.shape == a.shape, name
+            assert np.abs(got.astype(int) - a.astype(int)).mean() < 8.0, name
+
+
+# AC symbols the sweep cannot reach.  A single coefficient of size 10 needs an amplitude of at least 512 steps: at zig-zag positions
+# 4 and 12 (runs 3 and 11 of the luma sweep) the rounded pixels give back 511, and in chroma the RGB gamut leaves no room for them
+LUMA_AC_MISSING = {0x3A, 0xBA}
+CHROMA_AC_MISSING = {0x0A, 0x3A, 0x7A, 0xAA, 0xBA, 0xEA, 0xFA}
+
+
+def test_the_alphabet_inputs_reach_the_cases_they_are_there_for():
+    """tests/test_jpegenc_alphabet_gpu.py compares the scans of these groups byte for byte; counted on the restatement's stream, they
+    must hold what the entropy pass, the stuffing loop and the offsets kernel can get wrong"""
+    reach = cases.Reach()
+    for _g, quality, restart, images in GROUPS:
+        for _name, a in images:
+            reach.add(a, quality, restart)
+    every = cases.all_symbols()
+    assert len(every) == 162
+    for t, missing in ((0, LUMA_AC_MISSING), (1, CHROMA_AC_MISSING)):
+        assert every - reach.ac[t] == missing, (t, sorted(hex(s) for s in every - reach.ac[t]))
+        assert {0x00, 0xF0} <= reach.ac[t]
+        assert {(r << 4) | s for r in range(16) for s in range(1, 10)} <= reach.ac[t]        # every run at every size <= 9
+    assert len(reach.ac[0]) == 160 and len(reach.ac[1]) == 155
+    assert reach.zrl3 and reach.longest_word >= 56                                              # three ZRLs + code + value bits
+    for t in (0, 1):
+        assert {s for s, _ in reach.dc[t]} == set(range(12)), (t, sorted(reach.dc[t]))
+        assert {(11, 1), (11, -1)} <= reach.dc[t]
+    assert max(reach.block_bytes) == cases.FAT_BLOCK_WHOLE_BYTES >= 129                         # the stuffing loop's third pass
+    assert any(65 <= n <= 128 for n in reach.block_bytes)                                       # ... and its second
+    assert 63 in reach.ff_at and reach.ff_pad >= 1
+    assert reach.carries == set(range(8))
+    assert {256, 257} <= reach.n_int and max(reach.n_int) > 512
+    print(f"luma AC {len(reach.ac[0])}/162, chroma AC {len(reach.ac[1])}/162, longest word {reach.longest_word} bits, largest block "
+          f"{max(reach.block_bytes)} whole bytes, 0xFF at whole-byte indices {sorted(reach.ff_at)}, {reach.ff_pad} 0xFF pad bytes, "
+          f"interval counts up to {max(reach.n_int)}")
+
+
+def test_the_fat_block_is_what_the_search_found():
+    a = cases.fat_block_image()
+    z = ref.coefficients(a, 100)[0, :, 0, :]
+    assert int(z[2, 0]) == -1024 and int(z[3, 0]) - int(z[2, 0]) >= 1024                      # a DC difference of size 11
+    w = ref.BitWriter()
+    ref.encode_block(w, [int(v) for v in z[3]], int(z[2, 0]), ref.huff_codes(ref.DC_LUMA), ref.huff_codes(ref.AC_LUMA))
+    assert 8 * len(bytes(w.out).replace(b"\xff\x00", b"\xff")) + w.n == cases.FAT_BLOCK_BITS
+    assert (7 + cases.FAT_BLOCK_BITS) // 8 == cases.FAT_BLOCK_WHOLE_BYTES

@@ -55,7 +55,7 @@ def run_scans(ctx, images, quality, restart, pad=0, caps=None, slot=0):
             src = ctx.to_device(rows)
             cap = jpegenc.scan_bound(H, W, C, restart) if caps is None else caps[k]
             out = ctx.alloc(cap + GUARD)
-            ctx.memset(out, 0xA5)
+            ctx.memset(out, 0xA5, slot)       # asynchronous: on the stream the scan kernels follow on
             bufs += [src, out]
             jobs.append((src, H, W, C, stride if pad else 0, out, cap))
         d_len = ctx.alloc(8 * len(jobs))
