@@ -29,6 +29,7 @@ const OptDesc kOpts[kOptCount] = {
     {"table_stage", -1, -1, 1, "GS360_TABLE_STAGE"},  // LDS-staged table kernel (bilinear RGB through map plans): -1 auto, 0 never, 1 every job that can
     {"table_stage_rows", 32, 8, 32, nullptr},         // its output tile: rows (multiple of 8) of 64 pixels
     {"table_stage_wgs", 0, 0, 4, nullptr},            // workgroups per CU (0 auto: what the LDS holds, at most three)
+    {"jpeg_count_waves", 256, 1, 65535, nullptr},     // optimal Huffman tables: wavefronts that share the count pass of one image
 };
 
 }  // namespace gs360

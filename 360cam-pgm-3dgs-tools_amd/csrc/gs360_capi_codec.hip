@@ -130,29 +130,38 @@ int gs360_jpeg_scan_bound(int H, int W, int C, int restart_interval, size_t* byt
     return GS360_OK;
 }
 
-int gs360_jpeg_scan_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval,
-                       uint64_t* lengths_dev, int slot) {
+namespace {
+
+// gs360_jpeg_scan_u8 (tables_dev == nullptr: the Annex K tables) and gs360_jpeg_scan_opt_u8 (per-image optimal tables)
+int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval, uint64_t* lengths_dev,
+              uint8_t* tables_dev, bool optimal, int slot) {
     if (int rc = check_ctx_slot(c, slot)) return rc;
     if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
     if (n_jobs == 0) return GS360_OK;
-    if (!jobs || !lengths_dev) return fail(GS360_ERR_ARG, "NULL argument");
+    if (!jobs || !lengths_dev || (optimal && !tables_dev)) return fail(GS360_ERR_ARG, "NULL argument");
     if (quality < 1 || quality > 100) return fail(GS360_ERR_ARG, "quality %d outside 1..100", quality);
     for (int k = 0; k < n_jobs; ++k) {
         const gs360_jpeg_job& j = jobs[k];
         if (int rc = check_jpeg_geometry(j.H, j.W, j.C, restart_interval)) return rc;
         if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
         if (j.src_stride && j.src_stride < (size_t)j.W * j.C) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
+        // the table construction's range: counts in uint32 below libjpeg's 10^9 sentinel, code lengths below 64 before limiting
+        if (optimal && (int64_t)((j.H + 7) / 8) * ((j.W + 7) / 8) * j.C * 64 >= 1000000000ll)
+            return fail(GS360_ERR_UNSUPPORTED, "job %d: optimal Huffman tables take images below 10^9 coefficients", k);
     }
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream[slot];
     Staging& st = c->stage[slot];
-    // scratch of a launch batch: coefficients, the quantiser table, the intervals' lengths and offsets.  Sized for the call's largest
-    // batch before the first launch (growing it later would free memory that queued kernels still use)
-    auto layout = [](int64_t blocks, int64_t intervals, size_t* quant_at, size_t* len_at, size_t* off_at) {
+    // scratch of a launch batch: coefficients, the quantiser table, the intervals' lengths and offsets and, with optimal tables, the
+    // images' symbol counts and coder tables.  Sized for the call's largest batch before the first launch (growing it later would free
+    // memory that queued kernels still use)
+    constexpr size_t kTableWords = 2 * 272;
+    auto layout = [optimal](int64_t blocks, int64_t intervals, int images, size_t* quant_at, size_t* len_at, size_t* off_at, size_t* hist_at) {
         *quant_at = round_up((size_t)blocks * 128, 256);
         *len_at = *quant_at + 128 * sizeof(JpQuant);
         *off_at = *len_at + round_up((size_t)intervals * 4, 256);
-        return *off_at + (size_t)intervals * 8;
+        *hist_at = round_up(*off_at + (size_t)intervals * 8, 256);
+        return optimal ? *hist_at + 2 * (size_t)images * kTableWords * sizeof(uint32_t) : *off_at + (size_t)intervals * 8;
     };
     size_t need = 0;
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
@@ -162,8 +171,8 @@ int gs360_jpeg_scan_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int
             blocks += mcus * jobs[k].C;
             intervals += (mcus + restart_interval - 1) / restart_interval;
         }
-        size_t a, b, d;
-        need = std::max(need, layout(blocks, intervals, &a, &b, &d));
+        size_t a, b, d, e;
+        need = std::max(need, layout(blocks, intervals, std::min(GS360_MAX_VIEWS, n_jobs - k0), &a, &b, &d, &e));
     }
     if (int rc = ensure(&st.d_jpeg, &st.jpeg_cap, need)) return rc;
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
@@ -193,15 +202,43 @@ int gs360_jpeg_scan_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int
         if (tiles > INT32_MAX || intervals > INT32_MAX) return fail(GS360_ERR_ARG, "JPEG batch too large");
         L.total_tiles = (int32_t)tiles;
         L.total_int = (int32_t)intervals;
-        size_t quant_at, len_at, off_at;
-        if (layout(blocks, intervals, &quant_at, &len_at, &off_at) > st.jpeg_cap) return fail(GS360_ERR_ARG, "JPEG scratch layout");
+        size_t quant_at, len_at, off_at, hist_at;
+        if (layout(blocks, intervals, L.n_jobs, &quant_at, &len_at, &off_at, &hist_at) > st.jpeg_cap) return fail(GS360_ERR_ARG, "JPEG scratch layout");
         uint8_t* base = (uint8_t*)st.d_jpeg;
         L.coef = (int16_t*)base;
         L.quant = (JpQuant*)(base + quant_at);
         L.int_len = (uint32_t*)(base + len_at);
         L.int_off = (uint64_t*)(base + off_at);
         L.lengths = lengths_dev + k0;
+        if (optimal) {
+            L.hist = (uint32_t*)(base + hist_at);
+            L.huff = L.hist + (size_t)L.n_jobs * kTableWords;
+            L.tables = tables_dev + (size_t)k0 * 4 * GS360_JPEG_TABLE_BYTES;
+            L.count_waves = opt(c, kOptJpegCountWaves);
+        }
         HIP_TRY(launch_jpeg_scan(L, s));
     }
+    return GS360_OK;
+}
+
+}  // namespace
+
+int gs360_jpeg_scan_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval,
+                       uint64_t* lengths_dev, int slot) {
+    return jpeg_scan(c, jobs, n_jobs, quality, restart_interval, lengths_dev, nullptr, false, slot);
+}
+
+int gs360_jpeg_scan_opt_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval,
+                           uint64_t* lengths_dev, uint8_t* tables_dev, int slot) {
+    return jpeg_scan(c, jobs, n_jobs, quality, restart_interval, lengths_dev, tables_dev, true, slot);
+}
+
+int gs360_jpeg_huff_tables(gs360_ctx* c, const uint32_t* hist_dev, int n_tables, uint8_t* tables_dev, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (n_tables < 0) return fail(GS360_ERR_ARG, "n_tables < 0");
+    if (n_tables == 0) return GS360_OK;
+    if (!hist_dev || !tables_dev) return fail(GS360_ERR_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_jpeg_huff_tables(hist_dev, n_tables, tables_dev, c->stream[slot]));
     return GS360_OK;
 }

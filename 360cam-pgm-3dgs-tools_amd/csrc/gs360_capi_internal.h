@@ -41,7 +41,7 @@ constexpr double kPi = 3.14159265358979323846;
 // context options: name, default, range, environment seed (user switches only); the table is gs360_capi.hip's
 enum Opt { kOptLanemap, kOptStage, kOptRing, kOptXcdGroup, kOptEqPersist, kOptTablePersist, kOptLanczosTable, kOptTableRows, kOptColorCube,
            kOptSrcMajor, kOptSrcMajorBx, kOptSrcMajorRows, kOptSrcMajorImages, kOptSrcMajorAdapt, kOptSrcMajorStage, kOptTableStage, kOptTableStageRows,
-           kOptTableStageWgs, kOptCount };
+           kOptTableStageWgs, kOptJpegCountWaves, kOptCount };
 struct OptDesc { const char* key; int def, lo, hi; const char* env; };
 extern const OptDesc kOpts[kOptCount];
 

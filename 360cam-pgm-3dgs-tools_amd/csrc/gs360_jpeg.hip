@@ -13,7 +13,11 @@
 //   placement  size first: the entropy kernel runs once without stores for the intervals' lengths, one workgroup per image turns them
 //              into offsets (exclusive scan) and the scan's length, and the same kernel runs again writing at its final offsets.
 //              An image whose scan exceeds its capacity gets the length UINT64_MAX and is not written at all.
-// No float atomics; the LDS bit buffer is filled with integer ORs, so nothing depends on the order of the work.
+// Optimal tables ("JPG-SPEC v1, optimal tables"): between transform and size a count pass (the entropy pass's lane algorithm, adding
+// each lane's symbols to an LDS histogram that is flushed once per wavefront) and a table kernel (T.81 K.2 as libjpeg runs it, one
+// wavefront per image and table) give every image its own four tables; size and emit then read those in place of Annex K's.
+// No float atomics; the LDS bit buffer is filled with integer ORs and the histograms with integer adds, so nothing depends on the
+// order of the work.
 #include "gs360_kernels.h"
 
 namespace gs360 {
@@ -214,6 +218,20 @@ __global__ void __launch_bounds__(kJpThreads) jp_transform_kernel(const JpLaunch
 }
 
 // ---- entropy --------------------------------------------------------------------------------------------------------------------
+// What a lane codes of a block (lane = zig-zag position, `raw` its coefficient, `pred` the component's previous DC): lane 0 the DC
+// difference, a lane with a non-zero coefficient its value behind `run` zeros (run >> 4 ZRLs, then the symbol (run & 15) << 4 | size),
+// lane 63 with a zero the EOB.  The non-zero mask is a ballot, the run the gap to the next set bit below the lane.
+struct JpSym { int v, size, run; };
+__device__ __forceinline__ JpSym jp_lane_symbol(int raw, int pred, int lane, uint64_t lower) {
+    JpSym s;
+    s.v = lane == 0 ? raw - pred : raw;
+    s.size = 32 - __clz(abs(s.v));                                                // 0 for v == 0
+    const uint64_t mask = __ballot(s.v != 0) & ~1ull;                             // non-zero AC positions
+    const uint64_t below = mask & lower;
+    s.run = lane - (below ? 63 - __clzll(below) : 0) - 1;                         // zeros since the previous non-zero (or the DC)
+    return s;
+}
+
 // One wavefront, one restart interval.  kEmit = false counts the interval's bytes (stuffing and marker included) into int_len;
 // kEmit = true writes them at the image's out + int_off.
 template <bool kEmit>
@@ -227,7 +245,12 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
     const JpJob J = L.job[j];
     if (kEmit && L.lengths[j] == UINT64_MAX) return;            // the scan does not fit: nothing of it is written
     const int k = gi - J.int_base, C = J.C;
-    for (int i = lane; i < 2 * kJpHuffN; i += 64) (&huff[0][0])[i] = (&kJpHuff.e[0][0])[i];
+    if (L.huff) {                                                                 // the image's own tables (jp_tables_kernel)
+        const uint32_t* own = L.huff + (size_t)j * 2 * kJpHuffN;
+        for (int i = lane; i < 2 * kJpHuffN; i += 64) (&huff[0][0])[i] = own[i];
+    } else {
+        for (int i = lane; i < 2 * kJpHuffN; i += 64) (&huff[0][0])[i] = (&kJpHuff.e[0][0])[i];
+    }
     bitbuf[lane] = 0;
     __syncthreads();
 
@@ -246,12 +269,9 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
         const int dc = __shfl(raw, 0, 64);
         const int pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
         if (comp == 0) pred0 = dc; else if (comp == 1) pred1 = dc; else pred2 = dc;
-        const int v = lane == 0 ? raw - pred : raw;
-        const int size = 32 - __clz(abs(v));                                      // 0 for v == 0
+        const JpSym sym = jp_lane_symbol(raw, pred, lane, lower);
+        const int v = sym.v, size = sym.size, run = sym.run;
         const uint32_t vbits = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << size) - 1u);
-        const uint64_t mask = __ballot(v != 0) & ~1ull;                           // non-zero AC positions
-        const uint64_t below = mask & lower;
-        const int run = lane - (below ? 63 - __clzll(below) : 0) - 1;             // zeros since the previous non-zero (or the DC)
         uint64_t str = 0;
         int len = 0;
         if (lane == 0) {
@@ -336,6 +356,181 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
     }
 }
 
+// ---- optimal tables: count ----------------------------------------------------------------------------------------------------------
+// The symbols the entropy pass will emit, per image and table, in the layout of its code table ([2][272]: AC symbols, then DC sizes at
+// 256 + size).  Each image is cut into at most L.count_waves runs of whole restart intervals; a wavefront walks one run with the lane
+// algorithm of the entropy pass, adds to its LDS histogram and flushes the non-zero bins once.
+
+__global__ void __launch_bounds__(64) jp_count_kernel(const JpLaunch L) {
+    __shared__ uint32_t hist[2][kJpHuffN];
+    const int lane = threadIdx.x;
+    const int j = blockIdx.x / L.count_waves, w = blockIdx.x - j * L.count_waves;
+    const JpJob J = L.job[j];
+    const int per = (J.n_int + L.count_waves - 1) / L.count_waves;               // intervals per wavefront
+    const int k0 = w * per, k1 = min(J.n_int, k0 + per);
+    if (k0 >= k1) return;
+    for (int i = lane; i < 2 * kJpHuffN; i += 64) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    const int C = J.C;
+    const int64_t m0 = (int64_t)k0 * L.ri, m1 = min((int64_t)J.n_mcu, (int64_t)k1 * L.ri);
+    const int nblk = (int)(m1 - m0) * C, per_int = L.ri * C;                     // (ri * C <= 196605)
+    const int16_t* cf = L.coef + (J.coef_base + m0 * C) * 64 + lane;
+    const uint64_t lower = (1ull << lane) - 1ull;
+    int pred0 = 0, pred1 = 0, pred2 = 0, comp = 0, left = per_int;               // blocks left in the interval
+    int raw = cf[0];
+    for (int bi = 0; bi < nblk; ++bi) {
+        const int nxt = bi + 1 < nblk ? (int)cf[(int64_t)(bi + 1) * 64] : 0;
+        const int tab = comp ? 1 : 0;
+        const int dc = __shfl(raw, 0, 64);
+        const int pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
+        if (comp == 0) pred0 = dc; else if (comp == 1) pred1 = dc; else pred2 = dc;
+        const JpSym sym = jp_lane_symbol(raw, pred, lane, lower);
+        if (lane == 0) {
+            atomicAdd(&hist[tab][256 + sym.size], 1u);
+        } else if (sym.v != 0) {
+            atomicAdd(&hist[tab][((sym.run & 15) << 4) | sym.size], 1u);
+            if (sym.run >> 4) atomicAdd(&hist[tab][0xF0], (uint32_t)(sym.run >> 4));
+        } else if (lane == 63) {
+            atomicAdd(&hist[tab][0x00], 1u);
+        }
+        raw = nxt;
+        comp = comp + 1 == C ? 0 : comp + 1;
+        if (--left == 0) { left = per_int; pred0 = pred1 = pred2 = 0; }          // a restart interval ends: the predictions reset
+    }
+    __syncthreads();
+    uint32_t* g = L.hist + (size_t)j * 2 * kJpHuffN;
+    for (int i = lane; i < 2 * kJpHuffN; i += 64) {
+        const uint32_t n = (&hist[0][0])[i];
+        if (n) atomicAdd(&g[i], n);
+    }
+}
+
+// ---- optimal tables: construction ------------------------------------------------------------------------------------------------
+// T.81 K.2 as libjpeg's jpeg_gen_optimal_table runs it, one wavefront per table, entry e = lane + 64 * k (257 entries: the symbols and
+// the pseudo-symbol 256 with count 1, which reserves the all-ones code).  A merge step takes the two smallest non-zero counts, ties to
+// the LARGEST index (two wave minima of count << 9 | 511 - index), adds the second to the first and lengthens every symbol of both
+// trees: each entry carries its tree's id (the index that holds the tree's count), so the lanes lengthen and relabel their own
+// entries, the same set of symbols libjpeg reaches along its others[] chain.  Lane 0 then limits the lengths to 16 and drops the
+// pseudo-symbol's code; HUFFVAL orders the symbols by unlimited length, then value (a rank every lane counts for its entries), and
+// the codes follow Annex C.
+// hist: per_image ? the count pass's [image][2][272] (block = image * 4 + {DC0, AC0, DC1, AC1}) : [block][256] counts.
+// huff (optional): the coder's (code << 5) | length entries, [image][2][272].  tables: [block][272] = 16 BITS + HUFFVAL, zero padded.
+__device__ __forceinline__ uint64_t jp_wave_min(uint64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t u = __shfl_xor((unsigned long long)v, o, 64);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(64) jp_tables_kernel(const uint32_t* hist, int per_image, uint32_t* huff, uint8_t* tables) {
+    __shared__ uint8_t cs[257];                   // unlimited code lengths (< 64 for counts that sum below 10^9)
+    __shared__ int bits[64];
+    __shared__ uint32_t word[256];                // (code << 5) | length of the symbol of HUFFVAL rank r
+    __shared__ uint8_t out[kJpHuffN];
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int ac = b & 1;
+    const uint32_t* src = per_image ? hist + (size_t)(b >> 1) * kJpHuffN + (ac ? 0 : 256) : hist + (size_t)b * 256;
+    const int nsrc = per_image && !ac ? 16 : 256;
+    uint32_t f[5];
+    int grp[5], len[5];
+    bool used[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int e = lane + 64 * k;
+        f[k] = e < nsrc ? src[e] : (e == 256 ? 1u : 0u);
+        used[k] = f[k] != 0;
+        grp[k] = e;
+        len[k] = 0;
+    }
+    for (int i = lane; i < kJpHuffN; i += 64) out[i] = 0;
+    bits[lane] = 0;
+    const bool any = __ballot(used[0] || used[1] || used[2] || used[3]) != 0;     // a real symbol with a count
+    for (;;) {
+        uint64_t best = UINT64_MAX;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const uint64_t key = ((uint64_t)f[k] << 9) | (uint64_t)(511 - (lane + 64 * k));
+            if (f[k] && key < best) best = key;
+        }
+        const uint64_t key1 = jp_wave_min(best);
+        const int c1 = 511 - (int)(key1 & 511);
+        best = UINT64_MAX;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int e = lane + 64 * k;
+            const uint64_t key = ((uint64_t)f[k] << 9) | (uint64_t)(511 - e);
+            if (f[k] && e != c1 && key < best) best = key;
+        }
+        const uint64_t key2 = jp_wave_min(best);
+        if (key2 == UINT64_MAX) break;
+        const int c2 = 511 - (int)(key2 & 511);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int e = lane + 64 * k;
+            if (e == c1) f[k] += (uint32_t)(key2 >> 9);
+            if (e == c2) f[k] = 0;
+            if (used[k] && (grp[k] == c1 || grp[k] == c2)) { ++len[k]; grp[k] = c1; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int e = lane + 64 * k;
+        if (e < 257) cs[e] = (uint8_t)len[k];
+        if (e < 257 && len[k]) atomicAdd(&bits[len[k] & 63], 1);
+    }
+    __syncthreads();
+    if (lane == 0 && any) {
+        // (the j > 0 and i > 0 guards never bind for counts that sum below 10^9; they keep other input from walking out of bits[])
+        for (int i = 63; i > 16; --i) {
+            while (bits[i] > 0) {
+                int jj = i - 2;
+                while (jj > 0 && bits[jj] == 0) --jj;
+                if (jj == 0) { bits[i] = 0; break; }
+                bits[i] -= 2; bits[i - 1] += 1; bits[jj + 1] += 2; bits[jj] -= 1;
+            }
+        }
+        int i = 16;
+        while (i > 0 && bits[i] == 0) --i;
+        if (i > 0) bits[i] -= 1;                                                  // the pseudo-symbol's code
+        uint32_t code = 0;
+        int r = 0;
+        for (int l = 1; l <= 16; ++l) {
+            out[l - 1] = (uint8_t)bits[l];
+            for (int n = 0; n < bits[l] && r < 256; ++n) word[r++] = (code++ << 5) | (uint32_t)l;
+            code <<= 1;
+        }
+    }
+    __syncthreads();
+    uint32_t mine[4] = {0, 0, 0, 0};
+    if (any) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int e = lane + 64 * k, le = len[k];
+            if (!le) continue;
+            int rank = 0;
+            for (int s = 0; s < 256; ++s) {
+                const int ls = cs[s];
+                rank += (ls && (ls < le || (ls == le && s < e))) ? 1 : 0;
+            }
+            out[16 + rank] = (uint8_t)e;
+            mine[k] = word[rank];
+        }
+    }
+    __syncthreads();
+    uint8_t* dst = tables + (size_t)b * kJpHuffN;
+    for (int i = lane; i < kJpHuffN; i += 64) dst[i] = out[i];
+    if (huff) {
+        uint32_t* h = huff + (size_t)(b >> 1) * kJpHuffN + (ac ? 0 : 256);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int e = lane + 64 * k;
+            if (e < nsrc) h[e] = mine[k];
+        }
+    }
+}
+
 // ---- placement: one workgroup per image, exclusive scan of its intervals' lengths -------------------------------------------------
 __global__ void __launch_bounds__(kJpThreads) jp_offsets_kernel(const JpLaunch L) {
     __shared__ unsigned long long wsum[kJpThreads / 64];
@@ -371,9 +566,20 @@ __global__ void __launch_bounds__(kJpThreads) jp_offsets_kernel(const JpLaunch L
 hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s) {
     hipLaunchKernelGGL(jp_quant_kernel, dim3(1), dim3(128), 0, s, L.quant, L.quality);
     hipLaunchKernelGGL(jp_transform_kernel, dim3(L.total_tiles), dim3(kJpThreads), 0, s, L);
+    if (L.huff) {                                                                 // optimal tables: zero + count, tables
+        const hipError_t e = hipMemsetAsync(L.hist, 0, (size_t)L.n_jobs * 2 * kJpHuffN * sizeof(uint32_t), s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(jp_count_kernel, dim3(L.n_jobs * L.count_waves), dim3(64), 0, s, L);
+        hipLaunchKernelGGL(jp_tables_kernel, dim3(L.n_jobs * 4), dim3(64), 0, s, (const uint32_t*)L.hist, 1, L.huff, L.tables);
+    }
     hipLaunchKernelGGL(jp_entropy_kernel<false>, dim3(L.total_int), dim3(64), 0, s, L);
     hipLaunchKernelGGL(jp_offsets_kernel, dim3(L.n_jobs), dim3(kJpThreads), 0, s, L);
     hipLaunchKernelGGL(jp_entropy_kernel<true>, dim3(L.total_int), dim3(64), 0, s, L);
+    return hipGetLastError();
+}
+
+hipError_t launch_jpeg_huff_tables(const uint32_t* hist, int n_tables, uint8_t* tables, hipStream_t s) {
+    hipLaunchKernelGGL(jp_tables_kernel, dim3(n_tables), dim3(64), 0, s, hist, 0, (uint32_t*)nullptr, tables);
     return hipGetLastError();
 }
 

@@ -354,7 +354,8 @@ hipError_t launch_frame_flow_pairs(const FlLaunch& L, const FlPairs& Q, hipStrea
 
 // Baseline JPEG scans (gs360_jpeg.hip, JPG-SPEC v1 in DESIGN.md): one batch of up to GS360_MAX_VIEWS images.  Scratch of the batch:
 // quantised zig-zag coefficients (64 int16 per 8x8 block, the blocks of an MCU side by side), the quantiser table the set-up kernel
-// derives from `quality`, and per restart interval its coded length and its offset in the image's scan.
+// derives from `quality`, and per restart interval its coded length and its offset in the image's scan.  With optimal tables
+// (huff != nullptr) also per image the symbol counts and the coder's tables, both [2][272]: AC symbols, then DC sizes at 256 + size.
 struct JpQuant {                         // one entry per (table, natural index)
     uint32_t recip;                      // floor(2^24 / Q) + 1: n / Q == (n * recip) >> 24 for n < 65793
     uint16_t half, zpos;                 // Q >> 1; the coefficient's zig-zag position
@@ -372,12 +373,18 @@ struct JpJob {
 struct JpLaunch {
     JpJob job[GS360_MAX_VIEWS];
     int32_t n_jobs, quality, ri, total_tiles, total_int;
+    int32_t count_waves;                 // optimal tables only: wavefronts per image of the count pass
     int16_t* coef;
     JpQuant* quant;                      // 2 x 64
     uint32_t* int_len;
     uint64_t* int_off;
     uint64_t* lengths;                   // n_jobs: the scans' lengths, UINT64_MAX where one exceeds its capacity
+    uint32_t* hist;                      // optimal tables only: n_jobs x 2 x 272 symbol counts
+    uint32_t* huff;                      // n_jobs x 2 x 272 (code << 5) | length; nullptr = the Annex K tables
+    uint8_t* tables;                     // n_jobs x 4 x 272: 16 BITS + HUFFVAL of DC0, AC0, DC1, AC1 (the caller's buffer)
 };
 hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s);
+// n_tables x 256 symbol counts -> n_tables x 272 bytes (16 BITS + HUFFVAL, zero padded): the table kernel alone
+hipError_t launch_jpeg_huff_tables(const uint32_t* hist, int n_tables, uint8_t* tables, hipStream_t s);
 
 }  // namespace gs360

@@ -33,9 +33,10 @@ EXPORTS = (
     "gs360_png_unfilter", "gs360_event_sync", "gs360_stream_wait_event",
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
     "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
-    "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound",
+    "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound", "gs360_jpeg_scan_opt_u8", "gs360_jpeg_huff_tables",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
+JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
@@ -202,6 +203,8 @@ def load_library(path=None):
         L.gs360_frame_flow_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, i, i, i, i, u32, C.POINTER(C.c_int), i, vp, vp, i]
         L.gs360_jpeg_scan_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, vp, i]
         L.gs360_jpeg_scan_bound.argtypes = [i, i, i, i, C.POINTER(C.c_size_t)]
+        L.gs360_jpeg_scan_opt_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, vp, vp, i]
+        L.gs360_jpeg_huff_tables.argtypes = [vp, vp, i, vp, i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -581,15 +584,36 @@ class Context:
                                           len(pairs), out.ptr, points.ptr if points is not None else None, slot), self.L)
 
     # -- JPEG scans of device images (gs360/jpegenc.py) ---------------------------------------
-    def jpeg_scan_dev(self, jobs, lengths, quality=100, restart=8, slot=0):
-        """gs360_jpeg_scan_u8: jobs = iterable of (src DeviceBuffer, H, W, C, src_stride, out DeviceBuffer, out_capacity); lengths =
-        DeviceBuffer of len(jobs) uint64 (JPEG_OVERFLOW where a scan exceeded its capacity).  Asynchronous on `slot`."""
+    @staticmethod
+    def _jpeg_jobs(jobs):
         arr = (JpegJob * max(len(jobs), 1))()
         for k, (src, H, W, Cn, stride, out, cap) in enumerate(jobs):
             if cap > out.nbytes:
                 raise ValueError("out_capacity larger than the output buffer")
             arr[k] = JpegJob(src.ptr, int(H), int(W), int(Cn), int(stride), out.ptr, int(cap))
+        return arr
+
+    def jpeg_scan_dev(self, jobs, lengths, quality=100, restart=8, slot=0):
+        """gs360_jpeg_scan_u8: jobs = iterable of (src DeviceBuffer, H, W, C, src_stride, out DeviceBuffer, out_capacity); lengths =
+        DeviceBuffer of len(jobs) uint64 (JPEG_OVERFLOW where a scan exceeded its capacity).  Asynchronous on `slot`."""
+        arr = self._jpeg_jobs(jobs)
         _check(self.L.gs360_jpeg_scan_u8(self.handle, arr, len(jobs), int(quality), int(restart), lengths.ptr, slot), self.L)
+
+    def jpeg_scan_opt_dev(self, jobs, lengths, tables, quality=100, restart=8, slot=0):
+        """gs360_jpeg_scan_opt_u8: jpeg_scan_dev with every image's own optimal Huffman tables; tables = DeviceBuffer of
+        len(jobs) * 4 * JPEG_TABLE_BYTES bytes (per image DC0, AC0, DC1, AC1).  Asynchronous on `slot`."""
+        if tables is not None and tables.nbytes < 4 * JPEG_TABLE_BYTES * len(jobs):
+            raise ValueError("tables buffer below 4 x 272 bytes per job")
+        arr = self._jpeg_jobs(jobs)
+        _check(self.L.gs360_jpeg_scan_opt_u8(self.handle, arr, len(jobs), int(quality), int(restart), lengths.ptr,
+                                             tables.ptr if tables is not None else None, slot), self.L)
+
+    def jpeg_huff_tables_dev(self, hist, n, tables, slot=0):
+        """gs360_jpeg_huff_tables: hist = DeviceBuffer of n * 256 uint32 symbol counts -> tables = DeviceBuffer of n * JPEG_TABLE_BYTES
+        bytes (16 BITS + HUFFVAL, zero padded).  Asynchronous on `slot`."""
+        if hist.nbytes < 1024 * n or tables.nbytes < JPEG_TABLE_BYTES * n:
+            raise ValueError("histogram or tables buffer too small for n tables")
+        _check(self.L.gs360_jpeg_huff_tables(self.handle, hist.ptr, int(n), tables.ptr, slot), self.L)
 
     # -- hot path, host buffers (synchronous) -----------------------------------------------
     def equirect_views(self, src, views, slot=0, interp=INTERP_LINEAR, flags=0):

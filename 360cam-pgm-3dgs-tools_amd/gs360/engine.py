@@ -14,7 +14,8 @@ launch, queues all device->pinned-host copies on the same stream and synchronise
 own view in its own thread (the encoders are the end-to-end bound, scripts/bench_cli_e2e.py).
 
 GS360_JPEG_ENCODER=device moves that last step onto the GPU for 8-bit .jpg views: the batch's rendered views are entropy-coded where
-they are (gs360/jpegenc.py, one gs360_jpeg_scan_u8 call on the launch's stream), only the scans cross PCIe, and a job writes
+they are (gs360/jpegenc.py, one gs360_jpeg_scan_u8 call on the launch's stream; with GS360_JPEG_HUFFMAN=optimal one
+gs360_jpeg_scan_opt_u8 call, which builds every view's own Huffman tables first), only the scans cross PCIe, and a job writes
 header + scan + EOI with a plain file write.  The default, `host`, is the path above, unchanged.
 """
 import collections
@@ -332,27 +333,45 @@ class Engine:
 
     @staticmethod
     def _jpeg_mode(job: JobSpec, want_array=False):
-        """-> None (the host codecs write the view) or the device encoder's quality.  GS360_JPEG_ENCODER = host (default) | device, read
-        once per job; the device encoder takes the .jpg / .jpeg views nobody wants back as arrays."""
+        """-> None (the host codecs write the view) or the device encoder's (quality, Huffman mode).  GS360_JPEG_ENCODER = host (default)
+        | device and GS360_JPEG_HUFFMAN = standard (default: the Annex K tables) | optimal (every view's own tables, the reference's
+        `-huffman optimal`; only meaningful with `device`), read once per job; the device encoder takes the .jpg / .jpeg views nobody
+        wants back as arrays."""
         if want_array or os.environ.get("GS360_JPEG_ENCODER", "host") != "device":
             return None
         if pathlib.Path(str(job.dst)).suffix.lower() not in (".jpg", ".jpeg"):
             return None
-        return jpegenc.quality_for(job.jpeg_q)
+        huffman = os.environ.get("GS360_JPEG_HUFFMAN", "standard")
+        if huffman not in jpegenc.HUFFMAN_MODES:
+            raise ValueError(f"GS360_JPEG_HUFFMAN must be standard or optimal (got {huffman!r})")
+        return jpegenc.quality_for(job.jpeg_q), huffman
 
-    def _encode_views(self, st, ctx, slot, d_out, h_out, sizes, shapes, C, quality):
-        """(slot lock held, the views' launch queued on `slot`) one gs360_jpeg_scan_u8 call over the rendered views; only the scans'
-        bytes come back, into the views' pinned blocks.  A scan is given the view's raw size; one that needs more (noise at quality
-        100) is coded again into a buffer of the bound.  -> [_JpegScan]; h_out[i] is replaced where a larger block was needed."""
+    def _encode_views(self, st, ctx, slot, d_out, h_out, sizes, shapes, C, mode):
+        """(slot lock held, the views' launch queued on `slot`) one gs360_jpeg_scan_u8 call over the rendered views (mode = (quality,
+        "standard")) or one gs360_jpeg_scan_opt_u8 call ((quality, "optimal"): the views' own Huffman tables come back with the lengths,
+        1 088 bytes a view); only the scans' bytes come back, into the views' pinned blocks.  A scan is given the view's raw size; one
+        that needs more (noise at quality 100) is coded again, in the same mode, into a buffer of the bound.  -> [_JpegScan]; h_out[i]
+        is replaced where a larger block was needed."""
+        quality, huffman = mode
+        optimal = huffman == "optimal"
         n = len(sizes)
+        tb = 4 * jpegenc.TABLE_BYTES
         d_scan = [st.take(st.dev_pool, nb, ctx.alloc) for nb in sizes]
         d_len = st.take(st.dev_pool, 8 * capi.MAX_VIEWS * capi.MAX_FRAMES, ctx.alloc)
+        d_tab = st.take(st.dev_pool, tb * capi.MAX_VIEWS * capi.MAX_FRAMES, ctx.alloc) if optimal else None
+        tables = [None] * n
+
+        def scan(jobs):
+            if optimal:
+                ctx.jpeg_scan_opt_dev(jobs, d_len, d_tab, quality=quality, restart=_JPEG_RESTART, slot=slot)
+                tabs = ctx.download(d_tab, (len(jobs), tb), np.uint8, slot)
+                return [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)], [t.tobytes() for t in tabs]
+            ctx.jpeg_scan_dev(jobs, d_len, quality=quality, restart=_JPEG_RESTART, slot=slot)
+            return [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)], [None] * len(jobs)
         try:
             if 8 * n > d_len.nbytes:
                 raise capi.Gs360Error(-1, "too many views in one batch for the device JPEG encoder")
-            jobs = [(d, h, w, C, 0, o, nb) for d, (h, w), o, nb in zip(d_out, shapes, d_scan, sizes)]
-            ctx.jpeg_scan_dev(jobs, d_len, quality=quality, restart=_JPEG_RESTART, slot=slot)
-            lengths = [int(v) for v in ctx.download(d_len, (n,), np.uint64, slot)]
+            lengths, tables = scan([(d, h, w, C, 0, o, nb) for d, (h, w), o, nb in zip(d_out, shapes, d_scan, sizes)])
             for i, length in enumerate(lengths):
                 if length != capi.JPEG_OVERFLOW:
                     continue
@@ -362,8 +381,7 @@ class Engine:
                 d_scan[i] = st.take(st.dev_pool, bound, ctx.alloc)
                 st.give(st.pin_pool, h_out[i])
                 h_out[i] = st.take(st.pin_pool, bound, ctx.pinned)
-                ctx.jpeg_scan_dev([(d_out[i], h, w, C, 0, d_scan[i], bound)], d_len, quality=quality, restart=_JPEG_RESTART, slot=slot)
-                lengths[i] = int(ctx.download(d_len, (1,), np.uint64, slot)[0])
+                (lengths[i],), (tables[i],) = scan([(d_out[i], h, w, C, 0, d_scan[i], bound)])
                 if lengths[i] == capi.JPEG_OVERFLOW:
                     raise capi.Gs360Error(-2, "a JPEG scan exceeded its bound")
             L = ctx.L
@@ -371,11 +389,11 @@ class Engine:
                 capi._check(L.gs360_download(ctx.handle, hb.ptr, d.ptr, length, slot), L)
             ctx.sync(slot)
         finally:
-            for d in d_scan + [d_len]:
+            for d in d_scan + [d_len] + ([d_tab] if optimal else []):
                 st.give(st.dev_pool, d)
         out = []
-        for hb, length, (h, w) in zip(h_out, lengths, shapes):
-            head = jpegenc.header(h, w, C, quality, _JPEG_RESTART)
+        for hb, length, (h, w), tab in zip(h_out, lengths, shapes, tables):
+            head = jpegenc.header(h, w, C, quality, _JPEG_RESTART, tab)
             out.append(_JpegScan(head, np.frombuffer(hb.view, dtype=np.uint8, count=length)))
             with st.pool_lock:
                 st.stats["jpeg_device_images"] += 1
@@ -386,7 +404,7 @@ class Engine:
         """One batched launch for `views` of one resident frame -- or of a WINDOW of resident frames (`buf` a list: the frames of a video
         the view jobs walk together, PC:746-749, PC:1049-1078; ring families reach the source-major kernel from four frames per call).
         Returns [(array aliasing pinned memory, PinnedBuffer)] per view; for a window a list of those, one per frame.  With `jpeg` (a
-        quality) and an 8-bit gray or RGB frame the views are encoded where they are and the arrays are _JpegScan objects."""
+        (quality, Huffman mode) pair) and an 8-bit gray or RGB frame the views are encoded where they are and the arrays are _JpegScan objects."""
         with st.lock:
             slot = next(st.slot_cycle)
         ctx, L = st.ctx, st.ctx.L
@@ -436,8 +454,8 @@ class Engine:
         """Render `view` of the frame identified by `fkey`, coalesced with the other views of that frame that arrive
         within the linger window.  get_frame() -> (DeviceBuffer, H, W, C, dtype) is called by the batch leader only.
         Returns (array, release): the array aliases pinned host memory until release() is called.  `jpeg`: the device encoder's
-        quality for this view (_jpeg_mode); views that differ in it do not share a batch."""
-        key = (fkey, interp, flags) if jpeg is None else (fkey, interp, flags, "jpeg", jpeg)
+        quality and Huffman mode for this view (_jpeg_mode); views that differ in either do not share a batch."""
+        key = (fkey, interp, flags) if jpeg is None else (fkey, interp, flags, "jpeg") + tuple(jpeg)
         with st.batch_cond:
             b = st.open_batches.get(key)
             leader = b is None

@@ -1,8 +1,9 @@
 """Baseline JFIF files from images resident on the device (JPG-SPEC v1).
 
 The device writes the entropy-coded scan (gs360_jpeg_scan_u8: YCbCr 4:4:4 or gray, the Annex K Huffman tables, restart intervals);
-this module builds the header that describes it, appends EOI and offers the whole round trip for arrays and device buffers.  It
-stands in for the reference's image writer at PC:327-338 (ffmpeg's mjpeg encoder behind `-q:v`), which the host path leaves to Pillow.
+this module builds the header that describes it, appends EOI and offers the whole round trip for arrays and device buffers.  With
+huffman="optimal" the device builds every image's own tables (gs360_jpeg_scan_opt_u8, the reference's `-huffman optimal`) and the
+header's DHT segments carry those.  It stands in for the reference's image writer at PC:327-338 (ffmpeg's mjpeg encoder behind `-q:v`), which the host path leaves to Pillow.
 """
 import ctypes as ct
 
@@ -54,8 +55,13 @@ def _segment(marker, payload):
     return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, "big") + payload
 
 
-def header(H, W, C, quality, restart):
-    """Everything in front of the scan: SOI, APP0 (JFIF 1.01, density 1:1), DQT per table, SOF0, DHT per table, DRI, SOS."""
+TABLE_BYTES = 272            # GS360_JPEG_TABLE_BYTES: 16 BITS + up to 256 HUFFVAL, zero padded
+HUFFMAN_MODES = ("standard", "optimal")
+
+
+def header(H, W, C, quality, restart, tables=None):
+    """Everything in front of the scan: SOI, APP0 (JFIF 1.01, density 1:1), DQT per table, SOF0, DHT per table, DRI, SOS.  `tables`: the
+    4 * 272 bytes gs360_jpeg_scan_opt_u8 returned for the image (DC0, AC0, DC1, AC1); None: the Annex K tables."""
     H, W, C, restart = int(H), int(W), int(C), int(restart)
     if C not in (1, 3):
         raise ValueError("C must be 1 or 3")
@@ -74,7 +80,13 @@ def header(H, W, C, quality, restart):
         sof += bytes((c + 1, 0x11, min(c, 1)))
         sos += bytes((c + 1, 0x11 * min(c, 1)))
     out += _segment(0xC0, sof)
-    for ident, table in ((0x00, _DC_LUMA), (0x10, _AC_LUMA), (0x01, _DC_CHROMA), (0x11, _AC_CHROMA))[:2 * n_tab]:
+    dht = (_DC_LUMA, _AC_LUMA, _DC_CHROMA, _AC_CHROMA)
+    if tables is not None:
+        tables = bytes(tables)
+        if len(tables) != 4 * TABLE_BYTES:
+            raise ValueError("tables must hold 4 x 272 bytes")
+        dht = [tables[k * TABLE_BYTES:k * TABLE_BYTES + 16 + sum(tables[k * TABLE_BYTES:k * TABLE_BYTES + 16])] for k in range(4)]
+    for ident, table in zip((0x00, 0x10, 0x01, 0x11)[:2 * n_tab], dht):
         out += _segment(0xC4, bytes((ident,)) + table)
     out += _segment(0xDD, restart.to_bytes(2, "big"))
     return out + _segment(0xDA, sos + b"\x00\x3f\x00")
@@ -88,9 +100,12 @@ def scan_bound(H, W, C, restart=8):
     return int(n.value)
 
 
-def encode_device(ctx, images, quality=100, restart=8, slot=0):
+def encode_device(ctx, images, quality=100, restart=8, slot=0, huffman="standard"):
     """images: uint8 ndarrays (H x W or H x W x C) or (DeviceBuffer, H, W, C) tuples of tight device images -> [bytes], one whole
-    JFIF file each.  One gs360_jpeg_scan_u8 call encodes them all; only the scans' bytes come back from the device."""
+    JFIF file each.  One gs360_jpeg_scan_u8 call (huffman="optimal": gs360_jpeg_scan_opt_u8, every image's own tables) encodes them
+    all; only the scans' bytes, and with "optimal" 1 088 bytes of tables per image, come back from the device."""
+    if huffman not in HUFFMAN_MODES:
+        raise ValueError("huffman must be 'standard' or 'optimal'")
     jobs, shapes, owned = [], [], []
     try:
         for im in images:
@@ -112,14 +127,21 @@ def encode_device(ctx, images, quality=100, restart=8, slot=0):
         d_len = ctx.alloc(8 * len(jobs))
         owned.append(d_len)
         with ctx.slot_locks[slot]:
-            ctx.jpeg_scan_dev(jobs, d_len, quality=quality, restart=restart, slot=slot)
+            tables = [None] * len(jobs)
+            if huffman == "optimal":
+                d_tab = ctx.alloc(4 * TABLE_BYTES * len(jobs))
+                owned.append(d_tab)
+                ctx.jpeg_scan_opt_dev(jobs, d_len, d_tab, quality=quality, restart=restart, slot=slot)
+                tables = ctx.download(d_tab, (len(jobs), 4 * TABLE_BYTES), np.uint8, slot)
+            else:
+                ctx.jpeg_scan_dev(jobs, d_len, quality=quality, restart=restart, slot=slot)
             lengths = ctx.download(d_len, (len(jobs),), np.uint64, slot)
             files = []
-            for (H, W, Cn), job, n in zip(shapes, jobs, lengths):
+            for (H, W, Cn), job, n, tab in zip(shapes, jobs, lengths, tables):
                 if int(n) > job[6]:
                     raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
                 body = ctx.download(job[5], (int(n),), np.uint8, slot).tobytes()
-                files.append(header(H, W, Cn, quality, restart) + body + EOI)
+                files.append(header(H, W, Cn, quality, restart, None if tab is None else tab.tobytes()) + body + EOI)
         return files
     finally:
         for b in owned:

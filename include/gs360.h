@@ -113,6 +113,9 @@ int gs360_device_pci_bus_id(gs360_ctx *ctx, char *buf, size_t buf_len);
  *   "table_stage"    -1 auto | 0 never | 1 always       LDS-staged table kernel (bilinear RGB through map plans; auto: plans whose tiles have boxes);
  *                                                       "table_stage_rows" (8 | 16 | 32: rows of its 64-pixel tiles), "table_stage_wgs" (0 auto | 1..4
  *                                                       workgroups per CU)
+ *   "jpeg_count_waves" 1..65535 (256)                   gs360_jpeg_scan_opt_u8: wavefronts that share one image's symbol count (each walks a run of
+ *                                                       whole restart intervals and flushes its histogram once; at or above the interval count:
+ *                                                       one flush per interval)
  * Read-only (get): "last_eq_kernel" -- which kernel the last equirect call launched: 0 gather, 1 LDS-staged, 2 source-major, -1 none yet;
  * "last_srcmajor_box_pct" -- tile-box bytes of the last source-major plan in percent of the grid cells they stand for;
  * "last_srcmajor_rows", "last_srcmajor_images" -- tile rows and images per workgroup of the last source-major launch;
@@ -455,6 +458,20 @@ typedef struct gs360_jpeg_job {
 int gs360_jpeg_scan_u8(gs360_ctx *ctx, const gs360_jpeg_job *jobs, int n_jobs, int quality, int restart_interval,
                        uint64_t *lengths_dev, int slot);
 int gs360_jpeg_scan_bound(int H, int W, int C, int restart_interval, size_t *bytes);
+/* "JPG-SPEC v1, optimal tables" (DESIGN.md): what `-huffman optimal` asks of the reference's encoder.  gs360_jpeg_scan_opt_u8 is
+ * gs360_jpeg_scan_u8 with every image's own Huffman tables: one pass counts the symbols the coder will emit (they depend on
+ * restart_interval), one kernel builds the image's four tables by T.81 Annex K.2 as libjpeg implements it (pseudo-symbol 256, ties
+ * to the largest index, lengths limited to 16), and the scan is coded with them; nothing leaves the device in between.  tables_dev
+ * (device memory) receives n_jobs * 4 * GS360_JPEG_TABLE_BYTES bytes, per image DC0, AC0, DC1, AC1 (the last two all zero for
+ * C = 1), each 16 BITS then HUFFVAL, zero padded: the payloads of the file's DHT segments.  An image whose scan exceeds out_capacity
+ * still gets its tables.  gs360_jpeg_scan_bound holds (codes stay <= 16 bits).  Errors as gs360_jpeg_scan_u8, and
+ * GS360_ERR_UNSUPPORTED for an image of 10^9 or more coefficients (blocks * 64; about 18 000^2 RGB pixels).
+ * gs360_jpeg_huff_tables: the table construction alone, hist_dev = n_tables * 256 uint32 symbol counts (each table's sum below 10^9)
+ * -> n_tables * GS360_JPEG_TABLE_BYTES bytes; an all-zero histogram gives the all-zero table.  Asynchronous on `slot`. */
+#define GS360_JPEG_TABLE_BYTES 272   /* 16 BITS + up to 256 HUFFVAL, zero padded */
+int gs360_jpeg_scan_opt_u8(gs360_ctx *ctx, const gs360_jpeg_job *jobs, int n_jobs, int quality, int restart_interval,
+                           uint64_t *lengths_dev, uint8_t *tables_dev, int slot);
+int gs360_jpeg_huff_tables(gs360_ctx *ctx, const uint32_t *hist_dev, int n_tables, uint8_t *tables_dev, int slot);
 
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
