@@ -199,10 +199,18 @@ def _die(msg: str, code: int = 1):
     sys.exit(code)
 
 
+def _jpeg_quality(q: Optional[int]) -> int:
+    """the quality of a .jpg output: --perspective-jpeg-quality clipped to 1..100 (None: 95)"""
+    return int(max(1, min(100, q if q is not None else 95)))
+
+
 def _write_image(path: pathlib.Path, image, jpeg_quality: Optional[int]):
     """cv2.imwrite stand-in: arrays here are in file channel order already (decoded and encoded by the same codec)."""
     from gs360 import imageio
     path.parent.mkdir(parents=True, exist_ok=True)
+    if isinstance(image, bytes):                              # a whole file from the device encoder (GS360_JPEG_ENCODER=device)
+        path.write_bytes(image)
+        return
     if path.suffix.lower() in (".jpg", ".jpeg") and imageio.Image is not None:
         import numpy as np
         a = imageio.to_uint8(np.ascontiguousarray(image))       # JPEG is an 8-bit container
@@ -210,7 +218,7 @@ def _write_image(path: pathlib.Path, image, jpeg_quality: Optional[int]):
         im = imageio.Image.fromarray(a[:, :, 0] if (a.ndim == 3 and a.shape[2] == 1) else a, mode)
         if mode == "RGBA":
             im = im.convert("RGB")
-        im.save(path, "JPEG", quality=int(max(1, min(100, jpeg_quality if jpeg_quality is not None else 95))))
+        im.save(path, "JPEG", quality=_jpeg_quality(jpeg_quality))
         return
     imageio.write_image(path, image)
 
@@ -470,7 +478,13 @@ def main() -> None:
             processed += 2
     else:
         from gs360 import capi, hostmem, imageio
-        from gs360.dualfisheye import PairRenderer
+        from gs360.dualfisheye import PairRenderer, jpeg_mode_from_env
+        try:
+            huffman = jpeg_mode_from_env()                # GS360_JPEG_ENCODER / GS360_JPEG_HUFFMAN, read once per run
+        except ValueError as exc:
+            _die("[ERR] {}".format(exc), 1)
+        jpeg_views = (_jpeg_quality(jpeg_q), huffman) if huffman and persp_ext in (".jpg", ".jpeg") else None
+        jpeg_masks = (_jpeg_quality(jpeg_q), huffman) if huffman and mask_ext in (".jpg", ".jpeg") else None
         n_dev = capi.device_count()
         if n_dev <= 0:
             _die("[ERR] no MI355X visible: the gs360 engine has no CPU fallback", 2)
@@ -492,7 +506,7 @@ def main() -> None:
                 mx, my = imageio.read_image(pair_masks[base][0]), imageio.read_image(pair_masks[base][1])
             res = r.render_pair(img_x, img_y, sx, sy, interpolation=interpolation, mask_outside_model=bool(args.mask_outside_model),
                                 mask_value=mask_value, mask_x=mx, mask_y=my, want_fisheye=write_fisheye, want_perspective=write_persp,
-                                color_stage=stage, want_color=save_color)
+                                color_stage=stage, want_color=save_color, jpeg_views=jpeg_views, jpeg_masks=jpeg_masks)
             names = {"color": [], "fisheye": [], "persp": [], "mask": []}
             if save_color:
                 for key, p in (("X", x_path), ("Y", y_path)):

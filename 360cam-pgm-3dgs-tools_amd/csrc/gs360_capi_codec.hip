@@ -117,36 +117,64 @@ int check_jpeg_geometry(int H, int W, int C, int restart_interval) {
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+int check_jpeg_subsampling(int subsampling) {
+    if (subsampling != GS360_JPEG_444 && subsampling != GS360_JPEG_420)
+        return fail(GS360_ERR_ARG, "JPEG subsampling %d is neither GS360_JPEG_444 nor GS360_JPEG_420", subsampling);
+    return 0;
+}
+
+// the MCU grid of an image: 8 x 8 pixels and one block per component, or ("JPG-SPEC v1, 4:2:0", colour images only) 16 x 16 pixels
+// and six blocks
+struct JpGrid { int mcu_px, bpm, mw, mh; int64_t mcus() const { return (int64_t)mw * mh; } };
+JpGrid jpeg_grid(int H, int W, int C, int subsampling) {
+    JpGrid g;
+    const bool sub = subsampling == GS360_JPEG_420 && C == 3;
+    g.mcu_px = sub ? 16 : 8;
+    g.bpm = sub ? 6 : C;
+    g.mw = (W + g.mcu_px - 1) / g.mcu_px;
+    g.mh = (H + g.mcu_px - 1) / g.mcu_px;
+    return g;
+}
+
 }  // namespace
 
 int gs360_jpeg_scan_bound(int H, int W, int C, int restart_interval, size_t* bytes) {
+    return gs360_jpeg_scan_bound_sub(H, W, C, restart_interval, GS360_JPEG_444, bytes);
+}
+
+int gs360_jpeg_scan_bound_sub(int H, int W, int C, int restart_interval, int subsampling, size_t* bytes) {
     if (!bytes) return fail(GS360_ERR_ARG, "NULL argument");
     if (int rc = check_jpeg_geometry(H, W, C, restart_interval)) return rc;
+    if (int rc = check_jpeg_subsampling(subsampling)) return rc;
     // a block's 64 coefficients cost at most 26 bits each (a 16-bit code and 10 value bits): 208 bytes, twice that when every byte is
     // stuffed; an interval adds at most its marker and one slack byte
-    const size_t mcus = (size_t)((H + 7) / 8) * (size_t)((W + 7) / 8);
+    const JpGrid g = jpeg_grid(H, W, C, subsampling);
+    const size_t mcus = (size_t)g.mcus();
     const size_t intervals = (mcus + restart_interval - 1) / restart_interval;
-    *bytes = mcus * C * 416 + intervals * 3;
+    *bytes = mcus * g.bpm * 416 + intervals * 3;
     return GS360_OK;
 }
 
 namespace {
 
-// gs360_jpeg_scan_u8 (tables_dev == nullptr: the Annex K tables) and gs360_jpeg_scan_opt_u8 (per-image optimal tables)
-int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval, uint64_t* lengths_dev,
-              uint8_t* tables_dev, bool optimal, int slot) {
+// gs360_jpeg_scan_sub_u8; gs360_jpeg_scan_u8 (the Annex K tables) and gs360_jpeg_scan_opt_u8 (per-image optimal tables) with
+// GS360_JPEG_444
+int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval, int subsampling,
+              uint64_t* lengths_dev, uint8_t* tables_dev, bool optimal, int slot) {
     if (int rc = check_ctx_slot(c, slot)) return rc;
     if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
     if (n_jobs == 0) return GS360_OK;
     if (!jobs || !lengths_dev || (optimal && !tables_dev)) return fail(GS360_ERR_ARG, "NULL argument");
     if (quality < 1 || quality > 100) return fail(GS360_ERR_ARG, "quality %d outside 1..100", quality);
+    if (int rc = check_jpeg_subsampling(subsampling)) return rc;
     for (int k = 0; k < n_jobs; ++k) {
         const gs360_jpeg_job& j = jobs[k];
         if (int rc = check_jpeg_geometry(j.H, j.W, j.C, restart_interval)) return rc;
         if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
         if (j.src_stride && j.src_stride < (size_t)j.W * j.C) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
         // the table construction's range: counts in uint32 below libjpeg's 10^9 sentinel, code lengths below 64 before limiting
-        if (optimal && (int64_t)((j.H + 7) / 8) * ((j.W + 7) / 8) * j.C * 64 >= 1000000000ll)
+        const JpGrid g = jpeg_grid(j.H, j.W, j.C, subsampling);
+        if (optimal && g.mcus() * g.bpm * 64 >= 1000000000ll)
             return fail(GS360_ERR_UNSUPPORTED, "job %d: optimal Huffman tables take images below 10^9 coefficients", k);
     }
     HIP_TRY(hipSetDevice(c->device));
@@ -167,8 +195,9 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
         int64_t blocks = 0, intervals = 0;
         for (int k = k0; k < std::min(n_jobs, k0 + GS360_MAX_VIEWS); ++k) {
-            const int64_t mcus = (int64_t)((jobs[k].H + 7) / 8) * ((jobs[k].W + 7) / 8);
-            blocks += mcus * jobs[k].C;
+            const JpGrid g = jpeg_grid(jobs[k].H, jobs[k].W, jobs[k].C, subsampling);
+            const int64_t mcus = g.mcus();
+            blocks += mcus * g.bpm;
             intervals += (mcus + restart_interval - 1) / restart_interval;
         }
         size_t a, b, d, e;
@@ -190,14 +219,17 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
             J.cap = j.out_capacity;
             J.stride = (int64_t)(j.src_stride ? j.src_stride : (size_t)j.W * j.C);
             J.H = j.H; J.W = j.W; J.C = j.C;
-            J.bw = (j.W + 7) / 8;
-            J.n_mcu = J.bw * ((j.H + 7) / 8);
+            const JpGrid g = jpeg_grid(j.H, j.W, j.C, subsampling);
+            J.bw = g.mw;
+            J.bpm = g.bpm;
+            J.n_mcu = g.mw * g.mh;
             J.n_int = (J.n_mcu + restart_interval - 1) / restart_interval;
-            J.tiles_x = (J.bw + 31) / 32;
+            J.tiles_x = (g.mw * g.mcu_px + 255) / 256;                            // strips of 256 columns, one MCU row high
             J.coef_base = blocks; J.tile_base = (int32_t)tiles; J.int_base = (int32_t)intervals;
-            blocks += (int64_t)J.n_mcu * j.C;
-            tiles += (int64_t)J.tiles_x * ((j.H + 7) / 8);
+            blocks += (int64_t)J.n_mcu * g.bpm;
+            tiles += (int64_t)J.tiles_x * g.mh;
             intervals += J.n_int;
+            if (g.bpm == 6) L.any420 = 1;
         }
         if (tiles > INT32_MAX || intervals > INT32_MAX) return fail(GS360_ERR_ARG, "JPEG batch too large");
         L.total_tiles = (int32_t)tiles;
@@ -225,12 +257,17 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
 
 int gs360_jpeg_scan_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval,
                        uint64_t* lengths_dev, int slot) {
-    return jpeg_scan(c, jobs, n_jobs, quality, restart_interval, lengths_dev, nullptr, false, slot);
+    return jpeg_scan(c, jobs, n_jobs, quality, restart_interval, GS360_JPEG_444, lengths_dev, nullptr, false, slot);
 }
 
 int gs360_jpeg_scan_opt_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval,
                            uint64_t* lengths_dev, uint8_t* tables_dev, int slot) {
-    return jpeg_scan(c, jobs, n_jobs, quality, restart_interval, lengths_dev, tables_dev, true, slot);
+    return jpeg_scan(c, jobs, n_jobs, quality, restart_interval, GS360_JPEG_444, lengths_dev, tables_dev, true, slot);
+}
+
+int gs360_jpeg_scan_sub_u8(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval, int subsampling,
+                           uint64_t* lengths_dev, uint8_t* tables_dev, int slot) {
+    return jpeg_scan(c, jobs, n_jobs, quality, restart_interval, subsampling, lengths_dev, tables_dev, tables_dev != nullptr, slot);
 }
 
 int gs360_jpeg_huff_tables(gs360_ctx* c, const uint32_t* hist_dev, int n_tables, uint8_t* tables_dev, int slot) {

@@ -16,6 +16,9 @@
 // Optimal tables ("JPG-SPEC v1, optimal tables"): between transform and size a count pass (the entropy pass's lane algorithm, adding
 // each lane's symbols to an LDS histogram that is flushed once per wavefront) and a table kernel (T.81 K.2 as libjpeg runs it, one
 // wavefront per image and table) give every image its own four tables; size and emit then read those in place of Annex K's.
+// 4:2:0 ("JPG-SPEC v1, 4:2:0"; the writer of cli_tools/gs360_DualFisheyeDistortionCalibration.py, cv2.imwrite at DF:1826-1840): a
+// colour image's transform strips are 16 rows x 256 columns, 16 MCUs of four Y blocks and one Cb and one Cr block averaged over 2 x 2
+// cells; the other passes walk six blocks per MCU instead of C.
 // No float atomics; the LDS bit buffer is filled with integer ORs and the histograms with integer adds, so nothing depends on the
 // order of the work.
 #include "gs360_kernels.h"
@@ -119,8 +122,16 @@ struct JpLds {
     JpQuant quant[128];
 };
 
-template <int C>
-__device__ __forceinline__ void jp_transform_tile(JpLds& S, const JpLaunch& L, const JpJob& J, int t) {
+// the same with 16 staged rows: the strips of 4:2:0 images (96 blocks as well: 64 Y, 16 Cb, 16 Cr)
+struct JpLds420 {
+    uint32_t raw[16][kJpRawDw];
+    alignas(16) int16_t t1[3][8][kJpTileW];           // Y rows 0..7, Y rows 8..15, [row][Cb columns 0..127 | Cr columns 0..127]
+    alignas(16) int16_t zz[3 * kJpTileBlocks][64];    // [MCU * 6 + block of the MCU][zig-zag position]
+    JpQuant quant[128];
+};
+
+template <int C, class Lds>
+__device__ __forceinline__ void jp_transform_tile(Lds& S, const JpLaunch& L, const JpJob& J, int t) {
     const int tid = threadIdx.x;
     const int by = t / J.tiles_x, tx = t - by * J.tiles_x;
     const int bx0 = tx * kJpTileBlocks, nb = min(kJpTileBlocks, J.bw - bx0);
@@ -206,6 +217,116 @@ __device__ __forceinline__ void jp_transform_tile(JpLds& S, const JpLaunch& L, c
     }
 }
 
+// One strip of a 4:2:0 image: 16 rows x 256 columns = 16 MCUs.  J.bw counts 16 x 16 MCUs per row.
+__device__ __forceinline__ void jp_transform_tile420(JpLds420& S, const JpLaunch& L, const JpJob& J, int t) {
+    constexpr int kMcus = kJpTileW / 16;
+    const int tid = threadIdx.x;
+    const int my = t / J.tiles_x, tx = t - my * J.tiles_x;
+    const int m0 = tx * kMcus, nm = min(kMcus, J.bw - m0);                        // the strip's MCUs
+    const int x0 = m0 * 16, npx = min(kJpTileW, J.W - x0);
+    // 1. the strip's rows (the last row repeats below the image) -> LDS, dword loads
+    uint32_t v[16];
+    uint32_t offs = 0;                                                            // the rows' byte alignments, two bits each
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int y = min(my * 16 + r, J.H - 1);
+        const uintptr_t a = (uintptr_t)(J.src + (int64_t)y * J.stride + (int64_t)x0 * 3);
+        const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
+        offs |= (uint32_t)(a & 3) << (2 * r);
+        const int ndw = ((int)(a & 3) + npx * 3 + 3) >> 2;
+        v[r] = tid < ndw ? q[tid] : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if (tid < kJpRawDw) S.raw[r][tid] = v[r];
+    __syncthreads();
+    auto row_of = [&](int r) {                                                    // the staged bytes of strip row r, from its first pixel
+        return (const uint8_t*)S.raw[r] + ((offs >> (2 * r)) & 3u);
+    };
+    // 2a. Y: a lane per block row of the upper and of the lower block row: colour, level shift, row product
+    {
+        const int b = tid & (kJpTileBlocks - 1), y = tid >> 5;
+        if (b < 2 * nm) {
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const uint8_t* row = row_of(half * 8 + y);
+                int s[8], o[8];
+#pragma unroll
+                for (int x = 0; x < 8; ++x) {
+                    const uint8_t* p = row + min(b * 8 + x, npx - 1) * 3;          // the last column repeats beside the image
+                    s[x] = ((19595 * (int)p[0] + 38470 * (int)p[1] + 7471 * (int)p[2] + 32768) >> 16) - 128;
+                }
+                jp_dct8(s, o);
+                union { int16_t h[8]; uint4 q; } w;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) w.h[u] = (int16_t)((o[u] + 1024) >> 11);
+                *(uint4*)&S.t1[half][y][b * 8] = w.q;
+            }
+        }
+    }
+    // 2b. chroma: a lane per row of a Cb (threads 0..127) or Cr (128..255) block: the component at full resolution over the row's
+    // 2 x 16 pixels, libjpeg's h2v2 average (bias 1 at even, 2 at odd output columns), level shift, row product
+    {
+        const int cr = tid >> 7, y = (tid >> 4) & 7, m = tid & (kMcus - 1);
+        if (m < nm) {
+            const int kr = cr ? 32768 : -11059, kg = cr ? -27439 : -21709, kb = cr ? -5329 : 32768;
+            const uint8_t* r0 = row_of(2 * y);
+            const uint8_t* r1 = row_of(2 * y + 1);
+            int s[8], o[8];
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+                const int c0 = min(m * 16 + 2 * x, npx - 1) * 3, c1 = min(m * 16 + 2 * x + 1, npx - 1) * 3;
+                int sum = 1 + (x & 1);
+                sum += (kr * (int)r0[c0] + kg * (int)r0[c0 + 1] + kb * (int)r0[c0 + 2] + (128 << 16) + 32767) >> 16;
+                sum += (kr * (int)r0[c1] + kg * (int)r0[c1 + 1] + kb * (int)r0[c1 + 2] + (128 << 16) + 32767) >> 16;
+                sum += (kr * (int)r1[c0] + kg * (int)r1[c0 + 1] + kb * (int)r1[c0 + 2] + (128 << 16) + 32767) >> 16;
+                sum += (kr * (int)r1[c1] + kg * (int)r1[c1 + 1] + kb * (int)r1[c1 + 2] + (128 << 16) + 32767) >> 16;
+                s[x] = (sum >> 2) - 128;
+            }
+            jp_dct8(s, o);
+            union { int16_t h[8]; uint4 q; } w;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) w.h[u] = (int16_t)((o[u] + 1024) >> 11);
+            *(uint4*)&S.t1[2][y][cr * (kJpTileW / 2) + m * 8] = w.q;
+        }
+    }
+    __syncthreads();
+    // 3. a lane per block column: column product, quantiser, zig-zag.  Plane 0 and 1: Y block row 0 and 1 (block tid >> 3 of the row
+    // belongs to MCU tid >> 4); plane 2: the Cb blocks, then the Cr blocks
+    {
+        const int u = tid & 7;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int b = tid >> 3;
+            const int m = c < 2 ? b >> 1 : b & (kMcus - 1);
+            const int blk = m * 6 + (c < 2 ? c * 2 + (b & 1) : 4 + (b >> 4));
+            if (m < nm) {
+                int s[8], o[8];
+#pragma unroll
+                for (int y = 0; y < 8; ++y) s[y] = S.t1[c][y][tid];
+                jp_dct8(s, o);
+#pragma unroll
+                for (int vv = 0; vv < 8; ++vv) {
+                    const int coef = (o[vv] + 65536) >> 17;
+                    const JpQuant e = S.quant[(c == 2 ? 64 : 0) + vv * 8 + u];
+                    const uint32_t n = (uint32_t)abs(coef) + e.half;
+                    const int q = (int)__umulhi(n << 8, e.recip);                  // n / Q
+                    S.zz[blk][e.zpos] = (int16_t)(coef < 0 ? -q : q);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // 4. the strip's coefficients, contiguous in the scratch: MCU-major, the six blocks of an MCU side by side
+    {
+        const int mcu0 = my * J.bw + m0;
+        uint32_t* dst = (uint32_t*)(L.coef + (J.coef_base + (int64_t)mcu0 * 6) * 64);
+        const uint32_t* srcw = (const uint32_t*)&S.zz[0][0];
+        const int ndw = nm * 6 * 32;
+        for (int i = tid; i < ndw; i += kJpThreads) dst[i] = srcw[i];
+    }
+}
+
 __global__ void __launch_bounds__(kJpThreads) jp_transform_kernel(const JpLaunch L) {
     __shared__ JpLds S;
     const int t = blockIdx.x;
@@ -217,10 +338,25 @@ __global__ void __launch_bounds__(kJpThreads) jp_transform_kernel(const JpLaunch
     else jp_transform_tile<1>(S, L, J, t - J.tile_base);
 }
 
+// a batch with 4:2:0 images (L.any420): their strips, and the 8-row strips of the batch's gray images
+__global__ void __launch_bounds__(kJpThreads) jp_transform420_kernel(const JpLaunch L) {
+    __shared__ JpLds420 S;
+    const int t = blockIdx.x;
+    int j = 0;
+    while (j + 1 < L.n_jobs && t >= L.job[j + 1].tile_base) ++j;
+    const JpJob J = L.job[j];
+    if (threadIdx.x < 128) S.quant[threadIdx.x] = L.quant[threadIdx.x];      // (visible after the tile's first barrier)
+    if (J.bpm == 6) jp_transform_tile420(S, L, J, t - J.tile_base);
+    else jp_transform_tile<1>(S, L, J, t - J.tile_base);                      // (every C = 3 job of such a call has bpm == 6)
+}
+
 // ---- entropy --------------------------------------------------------------------------------------------------------------------
 // What a lane codes of a block (lane = zig-zag position, `raw` its coefficient, `pred` the component's previous DC): lane 0 the DC
 // difference, a lane with a non-zero coefficient its value behind `run` zeros (run >> 4 ZRLs, then the symbol (run & 15) << 4 | size),
 // lane 63 with a zero the EOB.  The non-zero mask is a ballot, the run the gap to the next set bit below the lane.
+// the component of the block at place `pos` of an MCU of bpm blocks: one block per component, or Y Y Y Y Cb Cr
+__device__ __forceinline__ int jp_component(int pos, int bpm) { return bpm == 6 ? max(pos - 3, 0) : pos; }
+
 struct JpSym { int v, size, run; };
 __device__ __forceinline__ JpSym jp_lane_symbol(int raw, int pred, int lane, uint64_t lower) {
     JpSym s;
@@ -244,7 +380,7 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
     while (j + 1 < L.n_jobs && gi >= L.job[j + 1].int_base) ++j;
     const JpJob J = L.job[j];
     if (kEmit && L.lengths[j] == UINT64_MAX) return;            // the scan does not fit: nothing of it is written
-    const int k = gi - J.int_base, C = J.C;
+    const int k = gi - J.int_base, bpm = J.bpm;
     if (L.huff) {                                                                 // the image's own tables (jp_tables_kernel)
         const uint32_t* own = L.huff + (size_t)j * 2 * kJpHuffN;
         for (int i = lane; i < 2 * kJpHuffN; i += 64) (&huff[0][0])[i] = own[i];
@@ -255,16 +391,17 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
     __syncthreads();
 
     const int m0 = k * L.ri, m1 = min(J.n_mcu, m0 + L.ri);
-    const int nblk = (m1 - m0) * C;
-    const int16_t* cf = L.coef + (J.coef_base + (int64_t)m0 * C) * 64 + lane;
+    const int nblk = (m1 - m0) * bpm;
+    const int16_t* cf = L.coef + (J.coef_base + (int64_t)m0 * bpm) * 64 + lane;
     uint8_t* dst = nullptr;
     if constexpr (kEmit) dst = J.out + L.int_off[gi];
     const uint64_t lower = (1ull << lane) - 1ull;
     uint32_t carry = 0, nout = 0;         // bits waiting in bitbuf (< 8), bytes produced so far
-    int pred0 = 0, pred1 = 0, pred2 = 0, comp = 0;
+    int pred0 = 0, pred1 = 0, pred2 = 0, pos = 0;                                // pos: the block's place in its MCU
     int raw = cf[0];
     for (int bi = 0; bi < nblk; ++bi) {
         const int nxt = bi + 1 < nblk ? (int)cf[(int64_t)(bi + 1) * 64] : 0;     // the next block's load flies during this one
+        const int comp = jp_component(pos, bpm);
         const int tab = comp ? 1 : 0;
         const int dc = __shfl(raw, 0, 64);
         const int pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
@@ -330,7 +467,7 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
         __syncthreads();
         carry = total & 7;
         raw = nxt;
-        comp = comp + 1 == C ? 0 : comp + 1;
+        pos = pos + 1 == bpm ? 0 : pos + 1;
     }
     if (carry) {                                                                  // pad with 1-bits; a 0xFF pad is stuffed like any byte
         const uint32_t byte = (bitbuf[0] >> 24) | ((1u << (8 - carry)) - 1u);
@@ -371,15 +508,16 @@ __global__ void __launch_bounds__(64) jp_count_kernel(const JpLaunch L) {
     if (k0 >= k1) return;
     for (int i = lane; i < 2 * kJpHuffN; i += 64) (&hist[0][0])[i] = 0;
     __syncthreads();
-    const int C = J.C;
+    const int bpm = J.bpm;
     const int64_t m0 = (int64_t)k0 * L.ri, m1 = min((int64_t)J.n_mcu, (int64_t)k1 * L.ri);
-    const int nblk = (int)(m1 - m0) * C, per_int = L.ri * C;                     // (ri * C <= 196605)
-    const int16_t* cf = L.coef + (J.coef_base + m0 * C) * 64 + lane;
+    const int nblk = (int)(m1 - m0) * bpm, per_int = L.ri * bpm;                 // (ri * bpm <= 393210)
+    const int16_t* cf = L.coef + (J.coef_base + m0 * bpm) * 64 + lane;
     const uint64_t lower = (1ull << lane) - 1ull;
-    int pred0 = 0, pred1 = 0, pred2 = 0, comp = 0, left = per_int;               // blocks left in the interval
+    int pred0 = 0, pred1 = 0, pred2 = 0, pos = 0, left = per_int;                // blocks left in the interval
     int raw = cf[0];
     for (int bi = 0; bi < nblk; ++bi) {
         const int nxt = bi + 1 < nblk ? (int)cf[(int64_t)(bi + 1) * 64] : 0;
+        const int comp = jp_component(pos, bpm);
         const int tab = comp ? 1 : 0;
         const int dc = __shfl(raw, 0, 64);
         const int pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
@@ -394,7 +532,7 @@ __global__ void __launch_bounds__(64) jp_count_kernel(const JpLaunch L) {
             atomicAdd(&hist[tab][0x00], 1u);
         }
         raw = nxt;
-        comp = comp + 1 == C ? 0 : comp + 1;
+        pos = pos + 1 == bpm ? 0 : pos + 1;
         if (--left == 0) { left = per_int; pred0 = pred1 = pred2 = 0; }          // a restart interval ends: the predictions reset
     }
     __syncthreads();
@@ -565,7 +703,8 @@ __global__ void __launch_bounds__(kJpThreads) jp_offsets_kernel(const JpLaunch L
 
 hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s) {
     hipLaunchKernelGGL(jp_quant_kernel, dim3(1), dim3(128), 0, s, L.quant, L.quality);
-    hipLaunchKernelGGL(jp_transform_kernel, dim3(L.total_tiles), dim3(kJpThreads), 0, s, L);
+    if (L.any420) hipLaunchKernelGGL(jp_transform420_kernel, dim3(L.total_tiles), dim3(kJpThreads), 0, s, L);
+    else hipLaunchKernelGGL(jp_transform_kernel, dim3(L.total_tiles), dim3(kJpThreads), 0, s, L);
     if (L.huff) {                                                                 // optimal tables: zero + count, tables
         const hipError_t e = hipMemsetAsync(L.hist, 0, (size_t)L.n_jobs * 2 * kJpHuffN * sizeof(uint32_t), s);
         if (e != hipSuccess) return e;

@@ -356,6 +356,8 @@ hipError_t launch_frame_flow_pairs(const FlLaunch& L, const FlPairs& Q, hipStrea
 // quantised zig-zag coefficients (64 int16 per 8x8 block, the blocks of an MCU side by side), the quantiser table the set-up kernel
 // derives from `quality`, and per restart interval its coded length and its offset in the image's scan.  With optimal tables
 // (huff != nullptr) also per image the symbol counts and the coder's tables, both [2][272]: AC symbols, then DC sizes at 256 + size.
+// An MCU holds bpm blocks: C of them, one per component, or with 4:2:0 subsampling ("JPG-SPEC v1, 4:2:0") of a C = 3 image six: four Y
+// blocks of a 16 x 16 pixel MCU in raster order, then Cb, then Cr.
 struct JpQuant {                         // one entry per (table, natural index)
     uint32_t recip;                      // floor(2^24 / Q) + 1: n / Q == (n * recip) >> 24 for n < 65793
     uint16_t half, zpos;                 // Q >> 1; the coefficient's zig-zag position
@@ -365,15 +367,16 @@ struct JpJob {
     uint8_t* out;
     uint64_t cap;
     int64_t stride, coef_base;           // row stride in bytes; first block of the image in the coefficient scratch
-    int32_t H, W, C, bw;                 // bw: 8x8 blocks per row
-    int32_t n_mcu, n_int;                // MCUs (one block per component), restart intervals
-    int32_t tile_base, tiles_x;          // transform workgroups: strips of 8 rows x 256 columns
-    int32_t int_base, pad;               // first interval of the image in int_len / int_off
+    int32_t H, W, C, bw;                 // bw: MCUs per row (8x8 blocks per row; 16x16 MCUs with bpm == 6)
+    int32_t n_mcu, n_int;                // MCUs, restart intervals
+    int32_t tile_base, tiles_x;          // transform workgroups: strips of 8 rows x 256 columns (16 rows with bpm == 6)
+    int32_t int_base, bpm;               // first interval of the image in int_len / int_off; blocks per MCU: C, or 6
 };
 struct JpLaunch {
     JpJob job[GS360_MAX_VIEWS];
     int32_t n_jobs, quality, ri, total_tiles, total_int;
     int32_t count_waves;                 // optimal tables only: wavefronts per image of the count pass
+    int32_t any420, pad;                 // a job of the batch has bpm == 6: the transform kernel with 16 staged rows runs
     int16_t* coef;
     JpQuant* quant;                      // 2 x 64
     uint32_t* int_len;

@@ -34,9 +34,12 @@ EXPORTS = (
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
     "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
     "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound", "gs360_jpeg_scan_opt_u8", "gs360_jpeg_huff_tables",
+    "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
+JPEG_444 = 0                         # GS360_JPEG_444 / GS360_JPEG_420: the `subsampling` of gs360_jpeg_scan_sub_u8 (Pillow's numbers)
+JPEG_420 = 2
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
@@ -205,6 +208,8 @@ def load_library(path=None):
         L.gs360_jpeg_scan_bound.argtypes = [i, i, i, i, C.POINTER(C.c_size_t)]
         L.gs360_jpeg_scan_opt_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, vp, vp, i]
         L.gs360_jpeg_huff_tables.argtypes = [vp, vp, i, vp, i]
+        L.gs360_jpeg_scan_sub_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, i, vp, vp, i]
+        L.gs360_jpeg_scan_bound_sub.argtypes = [i, i, i, i, i, C.POINTER(C.c_size_t)]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -606,6 +611,15 @@ class Context:
             raise ValueError("tables buffer below 4 x 272 bytes per job")
         arr = self._jpeg_jobs(jobs)
         _check(self.L.gs360_jpeg_scan_opt_u8(self.handle, arr, len(jobs), int(quality), int(restart), lengths.ptr,
+                                             tables.ptr if tables is not None else None, slot), self.L)
+
+    def jpeg_scan_sub_dev(self, jobs, lengths, tables=None, quality=100, restart=8, subsampling=JPEG_444, slot=0):
+        """gs360_jpeg_scan_sub_u8: jpeg_scan_dev (tables None: the Annex K tables) or jpeg_scan_opt_dev (tables = DeviceBuffer of
+        len(jobs) * 4 * JPEG_TABLE_BYTES bytes) with the chroma subsampling JPEG_444 or JPEG_420.  Asynchronous on `slot`."""
+        if tables is not None and tables.nbytes < 4 * JPEG_TABLE_BYTES * len(jobs):
+            raise ValueError("tables buffer below 4 x 272 bytes per job")
+        arr = self._jpeg_jobs(jobs)
+        _check(self.L.gs360_jpeg_scan_sub_u8(self.handle, arr, len(jobs), int(quality), int(restart), int(subsampling), lengths.ptr,
                                              tables.ptr if tables is not None else None, slot), self.L)
 
     def jpeg_huff_tables_dev(self, hist, n, tables, slot=0):

@@ -10,6 +10,11 @@ The tables of a run never change, so pairs go through MAP PLANS (include/gs360.h
 point cv2.remap derives from it on every call, 5 bytes per pixel instead of 9 -- same results, less to read per pair.  Plans are made
 on first use per (view, sampler class); sources beyond 4079 pixels keep the float tables.  GS360_MAP_PLANS=0
 turns them off (A/B).
+
+The reference writes every view with cv2.imwrite(path, image, [IMWRITE_JPEG_QUALITY, q]) (DF:1826-1840): libjpeg's defaults, 2 x 2 chroma
+subsampling and the Annex K Huffman tables.  With GS360_JPEG_ENCODER=device (jpeg_mode_from_env, read once per run by the CLI) the 8-bit
+.jpg views of a pair are entropy-coded where the remap left them ("JPG-SPEC v1, 4:2:0", gs360/jpegenc.py: one gs360_jpeg_scan_sub_u8
+call on the pair's slot) and only the scans cross PCIe; render_pair then returns whole files instead of arrays.
 """
 import os
 import threading
@@ -17,10 +22,24 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import capi
+from . import capi, jpegenc
 from .fisheye import SensorCalibration, UndistortTables
 
 INTERPOLATIONS = {"nearest": 0, "linear": 1, "cubic": 2, "lanczos4": 4}   # cv2.INTER_* values (DF:59-64)
+
+
+_JPEG_RESTART = 8                       # MCUs per restart interval of the device JPEG encoder (the engine's constant)
+
+
+def jpeg_mode_from_env():
+    """-> None (the host codecs write the views) or the device encoder's Huffman mode.  GS360_JPEG_ENCODER = host (default) | device and
+    GS360_JPEG_HUFFMAN = standard (default: the Annex K tables, what cv2 and Pillow write for this tool) | optimal, as in the engine."""
+    if os.environ.get("GS360_JPEG_ENCODER", "host") != "device":
+        return None
+    huffman = os.environ.get("GS360_JPEG_HUFFMAN", "standard")
+    if huffman not in jpegenc.HUFFMAN_MODES:
+        raise ValueError(f"GS360_JPEG_HUFFMAN must be standard or optimal (got {huffman!r})")
+    return huffman
 
 
 def engine_interpolation(flag: int) -> int:
@@ -49,6 +68,7 @@ class PairRenderer:
         self._scratch = None                # grow-only output buffer shared by the per-view launches of a pair
         self._plans = {}                    # (kind, id, nearest) -> map plan handle
         self.use_plans = os.environ.get("GS360_MAP_PLANS", "1") not in ("0", "off", "no")
+        self._stats = {"jpeg_device_images": 0, "jpeg_device_bytes": 0}
         self.dev_undistort = {}
         for sid, u in (undistort or {}).items():
             self.dev_undistort[sid] = (ctx.to_device(u.map_x), ctx.to_device(u.map_y),
@@ -65,6 +85,26 @@ class PairRenderer:
         if k not in self._plans:
             self._plans[k] = self.ctx.map_plan(maps[0], maps[1], maps[2], out_hw[0], out_hw[1], nearest=nearest, slot=0)
         return self._plans[k]
+
+    def stats(self):
+        """jpeg_device_images / jpeg_device_bytes: views the device encoder wrote (render_pair's jpeg_views / jpeg_masks) and their
+        files' bytes, as Engine.stats() counts them"""
+        with self.lock:
+            return dict(self._stats)
+
+    def _collect(self, keys, bufs, shapes, dtype, jpeg):
+        """(the views' launch queued on slot 0) -> {key: array}, or with `jpeg` = (quality, huffman) and 8-bit gray or RGB views
+        {key: bytes}: whole 4:2:0 JFIF files, encoded from the device buffers before they are freed.  A scan gets the view's raw size;
+        one that needs more is coded again, in the same mode, into a buffer of the bound."""
+        if jpeg is None or np.dtype(dtype) != np.uint8 or any(c not in (1, 3) for _h, _w, c in shapes):
+            return {k: self.ctx.download(b, shape, dtype=dtype, slot=0) for k, b, shape in zip(keys, bufs, shapes)}
+        quality, huffman = jpeg
+        with self.ctx.slot_locks[0]:
+            files = jpegenc.encode_buffers(self.ctx, [(b, h, w, c) for b, (h, w, c) in zip(bufs, shapes)], quality=int(quality),
+                                           restart=_JPEG_RESTART, slot=0, huffman=huffman, subsampling="4:2:0", raw_capacity=True)
+        self._stats["jpeg_device_images"] += len(files)
+        self._stats["jpeg_device_bytes"] += sum(len(f) for f in files)
+        return dict(zip(keys, files))
 
     def close(self):
         """release the plans (the context's own close releases everything else)"""
@@ -92,9 +132,9 @@ class PairRenderer:
                                      fill_value=valid_fill if valid_fill is not None else 0, slot=0, dtype=dtype)
         return self.ctx.download(self._scratch, (h, w, C), dtype=dtype, slot=0)
 
-    def _remap_views(self, dev, imgs, dmask, interp, border, valid_fill):
-        """All views of the pair in ONE batched launch (no per-view launch tails), then the downloads.  `dmask` set:
-        the per-lens mask images are the sources (DF:2031-2043), else the lens images."""
+    def _remap_views(self, dev, imgs, dmask, interp, border, valid_fill, jpeg=None):
+        """All views of the pair in ONE batched launch (no per-view launch tails), then the downloads (or, with `jpeg`, the device
+        encoder: _collect).  `dmask` set: the per-lens mask images are the sources (DF:2031-2043), else the lens images."""
         dtype = np.uint8
         if dmask is None and any(v.dtype == np.uint16 for v in imgs.values()):
             if any(v.dtype != np.uint16 for v in imgs.values()):
@@ -129,7 +169,7 @@ class PairRenderer:
                 self.ctx.remap_plans_dev(planned, channels.pop(), interp=interp, border_value=border, slot=0, dtype=dtype)
             else:
                 self.ctx.remap_tables_dev(jobs, channels.pop(), interp=interp, border_value=border, slot=0, dtype=dtype)
-            return {vid: self.ctx.download(b, shape, dtype=dtype, slot=0) for (vid, shape), b in zip(shapes, bufs)}
+            return self._collect([vid for vid, _s in shapes], bufs, [shape for _v, shape in shapes], dtype, jpeg)
         finally:
             for b in bufs:
                 self.ctx.free(b)
@@ -138,8 +178,14 @@ class PairRenderer:
                     interpolation: int, mask_outside_model: bool, mask_value: int,
                     mask_x: Optional[np.ndarray] = None, mask_y: Optional[np.ndarray] = None,
                     want_fisheye: bool = False, want_perspective: bool = True,
-                    color_stage=None, want_color: bool = False):
+                    color_stage=None, want_color: bool = False, jpeg_views=None, jpeg_masks=None):
         """-> dict(perspective={view_id: img}, masks={view_id: img}, fisheye={'X': img, 'Y': img}, color={'X','Y'})
+
+        `jpeg_views` = None | (quality, huffman): when set and the views are 8-bit with C = 1 or 3, the perspective entries are not
+        downloaded: the batch's device buffers go into one gs360_jpeg_scan_sub_u8(..., GS360_JPEG_420, ...) call on the same slot and
+        every entry is a whole JFIF file (bytes: header + scan + EOI), what cv2.imwrite writes at DF:1826-1840 up to the DCT's rounding.
+        `jpeg_masks`: the same for the mask entries, whose files carry their own extension (--perspective-mask-ext).  16-bit and
+        four-channel views, the undistorted-fisheye and the colour-corrected outputs stay arrays.
 
         `color_stage` (gs360.color.ColorStage) converts both lens images on the device right after the upload, i.e.
         before every resampling step, as load_prepared_input_image does on the host (DF:728-743); `want_color`
@@ -180,14 +226,14 @@ class PairRenderer:
                     if self.fused and imgs["X"].dtype == np.uint16:
                         raise RuntimeError("16-bit lens images need table mode (the fused-map kernel is 8-bit)")
                     if self.fused:
-                        self._render_fused(out, imgs, dev, sensor_id_x, sensor_id_y, interp, mask_outside_model, mask_value)
+                        self._render_fused(out, imgs, dev, sensor_id_x, sensor_id_y, interp, mask_outside_model, mask_value, jpeg_views)
                     else:
-                        out["perspective"] = self._remap_views(dev, imgs, None, interp, border, fill)
+                        out["perspective"] = self._remap_views(dev, imgs, None, interp, border, fill, jpeg_views)
                     if dmask:
                         if self.fused:   # masks always go through the table path (nearest, border 0, invalid -> 0)
                             raise RuntimeError("mask rendering needs table mode")
                         out["masks"] = self._remap_views(None, None, dmask, capi.INTERP_NEAREST, (0.0, 0.0, 0.0, 0.0),
-                                                         0 if mask_outside_model else None)
+                                                         0 if mask_outside_model else None, jpeg_masks)
             finally:
                 for b in dev.values():
                     self.ctx.free(b)
@@ -195,7 +241,7 @@ class PairRenderer:
                     self.ctx.free(b)
         return out
 
-    def _render_fused(self, out, imgs, dev, sid_x, sid_y, interp, mask_outside, mask_value):
+    def _render_fused(self, out, imgs, dev, sid_x, sid_y, interp, mask_outside, mask_value, jpeg=None):
         views, calibs, srcs, dsts = [], [], [], []
         C = imgs["X"].shape[2]
         for key, sid in (("X", sid_x), ("Y", sid_y)):
@@ -216,9 +262,8 @@ class PairRenderer:
         try:
             self.ctx.fisheye_views_dev(srcs, calibs, C, views, self.lens_fov_deg, dsts, interp=interp,
                                        mask_outside=mask_outside, mask_value=mask_value, slot=0)
-            for spec, d in zip(self.specs, dsts):
-                out["perspective"][str(spec["view_id"])] = self.ctx.download(
-                    d, (int(spec["height"]), int(spec["width"]), C), slot=0)
+            out["perspective"] = self._collect([str(spec["view_id"]) for spec in self.specs], dsts,
+                                               [(int(spec["height"]), int(spec["width"]), C) for spec in self.specs], np.uint8, jpeg)
         finally:
             for d in dsts:
                 self.ctx.free(d)

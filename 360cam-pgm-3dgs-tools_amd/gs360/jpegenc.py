@@ -57,12 +57,21 @@ def _segment(marker, payload):
 
 TABLE_BYTES = 272            # GS360_JPEG_TABLE_BYTES: 16 BITS + up to 256 HUFFVAL, zero padded
 HUFFMAN_MODES = ("standard", "optimal")
+SUBSAMPLINGS = {"4:4:4": capi.JPEG_444, "4:2:0": capi.JPEG_420}      # -> GS360_JPEG_444 / GS360_JPEG_420 (Pillow's numbers)
 
 
-def header(H, W, C, quality, restart, tables=None):
+def _subsampling(name):
+    if name not in SUBSAMPLINGS:
+        raise ValueError("subsampling must be '4:4:4' or '4:2:0'")
+    return SUBSAMPLINGS[name]
+
+
+def header(H, W, C, quality, restart, tables=None, subsampling="4:4:4"):
     """Everything in front of the scan: SOI, APP0 (JFIF 1.01, density 1:1), DQT per table, SOF0, DHT per table, DRI, SOS.  `tables`: the
-    4 * 272 bytes gs360_jpeg_scan_opt_u8 returned for the image (DC0, AC0, DC1, AC1); None: the Annex K tables."""
+    4 * 272 bytes gs360_jpeg_scan_opt_u8 returned for the image (DC0, AC0, DC1, AC1); None: the Annex K tables.  subsampling="4:2:0"
+    ("JPG-SPEC v1, 4:2:0"): component 1 of a colour image samples 2 x 2; a gray image's header does not change."""
     H, W, C, restart = int(H), int(W), int(C), int(restart)
+    luma = 0x22 if _subsampling(subsampling) == capi.JPEG_420 else 0x11
     if C not in (1, 3):
         raise ValueError("C must be 1 or 3")
     if not (1 <= H <= 65535 and 1 <= W <= 65535):
@@ -77,7 +86,7 @@ def header(H, W, C, quality, restart, tables=None):
     sof = bytes((8,)) + H.to_bytes(2, "big") + W.to_bytes(2, "big") + bytes((C,))
     sos = bytes((C,))
     for c in range(C):
-        sof += bytes((c + 1, 0x11, min(c, 1)))
+        sof += bytes((c + 1, luma if (c == 0 and C == 3) else 0x11, min(c, 1)))
         sos += bytes((c + 1, 0x11 * min(c, 1)))
     out += _segment(0xC0, sof)
     dht = (_DC_LUMA, _AC_LUMA, _DC_CHROMA, _AC_CHROMA)
@@ -92,21 +101,72 @@ def header(H, W, C, quality, restart, tables=None):
     return out + _segment(0xDA, sos + b"\x00\x3f\x00")
 
 
-def scan_bound(H, W, C, restart=8):
-    """bytes that hold any scan of an H x W x C image (gs360_jpeg_scan_bound)"""
+def scan_bound(H, W, C, restart=8, subsampling="4:4:4"):
+    """bytes that hold any scan of an H x W x C image (gs360_jpeg_scan_bound_sub)"""
     n = ct.c_size_t(0)
     L = capi.load_library()
-    capi._check(L.gs360_jpeg_scan_bound(int(H), int(W), int(C), int(restart), ct.byref(n)), L)
+    capi._check(L.gs360_jpeg_scan_bound_sub(int(H), int(W), int(C), int(restart), _subsampling(subsampling), ct.byref(n)), L)
     return int(n.value)
 
 
-def encode_device(ctx, images, quality=100, restart=8, slot=0, huffman="standard"):
-    """images: uint8 ndarrays (H x W or H x W x C) or (DeviceBuffer, H, W, C) tuples of tight device images -> [bytes], one whole
-    JFIF file each.  One gs360_jpeg_scan_u8 call (huffman="optimal": gs360_jpeg_scan_opt_u8, every image's own tables) encodes them
-    all; only the scans' bytes, and with "optimal" 1 088 bytes of tables per image, come back from the device."""
+def encode_buffers(ctx, items, quality=100, restart=8, slot=0, huffman="standard", subsampling="4:4:4", raw_capacity=True):
+    """(the caller holds `slot`) items: [(DeviceBuffer, H, W, C)] tight 8-bit device images -> [bytes], one whole JFIF file each.  One
+    gs360_jpeg_scan_sub_u8 call on `slot` encodes them all where they are; the lengths, with "optimal" the tables (1 088 bytes an image)
+    and each scan's bytes come back.  raw_capacity: a scan gets the image's raw size and one that needs more (noise at quality 100) is
+    coded again, in the same mode, into a buffer of the bound; otherwise every scan gets the bound at once."""
     if huffman not in HUFFMAN_MODES:
         raise ValueError("huffman must be 'standard' or 'optimal'")
-    jobs, shapes, owned = [], [], []
+    sub = _subsampling(subsampling)
+    n = len(items)
+    if not n:
+        return []
+    optimal = huffman == "optimal"
+    owned = []
+
+    def alloc(nbytes):
+        owned.append(ctx.alloc(nbytes))
+        return owned[-1]
+
+    def run(jobs):
+        ctx.jpeg_scan_sub_dev(jobs, d_len, d_tab, quality=quality, restart=restart, subsampling=sub, slot=slot)
+        tabs = ctx.download(d_tab, (len(jobs), 4 * TABLE_BYTES), np.uint8, slot) if optimal else [None] * len(jobs)
+        return [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)], [None if t is None else t.tobytes() for t in tabs]
+    try:
+        caps = [H * W * C if raw_capacity else scan_bound(H, W, C, restart, subsampling) for _b, H, W, C in items]
+        jobs = [(buf, H, W, C, 0, alloc(cap), cap) for (buf, H, W, C), cap in zip(items, caps)]
+        d_len = alloc(8 * n)
+        d_tab = alloc(4 * TABLE_BYTES * n) if optimal else None
+        lengths, tables = run(jobs)
+        for i, length in enumerate(lengths):
+            if length != capi.JPEG_OVERFLOW:
+                continue
+            buf, H, W, C = items[i]
+            bound = scan_bound(H, W, C, restart, subsampling)
+            if bound <= caps[i]:
+                raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
+            jobs[i] = (buf, H, W, C, 0, alloc(bound), bound)
+            (lengths[i],), (tables[i],) = run([jobs[i]])
+            if lengths[i] == capi.JPEG_OVERFLOW:
+                raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
+        files = []
+        for (_b, H, W, C), job, length, tab in zip(items, jobs, lengths, tables):
+            body = ctx.download(job[5], (length,), np.uint8, slot).tobytes()
+            files.append(header(H, W, C, quality, restart, tab, subsampling) + body + EOI)
+        return files
+    finally:
+        for b in owned:
+            ctx.free(b)
+
+
+def encode_device(ctx, images, quality=100, restart=8, slot=0, huffman="standard", subsampling="4:4:4"):
+    """images: uint8 ndarrays (H x W or H x W x C) or (DeviceBuffer, H, W, C) tuples of tight device images -> [bytes], one whole
+    JFIF file each.  One gs360_jpeg_scan_sub_u8 call (huffman="optimal": every image's own tables; subsampling="4:2:0": 2 x 2 chroma
+    subsampling for colour images) encodes them all; only the scans' bytes, and with "optimal" 1 088 bytes of tables per image, come
+    back from the device."""
+    if huffman not in HUFFMAN_MODES:
+        raise ValueError("huffman must be 'standard' or 'optimal'")
+    _subsampling(subsampling)
+    items, owned = [], []
     try:
         for im in images:
             if isinstance(im, tuple):
@@ -117,32 +177,9 @@ def encode_device(ctx, images, quality=100, restart=8, slot=0, huffman="standard
                 Cn = 1 if a.ndim == 2 else a.shape[2]
                 buf = ctx.to_device(a, slot)
                 owned.append(buf)
-            cap = scan_bound(H, W, Cn, restart)
-            out = ctx.alloc(cap)
-            owned.append(out)
-            jobs.append((buf, H, W, Cn, 0, out, cap))
-            shapes.append((H, W, Cn))
-        if not jobs:
-            return []
-        d_len = ctx.alloc(8 * len(jobs))
-        owned.append(d_len)
+            items.append((buf, H, W, Cn))
         with ctx.slot_locks[slot]:
-            tables = [None] * len(jobs)
-            if huffman == "optimal":
-                d_tab = ctx.alloc(4 * TABLE_BYTES * len(jobs))
-                owned.append(d_tab)
-                ctx.jpeg_scan_opt_dev(jobs, d_len, d_tab, quality=quality, restart=restart, slot=slot)
-                tables = ctx.download(d_tab, (len(jobs), 4 * TABLE_BYTES), np.uint8, slot)
-            else:
-                ctx.jpeg_scan_dev(jobs, d_len, quality=quality, restart=restart, slot=slot)
-            lengths = ctx.download(d_len, (len(jobs),), np.uint64, slot)
-            files = []
-            for (H, W, Cn), job, n, tab in zip(shapes, jobs, lengths, tables):
-                if int(n) > job[6]:
-                    raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
-                body = ctx.download(job[5], (int(n),), np.uint8, slot).tobytes()
-                files.append(header(H, W, Cn, quality, restart, None if tab is None else tab.tobytes()) + body + EOI)
-        return files
+            return encode_buffers(ctx, items, quality, restart, slot, huffman, subsampling, raw_capacity=False)
     finally:
         for b in owned:
             ctx.free(b)

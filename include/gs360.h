@@ -472,6 +472,23 @@ int gs360_jpeg_scan_bound(int H, int W, int C, int restart_interval, size_t *byt
 int gs360_jpeg_scan_opt_u8(gs360_ctx *ctx, const gs360_jpeg_job *jobs, int n_jobs, int quality, int restart_interval,
                            uint64_t *lengths_dev, uint8_t *tables_dev, int slot);
 int gs360_jpeg_huff_tables(gs360_ctx *ctx, const uint32_t *hist_dev, int n_tables, uint8_t *tables_dev, int slot);
+/* "JPG-SPEC v1, 4:2:0" (DESIGN.md): the image writer behind the views of cli_tools/gs360_DualFisheyeDistortionCalibration.py,
+ * cv2.imwrite(path, image, [IMWRITE_JPEG_QUALITY, q]) at DF:1826-1840, i.e. libjpeg's defaults: 2 x 2 chroma subsampling, the Annex K
+ * Huffman tables, any quality 1..100 (the host path gives the same pixels to Pillow's default subsampling).  gs360_jpeg_scan_sub_u8 is
+ * the two scan entry points above in one, with a `subsampling` argument: tables_dev == NULL codes with the Annex K tables
+ * (gs360_jpeg_scan_u8), tables_dev != NULL with every image's own (gs360_jpeg_scan_opt_u8, 4 * GS360_JPEG_TABLE_BYTES bytes per image;
+ * table 0 serves Y, table 1 Cb and Cr); GS360_JPEG_444 gives exactly the bytes of those two.  With GS360_JPEG_420 a C = 3 image's Y, Cb
+ * and Cr planes are padded to multiples of 16, Cb and Cr are averaged over 2 x 2 cells as libjpeg's h2v2_downsample does ((a + b + c
+ * + d + bias) >> 2, bias 1 at even and 2 at odd output columns), an MCU is 16 x 16 pixels and holds the blocks Y(0,0), Y(0,1), Y(1,0),
+ * Y(1,1), Cb, Cr, and restart_interval counts those MCUs; a C = 1 image has no chroma and gets the bytes of GS360_JPEG_444.  The
+ * file's SOF0 then gives component 1 the sampling byte 0x22 (gs360/jpegenc.py).  Errors as the two entry points above, and
+ * GS360_ERR_ARG for any other `subsampling`.  gs360_jpeg_scan_bound_sub: gs360_jpeg_scan_bound for that mode, 416 bytes per block + 3
+ * per restart interval with 6 * ceil(H / 16) * ceil(W / 16) blocks for a C = 3 image under GS360_JPEG_420. */
+#define GS360_JPEG_444 0             /* Pillow's numbers for the same modes */
+#define GS360_JPEG_420 2
+int gs360_jpeg_scan_sub_u8(gs360_ctx *ctx, const gs360_jpeg_job *jobs, int n_jobs, int quality, int restart_interval, int subsampling,
+                           uint64_t *lengths_dev, uint8_t *tables_dev, int slot);
+int gs360_jpeg_scan_bound_sub(int H, int W, int C, int restart_interval, int subsampling, size_t *bytes);
 
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,

@@ -5,10 +5,13 @@ Reports pairs/s and views/s of the whole command (map building, image decode, GP
 image codecs run on the host; bench.py / tests/tools/bench_configs.py measure the device-resident remap (cfg4: ~0.11 ms per 6 views).
 
     python scripts/bench_df_cli_e2e.py [--pairs 8] [--workers 16] [--interpolation cubic] [--ext jpg]
+
+GS360_JPEG_ENCODER=device (and GS360_JPEG_HUFFMAN) in the environment reach the tool as in any run of it; the result names them.
 """
 import argparse
 import io
 import json
+import os
 import pathlib
 import sys
 import tempfile
@@ -71,7 +74,9 @@ def main():
         n_out = len(list((d.resolve().with_name("shots_perspective_colmap") / "Images").glob("*")))
     print(json.dumps({"pairs": args.pairs, "workers": args.workers, "interpolation": args.interpolation, "ext": args.ext,
                       "seconds": round(dt, 2), "pairs_per_s": round(args.pairs / dt, 2), "views_per_s": round(n_out / dt, 1),
-                      "views_written": n_out, "done_line": done[-1] if done else None}))
+                      "views_written": n_out, "done_line": done[-1] if done else None,
+                      "jpeg_encoder": os.environ.get("GS360_JPEG_ENCODER", "host"),
+                      "jpeg_huffman": os.environ.get("GS360_JPEG_HUFFMAN", "standard")}))
 
 
 if __name__ == "__main__":
