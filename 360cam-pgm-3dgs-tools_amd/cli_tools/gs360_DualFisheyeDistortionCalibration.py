@@ -23,6 +23,7 @@ import argparse
 import os
 import pathlib
 import sys
+import threading
 from concurrent.futures import FIRST_COMPLETED, ThreadPoolExecutor, wait
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
@@ -477,10 +478,11 @@ def main() -> None:
                     mask_count += len(specs)
             processed += 2
     else:
-        from gs360 import capi, hostmem, imageio
-        from gs360.dualfisheye import PairRenderer, jpeg_mode_from_env
+        from gs360 import capi, hostmem, imageio, jpegdec
+        from gs360.dualfisheye import DeviceImage, PairRenderer, jpeg_mode_from_env
         try:
             huffman = jpeg_mode_from_env()                # GS360_JPEG_ENCODER / GS360_JPEG_HUFFMAN, read once per run
+            device_decoder = jpegdec.device_decoder_enabled()      # GS360_JPEG_DECODER
         except ValueError as exc:
             _die("[ERR] {}".format(exc), 1)
         jpeg_views = (_jpeg_quality(jpeg_q), huffman) if huffman and persp_ext in (".jpg", ".jpeg") else None
@@ -489,7 +491,7 @@ def main() -> None:
         if n_dev <= 0:
             _die("[ERR] no MI355X visible: the gs360 engine has no CPU fallback", 2)
         hostmem.tune_malloc()                     # the worker threads' large short-lived image buffers (gs360/hostmem.py)
-        contexts = [capi.Context(device=d, n_slots=1) for d in range(n_dev)]
+        contexts = [capi.Context(device=d, n_slots=2 if device_decoder else 1) for d in range(n_dev)]   # slot 1: the device JPEG decoder
         stage = color.ColorStage(input_lut, lut_space) if input_lut is not None else None
         renderers = {}
         for d, ctx in enumerate(contexts):
@@ -498,12 +500,32 @@ def main() -> None:
                                                   {sid: undistort[sid] for sid in sp if sid in undistort},
                                                   float(args.lens_fov_deg), fused=(args.map_mode == "fused"))
 
+        decode_counts = {"device": 0, "host": 0}
+        decode_counts_lock = threading.Lock()
+
+        def load_lens(r, path):
+            """the lens image: with GS360_JPEG_DECODER=device a baseline .jpg is decoded on the renderer's GPU from its file bytes (JPD-SPEC
+            v1) and stays there; everything else, and whatever the device path does not take, is read on the host as before"""
+            if device_decoder and jpegdec.is_jpeg_path(path):
+                got = jpegdec.try_decode_file(r.ctx, path, slot=1)      # (its own stream and lock: overlaps other pairs' rendering on slot 0)
+                with decode_counts_lock:
+                    decode_counts["device" if got is not None else "host"] += 1
+                if got is not None:
+                    return DeviceImage(got.buf, got.shape)
+            return imageio.read_image(path)
+
         def pair_task(idx, base, x_path, y_path, sx, sy):
             r = renderers[((idx - 1) % n_dev, (sx, sy))]           # pairs shard across GPUs, no exchange step
-            img_x, img_y = imageio.read_image(x_path), imageio.read_image(y_path)
             mx = my = None
-            if base in pair_masks:
+            if base in pair_masks:               # (host arrays, read before anything is put on the device for this pair)
                 mx, my = imageio.read_image(pair_masks[base][0]), imageio.read_image(pair_masks[base][1])
+            img_x = load_lens(r, x_path)
+            try:
+                img_y = load_lens(r, y_path)
+            except Exception:
+                if isinstance(img_x, DeviceImage):
+                    r.ctx.free(img_x.buf)
+                raise
             res = r.render_pair(img_x, img_y, sx, sy, interpolation=interpolation, mask_outside_model=bool(args.mask_outside_model),
                                 mask_value=mask_value, mask_x=mx, mask_y=my, want_fisheye=write_fisheye, want_perspective=write_persp,
                                 color_stage=stage, want_color=save_color, jpeg_views=jpeg_views, jpeg_masks=jpeg_masks)
@@ -566,6 +588,8 @@ def main() -> None:
             while pending:
                 done, pending = wait(pending, return_when=FIRST_COMPLETED)
                 drain(list(done))
+        if device_decoder:
+            say("[INFO] JPEG decoder: {} lens images decoded on the device, {} on the host".format(decode_counts["device"], decode_counts["host"]))
         if stage is not None:
             stage.close()
         for r in renderers.values():

@@ -1,6 +1,6 @@
 // gs360_capi_codec.hip -- image-codec entry points of libgs360hip.so (include/gs360.h): PNG scanline unfiltering and TIFF LZW strip
 // decoding for the Python-side codec (gs360/imageio.py; host only, no GPU involved), and the glue of the device JPEG scans
-// (gs360_jpeg.hip).
+// (gs360_jpeg.hip) and of the device JPEG decoder (gs360_jpegdec.hip).
 #include "gs360_capi_internal.h"
 
 using namespace gs360;
@@ -277,5 +277,99 @@ int gs360_jpeg_huff_tables(gs360_ctx* c, const uint32_t* hist_dev, int n_tables,
     if (!hist_dev || !tables_dev) return fail(GS360_ERR_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_jpeg_huff_tables(hist_dev, n_tables, tables_dev, c->stream[slot]));
+    return GS360_OK;
+}
+
+// ---- baseline JPEG files decoded on the device (JPD-SPEC v1; kernels in gs360_jpegdec.hip) --------------------------------
+namespace {
+
+int check_jpeg_dec_geometry(int H, int W, int C, int subsampling) {
+    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(GS360_ERR_ARG, "JPEG sides are 1..65535 (got %d x %d)", W, H);
+    if (C != 1 && C != 3) return fail(GS360_ERR_UNSUPPORTED, "the JPEG decoder takes C = 1 or 3 (got %d)", C);
+    if (subsampling != GS360_JPEG_444 && subsampling != GS360_JPEG_420)
+        return fail(GS360_ERR_UNSUPPORTED, "the JPEG decoder takes GS360_JPEG_444 or GS360_JPEG_420 (got %d)", subsampling);
+    return 0;
+}
+
+}  // namespace
+
+int gs360_jpeg_decode_scratch(int H, int W, int C, int subsampling, uint32_t n_subseq, size_t* bytes) {
+    if (!bytes) return fail(GS360_ERR_ARG, "NULL argument");
+    if (int rc = check_jpeg_dec_geometry(H, W, C, subsampling)) return rc;
+    if (n_subseq < 1 || n_subseq > (1u << 31) / kJdSubseq) return fail(GS360_ERR_ARG, "n_subseq %u outside 1..2^24", n_subseq);
+    *bytes = jd_layout(H, W, C, subsampling == GS360_JPEG_420, n_subseq).total;
+    return GS360_OK;
+}
+
+int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_jobs, uint32_t* status_dev, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
+    if (n_jobs == 0) return GS360_OK;
+    if (!jobs || !status_dev) return fail(GS360_ERR_ARG, "NULL argument");
+    for (int k = 0; k < n_jobs; ++k) {
+        const gs360_jpeg_dec_job& j = jobs[k];
+        if (int rc = check_jpeg_dec_geometry(j.H, j.W, j.C, j.subsampling)) return rc;
+        if (!j.scan || !j.segments || !j.tables || !j.scratch || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL pointer", k);
+        if (j.scan_len < 1 || j.scan_len > (uint32_t)INT32_MAX) return fail(GS360_ERR_ARG, "job %d: scan of %u bytes outside 1..2^31-1", k, j.scan_len);
+        if (j.n_segments < 1 || (uint32_t)j.n_segments > j.scan_len) return fail(GS360_ERR_ARG, "job %d: %d segments for %u bytes", k, j.n_segments, j.scan_len);
+        if (j.restart_interval < 0 || j.restart_interval > 65535) return fail(GS360_ERR_ARG, "job %d: restart interval %d outside 0..65535", k, j.restart_interval);
+        if (j.out_stride && j.out_stride < (size_t)j.W * j.C) return fail(GS360_ERR_ARG, "job %d: out_stride below a row", k);
+        if ((uintptr_t)j.scratch % 256) return fail(GS360_ERR_ARG, "job %d: scratch is not 256-byte aligned", k);
+        if ((uintptr_t)j.segments % 16) return fail(GS360_ERR_ARG, "job %d: segments is not 16-byte aligned", k);
+        for (int q = 0; q < j.C; ++q)
+            if (j.comp_tq[q] > 3 || j.comp_td[q] > 1 || j.comp_ta[q] > 1) return fail(GS360_ERR_UNSUPPORTED, "job %d: table selector outside baseline", k);
+        // every interval takes at least one subsequence and none crosses an interval
+        if (j.n_subseq < 1 || j.n_subseq > (uint64_t)j.scan_len / kJdSubseq + (uint32_t)j.n_segments)
+            return fail(GS360_ERR_ARG, "job %d: %u subsequences for %u bytes in %d segments", k, j.n_subseq, j.scan_len, j.n_segments);
+        if (jd_layout(j.H, j.W, j.C, j.subsampling == GS360_JPEG_420, j.n_subseq).total > j.scratch_bytes)
+            return fail(GS360_ERR_ARG, "job %d: scratch too small", k);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream[slot];
+    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
+        JdLaunch L;
+        std::memset(&L, 0, sizeof(L));
+        L.n_jobs = std::min(GS360_MAX_VIEWS, n_jobs - k0);
+        L.status = status_dev + k0;
+        int64_t wgs = 0, tiles = 0;
+        for (int k = 0; k < L.n_jobs; ++k) {
+            const gs360_jpeg_dec_job& j = jobs[k0 + k];
+            JdJob& J = L.job[k];
+            const bool sub = j.subsampling == GS360_JPEG_420 && j.C == 3;
+            const uint32_t n_sub = j.n_subseq;
+            const JdLayout l = jd_layout(j.H, j.W, j.C, sub, n_sub);
+            J.scan = (const uint8_t*)j.scan;
+            J.seg = (const uint4*)j.segments;
+            J.meta = j.tables;
+            J.scratch = (uint8_t*)j.scratch;
+            J.out = (uint8_t*)j.out;
+            J.stride = (int64_t)(j.out_stride ? j.out_stride : (size_t)j.W * j.C);
+            J.n_seg = (uint32_t)j.n_segments;
+            J.n_sub = n_sub;
+            J.scan_len = j.scan_len;
+            J.H = j.H; J.W = j.W; J.C = j.C;
+            J.bpm = sub ? 6 : j.C;
+            const int px = sub ? 16 : 8;
+            J.mw = (j.W + px - 1) / px;
+            J.mh = (j.H + px - 1) / px;
+            J.ri = j.restart_interval;
+            J.wg_base = (int32_t)wgs;
+            J.tile_base = (int32_t)tiles;
+            J.tiles_x = (j.W + 127) / 128;
+            J.n_wg = l.n_wg;
+            J.dc_chunks = l.dc_chunks;
+            for (int q = 0; q < 4; ++q) { J.tq[q] = j.comp_tq[q] & 3; J.td[q] = j.comp_td[q] & 1; J.ta[q] = j.comp_ta[q] & 1; }
+            J.lay.exits = l.exits; J.lay.sums = l.sums; J.lay.used = l.used; J.lay.recs = l.recs; J.lay.carry = l.carry; J.lay.dc = l.dc;
+            J.lay.coef = l.coef;
+            J.blocks = l.blocks;
+            wgs += l.n_wg;
+            tiles += (int64_t)J.tiles_x * ((j.H + 63) / 64);
+            L.max_dc_chunks = std::max(L.max_dc_chunks, l.dc_chunks);
+        }
+        if (wgs > INT32_MAX || tiles > INT32_MAX) return fail(GS360_ERR_ARG, "JPEG batch too large");
+        L.total_wg = (int32_t)wgs;
+        L.total_tiles = (int32_t)tiles;
+        HIP_TRY(launch_jpeg_decode(L, s));
+    }
     return GS360_OK;
 }

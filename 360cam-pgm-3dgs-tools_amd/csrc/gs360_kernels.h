@@ -390,4 +390,55 @@ hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s);
 // n_tables x 256 symbol counts -> n_tables x 272 bytes (16 BITS + HUFFVAL, zero padded): the table kernel alone
 hipError_t launch_jpeg_huff_tables(const uint32_t* hist, int n_tables, uint8_t* tables, hipStream_t s);
 
+// Baseline JPEG decoding (gs360_jpegdec.hip, JPD-SPEC v1 in DESIGN.md): one batch of up to GS360_MAX_VIEWS files.  A job's scratch
+// (JdLayout) holds a header of three counters, per subsequence its exit state and the exclusive sum of the blocks completed before it,
+// per workgroup boundary the entry state last propagated across it, the DC scan's chunk records, the blocks' DC values and, last,
+// the coefficients (64 int16 per block in natural order, blocks in scan order).
+constexpr int kJdSubseq = 128;           // GS360_JPEG_DEC_SUBSEQ_BYTES
+constexpr int kJdWgSubs = 256;           // GS360_JPEG_DEC_WG_SUBSEQS: subsequences (lanes) per workgroup of the entropy passes
+constexpr int kJdDcChunk = 1024;         // DC values one workgroup of the DC scan covers
+struct JdLayout {
+    size_t exits, sums, used, recs, carry, dc, coef, total;
+    int64_t blocks;
+    int32_t n_wg, dc_chunks;             // entropy workgroups; DC chunks of the component with the most blocks
+};
+inline JdLayout jd_layout(int H, int W, int C, int sub420, uint32_t n_sub) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const int px = (sub420 && C == 3) ? 16 : 8, bpm = (sub420 && C == 3) ? 6 : C;
+    const int64_t mcus = (int64_t)((W + px - 1) / px) * ((H + px - 1) / px);
+    JdLayout l;
+    l.blocks = mcus * bpm;
+    l.n_wg = (int32_t)((n_sub + kJdWgSubs - 1) / kJdWgSubs);
+    l.dc_chunks = (int32_t)((mcus * (bpm == 6 ? 4 : 1) + kJdDcChunk - 1) / kJdDcChunk);
+    l.exits = 256;
+    l.sums = l.exits + up((size_t)n_sub * 4);
+    l.used = l.sums + up((size_t)n_sub * 4);
+    l.recs = l.used + up((size_t)l.n_wg * 4);
+    l.carry = l.recs + up((size_t)l.dc_chunks * 3 * 8);
+    l.dc = l.carry + up((size_t)l.dc_chunks * 3 * 4);
+    l.coef = l.dc + up((size_t)l.blocks * 4);
+    l.total = l.coef + (size_t)l.blocks * 128;
+    return l;
+}
+struct JdJob {
+    const uint8_t* scan;                 // the entropy-coded segment
+    const uint4* seg;                    // per restart interval: start, length, first subsequence, first MCU
+    const uint8_t* meta;                 // 4 x 272 Huffman table bytes, then 4 x 64 quantiser bytes (zig-zag order)
+    uint8_t* scratch;
+    uint8_t* out;
+    int64_t stride, blocks;
+    uint32_t n_seg, n_sub, scan_len, pad;
+    int32_t H, W, C, bpm, mw, mh, ri;    // bpm: blocks per MCU (1, 3 or 6); MCU grid; MCUs per restart interval (0: none)
+    int32_t wg_base, tile_base, tiles_x; // first entropy workgroup, first reconstruction tile (64 rows x 128 columns), tiles per row
+    int32_t n_wg, dc_chunks;
+    uint8_t tq[4], td[4], ta[4];         // per component: quantiser, DC table, AC table
+    struct { size_t exits, sums, used, recs, carry, dc, coef; } lay;     // JdLayout's offsets (a launch's jobs travel as kernel arguments)
+};
+struct JdLaunch {
+    JdJob job[GS360_MAX_VIEWS];
+    int32_t n_jobs, total_wg, total_tiles, max_dc_chunks;
+    uint32_t* status;                    // n_jobs
+};
+hipError_t launch_jpeg_decode(const JdLaunch& L, hipStream_t s);
+
 }  // namespace gs360

@@ -34,12 +34,14 @@ EXPORTS = (
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
     "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
     "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound", "gs360_jpeg_scan_opt_u8", "gs360_jpeg_huff_tables",
-    "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub",
+    "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub", "gs360_jpeg_decode_u8", "gs360_jpeg_decode_scratch",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
 JPEG_444 = 0                         # GS360_JPEG_444 / GS360_JPEG_420: the `subsampling` of gs360_jpeg_scan_sub_u8 (Pillow's numbers)
 JPEG_420 = 2
+JPEG_DEC_SUBSEQ_BYTES = 128          # GS360_JPEG_DEC_SUBSEQ_BYTES: bytes of a scan one lane of gs360_jpeg_decode_u8 decodes first
+JPEG_DEC_WG_SUBSEQS = 256            # GS360_JPEG_DEC_WG_SUBSEQS: subsequences one workgroup synchronises among themselves
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
@@ -85,6 +87,14 @@ class JpegJob(C.Structure):
     """gs360_jpeg_job: one image of a batched JPEG scan call (device pointers)."""
     _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("src_stride", C.c_size_t),
                 ("out", C.c_void_p), ("out_capacity", C.c_size_t)]
+
+
+class JpegDecJob(C.Structure):
+    """gs360_jpeg_dec_job: one file of a batched JPEG decode call (device pointers)."""
+    _fields_ = [("scan", C.c_void_p), ("scan_len", C.c_uint32), ("n_subseq", C.c_uint32), ("segments", C.c_void_p), ("n_segments", C.c_int32),
+                ("tables", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("subsampling", C.c_int32),
+                ("restart_interval", C.c_int32), ("comp_tq", C.c_uint8 * 4), ("comp_td", C.c_uint8 * 4), ("comp_ta", C.c_uint8 * 4),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("out", C.c_void_p), ("out_stride", C.c_size_t)]
 
 
 class FrameStats(C.Structure):
@@ -210,6 +220,8 @@ def load_library(path=None):
         L.gs360_jpeg_huff_tables.argtypes = [vp, vp, i, vp, i]
         L.gs360_jpeg_scan_sub_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, i, vp, vp, i]
         L.gs360_jpeg_scan_bound_sub.argtypes = [i, i, i, i, i, C.POINTER(C.c_size_t)]
+        L.gs360_jpeg_decode_u8.argtypes = [vp, C.POINTER(JpegDecJob), i, vp, i]
+        L.gs360_jpeg_decode_scratch.argtypes = [i, i, i, i, u32, C.POINTER(C.c_size_t)]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -628,6 +640,15 @@ class Context:
         if hist.nbytes < 1024 * n or tables.nbytes < JPEG_TABLE_BYTES * n:
             raise ValueError("histogram or tables buffer too small for n tables")
         _check(self.L.gs360_jpeg_huff_tables(self.handle, hist.ptr, int(n), tables.ptr, slot), self.L)
+
+    # -- JPEG files decoded into device images (gs360/jpegdec.py) ------------------------------
+    def jpeg_decode_dev(self, jobs, status, slot=0):
+        """gs360_jpeg_decode_u8: jobs = sequence of JpegDecJob (device pointers; gs360/jpegdec.py fills them), status = DeviceBuffer of
+        len(jobs) uint32.  Asynchronous on `slot`."""
+        if status.nbytes < 4 * len(jobs):
+            raise ValueError("status buffer below 4 bytes per job")
+        arr = (JpegDecJob * max(len(jobs), 1))(*jobs)
+        _check(self.L.gs360_jpeg_decode_u8(self.handle, arr, len(jobs), status.ptr, slot), self.L)
 
     # -- hot path, host buffers (synchronous) -----------------------------------------------
     def equirect_views(self, src, views, slot=0, interp=INTERP_LINEAR, flags=0):

@@ -194,10 +194,18 @@ class PairRenderer:
         out = {"perspective": {}, "masks": {}, "fisheye": {}, "color": {}}
         with self.lock:
             imgs = {"X": _hwc(image_x), "Y": _hwc(image_y)}
-            if color_stage is not None:
-                for v in imgs.values():
-                    color_stage.check_image(v.shape, v.dtype)
-            dev = {k: self.ctx.to_device(v) for k, v in imgs.items()}
+            dev = {k: v.buf for k, v in imgs.items() if isinstance(v, DeviceImage)}      # (freed below with the uploads)
+            try:
+                if color_stage is not None:
+                    for v in imgs.values():
+                        color_stage.check_image(v.shape, v.dtype)
+                for k, v in imgs.items():
+                    if k not in dev:
+                        dev[k] = self.ctx.to_device(v)
+            except Exception:
+                for b in dev.values():
+                    self.ctx.free(b)
+                raise
             dmask = {}
             for k, m in (("X", mask_x), ("Y", mask_y)):
                 if m is not None:
@@ -208,7 +216,8 @@ class PairRenderer:
                         color_stage.apply_dev(self.ctx, dev[k], v.shape, red_index=0, slot=0, dtype=v.dtype)   # arrays here are RGB(A)
                 if want_color:
                     for k, v in imgs.items():
-                        out["color"][k] = self.ctx.download(dev[k], v.shape, dtype=v.dtype, slot=0) if color_stage is not None else v
+                        on_device = color_stage is not None or isinstance(v, DeviceImage)
+                        out["color"][k] = self.ctx.download(dev[k], v.shape, dtype=v.dtype, slot=0) if on_device else v
                 # borderValue=float(mask_value) -> cv::Scalar(v,0,0,0): only channel 0 gets v, and channel 0 of a
                 # cv2.imread image is BLUE.  Arrays here are RGB(A), so the value goes to index 2 for colour images.
                 C_in = imgs["X"].shape[2]
@@ -269,7 +278,18 @@ class PairRenderer:
                 self.ctx.free(d)
 
 
+class DeviceImage:
+    """An 8-bit H x W x C lens image that is in device memory already (gs360.jpegdec with GS360_JPEG_DECODER=device): render_pair
+    takes it in place of an array, uses the buffer as the uploaded image and frees it."""
+    ndim = 3
+
+    def __init__(self, buf, shape):
+        self.buf, self.shape, self.dtype = buf, tuple(int(v) for v in shape), np.dtype(np.uint8)
+
+
 def _hwc(a: np.ndarray) -> np.ndarray:
     """uint8 stays uint8; uint16 sources (cv2.imread(IMREAD_UNCHANGED), DF:735) stay uint16"""
+    if isinstance(a, DeviceImage):
+        return a
     a = np.ascontiguousarray(a, dtype=np.uint16 if np.asarray(a).dtype == np.uint16 else np.uint8)
     return a if a.ndim == 3 else a[:, :, None]

@@ -17,6 +17,10 @@ GS360_JPEG_ENCODER=device moves that last step onto the GPU for 8-bit .jpg views
 they are (gs360/jpegenc.py, one gs360_jpeg_scan_u8 call on the launch's stream; with GS360_JPEG_HUFFMAN=optimal one
 gs360_jpeg_scan_opt_u8 call, which builds every view's own Huffman tables first), only the scans cross PCIe, and a job writes
 header + scan + EOI with a plain file write.  The default, `host`, is the path above, unchanged.
+
+GS360_JPEG_DECODER=device does the same for the input side (gs360/jpegdec.py, JPD-SPEC v1): a baseline .jpg / .jpeg still is not
+decoded by Pillow and uploaded as pixels; its scan is uploaded and gs360_jpeg_decode_u8 leaves the frame resident.  Files the device
+path does not take (progressive, 4:2:2, CMYK, cut short ...) and every other format go through imageio.read_image as before.
 """
 import collections
 import itertools
@@ -27,7 +31,7 @@ import time
 
 import numpy as np
 
-from . import capi, hostmem, imageio, jpegenc, video
+from . import capi, hostmem, imageio, jpegdec, jpegenc, video
 from .jobspec import JobSpec
 
 _FRAME_CACHE_BYTES = int(os.environ.get("GS360_FRAME_CACHE_MB", "4096")) << 20
@@ -144,6 +148,7 @@ class Engine:
         self.devices = list(devices) if devices is not None else list(range(n))
         self.states = [_DeviceState(d) for d in self.devices]
         self._warned_cubic = False
+        self.device_decoder = jpegdec.device_decoder_enabled()    # GS360_JPEG_DECODER, read (and checked) once per engine
         self.videos = {}                          # DecodePlan.key -> the video.VideoSession new view jobs join
         self._video_done = {}                     # DecodePlan.key -> view jobs finished so far (all sessions of that video)
         self.videos_lock = threading.Lock()
@@ -270,17 +275,27 @@ class Engine:
                 if hit is not None:
                     hit[4] += 1
                     return hit
-            img = imageio.read_image(path)
-            H, W, C = img.shape
-            if C not in (1, 3, 4):
-                raise capi.Gs360Error(-1, f"{path}: unsupported channel count {C}")
-            buf = st.ctx.alloc(img.nbytes)
-            with st.upload_lock:
-                st.ctx.upload(buf, img, slot=st.upload_slot, sync=True)
-            entry = [buf, H, W, C, 1, img.dtype]  # [4]: users currently holding the frame; [5]: uint8 / uint16
+            decoded = None
+            if self.device_decoder and jpegdec.is_jpeg_path(path):
+                with st.upload_lock:
+                    decoded = jpegdec.try_decode_file(st.ctx, path, slot=st.upload_slot)
+                with st.lock:
+                    st.stats["device_decoded_frames" if decoded is not None else "device_decode_fallbacks"] += 1
+            if decoded is not None:
+                buf, (H, W, C), dtype = decoded.buf, decoded.shape, np.dtype(np.uint8)
+                nbytes = H * W * C
+            else:
+                img = imageio.read_image(path)
+                H, W, C = img.shape
+                if C not in (1, 3, 4):
+                    raise capi.Gs360Error(-1, f"{path}: unsupported channel count {C}")
+                buf, dtype, nbytes = st.ctx.alloc(img.nbytes), img.dtype, img.nbytes
+                with st.upload_lock:
+                    st.ctx.upload(buf, img, slot=st.upload_slot, sync=True)
+            entry = [buf, H, W, C, 1, dtype]  # [4]: users currently holding the frame; [5]: uint8 / uint16
             with st.lock:
                 st.frames[key] = entry
-                st.frame_bytes += img.nbytes
+                st.frame_bytes += nbytes
                 for k in list(st.frames):         # evict least-recently-used frames nobody is reading
                     if st.frame_bytes <= _FRAME_CACHE_BYTES:
                         break
@@ -659,8 +674,9 @@ class Engine:
 
     def stats(self):
         """Counters since start: batched launches, views, seconds the launch+copy sections held a stream; jpeg_device_images /
-        jpeg_device_bytes: views the device encoder wrote (GS360_JPEG_ENCODER=device) and their files' bytes."""
-        total = collections.Counter(jpeg_device_images=0, jpeg_device_bytes=0)
+        jpeg_device_bytes: views the device encoder wrote (GS360_JPEG_ENCODER=device) and their files' bytes; device_decoded_frames /
+        device_decode_fallbacks: .jpg stills the device decoder took (GS360_JPEG_DECODER=device) and those it left to the host."""
+        total = collections.Counter(jpeg_device_images=0, jpeg_device_bytes=0, device_decoded_frames=0, device_decode_fallbacks=0)
         for st in self.states:
             total.update(st.stats)
         return dict(total)

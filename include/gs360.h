@@ -35,7 +35,9 @@ extern "C" {
 
 /* 2 (round 6): + gs360_ctx_set_option / _get_option / gs360_device_pci_bus_id (added in round 5 without a bump), the table_stage* options; the
  * library no longer reads GS360_RING, GS360_XCD_GROUP, GS360_EQ_PERSIST, GS360_TABLE_PERSIST, GS360_LANCZOS_TABLE, GS360_TABLE_ROWS from
- * the environment (context options of the same names do that: INTEGRATION.md section 2.1).  A binding checks gs360_abi_version() first. */
+ * the environment (context options of the same names do that: INTEGRATION.md section 2.1).  A binding checks gs360_abi_version() first.
+ * Entry points added since (frame statistics, JPEG scans, gs360_jpeg_decode_u8 / gs360_jpeg_decode_scratch) only add symbols and leave
+ * every existing signature and struct alone, so the number stays. */
 #define GS360_ABI_VERSION 2
 
 typedef enum gs360_status {
@@ -489,6 +491,40 @@ int gs360_jpeg_huff_tables(gs360_ctx *ctx, const uint32_t *hist_dev, int n_table
 int gs360_jpeg_scan_sub_u8(gs360_ctx *ctx, const gs360_jpeg_job *jobs, int n_jobs, int quality, int restart_interval, int subsampling,
                            uint64_t *lengths_dev, uint8_t *tables_dev, int slot);
 int gs360_jpeg_scan_bound_sub(int H, int W, int C, int restart_interval, int subsampling, size_t *bytes);
+
+/* ---- baseline JPEG files decoded on the device (JPD-SPEC v1) -------------------------------------------
+ * The inverse of the scans above for the input side: a baseline sequential JPEG (SOF0, 8 bits, one interleaved scan; gray, 4:4:4 or
+ * 4:2:0) becomes an H x W x C uint8 image in device memory (C = 3: R, G, B), byte for byte what libjpeg's default decoder returns
+ * (islow IDCT, "fancy" h2v2 upsampling, its fixed-point YCbCr -> RGB tables).  The host parses the header (gs360/jpegdec.py) and hands
+ * over, all in device memory: `scan`, the entropy-coded segment (everything between the SOS header and EOI, restart markers
+ * included); `segments`, per restart interval four uint32: its first byte in `scan`, its length (marker excluded), the number of
+ * subsequences of GS360_JPEG_DEC_SUBSEQ_BYTES bytes all earlier intervals take (each ceil(length / that)), and its first MCU (the
+ * records are read as 16-byte vectors: `segments` is 16-byte aligned);
+ * `tables`, 4 * GS360_JPEG_TABLE_BYTES bytes (DC0, AC0, DC1, AC1: 16 BITS + HUFFVAL, zero padded) followed by four quantiser tables of
+ * 64 bytes in file (zig-zag) order; `scratch`, 256-byte aligned, of the size gs360_jpeg_decode_scratch gives for the file (n_subseq:
+ * the subsequences of all intervals together).  `out` / out_stride (0 = tight) follow the stride rules of the memory section.
+ * status_dev[k] (device memory) is 0 when job k's stream decoded to exactly its blocks and every interval ended at its last byte,
+ * 1 when the decoder met an invalid code and 2 when an interval held fewer or more blocks than it should; `out` then holds no image.
+ * A truncated or corrupt stream never makes the device read or write outside the job's buffers.  Asynchronous on `slot`.
+ * GS360_ERR_UNSUPPORTED: C not 1 or 3, a subsampling other than GS360_JPEG_444 / GS360_JPEG_420, a table selector above 1 (3 for
+ * quantisers); GS360_ERR_ARG: sizes of 2^31 bytes or more, a scratch that is too small or misaligned, misaligned segments. */
+#define GS360_JPEG_DEC_SUBSEQ_BYTES 128  /* the entropy decoder's unit: one lane decodes one subsequence first */
+#define GS360_JPEG_DEC_WG_SUBSEQS 256    /* subsequences one workgroup synchronises among themselves */
+typedef struct gs360_jpeg_dec_job {
+    const void *scan;
+    uint32_t scan_len, n_subseq;                     /* n_subseq: as given to gs360_jpeg_decode_scratch */
+    const uint32_t *segments;
+    int32_t n_segments;
+    const uint8_t *tables;
+    int32_t H, W, C, subsampling, restart_interval;  /* restart_interval: MCUs, 0 = none */
+    uint8_t comp_tq[4], comp_td[4], comp_ta[4];      /* per component: quantiser, DC and AC table */
+    void *scratch;
+    size_t scratch_bytes;
+    void *out;
+    size_t out_stride;
+} gs360_jpeg_dec_job;
+int gs360_jpeg_decode_u8(gs360_ctx *ctx, const gs360_jpeg_dec_job *jobs, int n_jobs, uint32_t *status_dev, int slot);
+int gs360_jpeg_decode_scratch(int H, int W, int C, int subsampling, uint32_t n_subseq, size_t *bytes);
 
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,

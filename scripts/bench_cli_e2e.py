@@ -11,7 +11,11 @@ thread-summed wall time spent inside launch + copy + sync sections (waiting for 
 -- an UPPER bound of the share of time the GPU is busy (with many workers the sections of different frames overlap).  Informational: the image codecs run on
 the host and bound both figures; bench.py's `value` is the device-resident hot path.
 
-    python scripts/bench_cli_e2e.py [--frames 6] [--video-frames 8] [--jobs 16] [--ext jpg] [--only stills|video]
+    python scripts/bench_cli_e2e.py [--frames 6] [--video-frames 8] [--jobs 16] [--ext jpg] [--input-ext png|jpg] [--only stills|video]
+
+--input-ext jpg writes the stills as quality-92 4:2:0 JPEGs (what cameras and ffmpeg leave in such folders) instead of PNG; with
+GS360_JPEG_DECODER=device in the environment the engine then decodes them on the GPU (gs360/jpegdec.py), and the row names the decoder
+and how many frames took which path.
 """
 import argparse
 import io
@@ -96,7 +100,7 @@ def run_cli(argv):
         sys.argv = old
     wall = time.perf_counter() - t0
     after = eng.stats()
-    st = {k: after.get(k, 0) - before.get(k, 0) for k in ("launches", "views", "gpu_s")}
+    st = {k: after.get(k, 0) - before.get(k, 0) for k in ("launches", "views", "gpu_s", "device_decoded_frames", "device_decode_fallbacks")}
     tail = [ln for ln in buf.getvalue().splitlines() if ln.startswith("[OK]")]
     return wall, st, tm.t, (tail[-1] if tail else "")
 
@@ -107,6 +111,7 @@ def main():
     ap.add_argument("--video-frames", type=int, default=8)
     ap.add_argument("--jobs", type=int, default=16)
     ap.add_argument("--ext", default="jpg")
+    ap.add_argument("--input-ext", default="png", choices=("png", "jpg"))
     ap.add_argument("--only", default="")
     args = ap.parse_args()
     rows = []
@@ -116,15 +121,21 @@ def main():
             d = td / "stills"
             d.mkdir()
             for k in range(args.frames):
-                imageio.write_image(d / f"pano_{k:03d}.png", synth(2880, 5760, k))
+                if args.input_ext == "jpg":
+                    from PIL import Image
+                    Image.fromarray(synth(2880, 5760, k)).save(d / f"pano_{k:03d}.jpg", quality=92)
+                else:
+                    imageio.write_image(d / f"pano_{k:03d}.png", synth(2880, 5760, k))
             wall, st, tm, ok = run_cli(["-i", str(d), "--preset", "default", "--ext", args.ext, "-j", str(args.jobs)])
             nv = args.frames * 8
-            rows.append({"what": f"CLI stills: {args.frames} x 5760x2880 PNG -> default preset 8 x 1600^2 .{args.ext}, -j {args.jobs}",
+            rows.append({"what": f"CLI stills: {args.frames} x 5760x2880 {args.input_ext.upper()} -> default preset 8 x 1600^2 .{args.ext}, -j {args.jobs}",
                          "wall_s": round(wall, 3), "frames_per_s": round(args.frames / wall, 2), "views_per_s": round(nv / wall, 1),
                          "out_MPix_per_s": round(nv * 2.56 / wall, 1), "batched_launches": st["launches"], "views_rendered": st["views"],
                          "views_per_launch": round(st["views"] / max(1, st["launches"]), 2),
                          "gpu_section_s": round(st["gpu_s"], 4), "gpu_busy_share": round(st["gpu_s"] / wall, 4),
-                         "decode_s_thread_sum": round(tm["decode_s"], 2), "encode_s_thread_sum": round(tm["encode_s"], 2), "cli": ok})
+                         "decode_s_thread_sum": round(tm["decode_s"], 2), "encode_s_thread_sum": round(tm["encode_s"], 2), "cli": ok,
+                         "jpeg_decoder": os.environ.get("GS360_JPEG_DECODER", "host"), "device_decoded_frames": st["device_decoded_frames"],
+                         "device_decode_fallbacks": st["device_decode_fallbacks"]})
         if args.only in ("", "video"):
             clip = np.stack([synth(3840, 7680, 100 + k) for k in range(args.video_frames)])
             np.save(td / "clip.npy", clip)

@@ -6,7 +6,7 @@ image codecs run on the host; bench.py / tests/tools/bench_configs.py measure th
 
     python scripts/bench_df_cli_e2e.py [--pairs 8] [--workers 16] [--interpolation cubic] [--ext jpg]
 
-GS360_JPEG_ENCODER=device (and GS360_JPEG_HUFFMAN) in the environment reach the tool as in any run of it; the result names them.
+GS360_JPEG_ENCODER=device (and GS360_JPEG_HUFFMAN) and GS360_JPEG_DECODER=device (the .jpg pairs decoded on the GPU) in the environment reach the tool as in any run of it; the result names them.
 """
 import argparse
 import io
@@ -76,7 +76,9 @@ def main():
                       "seconds": round(dt, 2), "pairs_per_s": round(args.pairs / dt, 2), "views_per_s": round(n_out / dt, 1),
                       "views_written": n_out, "done_line": done[-1] if done else None,
                       "jpeg_encoder": os.environ.get("GS360_JPEG_ENCODER", "host"),
-                      "jpeg_huffman": os.environ.get("GS360_JPEG_HUFFMAN", "standard")}))
+                      "jpeg_huffman": os.environ.get("GS360_JPEG_HUFFMAN", "standard"),
+                      "jpeg_decoder": os.environ.get("GS360_JPEG_DECODER", "host"),
+                      "decoder_line": next((l for l in lines if l.startswith("[INFO] JPEG decoder:")), None)}))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,85 @@
+"""The device JPEG decoder's bounds, checked on the CPU: tests/tools/jpegdec_hostcheck.hip steps the kernels' own stage functions
+(csrc/gs360_jpegdec.hip) lane by lane on the host, built with AddressSanitizer and UndefinedBehaviorSanitizer and with every buffer at
+its exact size.  Valid files must give Pillow's pixels with status 0; truncated and corrupted scans must give a status (or the
+restatement's pixels) and, like the valid ones, no sanitizer report.  A stand-alone program: nothing is loaded into python."""
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+pytest.importorskip("PIL.Image")
+
+from conftest import ROOT  # noqa: E402
+from gs360 import jpegdec  # noqa: E402
+
+import jpegdec_cases as cases  # noqa: E402
+import jpegdec_np as ref  # noqa: E402
+
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc to build the host check with")
+    if os.environ.get("LD_PRELOAD"):
+        pytest.skip("a preloaded library and a sanitized program do not go together")
+    exe = tmp_path_factory.mktemp("hostcheck") / "jpegdec_hostcheck"
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-Xarch_host", "-fno-sanitize-recover=all", "-o", str(exe), str(ROOT / "tests" / "tools" / "jpegdec_hostcheck.hip")],
+                   check=True, capture_output=True, timeout=600)
+    return exe
+
+
+def run(program, tmp_path, data):
+    """-> (status, pixels H x W x C) of the host-stepped decoder on one file"""
+    d = jpegdec.parse(data)
+    seg, n_sub = jpegdec.segment_table(d)
+    head = struct.pack("16i", d.H, d.W, d.C, d.subsampling, d.restart, d.scan_len, seg.shape[0], n_sub, *([0] * 8))
+    sel = bytes((d.comp_tq + [0] * 4)[:4] + (d.comp_td + [0] * 4)[:4] + (d.comp_ta + [0] * 4)[:4])
+    (tmp_path / "in.bin").write_bytes(head + sel + data[d.scan_off:d.scan_off + d.scan_len] + seg.tobytes() + d.huff.tobytes() + d.quant.tobytes())
+    r = subprocess.run([str(program), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return int(r.stdout.split()[1]), np.fromfile(tmp_path / "out.bin", np.uint8).reshape(d.H, d.W, d.C)
+
+
+def files():
+    out = [(n, d) for n, d in cases.matrix_once() if n.startswith(("37x53-noise", "33x130-smooth", "1x1-noise")) and "-q90-" in n or n.endswith("gray")]
+    noise = cases.image(160, 224, "noise", seed=5)
+    out += [("noise-%d" % sub, cases.encode(noise, quality=100, subsampling=sub)) for sub in (0, 2)]              # several workgroups
+    out += [("flat-%d" % sub, cases.encode(np.full((96, 160, 3), 77, np.uint8), quality=90, subsampling=sub)) for sub in (0, 2)]
+    out += [("ri%d-%d" % (ri, sub), cases.encode(cases.image(100, 150, "noise", seed=3), quality=95, subsampling=sub, restart_marker_blocks=ri))
+            for ri in (1, 7) for sub in (0, 2)]
+    return out
+
+
+def test_valid_files_equal_pillow_without_a_sanitizer_report(program, tmp_path):
+    for name, data in files():
+        status, got = run(program, tmp_path, data)
+        want = cases.pillow(data)
+        assert status == 0 and np.array_equal(got, want if want.ndim == 3 else want[:, :, None]), name
+
+
+@pytest.mark.parametrize("sub", (0, 2))
+def test_truncated_and_corrupt_scans_stay_in_bounds(program, tmp_path, sub):
+    data = cases.encode(cases.image(64, 64, "noise"), quality=90, subsampling=sub)
+    d = jpegdec.parse(data)
+    status, _ = run(program, tmp_path, data[:d.scan_off + d.scan_len // 2] + b"\xff\xd9")
+    assert status != 0
+    tried = 0
+    for seed in range(8):
+        bad = bytearray(data)
+        at = d.scan_off + d.scan_len // 2
+        bad[at:at + 64] = np.random.default_rng(seed).integers(0, 256, 64, dtype=np.uint8).tobytes()
+        try:
+            jpegdec.parse(bytes(bad))
+        except jpegdec.Unsupported:
+            continue                     # (a marker among the random bytes: the host keeps the file)
+        tried += 1
+        status, got = run(program, tmp_path, bytes(bad))
+        if status == 0:
+            assert np.array_equal(got, ref.decode(bytes(bad)))
+    assert tried >= 4
