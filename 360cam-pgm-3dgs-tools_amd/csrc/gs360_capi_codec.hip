@@ -108,9 +108,15 @@ int gs360_tiff_lzw_decode(const uint8_t* in, size_t in_len, uint8_t* out, size_t
 // ---- baseline JPEG scans on the device (JPG-SPEC v1; kernels in gs360_jpeg.hip) ------------------------------------------
 namespace {
 
-int check_jpeg_geometry(int H, int W, int C, int restart_interval) {
+// the sides and components either codec ("encoder", "decoder") takes
+int check_jpeg_image(const char* codec, int H, int W, int C) {
     if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(GS360_ERR_ARG, "JPEG sides are 1..65535 (got %d x %d)", W, H);
-    if (C != 1 && C != 3) return fail(GS360_ERR_UNSUPPORTED, "the JPEG encoder takes C = 1 or 3 (got %d)", C);
+    if (C != 1 && C != 3) return fail(GS360_ERR_UNSUPPORTED, "the JPEG %s takes C = 1 or 3 (got %d)", codec, C);
+    return 0;
+}
+
+int check_jpeg_geometry(int H, int W, int C, int restart_interval) {
+    if (int rc = check_jpeg_image("encoder", H, W, C)) return rc;
     if (restart_interval < 1 || restart_interval > 65535) return fail(GS360_ERR_ARG, "restart interval %d outside 1..65535", restart_interval);
     return 0;
 }
@@ -121,19 +127,6 @@ int check_jpeg_subsampling(int subsampling) {
     if (subsampling != GS360_JPEG_444 && subsampling != GS360_JPEG_420)
         return fail(GS360_ERR_ARG, "JPEG subsampling %d is neither GS360_JPEG_444 nor GS360_JPEG_420", subsampling);
     return 0;
-}
-
-// the MCU grid of an image: 8 x 8 pixels and one block per component, or ("JPG-SPEC v1, 4:2:0", colour images only) 16 x 16 pixels
-// and six blocks
-struct JpGrid { int mcu_px, bpm, mw, mh; int64_t mcus() const { return (int64_t)mw * mh; } };
-JpGrid jpeg_grid(int H, int W, int C, int subsampling) {
-    JpGrid g;
-    const bool sub = subsampling == GS360_JPEG_420 && C == 3;
-    g.mcu_px = sub ? 16 : 8;
-    g.bpm = sub ? 6 : C;
-    g.mw = (W + g.mcu_px - 1) / g.mcu_px;
-    g.mh = (H + g.mcu_px - 1) / g.mcu_px;
-    return g;
 }
 
 }  // namespace
@@ -148,7 +141,7 @@ int gs360_jpeg_scan_bound_sub(int H, int W, int C, int restart_interval, int sub
     if (int rc = check_jpeg_subsampling(subsampling)) return rc;
     // a block's 64 coefficients cost at most 26 bits each (a 16-bit code and 10 value bits): 208 bytes, twice that when every byte is
     // stuffed; an interval adds at most its marker and one slack byte
-    const JpGrid g = jpeg_grid(H, W, C, subsampling);
+    const JpGrid g = jpeg_grid(H, W, C, subsampling == GS360_JPEG_420);
     const size_t mcus = (size_t)g.mcus();
     const size_t intervals = (mcus + restart_interval - 1) / restart_interval;
     *bytes = mcus * g.bpm * 416 + intervals * 3;
@@ -173,7 +166,7 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
         if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
         if (j.src_stride && j.src_stride < (size_t)j.W * j.C) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
         // the table construction's range: counts in uint32 below libjpeg's 10^9 sentinel, code lengths below 64 before limiting
-        const JpGrid g = jpeg_grid(j.H, j.W, j.C, subsampling);
+        const JpGrid g = jpeg_grid(j.H, j.W, j.C, subsampling == GS360_JPEG_420);
         if (optimal && g.mcus() * g.bpm * 64 >= 1000000000ll)
             return fail(GS360_ERR_UNSUPPORTED, "job %d: optimal Huffman tables take images below 10^9 coefficients", k);
     }
@@ -195,7 +188,7 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
         int64_t blocks = 0, intervals = 0;
         for (int k = k0; k < std::min(n_jobs, k0 + GS360_MAX_VIEWS); ++k) {
-            const JpGrid g = jpeg_grid(jobs[k].H, jobs[k].W, jobs[k].C, subsampling);
+            const JpGrid g = jpeg_grid(jobs[k].H, jobs[k].W, jobs[k].C, subsampling == GS360_JPEG_420);
             const int64_t mcus = g.mcus();
             blocks += mcus * g.bpm;
             intervals += (mcus + restart_interval - 1) / restart_interval;
@@ -219,7 +212,7 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
             J.cap = j.out_capacity;
             J.stride = (int64_t)(j.src_stride ? j.src_stride : (size_t)j.W * j.C);
             J.H = j.H; J.W = j.W; J.C = j.C;
-            const JpGrid g = jpeg_grid(j.H, j.W, j.C, subsampling);
+            const JpGrid g = jpeg_grid(j.H, j.W, j.C, subsampling == GS360_JPEG_420);
             J.bw = g.mw;
             J.bpm = g.bpm;
             J.n_mcu = g.mw * g.mh;
@@ -284,8 +277,7 @@ int gs360_jpeg_huff_tables(gs360_ctx* c, const uint32_t* hist_dev, int n_tables,
 namespace {
 
 int check_jpeg_dec_geometry(int H, int W, int C, int subsampling) {
-    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(GS360_ERR_ARG, "JPEG sides are 1..65535 (got %d x %d)", W, H);
-    if (C != 1 && C != 3) return fail(GS360_ERR_UNSUPPORTED, "the JPEG decoder takes C = 1 or 3 (got %d)", C);
+    if (int rc = check_jpeg_image("decoder", H, W, C)) return rc;
     if (subsampling != GS360_JPEG_444 && subsampling != GS360_JPEG_420)
         return fail(GS360_ERR_UNSUPPORTED, "the JPEG decoder takes GS360_JPEG_444 or GS360_JPEG_420 (got %d)", subsampling);
     return 0;
@@ -335,36 +327,12 @@ int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_job
         for (int k = 0; k < L.n_jobs; ++k) {
             const gs360_jpeg_dec_job& j = jobs[k0 + k];
             JdJob& J = L.job[k];
-            const bool sub = j.subsampling == GS360_JPEG_420 && j.C == 3;
-            const uint32_t n_sub = j.n_subseq;
-            const JdLayout l = jd_layout(j.H, j.W, j.C, sub, n_sub);
-            J.scan = (const uint8_t*)j.scan;
-            J.seg = (const uint4*)j.segments;
-            J.meta = j.tables;
-            J.scratch = (uint8_t*)j.scratch;
-            J.out = (uint8_t*)j.out;
-            J.stride = (int64_t)(j.out_stride ? j.out_stride : (size_t)j.W * j.C);
-            J.n_seg = (uint32_t)j.n_segments;
-            J.n_sub = n_sub;
-            J.scan_len = j.scan_len;
-            J.H = j.H; J.W = j.W; J.C = j.C;
-            J.bpm = sub ? 6 : j.C;
-            const int px = sub ? 16 : 8;
-            J.mw = (j.W + px - 1) / px;
-            J.mh = (j.H + px - 1) / px;
-            J.ri = j.restart_interval;
+            jd_fill_job(J, j);
             J.wg_base = (int32_t)wgs;
             J.tile_base = (int32_t)tiles;
-            J.tiles_x = (j.W + 127) / 128;
-            J.n_wg = l.n_wg;
-            J.dc_chunks = l.dc_chunks;
-            for (int q = 0; q < 4; ++q) { J.tq[q] = j.comp_tq[q] & 3; J.td[q] = j.comp_td[q] & 1; J.ta[q] = j.comp_ta[q] & 1; }
-            J.lay.exits = l.exits; J.lay.sums = l.sums; J.lay.used = l.used; J.lay.recs = l.recs; J.lay.carry = l.carry; J.lay.dc = l.dc;
-            J.lay.coef = l.coef;
-            J.blocks = l.blocks;
-            wgs += l.n_wg;
+            wgs += J.lay.n_wg;
             tiles += (int64_t)J.tiles_x * ((j.H + 63) / 64);
-            L.max_dc_chunks = std::max(L.max_dc_chunks, l.dc_chunks);
+            L.max_dc_chunks = std::max(L.max_dc_chunks, J.lay.dc_chunks);
         }
         if (wgs > INT32_MAX || tiles > INT32_MAX) return fail(GS360_ERR_ARG, "JPEG batch too large");
         L.total_wg = (int32_t)wgs;

@@ -19,6 +19,8 @@
 // 4:2:0 ("JPG-SPEC v1, 4:2:0"; the writer of cli_tools/gs360_DualFisheyeDistortionCalibration.py, cv2.imwrite at DF:1826-1840): a
 // colour image's transform strips are 16 rows x 256 columns, 16 MCUs of four Y blocks and one Cb and one Cr block averaged over 2 x 2
 // cells; the other passes walk six blocks per MCU instead of C.
+// Both transform kernels are built from the same steps (jp_stage_rows, jp_luma / jp_chroma, jp_row_product, jp_column_product,
+// jp_copy_out) and the entropy and count kernels from the same block walk (JpWalk).
 // No float atomics; the LDS bit buffer is filled with integer ORs and the histograms with integer adds, so nothing depends on the
 // order of the work.
 #include "gs360_kernels.h"
@@ -115,152 +117,146 @@ __device__ __forceinline__ void jp_dct8(const int (&s)[8], int (&o)[8]) {
     o[7] = c7 * d0 - c5 * d1 + c3 * d2 - c1 * d3;
 }
 
+// R staged rows; the strips of 4:2:0 images stage 16 (96 blocks as well: 64 Y, 16 Cb, 16 Cr)
+template <int R>
 struct JpLds {
-    uint32_t raw[8][kJpRawDw];
-    alignas(16) int16_t t1[3][8][kJpTileW];           // row products, [component][row][column]
-    alignas(16) int16_t zz[3 * kJpTileBlocks][64];    // [block * C + component][zig-zag position]
+    uint32_t raw[R][kJpRawDw];
+    alignas(16) int16_t t1[3][8][kJpTileW];           // row products, [component][row][column]; 4:2:0: Y rows 0..7, Y rows 8..15,
+                                                      // [row][Cb columns 0..127 | Cr columns 0..127]
+    alignas(16) int16_t zz[3 * kJpTileBlocks][64];    // [block * C + component][zig-zag position]; 4:2:0: [MCU * 6 + block of the MCU]
     JpQuant quant[128];
 };
 
-// the same with 16 staged rows: the strips of 4:2:0 images (96 blocks as well: 64 Y, 16 Cb, 16 Cr)
-struct JpLds420 {
-    uint32_t raw[16][kJpRawDw];
-    alignas(16) int16_t t1[3][8][kJpTileW];           // Y rows 0..7, Y rows 8..15, [row][Cb columns 0..127 | Cr columns 0..127]
-    alignas(16) int16_t zz[3 * kJpTileBlocks][64];    // [MCU * 6 + block of the MCU][zig-zag position]
-    JpQuant quant[128];
-};
+// Step 1: R rows from image row y0 on (the last row repeats below the image), npx pixels of C bytes from column x0 -> LDS with dword
+// loads.  -> the rows' byte alignments, two bits each
+template <int R, int C, int N>
+__device__ __forceinline__ uint32_t jp_stage_rows(JpLds<N>& S, const JpJob& J, int y0, int x0, int npx) {
+    static_assert(R <= N && R <= 16, "rows of the strip, alignments in one word");
+    const int tid = threadIdx.x;
+    uint32_t v[R], offs = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int y = min(y0 + r, J.H - 1);
+        const uintptr_t a = (uintptr_t)(J.src + (int64_t)y * J.stride + (int64_t)x0 * C);
+        const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
+        offs |= (uint32_t)(a & 3) << (2 * r);
+        const int ndw = ((int)(a & 3) + npx * C + 3) >> 2;
+        v[r] = tid < ndw ? q[tid] : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (tid < kJpRawDw) S.raw[r][tid] = v[r];
+    __syncthreads();
+    return offs;
+}
+// the staged bytes of strip row r, from its first pixel
+template <int N>
+__device__ __forceinline__ const uint8_t* jp_row(const JpLds<N>& S, uint32_t offs, int r) {
+    return (const uint8_t*)S.raw[r] + ((offs >> (2 * r)) & 3u);
+}
 
-template <int C, class Lds>
-__device__ __forceinline__ void jp_transform_tile(Lds& S, const JpLaunch& L, const JpJob& J, int t) {
+// JFIF's Y and (cr ? Cr : Cb) of a pixel in 16-bit fixed point, as libjpeg rounds them
+__device__ __forceinline__ int jp_luma(int R, int G, int B) { return (19595 * R + 38470 * G + 7471 * B + 32768) >> 16; }
+__device__ __forceinline__ int jp_chroma(int cr, int R, int G, int B) {
+    const int kr = cr ? 32768 : -11059, kg = cr ? -27439 : -21709, kb = cr ? -5329 : 32768;
+    return (kr * R + kg * G + kb * B + (128 << 16) + 32767) >> 16;
+}
+
+// Step 2's end: the row product of eight level-shifted samples, rounded, as one 16-byte store
+__device__ __forceinline__ void jp_row_product(const int (&s)[8], int16_t* dst) {
+    int o[8];
+    jp_dct8(s, o);
+    union { int16_t h[8]; uint4 q; } w;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) w.h[u] = (int16_t)((o[u] + 1024) >> 11);
+    *(uint4*)dst = w.q;
+}
+
+// Step 3, a lane per block column (thread tid: column tid of the plane): column product, quantiser, zig-zag scatter to the block zz
+__device__ __forceinline__ void jp_column_product(const int16_t (&t1)[8][kJpTileW], const JpQuant* quant, int16_t* zz) {
+    const int tid = threadIdx.x, u = tid & 7;
+    int s[8], o[8];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) s[y] = t1[y][tid];
+    jp_dct8(s, o);
+#pragma unroll
+    for (int vv = 0; vv < 8; ++vv) {
+        const int coef = (o[vv] + 65536) >> 17;
+        const JpQuant e = quant[vv * 8 + u];
+        const uint32_t n = (uint32_t)abs(coef) + e.half;
+        const int q = (int)__umulhi(n << 8, e.recip);                              // n / Q
+        zz[e.zpos] = (int16_t)(coef < 0 ? -q : q);
+    }
+}
+
+// Step 4: the strip's n coefficient blocks, contiguous in the scratch from block `first` on
+template <int N>
+__device__ __forceinline__ void jp_copy_out(const JpLds<N>& S, const JpLaunch& L, int64_t first, int n) {
+    uint32_t* dst = (uint32_t*)(L.coef + first * 64);
+    const uint32_t* srcw = (const uint32_t*)&S.zz[0][0];
+    for (int i = threadIdx.x; i < n * 32; i += kJpThreads) dst[i] = srcw[i];
+}
+
+// One strip of 8 rows x 256 columns, one block per component and MCU.
+template <int C, int N>
+__device__ __forceinline__ void jp_transform_tile(JpLds<N>& S, const JpLaunch& L, const JpJob& J, int t) {
     const int tid = threadIdx.x;
     const int by = t / J.tiles_x, tx = t - by * J.tiles_x;
     const int bx0 = tx * kJpTileBlocks, nb = min(kJpTileBlocks, J.bw - bx0);
     const int x0 = bx0 * 8, npx = min(kJpTileW, J.W - x0);
-    // 1. the strip's rows (the last row repeats below the image) -> LDS, dword loads
-    uint32_t v[8];
-    int off[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int y = min(by * 8 + r, J.H - 1);
-        const uintptr_t a = (uintptr_t)(J.src + (int64_t)y * J.stride + (int64_t)x0 * C);
-        const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
-        off[r] = (int)(a & 3);
-        const int ndw = (off[r] + npx * C + 3) >> 2;
-        v[r] = tid < ndw ? q[tid] : 0u;
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-        if (tid < kJpRawDw) S.raw[r][tid] = v[r];
-    __syncthreads();
+    const uint32_t offs = jp_stage_rows<8, C>(S, J, by * 8, x0, npx);
     // 2. a lane per block row: colour, level shift, row product
     {
         const int b = tid & (kJpTileBlocks - 1), y = tid >> 5;
         if (b < nb) {
             int s[C][8];
-            int offy = 0;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) offy = r == y ? off[r] : offy;
-            const uint8_t* row = (const uint8_t*)S.raw[y] + offy;
+            const uint8_t* row = jp_row(S, offs, y);
 #pragma unroll
             for (int x = 0; x < 8; ++x) {
                 const uint8_t* p = row + min(b * 8 + x, npx - 1) * C;      // the last column repeats beside the image
                 if constexpr (C == 1) {
                     s[0][x] = (int)p[0] - 128;
                 } else {
-                    const int R = p[0], G = p[1], B = p[2];
-                    s[0][x] = ((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128;
-                    s[1][x] = ((-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16) - 128;
-                    s[2][x] = ((32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16) - 128;
+                    s[0][x] = jp_luma(p[0], p[1], p[2]) - 128;
+                    s[1][x] = jp_chroma(0, p[0], p[1], p[2]) - 128;
+                    s[2][x] = jp_chroma(1, p[0], p[1], p[2]) - 128;
                 }
             }
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-                int o[8];
-                jp_dct8(s[c], o);
-                union { int16_t h[8]; uint4 q; } w;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) w.h[u] = (int16_t)((o[u] + 1024) >> 11);
-                *(uint4*)&S.t1[c][y][b * 8] = w.q;
-            }
+            for (int c = 0; c < C; ++c) jp_row_product(s[c], &S.t1[c][y][b * 8]);
         }
     }
     __syncthreads();
-    // 3. a lane per block column: column product, quantiser, zig-zag
-    {
-        const int b = tid >> 3, u = tid & 7;
-        if (b < nb) {
+    if (const int b = tid >> 3; b < nb) {
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-                int s[8], o[8];
-#pragma unroll
-                for (int y = 0; y < 8; ++y) s[y] = S.t1[c][y][tid];
-                jp_dct8(s, o);
-#pragma unroll
-                for (int vv = 0; vv < 8; ++vv) {
-                    const int coef = (o[vv] + 65536) >> 17;
-                    const JpQuant e = S.quant[(c ? 64 : 0) + vv * 8 + u];
-                    const uint32_t n = (uint32_t)abs(coef) + e.half;
-                    const int q = (int)__umulhi(n << 8, e.recip);              // n / Q
-                    S.zz[b * C + c][e.zpos] = (int16_t)(coef < 0 ? -q : q);
-                }
-            }
-        }
+        for (int c = 0; c < C; ++c) jp_column_product(S.t1[c], &S.quant[c ? 64 : 0], S.zz[b * C + c]);
     }
     __syncthreads();
-    // 4. the strip's coefficients, contiguous in the scratch
-    {
-        const int mcu0 = by * J.bw + bx0;
-        uint32_t* dst = (uint32_t*)(L.coef + (J.coef_base + (int64_t)mcu0 * C) * 64);
-        const uint32_t* srcw = (const uint32_t*)&S.zz[0][0];
-        const int ndw = nb * C * 32;
-        for (int i = tid; i < ndw; i += kJpThreads) dst[i] = srcw[i];
-    }
+    jp_copy_out(S, L, J.coef_base + (int64_t)(by * J.bw + bx0) * C, nb * C);
 }
 
 // One strip of a 4:2:0 image: 16 rows x 256 columns = 16 MCUs.  J.bw counts 16 x 16 MCUs per row.
-__device__ __forceinline__ void jp_transform_tile420(JpLds420& S, const JpLaunch& L, const JpJob& J, int t) {
+__device__ __forceinline__ void jp_transform_tile420(JpLds<16>& S, const JpLaunch& L, const JpJob& J, int t) {
     constexpr int kMcus = kJpTileW / 16;
     const int tid = threadIdx.x;
     const int my = t / J.tiles_x, tx = t - my * J.tiles_x;
     const int m0 = tx * kMcus, nm = min(kMcus, J.bw - m0);                        // the strip's MCUs
     const int x0 = m0 * 16, npx = min(kJpTileW, J.W - x0);
-    // 1. the strip's rows (the last row repeats below the image) -> LDS, dword loads
-    uint32_t v[16];
-    uint32_t offs = 0;                                                            // the rows' byte alignments, two bits each
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int y = min(my * 16 + r, J.H - 1);
-        const uintptr_t a = (uintptr_t)(J.src + (int64_t)y * J.stride + (int64_t)x0 * 3);
-        const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
-        offs |= (uint32_t)(a & 3) << (2 * r);
-        const int ndw = ((int)(a & 3) + npx * 3 + 3) >> 2;
-        v[r] = tid < ndw ? q[tid] : 0u;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-        if (tid < kJpRawDw) S.raw[r][tid] = v[r];
-    __syncthreads();
-    auto row_of = [&](int r) {                                                    // the staged bytes of strip row r, from its first pixel
-        return (const uint8_t*)S.raw[r] + ((offs >> (2 * r)) & 3u);
-    };
+    const uint32_t offs = jp_stage_rows<16, 3>(S, J, my * 16, x0, npx);
     // 2a. Y: a lane per block row of the upper and of the lower block row: colour, level shift, row product
     {
         const int b = tid & (kJpTileBlocks - 1), y = tid >> 5;
         if (b < 2 * nm) {
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
-                const uint8_t* row = row_of(half * 8 + y);
-                int s[8], o[8];
+                const uint8_t* row = jp_row(S, offs, half * 8 + y);
+                int s[8];
 #pragma unroll
                 for (int x = 0; x < 8; ++x) {
                     const uint8_t* p = row + min(b * 8 + x, npx - 1) * 3;          // the last column repeats beside the image
-                    s[x] = ((19595 * (int)p[0] + 38470 * (int)p[1] + 7471 * (int)p[2] + 32768) >> 16) - 128;
+                    s[x] = jp_luma(p[0], p[1], p[2]) - 128;
                 }
-                jp_dct8(s, o);
-                union { int16_t h[8]; uint4 q; } w;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) w.h[u] = (int16_t)((o[u] + 1024) >> 11);
-                *(uint4*)&S.t1[half][y][b * 8] = w.q;
+                jp_row_product(s, &S.t1[half][y][b * 8]);
             }
         }
     }
@@ -269,95 +265,59 @@ __device__ __forceinline__ void jp_transform_tile420(JpLds420& S, const JpLaunch
     {
         const int cr = tid >> 7, y = (tid >> 4) & 7, m = tid & (kMcus - 1);
         if (m < nm) {
-            const int kr = cr ? 32768 : -11059, kg = cr ? -27439 : -21709, kb = cr ? -5329 : 32768;
-            const uint8_t* r0 = row_of(2 * y);
-            const uint8_t* r1 = row_of(2 * y + 1);
-            int s[8], o[8];
+            const uint8_t* r0 = jp_row(S, offs, 2 * y);
+            const uint8_t* r1 = jp_row(S, offs, 2 * y + 1);
+            int s[8];
 #pragma unroll
             for (int x = 0; x < 8; ++x) {
                 const int c0 = min(m * 16 + 2 * x, npx - 1) * 3, c1 = min(m * 16 + 2 * x + 1, npx - 1) * 3;
-                int sum = 1 + (x & 1);
-                sum += (kr * (int)r0[c0] + kg * (int)r0[c0 + 1] + kb * (int)r0[c0 + 2] + (128 << 16) + 32767) >> 16;
-                sum += (kr * (int)r0[c1] + kg * (int)r0[c1 + 1] + kb * (int)r0[c1 + 2] + (128 << 16) + 32767) >> 16;
-                sum += (kr * (int)r1[c0] + kg * (int)r1[c0 + 1] + kb * (int)r1[c0 + 2] + (128 << 16) + 32767) >> 16;
-                sum += (kr * (int)r1[c1] + kg * (int)r1[c1 + 1] + kb * (int)r1[c1 + 2] + (128 << 16) + 32767) >> 16;
+                const int sum = 1 + (x & 1) + jp_chroma(cr, r0[c0], r0[c0 + 1], r0[c0 + 2]) + jp_chroma(cr, r0[c1], r0[c1 + 1], r0[c1 + 2]) +
+                                jp_chroma(cr, r1[c0], r1[c0 + 1], r1[c0 + 2]) + jp_chroma(cr, r1[c1], r1[c1 + 1], r1[c1 + 2]);
                 s[x] = (sum >> 2) - 128;
             }
-            jp_dct8(s, o);
-            union { int16_t h[8]; uint4 q; } w;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) w.h[u] = (int16_t)((o[u] + 1024) >> 11);
-            *(uint4*)&S.t1[2][y][cr * (kJpTileW / 2) + m * 8] = w.q;
+            jp_row_product(s, &S.t1[2][y][cr * (kJpTileW / 2) + m * 8]);
         }
     }
     __syncthreads();
-    // 3. a lane per block column: column product, quantiser, zig-zag.  Plane 0 and 1: Y block row 0 and 1 (block tid >> 3 of the row
-    // belongs to MCU tid >> 4); plane 2: the Cb blocks, then the Cr blocks
-    {
-        const int u = tid & 7;
+    // 3. plane 0 and 1: Y block row 0 and 1 (block tid >> 3 of the row belongs to MCU tid >> 4); plane 2: the Cb blocks, then the Cr blocks
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int b = tid >> 3;
-            const int m = c < 2 ? b >> 1 : b & (kMcus - 1);
-            const int blk = m * 6 + (c < 2 ? c * 2 + (b & 1) : 4 + (b >> 4));
-            if (m < nm) {
-                int s[8], o[8];
-#pragma unroll
-                for (int y = 0; y < 8; ++y) s[y] = S.t1[c][y][tid];
-                jp_dct8(s, o);
-#pragma unroll
-                for (int vv = 0; vv < 8; ++vv) {
-                    const int coef = (o[vv] + 65536) >> 17;
-                    const JpQuant e = S.quant[(c == 2 ? 64 : 0) + vv * 8 + u];
-                    const uint32_t n = (uint32_t)abs(coef) + e.half;
-                    const int q = (int)__umulhi(n << 8, e.recip);                  // n / Q
-                    S.zz[blk][e.zpos] = (int16_t)(coef < 0 ? -q : q);
-                }
-            }
-        }
+    for (int c = 0; c < 3; ++c) {
+        const int b = tid >> 3;
+        const int m = c < 2 ? b >> 1 : b & (kMcus - 1);
+        const int blk = m * 6 + (c < 2 ? c * 2 + (b & 1) : 4 + (b >> 4));
+        if (m < nm) jp_column_product(S.t1[c], &S.quant[c == 2 ? 64 : 0], S.zz[blk]);
     }
     __syncthreads();
-    // 4. the strip's coefficients, contiguous in the scratch: MCU-major, the six blocks of an MCU side by side
-    {
-        const int mcu0 = my * J.bw + m0;
-        uint32_t* dst = (uint32_t*)(L.coef + (J.coef_base + (int64_t)mcu0 * 6) * 64);
-        const uint32_t* srcw = (const uint32_t*)&S.zz[0][0];
-        const int ndw = nm * 6 * 32;
-        for (int i = tid; i < ndw; i += kJpThreads) dst[i] = srcw[i];
-    }
+    jp_copy_out(S, L, J.coef_base + (int64_t)(my * J.bw + m0) * 6, nm * 6);       // MCU-major, the six blocks of an MCU side by side
+}
+
+// the workgroup's job; its quantiser tables -> LDS (visible after the tile's first barrier)
+template <int N>
+__device__ __forceinline__ JpJob jp_tile_job(JpLds<N>& S, const JpLaunch& L) {
+    if (threadIdx.x < 128) S.quant[threadIdx.x] = L.quant[threadIdx.x];
+    return L.job[job_of(L, blockIdx.x, &JpJob::tile_base)];
 }
 
 __global__ void __launch_bounds__(kJpThreads) jp_transform_kernel(const JpLaunch L) {
-    __shared__ JpLds S;
-    const int t = blockIdx.x;
-    int j = 0;
-    while (j + 1 < L.n_jobs && t >= L.job[j + 1].tile_base) ++j;
-    const JpJob J = L.job[j];
-    if (threadIdx.x < 128) S.quant[threadIdx.x] = L.quant[threadIdx.x];      // (visible after the tile's first barrier)
-    if (J.C == 3) jp_transform_tile<3>(S, L, J, t - J.tile_base);
-    else jp_transform_tile<1>(S, L, J, t - J.tile_base);
+    __shared__ JpLds<8> S;
+    const JpJob J = jp_tile_job(S, L);
+    if (J.C == 3) jp_transform_tile<3>(S, L, J, blockIdx.x - J.tile_base);
+    else jp_transform_tile<1>(S, L, J, blockIdx.x - J.tile_base);
 }
 
 // a batch with 4:2:0 images (L.any420): their strips, and the 8-row strips of the batch's gray images
 __global__ void __launch_bounds__(kJpThreads) jp_transform420_kernel(const JpLaunch L) {
-    __shared__ JpLds420 S;
-    const int t = blockIdx.x;
-    int j = 0;
-    while (j + 1 < L.n_jobs && t >= L.job[j + 1].tile_base) ++j;
-    const JpJob J = L.job[j];
-    if (threadIdx.x < 128) S.quant[threadIdx.x] = L.quant[threadIdx.x];      // (visible after the tile's first barrier)
-    if (J.bpm == 6) jp_transform_tile420(S, L, J, t - J.tile_base);
-    else jp_transform_tile<1>(S, L, J, t - J.tile_base);                      // (every C = 3 job of such a call has bpm == 6)
+    __shared__ JpLds<16> S;
+    const JpJob J = jp_tile_job(S, L);
+    if (J.bpm == 6) jp_transform_tile420(S, L, J, blockIdx.x - J.tile_base);
+    else jp_transform_tile<1>(S, L, J, blockIdx.x - J.tile_base);             // (every C = 3 job of such a call has bpm == 6)
 }
 
 // ---- entropy --------------------------------------------------------------------------------------------------------------------
 // What a lane codes of a block (lane = zig-zag position, `raw` its coefficient, `pred` the component's previous DC): lane 0 the DC
 // difference, a lane with a non-zero coefficient its value behind `run` zeros (run >> 4 ZRLs, then the symbol (run & 15) << 4 | size),
 // lane 63 with a zero the EOB.  The non-zero mask is a ballot, the run the gap to the next set bit below the lane.
-// the component of the block at place `pos` of an MCU of bpm blocks: one block per component, or Y Y Y Y Cb Cr
-__device__ __forceinline__ int jp_component(int pos, int bpm) { return bpm == 6 ? max(pos - 3, 0) : pos; }
-
-struct JpSym { int v, size, run; };
+struct JpSym { int v, size, run, tab; };                                          // tab: the block's tables, 0 for Y, 1 for Cb and Cr
 __device__ __forceinline__ JpSym jp_lane_symbol(int raw, int pred, int lane, uint64_t lower) {
     JpSym s;
     s.v = lane == 0 ? raw - pred : raw;
@@ -368,6 +328,47 @@ __device__ __forceinline__ JpSym jp_lane_symbol(int raw, int pred, int lane, uin
     return s;
 }
 
+// A wavefront's walk over nblk blocks in scan order, cf the lane's coefficient of the first: per block the lane's symbol.  The DC
+// predictions start at 0 and return to it after every per_int blocks (a restart interval).
+struct JpWalk {
+    const int16_t* cf;
+    int nblk, bpm, per_int, bi = 0, pos = 0, left, raw;                           // pos: the block's place in its MCU
+    int pred0 = 0, pred1 = 0, pred2 = 0;
+    __device__ __forceinline__ JpWalk(const int16_t* cf_, int nblk_, int bpm_, int per_int_)
+        : cf(cf_), nblk(nblk_), bpm(bpm_), per_int(per_int_), left(per_int_), raw(cf_[0]) {}
+    __device__ __forceinline__ bool more() const { return bi < nblk; }
+    __device__ __forceinline__ JpSym next(int lane, uint64_t lower) {
+        const int nxt = bi + 1 < nblk ? (int)cf[(int64_t)(bi + 1) * 64] : 0;     // the next block's load flies during this one
+        const int comp = bpm == 6 ? max(pos - 3, 0) : pos;                       // one block per component, or Y Y Y Y Cb Cr
+        const int dc = __shfl(raw, 0, 64);
+        // (named predictors, each read and written on every path: an array, or accesses under the compare chain, which become one
+        // access at an indexed member, put the walk into scratch memory)
+        const int p0 = pred0, p1 = pred1, p2 = pred2;
+        const int pred = comp == 0 ? p0 : (comp == 1 ? p1 : p2);
+        pred0 = comp == 0 ? dc : p0;
+        pred1 = comp == 1 ? dc : p1;
+        pred2 = comp == 2 ? dc : p2;
+        JpSym sym = jp_lane_symbol(raw, pred, lane, lower);
+        sym.tab = comp ? 1 : 0;
+        raw = nxt;
+        ++bi;
+        pos = pos + 1 == bpm ? 0 : pos + 1;
+        if (--left == 0) { left = per_int; pred0 = pred1 = pred2 = 0; }
+        return sym;
+    }
+};
+
+// inclusive sum over the lanes of a wavefront
+template <class T>
+__device__ __forceinline__ T jp_wave_scan(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
+    }
+    return v;
+}
+
 // One wavefront, one restart interval.  kEmit = false counts the interval's bytes (stuffing and marker included) into int_len;
 // kEmit = true writes them at the image's out + int_off.
 template <bool kEmit>
@@ -376,8 +377,7 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
     __shared__ uint32_t bitbuf[64];       // MSB-first: stream byte i is bits 31-8*(i&3) .. 24-8*(i&3) of word i >> 2
     const int lane = threadIdx.x;
     const int gi = blockIdx.x;
-    int j = 0;
-    while (j + 1 < L.n_jobs && gi >= L.job[j + 1].int_base) ++j;
+    const int j = job_of(L, gi, &JpJob::int_base);
     const JpJob J = L.job[j];
     if (kEmit && L.lengths[j] == UINT64_MAX) return;            // the scan does not fit: nothing of it is written
     const int k = gi - J.int_base, bpm = J.bpm;
@@ -397,17 +397,10 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
     if constexpr (kEmit) dst = J.out + L.int_off[gi];
     const uint64_t lower = (1ull << lane) - 1ull;
     uint32_t carry = 0, nout = 0;         // bits waiting in bitbuf (< 8), bytes produced so far
-    int pred0 = 0, pred1 = 0, pred2 = 0, pos = 0;                                // pos: the block's place in its MCU
-    int raw = cf[0];
-    for (int bi = 0; bi < nblk; ++bi) {
-        const int nxt = bi + 1 < nblk ? (int)cf[(int64_t)(bi + 1) * 64] : 0;     // the next block's load flies during this one
-        const int comp = jp_component(pos, bpm);
-        const int tab = comp ? 1 : 0;
-        const int dc = __shfl(raw, 0, 64);
-        const int pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
-        if (comp == 0) pred0 = dc; else if (comp == 1) pred1 = dc; else pred2 = dc;
-        const JpSym sym = jp_lane_symbol(raw, pred, lane, lower);
-        const int v = sym.v, size = sym.size, run = sym.run;
+    JpWalk walk(cf, nblk, bpm, nblk);                                             // (one interval: no reset on the way)
+    while (walk.more()) {
+        const JpSym sym = walk.next(lane, lower);
+        const int v = sym.v, size = sym.size, run = sym.run, tab = sym.tab;
         const uint32_t vbits = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << size) - 1u);
         uint64_t str = 0;
         int len = 0;
@@ -429,12 +422,7 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
             str = e >> 5;
             len = (int)(e & 31);
         }
-        int incl = len;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += up;
-        }
+        const int incl = jp_wave_scan(len, lane);
         const uint32_t total = carry + (uint32_t)__shfl(incl, 63, 64);            // <= 7 + 64 * 26 bits
         if (len) {
             const uint32_t at = carry + (uint32_t)(incl - len), w0 = at >> 5, sh = at & 31;
@@ -466,8 +454,6 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
         bitbuf[lane] = lane == 0 ? left << 24 : 0u;
         __syncthreads();
         carry = total & 7;
-        raw = nxt;
-        pos = pos + 1 == bpm ? 0 : pos + 1;
     }
     if (carry) {                                                                  // pad with 1-bits; a 0xFF pad is stuffed like any byte
         const uint32_t byte = (bitbuf[0] >> 24) | ((1u << (8 - carry)) - 1u);
@@ -513,27 +499,17 @@ __global__ void __launch_bounds__(64) jp_count_kernel(const JpLaunch L) {
     const int nblk = (int)(m1 - m0) * bpm, per_int = L.ri * bpm;                 // (ri * bpm <= 393210)
     const int16_t* cf = L.coef + (J.coef_base + m0 * bpm) * 64 + lane;
     const uint64_t lower = (1ull << lane) - 1ull;
-    int pred0 = 0, pred1 = 0, pred2 = 0, pos = 0, left = per_int;                // blocks left in the interval
-    int raw = cf[0];
-    for (int bi = 0; bi < nblk; ++bi) {
-        const int nxt = bi + 1 < nblk ? (int)cf[(int64_t)(bi + 1) * 64] : 0;
-        const int comp = jp_component(pos, bpm);
-        const int tab = comp ? 1 : 0;
-        const int dc = __shfl(raw, 0, 64);
-        const int pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
-        if (comp == 0) pred0 = dc; else if (comp == 1) pred1 = dc; else pred2 = dc;
-        const JpSym sym = jp_lane_symbol(raw, pred, lane, lower);
+    JpWalk walk(cf, nblk, bpm, per_int);
+    while (walk.more()) {
+        const JpSym sym = walk.next(lane, lower);
         if (lane == 0) {
-            atomicAdd(&hist[tab][256 + sym.size], 1u);
+            atomicAdd(&hist[sym.tab][256 + sym.size], 1u);
         } else if (sym.v != 0) {
-            atomicAdd(&hist[tab][((sym.run & 15) << 4) | sym.size], 1u);
-            if (sym.run >> 4) atomicAdd(&hist[tab][0xF0], (uint32_t)(sym.run >> 4));
+            atomicAdd(&hist[sym.tab][((sym.run & 15) << 4) | sym.size], 1u);
+            if (sym.run >> 4) atomicAdd(&hist[sym.tab][0xF0], (uint32_t)(sym.run >> 4));
         } else if (lane == 63) {
-            atomicAdd(&hist[tab][0x00], 1u);
+            atomicAdd(&hist[sym.tab][0x00], 1u);
         }
-        raw = nxt;
-        pos = pos + 1 == bpm ? 0 : pos + 1;
-        if (--left == 0) { left = per_int; pred0 = pred1 = pred2 = 0; }          // a restart interval ends: the predictions reset
     }
     __syncthreads();
     uint32_t* g = L.hist + (size_t)j * 2 * kJpHuffN;
@@ -678,12 +654,7 @@ __global__ void __launch_bounds__(kJpThreads) jp_offsets_kernel(const JpLaunch L
     for (int i0 = 0; i0 < J.n_int; i0 += kJpThreads) {
         const int i = i0 + tid;
         const unsigned long long mine = i < J.n_int ? L.int_len[J.int_base + i] : 0ull;
-        unsigned long long incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += up;
-        }
+        const unsigned long long incl = jp_wave_scan(mine, lane);
         if (lane == 63) wsum[wave] = incl;
         __syncthreads();
         unsigned long long before = run, all = run;

@@ -10,7 +10,7 @@
 // (jd_chain_kernel), and that fixed point is the sequential decoder's state at every subsequence boundary, exactly.  The same kernel
 // sums the blocks completed per subsequence, so the second decode pass (jd_write_kernel) knows every lane's first block and writes the
 // coefficients.  DC differences are summed per component within each segment by a three-step segmented scan (jd_dc_kernel /
-// jd_dc_carry_kernel), and jd_pixels_kernel turns 64 x 128 pixel tiles of blocks into pixels.
+// jd_dc_carry_kernel, both over jd_seg_scan), and jd_pixels_kernel turns 64 x 128 pixel tiles of blocks into pixels.
 //
 // Every loop below is bounded by a launch-time size: symbols of a subsequence (each takes at least one bit), subsequences of a
 // workgroup, workgroups of a file, segments (binary search), chunks of a scan.  No workgroup waits for another one.  Every byte
@@ -242,18 +242,11 @@ JD_HD uint32_t jd_decode(const JdTables& T, const JdJob& J, const JdSegment& S, 
     return rel | (c << 8) | (z << 11) | (n << 18);
 }
 
-__device__ inline int jd_job_of_wg(const JdLaunch& L, int wg) {
-    int k = 0;
-    for (int q = 1; q < L.n_jobs; ++q)
-        if (wg >= L.job[q].wg_base) k = q;
-    return k;
-}
-
 // pass 1: every lane decodes its subsequence from the cold state, then runs on until it arrives with the recorded state
 __global__ __launch_bounds__(kJdWgSubs) void jd_sync_kernel(const JdLaunch L) {
     __shared__ JdTables T;
     __shared__ uint32_t sh[kJdWgSubs];
-    const JdJob& J = L.job[jd_job_of_wg(L, blockIdx.x)];
+    const JdJob& J = L.job[job_of(L, blockIdx.x, &JdJob::wg_base)];
     jd_build_tables(J.meta, T);
     const int t = threadIdx.x;
     const uint32_t j = (uint32_t)(blockIdx.x - J.wg_base) * kJdWgSubs + t;
@@ -296,15 +289,15 @@ __global__ __launch_bounds__(1024) void jd_chain_kernel(const JdLaunch L) {
     uint32_t* used = (uint32_t*)(J.scratch + J.lay.used);
     uint32_t* sums = (uint32_t*)(J.scratch + J.lay.sums);
     JdHeader* hdr = (JdHeader*)J.scratch;
-    for (int w = 1 + t; w < J.n_wg; w += 1024) {
+    for (int w = 1 + t; w < J.lay.n_wg; w += 1024) {
         const uint32_t j0 = (uint32_t)w * kJdWgSubs;
         const JdSegment S = jd_find_segment(J, j0);
         used[w] = jd_cold(S.bytes, S.len, j0 - S.first_sub);
     }
     uint32_t rounds = 0;
-    for (int r = 0; r < J.n_wg; ++r) {                      // a round settles at least one more boundary
+    for (int r = 0; r < J.lay.n_wg; ++r) {                      // a round settles at least one more boundary
         int changed = 0;
-        for (int w = 1 + t; w < J.n_wg; w += 1024) {
+        for (int w = 1 + t; w < J.lay.n_wg; w += 1024) {
             const uint32_t j0 = (uint32_t)w * kJdWgSubs;
             const JdSegment S = jd_find_segment(J, j0);
             if (j0 == S.first_sub) continue;                // a segment starts here: its entry state is known
@@ -351,7 +344,7 @@ __global__ __launch_bounds__(1024) void jd_chain_kernel(const JdLaunch L) {
 // pass 3: the same decode from the true entry states, writing coefficients
 __global__ __launch_bounds__(kJdWgSubs) void jd_write_kernel(const JdLaunch L) {
     __shared__ JdTables T;
-    const JdJob& J = L.job[jd_job_of_wg(L, blockIdx.x)];
+    const JdJob& J = L.job[job_of(L, blockIdx.x, &JdJob::wg_base)];
     jd_build_tables(J.meta, T);
     const uint32_t j = (uint32_t)(blockIdx.x - J.wg_base) * kJdWgSubs + threadIdx.x;
     if (j >= J.n_sub) return;
@@ -376,11 +369,32 @@ JD_HD inline JdDcSeq jd_dc_seq(const JdJob& J, int comp) {
     return q;
 }
 
+// what a value continues from: the carry, unless a segment started at or before `sum`'s last term
+JD_HD inline int jd_carry_in(int carry, int sum, int flag) { return flag ? sum : carry + sum; }
+
+// 256 lanes' (sum since the lane's last segment start, whether it holds one) -> the same over lanes 0..t, in place and in S
+struct JdScan { int sum[256], flag[256]; };
+__device__ __forceinline__ void jd_seg_scan(JdScan& S, int t, int& sum, int& flag) {
+    S.sum[t] = sum; S.flag[t] = flag;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const int os = t >= d ? S.sum[t - d] : 0, of = t >= d ? S.flag[t - d] : 0;
+        __syncthreads();
+        if (!flag) sum += os;
+        flag |= of;
+        S.sum[t] = sum; S.flag[t] = flag;
+        __syncthreads();
+    }
+}
+// after the scan: what lane t's own values continue from, `carry` being what lane 0's do
+__device__ __forceinline__ int jd_scan_before(const JdScan& S, int t, int carry) {
+    return t == 0 ? carry : jd_carry_in(carry, S.sum[t - 1], S.flag[t - 1]);
+}
+
 // kApply false: the chunk's aggregate (sum since its last segment start, whether it holds one) -> recs; true: carry in, DC values out
 template <bool kApply>
 __global__ __launch_bounds__(256) void jd_dc_kernel(const JdLaunch L) {
-    __shared__ int sh_sum[256];
-    __shared__ int sh_flag[256];
+    __shared__ JdScan S;
     const int comp = blockIdx.y % 3;
     const JdJob& J = L.job[blockIdx.y / 3];
     if (comp >= J.C) return;
@@ -402,60 +416,38 @@ __global__ __launch_bounds__(256) void jd_dc_kernel(const JdLaunch L) {
         }
     }
     const int t = threadIdx.x;
-    sh_sum[t] = sum; sh_flag[t] = flag;
-    __syncthreads();
-    int asum = sum, aflag = flag;
-    for (int d = 1; d < 256; d <<= 1) {
-        const int os = t >= d ? sh_sum[t - d] : 0, of = t >= d ? sh_flag[t - d] : 0;
-        __syncthreads();
-        if (!aflag) asum += os;
-        aflag |= of;
-        sh_sum[t] = asum; sh_flag[t] = aflag;
-        __syncthreads();
-    }
+    jd_seg_scan(S, t, sum, flag);
     if (!kApply) {
-        if (t == 255) ((int2*)(J.scratch + J.lay.recs))[comp * J.dc_chunks + chunk] = make_int2(asum, aflag);
+        if (t == 255) ((int2*)(J.scratch + J.lay.recs))[comp * J.lay.dc_chunks + chunk] = make_int2(sum, flag);
         return;
     }
-    const int carry = ((const int*)(J.scratch + J.lay.carry))[comp * J.dc_chunks + chunk];
-    int run = t == 0 ? carry : (sh_flag[t - 1] ? sh_sum[t - 1] : carry + sh_sum[t - 1]);
+    int run = jd_scan_before(S, t, ((const int*)(J.scratch + J.lay.carry))[comp * J.lay.dc_chunks + chunk]);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         if (q0 + e >= Q.n) break;
-        run = head[e] ? v[e] : run + v[e];
+        run = jd_carry_in(run, v[e], head[e]);
         dc[at[e]] = run;
     }
 }
 
 // exclusive scan of the chunk aggregates: what every chunk's first value continues from
 __global__ __launch_bounds__(256) void jd_dc_carry_kernel(const JdLaunch L) {
-    __shared__ int sh_sum[256];
-    __shared__ int sh_flag[256];
+    __shared__ JdScan S;
     const int comp = blockIdx.x % 3, t = threadIdx.x;
     const JdJob& J = L.job[blockIdx.x / 3];
     if (comp >= J.C) return;
     const JdDcSeq Q = jd_dc_seq(J, comp);
     const int chunks = (int)((Q.n + kJdDcChunk - 1) / kJdDcChunk);
-    const int2* recs = (const int2*)(J.scratch + J.lay.recs) + comp * J.dc_chunks;
-    int* carry = (int*)(J.scratch + J.lay.carry) + comp * J.dc_chunks;
+    const int2* recs = (const int2*)(J.scratch + J.lay.recs) + comp * J.lay.dc_chunks;
+    int* carry = (int*)(J.scratch + J.lay.carry) + comp * J.lay.dc_chunks;
     int run = 0;
     for (int base = 0; base < chunks; base += 256) {
         const int ch = base + t;
-        const int2 rec = ch < chunks ? recs[ch] : make_int2(0, 0);
-        __syncthreads();
-        sh_sum[t] = rec.x; sh_flag[t] = rec.y;
-        __syncthreads();
-        int asum = rec.x, aflag = rec.y;
-        for (int d = 1; d < 256; d <<= 1) {
-            const int os = t >= d ? sh_sum[t - d] : 0, of = t >= d ? sh_flag[t - d] : 0;
-            __syncthreads();
-            if (!aflag) asum += os;
-            aflag |= of;
-            sh_sum[t] = asum; sh_flag[t] = aflag;
-            __syncthreads();
-        }
-        if (ch < chunks) carry[ch] = t == 0 ? run : (sh_flag[t - 1] ? sh_sum[t - 1] : run + sh_sum[t - 1]);
-        run = sh_flag[255] ? sh_sum[255] : run + sh_sum[255];
+        int2 rec = ch < chunks ? recs[ch] : make_int2(0, 0);
+        __syncthreads();                                    // (the previous round still reads S)
+        jd_seg_scan(S, t, rec.x, rec.y);
+        if (ch < chunks) carry[ch] = jd_scan_before(S, t, run);
+        run = jd_carry_in(run, S.sum[255], S.flag[255]);
     }
 }
 
@@ -595,10 +587,7 @@ JD_HD inline void jd_tile_pixels(const JdJob& J, const JdTile& T, int tx, int ty
 
 __global__ __launch_bounds__(256) void jd_pixels_kernel(const JdLaunch L) {
     __shared__ JdTile T;
-    int jk = 0;
-    for (int q = 1; q < L.n_jobs; ++q)
-        if ((int)blockIdx.x >= L.job[q].tile_base) jk = q;
-    const JdJob& J = L.job[jk];
+    const JdJob& J = L.job[job_of(L, blockIdx.x, &JdJob::tile_base)];
     const int tile = blockIdx.x - J.tile_base, tx = tile % J.tiles_x, ty = tile / J.tiles_x;
     jd_tile_quant(J, T, threadIdx.x);
     __syncthreads();
@@ -619,8 +608,8 @@ __global__ void jd_status_kernel(const JdLaunch L) {
 hipError_t launch_jpeg_decode(const JdLaunch& L, hipStream_t s) {
     for (int k = 0; k < L.n_jobs; ++k) {
         const JdJob& J = L.job[k];
-        if (hipError_t e = hipMemsetAsync(J.scratch + J.lay.coef, 0, (size_t)J.blocks * 128, s)) return e;
-        if (hipError_t e = hipMemsetAsync(J.scratch + J.lay.dc, 0, (size_t)J.blocks * 4, s)) return e;
+        if (hipError_t e = hipMemsetAsync(J.scratch + J.lay.coef, 0, (size_t)J.lay.blocks * 128, s)) return e;
+        if (hipError_t e = hipMemsetAsync(J.scratch + J.lay.dc, 0, (size_t)J.lay.blocks * 4, s)) return e;
     }
     hipLaunchKernelGGL(jd_sync_kernel, dim3(L.total_wg), dim3(kJdWgSubs), 0, s, L);
     hipLaunchKernelGGL(jd_chain_kernel, dim3(L.n_jobs), dim3(1024), 0, s, L);

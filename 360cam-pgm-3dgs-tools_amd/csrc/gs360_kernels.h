@@ -386,9 +386,31 @@ struct JpLaunch {
     uint32_t* huff;                      // n_jobs x 2 x 272 (code << 5) | length; nullptr = the Annex K tables
     uint8_t* tables;                     // n_jobs x 4 x 272: 16 BITS + HUFFVAL of DC0, AC0, DC1, AC1 (the caller's buffer)
 };
+static_assert(sizeof(JpLaunch) <= 4096, "a launch travels by value as the kernels' argument");
 hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s);
 // n_tables x 256 symbol counts -> n_tables x 272 bytes (16 BITS + HUFFVAL, zero padded): the table kernel alone
 hipError_t launch_jpeg_huff_tables(const uint32_t* hist, int n_tables, uint8_t* tables, hipStream_t s);
+
+// The MCU grid of an image, for both codecs: 8 x 8 pixels and one block per component, or (4:2:0, colour images only) 16 x 16 pixels
+// and six blocks
+struct JpGrid { int mcu_px, bpm, mw, mh; int64_t mcus() const { return (int64_t)mw * mh; } };
+inline JpGrid jpeg_grid(int H, int W, int C, int sub420) {
+    JpGrid g;
+    const bool sub = sub420 && C == 3;
+    g.mcu_px = sub ? 16 : 8;
+    g.bpm = sub ? 6 : C;
+    g.mw = (W + g.mcu_px - 1) / g.mcu_px;
+    g.mh = (H + g.mcu_px - 1) / g.mcu_px;
+    return g;
+}
+
+// the job of a launch that workgroup (tile, interval) `index` belongs to: the last one whose `base` is <= index
+template <class Launch, class Job>
+__device__ __forceinline__ int job_of(const Launch& L, int index, int32_t Job::*base) {
+    int j = 0;
+    while (j + 1 < L.n_jobs && index >= L.job[j + 1].*base) ++j;
+    return j;
+}
 
 // Baseline JPEG decoding (gs360_jpegdec.hip, JPD-SPEC v1 in DESIGN.md): one batch of up to GS360_MAX_VIEWS files.  A job's scratch
 // (JdLayout) holds a header of three counters, per subsequence its exit state and the exclusive sum of the blocks completed before it,
@@ -404,12 +426,11 @@ struct JdLayout {
 };
 inline JdLayout jd_layout(int H, int W, int C, int sub420, uint32_t n_sub) {
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const int px = (sub420 && C == 3) ? 16 : 8, bpm = (sub420 && C == 3) ? 6 : C;
-    const int64_t mcus = (int64_t)((W + px - 1) / px) * ((H + px - 1) / px);
+    const JpGrid g = jpeg_grid(H, W, C, sub420);
     JdLayout l;
-    l.blocks = mcus * bpm;
+    l.blocks = g.mcus() * g.bpm;
     l.n_wg = (int32_t)((n_sub + kJdWgSubs - 1) / kJdWgSubs);
-    l.dc_chunks = (int32_t)((mcus * (bpm == 6 ? 4 : 1) + kJdDcChunk - 1) / kJdDcChunk);
+    l.dc_chunks = (int32_t)((g.mcus() * (g.bpm == 6 ? 4 : 1) + kJdDcChunk - 1) / kJdDcChunk);
     l.exits = 256;
     l.sums = l.exits + up((size_t)n_sub * 4);
     l.used = l.sums + up((size_t)n_sub * 4);
@@ -426,19 +447,38 @@ struct JdJob {
     const uint8_t* meta;                 // 4 x 272 Huffman table bytes, then 4 x 64 quantiser bytes (zig-zag order)
     uint8_t* scratch;
     uint8_t* out;
-    int64_t stride, blocks;
-    uint32_t n_seg, n_sub, scan_len, pad;
+    int64_t stride;
+    uint32_t n_seg, n_sub, scan_len;
     int32_t H, W, C, bpm, mw, mh, ri;    // bpm: blocks per MCU (1, 3 or 6); MCU grid; MCUs per restart interval (0: none)
     int32_t wg_base, tile_base, tiles_x; // first entropy workgroup, first reconstruction tile (64 rows x 128 columns), tiles per row
-    int32_t n_wg, dc_chunks;
     uint8_t tq[4], td[4], ta[4];         // per component: quantiser, DC table, AC table
-    struct { size_t exits, sums, used, recs, carry, dc, coef; } lay;     // JdLayout's offsets (a launch's jobs travel as kernel arguments)
+    JdLayout lay;
 };
+// everything of a (checked) job but its places in the batch, wg_base and tile_base
+inline void jd_fill_job(JdJob& J, const gs360_jpeg_dec_job& j) {
+    const JpGrid g = jpeg_grid(j.H, j.W, j.C, j.subsampling == GS360_JPEG_420);
+    J.scan = (const uint8_t*)j.scan;
+    J.seg = (const uint4*)j.segments;
+    J.meta = j.tables;
+    J.scratch = (uint8_t*)j.scratch;
+    J.out = (uint8_t*)j.out;
+    J.stride = (int64_t)(j.out_stride ? j.out_stride : (size_t)j.W * j.C);
+    J.n_seg = (uint32_t)j.n_segments;
+    J.n_sub = j.n_subseq;
+    J.scan_len = j.scan_len;
+    J.H = j.H; J.W = j.W; J.C = j.C;
+    J.bpm = g.bpm; J.mw = g.mw; J.mh = g.mh;
+    J.ri = j.restart_interval;
+    J.tiles_x = (j.W + 127) / 128;
+    for (int q = 0; q < 4; ++q) { J.tq[q] = j.comp_tq[q] & 3; J.td[q] = j.comp_td[q] & 1; J.ta[q] = j.comp_ta[q] & 1; }
+    J.lay = jd_layout(j.H, j.W, j.C, j.subsampling == GS360_JPEG_420, j.n_subseq);
+}
 struct JdLaunch {
     JdJob job[GS360_MAX_VIEWS];
     int32_t n_jobs, total_wg, total_tiles, max_dc_chunks;
     uint32_t* status;                    // n_jobs
 };
+static_assert(sizeof(JdLaunch) <= 4096, "a launch travels by value as the kernels' argument");
 hipError_t launch_jpeg_decode(const JdLaunch& L, hipStream_t s);
 
 }  // namespace gs360

@@ -21,19 +21,18 @@ int main(int argc, char** argv) {
     if (fread(sel, 1, 12, f) != 12 || fread(scan.data(), 1, scan_len, f) != (size_t)scan_len ||
         fread(seg.data(), 4, n_seg * 4, f) != (size_t)n_seg * 4 || fread(meta.data(), 1, meta.size(), f) != meta.size()) return 2;
     fclose(f);
-    bool s420 = sub == 2 && C == 3;
-    JdLayout l = jd_layout(H, W, C, s420, n_sub);
+    JdLayout l = jd_layout(H, W, C, sub == GS360_JPEG_420, n_sub);
     std::vector<uint8_t> scratch(l.total);   // exact size: the sanitizer guards its end
     size_t stride = (size_t)W * C + pad;
     std::vector<uint8_t> out(stride * H, 0xA5);
+    gs360_jpeg_dec_job job = {};
+    job.scan = scan.data(); job.scan_len = scan_len; job.n_subseq = n_sub; job.segments = seg.data(); job.n_segments = n_seg;
+    job.tables = meta.data(); job.H = H; job.W = W; job.C = C; job.subsampling = sub; job.restart_interval = ri;
+    memcpy(job.comp_tq, sel, 4); memcpy(job.comp_td, sel + 4, 4); memcpy(job.comp_ta, sel + 8, 4);
+    job.scratch = scratch.data(); job.scratch_bytes = scratch.size(); job.out = out.data(); job.out_stride = stride;
     JdJob J;
     memset(&J, 0, sizeof(J));
-    J.scan = scan.data(); J.seg = (const uint4*)seg.data(); J.meta = meta.data(); J.scratch = scratch.data(); J.out = out.data();
-    J.stride = stride; J.blocks = l.blocks; J.n_seg = n_seg; J.n_sub = n_sub; J.scan_len = scan_len;
-    J.H = H; J.W = W; J.C = C; J.bpm = s420 ? 6 : C; int px = s420 ? 16 : 8; J.mw = (W + px - 1) / px; J.mh = (H + px - 1) / px; J.ri = ri;
-    J.tiles_x = (W + 127) / 128; J.n_wg = l.n_wg; J.dc_chunks = l.dc_chunks;
-    for (int q = 0; q < 4; ++q) { J.tq[q] = sel[q]; J.td[q] = sel[4 + q]; J.ta[q] = sel[8 + q]; }
-    J.lay.exits = l.exits; J.lay.sums = l.sums; J.lay.used = l.used; J.lay.recs = l.recs; J.lay.carry = l.carry; J.lay.dc = l.dc; J.lay.coef = l.coef;
+    jd_fill_job(J, job);                     // the set-up of gs360_jpeg_decode_u8
     memset(scratch.data() + l.coef, 0, l.blocks * 128);
     memset(scratch.data() + l.dc, 0, l.blocks * 4);
     JdTables* T = new JdTables;
@@ -45,7 +44,7 @@ int main(int argc, char** argv) {
     JdHeader* hdr = (JdHeader*)J.scratch;
     int max_rounds_wg = 0;
     // jd_sync_kernel
-    for (int wg = 0; wg < J.n_wg; ++wg) {
+    for (int wg = 0; wg < J.lay.n_wg; ++wg) {
         uint32_t sh[256] = {}, cur[256] = {};
         bool active[256];
         JdSegment S[256];
@@ -84,11 +83,11 @@ int main(int argc, char** argv) {
         for (int t = 0; t < 256; ++t) if ((uint32_t)(wg * 256 + t) < J.n_sub) exits[wg * 256 + t] = sh[t];
     }
     // jd_chain_kernel
-    for (int w = 1; w < J.n_wg; ++w) { uint32_t j0 = w * 256; JdSegment S = jd_find_segment(J, j0); used[w] = jd_cold(S.bytes, S.len, j0 - S.first_sub); }
+    for (int w = 1; w < J.lay.n_wg; ++w) { uint32_t j0 = w * 256; JdSegment S = jd_find_segment(J, j0); used[w] = jd_cold(S.bytes, S.len, j0 - S.first_sub); }
     uint32_t rounds = 0;
-    for (int r = 0; r < J.n_wg; ++r) {
+    for (int r = 0; r < J.lay.n_wg; ++r) {
         int changed = 0;
-        for (int w = 1; w < J.n_wg; ++w) {
+        for (int w = 1; w < J.lay.n_wg; ++w) {
             uint32_t j0 = w * 256; JdSegment S = jd_find_segment(J, j0);
             if (j0 == S.first_sub) continue;
             uint32_t ent = exits[j0 - 1] & kStateMask;
@@ -123,7 +122,7 @@ int main(int argc, char** argv) {
         for (uint32_t q = 0; q < Q.n; ++q) {
             uint32_t m = q / Q.per_mcu, sb = q % Q.per_mcu, at = m * J.bpm + Q.off + sb;
             bool head = sb == 0 && (J.ri ? m % J.ri == 0 : m == 0);
-            run = head ? dc[at] : run + dc[at];
+            run = jd_carry_in(run, dc[at], head);
             dc[at] = run;
         }
     }
@@ -138,7 +137,7 @@ int main(int argc, char** argv) {
     uint32_t status = hdr->err ? 1u : (hdr->ok != J.n_seg ? 2u : 0u);
     delete T;
     delete TL;
-    printf("status %u rounds %u wg_rounds %d n_sub %u n_wg %d\n", status, rounds, max_rounds_wg, J.n_sub, J.n_wg);
+    printf("status %u rounds %u wg_rounds %d n_sub %u n_wg %d\n", status, rounds, max_rounds_wg, J.n_sub, J.lay.n_wg);
     f = fopen(argv[2], "wb"); fwrite(out.data(), 1, out.size(), f); fclose(f);
     return 0;
 }
