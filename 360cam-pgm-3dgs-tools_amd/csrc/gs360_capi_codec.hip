@@ -217,7 +217,7 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
             J.bpm = g.bpm;
             J.n_mcu = g.mw * g.mh;
             J.n_int = (J.n_mcu + restart_interval - 1) / restart_interval;
-            J.tiles_x = (g.mw * g.mcu_px + 255) / 256;                            // strips of 256 columns, one MCU row high
+            J.tiles_x = (g.mw * g.mcu_w + 255) / 256;                             // strips of 256 columns, one MCU row high
             J.coef_base = blocks; J.tile_base = (int32_t)tiles; J.int_base = (int32_t)intervals;
             blocks += (int64_t)J.n_mcu * g.bpm;
             tiles += (int64_t)J.tiles_x * g.mh;
@@ -278,8 +278,9 @@ namespace {
 
 int check_jpeg_dec_geometry(int H, int W, int C, int subsampling) {
     if (int rc = check_jpeg_image("decoder", H, W, C)) return rc;
-    if (subsampling != GS360_JPEG_444 && subsampling != GS360_JPEG_420)
-        return fail(GS360_ERR_UNSUPPORTED, "the JPEG decoder takes GS360_JPEG_444 or GS360_JPEG_420 (got %d)", subsampling);
+    if (subsampling != GS360_JPEG_444 && subsampling != GS360_JPEG_422 && subsampling != GS360_JPEG_420 &&
+        subsampling != GS360_JPEG_440 && subsampling != GS360_JPEG_411)
+        return fail(GS360_ERR_UNSUPPORTED, "the JPEG decoder takes GS360_JPEG_444, _422, _420, _440 or _411 (got %d)", subsampling);
     return 0;
 }
 
@@ -289,7 +290,7 @@ int gs360_jpeg_decode_scratch(int H, int W, int C, int subsampling, uint32_t n_s
     if (!bytes) return fail(GS360_ERR_ARG, "NULL argument");
     if (int rc = check_jpeg_dec_geometry(H, W, C, subsampling)) return rc;
     if (n_subseq < 1 || n_subseq > (1u << 31) / kJdSubseq) return fail(GS360_ERR_ARG, "n_subseq %u outside 1..2^24", n_subseq);
-    *bytes = jd_layout(H, W, C, subsampling == GS360_JPEG_420, n_subseq).total;
+    *bytes = jd_layout_sub(H, W, C, subsampling, n_subseq).total;
     return GS360_OK;
 }
 
@@ -313,7 +314,7 @@ int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_job
         // every interval takes at least one subsequence and none crosses an interval
         if (j.n_subseq < 1 || j.n_subseq > (uint64_t)j.scan_len / kJdSubseq + (uint32_t)j.n_segments)
             return fail(GS360_ERR_ARG, "job %d: %u subsequences for %u bytes in %d segments", k, j.n_subseq, j.scan_len, j.n_segments);
-        if (jd_layout(j.H, j.W, j.C, j.subsampling == GS360_JPEG_420, j.n_subseq).total > j.scratch_bytes)
+        if (jd_layout_sub(j.H, j.W, j.C, j.subsampling, j.n_subseq).total > j.scratch_bytes)
             return fail(GS360_ERR_ARG, "job %d: scratch too small", k);
     }
     HIP_TRY(hipSetDevice(c->device));

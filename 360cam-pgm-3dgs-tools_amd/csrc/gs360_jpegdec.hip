@@ -182,12 +182,12 @@ JD_HD uint32_t jd_decode(const JdTables& T, const JdJob& J, const JdSegment& S, 
     R.init(S.bytes, S.len, k * kJdSubseq + ((state & 255) >> 3), state & 7);
     uint32_t c = (state >> 8) & 7, z = (state >> 11) & 63, n = 0, err = 0;
     const uint32_t boundary = jd_min((k + 1) * kJdSubseq, S.len);
-    const uint32_t bpm = J.bpm;
+    const uint32_t bpm = J.bpm, n_luma = (uint32_t)(J.hs * J.vs);     // an MCU's cycle: n_luma Y blocks, then one block per further component
     for (int it = 0; it < kJdSubseq * 8 + 64; ++it) {      // every symbol takes at least one bit
         if (R.i >= boundary) break;
         if (kWrite && blk >= S.blk_end) break;
         R.refill();
-        const uint32_t comp = bpm == 6 ? (c < 4 ? 0 : c - 3) : c;
+        const uint32_t comp = c < n_luma ? 0 : c - n_luma + 1;
         const uint32_t t = z == 0 ? J.td[comp] * 2 : J.ta[comp] * 2 + 1;
         const uint32_t code = (uint32_t)(R.buf >> 48);
         uint32_t e = T.fast[t][code >> (16 - kFastBits)], len = e >> 8, sym = e & 255;
@@ -363,8 +363,8 @@ __global__ __launch_bounds__(kJdWgSubs) void jd_write_kernel(const JdLaunch L) {
 struct JdDcSeq { uint32_t n, per_mcu, off; };
 JD_HD inline JdDcSeq jd_dc_seq(const JdJob& J, int comp) {
     JdDcSeq q;
-    q.per_mcu = (J.bpm == 6 && comp == 0) ? 4 : 1;
-    q.off = J.bpm == 6 ? (comp == 0 ? 0 : 3 + comp) : comp;
+    q.per_mcu = comp == 0 ? J.hs * J.vs : 1;
+    q.off = comp == 0 ? 0 : J.hs * J.vs + comp - 1;
     q.n = (uint32_t)J.mw * J.mh * q.per_mcu;
     return q;
 }
@@ -476,8 +476,10 @@ JD_HD __forceinline__ void jd_idct8(int& v0, int& v1, int& v2, int& v3, int& v4,
 
 JD_HD inline uint32_t jd_clamp8(int v) { return (uint32_t)jd_min(jd_max(v, 0), 255); }
 
-// one block: dequantise, inverse DCT, +128, clamp; 8 rows of 8 bytes to `dst` (LDS, 8-byte aligned rows of `pitch` bytes)
-JD_HD inline void jd_block(const int16_t* coef, int dcv, const uint8_t* quant, uint8_t* dst, int pitch) {
+// one block: dequantise, inverse DCT, +128, clamp; 8 rows of 8 bytes to `dst` (LDS, 8-byte aligned rows of `pitch` bytes).  Always
+// inline: its 64 values live in registers, and as a called function (what the compiler chooses once every sampling's code has a
+// call site) the pixel kernel would take 180 VGPRs and run two wavefronts per SIMD instead of four
+JD_HD __forceinline__ void jd_block(const int16_t* coef, int dcv, const uint8_t* quant, uint8_t* dst, int pitch) {
     int w[64];
     const uint4* src = (const uint4*)coef;
 #pragma unroll
@@ -506,14 +508,40 @@ JD_HD inline void jd_block(const int16_t* coef, int dcv, const uint8_t* quant, u
 }
 
 constexpr int kTileH = 64, kTileW = 128;
-constexpr int kCPitch = 80;   // 4:2:0 chroma tile: 32 x 64 samples and a halo of one block all round
 
-// One workgroup, one 64 x 128 pixel tile: its blocks' samples go to LDS (with 4:2:0 the chroma blocks all round the tile too, so the
-// upsampling filter never leaves LDS and Y is read from memory once), then every lane converts and stores pixels.
+// One workgroup, one 64 x 128 pixel tile: its blocks' samples go to LDS, then every lane converts and stores pixels.  Where chroma is
+// subsampled along an axis that libjpeg filters (by two), the chroma blocks next to the tile along that axis come along as a halo, so
+// the upsampling filter never leaves LDS and Y is read from memory once.
 struct JdTile {
     __attribute__((aligned(16))) uint8_t plane[3][kTileH * kTileW];
     uint8_t quant[3][64];                                  // per component, natural order
 };
+
+// A tile's chroma plane under luma sampling kHs x kVs, in 8 x 8 blocks: 16 / kHs x 8 / kVs of them and the halo.
+//   1x1 (4:4:4, gray)  128 x 64 samples, no halo              128 blocks, rows of 128 bytes
+//   2x2 (4:2:0)         64 x 32, one block all round           60 blocks, rows of 80
+//   2x1 (4:2:2)         64 x 64, one block left and right      80 blocks, rows of 80
+//   1x2 (4:4:0)        128 x 32, one block above and below     96 blocks, rows of 128
+//   4x1 (4:1:1)         32 x 64, no halo (plain replication)   32 blocks, rows of 32
+template <int kHs, int kVs>
+struct JdChroma {
+    static constexpr int hs = kHs, vs = kVs, halo_x = kHs == 2, halo_y = kVs == 2;
+    static constexpr int bw = 16 / kHs + 2 * halo_x, bh = 8 / kVs + 2 * halo_y, blocks = bw * bh, pitch = 8 * bw;
+    static_assert(blocks * 64 <= kTileH * kTileW, "a chroma plane with its halo fits the plane of a tile");
+};
+
+// calls f(JdChroma<hs, vs>) for the job's sampling: the one place the decoder branches on it, uniform over a workgroup
+template <class F>
+JD_HD inline void jd_with_sampling(const JdJob& J, F f) {
+    switch (J.hs * 4 + J.vs) {
+        case 1 * 4 + 1: f(JdChroma<1, 1>()); break;
+        case 2 * 4 + 2: f(JdChroma<2, 2>()); break;
+        case 2 * 4 + 1: f(JdChroma<2, 1>()); break;
+        case 1 * 4 + 2: f(JdChroma<1, 2>()); break;
+        case 4 * 4 + 1: f(JdChroma<4, 1>()); break;
+        default: break;                                    // (jd_fill_job sets no other)
+    }
+}
 
 JD_HD inline void jd_tile_quant(const JdJob& J, JdTile& T, int tid) {
     if (tid < 192) {
@@ -522,61 +550,74 @@ JD_HD inline void jd_tile_quant(const JdJob& J, JdTile& T, int tid) {
     }
 }
 
-JD_HD inline void jd_tile_blocks(const JdJob& J, JdTile& T, int tx, int ty, int tid) {
+template <int kHs, int kVs>
+JD_HD inline void jd_tile_blocks_s(const JdJob& J, JdTile& T, int tx, int ty, int tid) {
+    using G = JdChroma<kHs, kVs>;
     const int16_t* coef = (const int16_t*)(J.scratch + J.lay.coef);
     const int32_t* dc = (const int32_t*)(J.scratch + J.lay.dc);
-    const bool sub = J.bpm == 6;
-    const int n_tasks = sub ? 128 + 2 * 60 : J.C * 128;
+    const int bpm = kHs * kVs > 1 ? kHs * kVs + 2 : J.C;
+    const int n_tasks = 128 + (J.C == 3 ? 2 * G::blocks : 0);
     for (int task = tid; task < n_tasks; task += 256) {
-        int comp, blk = -1, pitch = kTileW, at;
-        if (task < 128 || !sub) {
-            comp = task >> 7;
-            const int bi = task & 127, by = bi >> 4, bx = bi & 15, gx = tx * 16 + bx, gy = ty * 8 + by;
+        int comp = 0, blk = -1, pitch = kTileW, at;
+        if (task < 128) {
+            const int by = task >> 4, bx = task & 15, gx = tx * 16 + bx, gy = ty * 8 + by;
             at = by * 8 * kTileW + bx * 8;
-            if (sub) {
-                if (gx < 2 * J.mw && gy < 2 * J.mh) blk = ((gy >> 1) * J.mw + (gx >> 1)) * 6 + (gy & 1) * 2 + (gx & 1);
-            } else if (gx < J.mw && gy < J.mh) {
-                blk = (gy * J.mw + gx) * J.C + comp;
-            }
+            if (gx < kHs * J.mw && gy < kVs * J.mh) blk = ((gy / kVs) * J.mw + gx / kHs) * bpm + (gy % kVs) * kHs + gx % kHs;
         } else {
             const int ci = task - 128;
-            comp = 1 + ci / 60;
-            const int bi = ci % 60, cy = bi / 10, cx = bi % 10, gx = tx * 8 - 1 + cx, gy = ty * 4 - 1 + cy;
-            pitch = kCPitch;
-            at = cy * 8 * kCPitch + cx * 8;
-            if (gx >= 0 && gy >= 0 && gx < J.mw && gy < J.mh) blk = (gy * J.mw + gx) * 6 + 3 + comp;
+            comp = 1 + ci / G::blocks;
+            const int bi = ci % G::blocks, cy = bi / G::bw, cx = bi % G::bw;
+            const int gx = tx * (16 / kHs) - G::halo_x + cx, gy = ty * (8 / kVs) - G::halo_y + cy;
+            pitch = G::pitch;
+            at = cy * 8 * G::pitch + cx * 8;
+            if (gx >= 0 && gy >= 0 && gx < J.mw && gy < J.mh) blk = (gy * J.mw + gx) * bpm + kHs * kVs + comp - 1;
         }
         if (blk >= 0) jd_block(coef + (size_t)blk * 64, dc[blk], T.quant[comp], &T.plane[comp][at], pitch);
     }
 }
 
-JD_HD inline void jd_tile_pixels(const JdJob& J, const JdTile& T, int tx, int ty, int tid) {
-    const bool sub = J.bpm == 6;
+// libjpeg's upsampling of a chroma plane cropped to cw x ch samples, the cropped edges replicated, at pixel (gx, gy):
+//   by two along one axis ("fancy" h2v1 / h1v2): (3 s + the nearer neighbour + 1 (even pixels) or 2 (odd)) >> 2
+//   by two along both (h2v2): that filter down the columns without its shift, then along the rows: + 8 (even) or 7 (odd), >> 4
+//   by four (h4v1): the sample itself
+template <int kHs, int kVs>
+JD_HD inline void jd_tile_pixels_s(const JdJob& J, const JdTile& T, int tx, int ty, int tid) {
+    using G = JdChroma<kHs, kVs>;
     const int x = tid & 127, gx = tx * kTileW + x;
     if (gx >= J.W) return;
-    const int cw = (J.W + 1) >> 1, ch = (J.H + 1) >> 1;
-    const int cx = gx >> 1, nx = (gx & 1) ? jd_min(cx + 1, cw - 1) : jd_max(cx - 1, 0);
-    const int lcx = cx - (tx * 64 - 8), lnx = nx - (tx * 64 - 8), bias = (gx & 1) ? 7 : 8;
+    const int cw = (J.W + kHs - 1) / kHs, ch = (J.H + kVs - 1) / kVs;
+    const int x0 = tx * (kTileW / kHs) - 8 * G::halo_x, y0 = ty * (kTileH / kVs) - 8 * G::halo_y;   // the chroma tile's first sample
+    const int cx = gx / kHs, nx = (gx & 1) ? jd_min(cx + 1, cw - 1) : jd_max(cx - 1, 0);
+    const int lcx = cx - x0, lnx = nx - x0;
     for (int i = 0; i < kTileH / 2; ++i) {
         const int y = (tid >> 7) + 2 * i, gy = ty * kTileH + y;
         if (gy >= J.H) break;
         uint8_t* o = J.out + (size_t)gy * J.stride + (size_t)gx * J.C;
         const int Y = T.plane[0][y * kTileW + x];
-        if (J.C == 1) {
+        if (kHs * kVs == 1 && J.C == 1) {
             o[0] = (uint8_t)Y;
             continue;
         }
+        const int cy = gy / kVs, ny = (gy & 1) ? jd_min(cy + 1, ch - 1) : jd_max(cy - 1, 0);
+        const int r0 = (cy - y0) * G::pitch, r1 = (ny - y0) * G::pitch;
         int cb, cr;
-        if (sub) {
-            const int cy = gy >> 1, ny = (gy & 1) ? jd_min(cy + 1, ch - 1) : jd_max(cy - 1, 0);
-            const int r0 = (cy - (ty * 32 - 8)) * kCPitch, r1 = (ny - (ty * 32 - 8)) * kCPitch;
+        if (kHs == 2 && kVs == 2) {
+            const int bias = (gx & 1) ? 7 : 8;
             const int sb = 3 * T.plane[1][r0 + lcx] + T.plane[1][r1 + lcx], sbn = 3 * T.plane[1][r0 + lnx] + T.plane[1][r1 + lnx];
             const int sr = 3 * T.plane[2][r0 + lcx] + T.plane[2][r1 + lcx], srn = 3 * T.plane[2][r0 + lnx] + T.plane[2][r1 + lnx];
             cb = (3 * sb + sbn + bias) >> 4;
             cr = (3 * sr + srn + bias) >> 4;
+        } else if (kHs == 2) {
+            const int bias = (gx & 1) ? 2 : 1;
+            cb = (3 * T.plane[1][r0 + lcx] + T.plane[1][r0 + lnx] + bias) >> 2;
+            cr = (3 * T.plane[2][r0 + lcx] + T.plane[2][r0 + lnx] + bias) >> 2;
+        } else if (kVs == 2) {
+            const int bias = (gy & 1) ? 2 : 1;
+            cb = (3 * T.plane[1][r0 + lcx] + T.plane[1][r1 + lcx] + bias) >> 2;
+            cr = (3 * T.plane[2][r0 + lcx] + T.plane[2][r1 + lcx] + bias) >> 2;
         } else {
-            cb = T.plane[1][y * kTileW + x];
-            cr = T.plane[2][y * kTileW + x];
+            cb = T.plane[1][r0 + lcx];
+            cr = T.plane[2][r0 + lcx];
         }
         cb -= 128; cr -= 128;
         o[0] = (uint8_t)jd_clamp8(Y + ((91881 * cr + 32768) >> 16));
@@ -585,15 +626,25 @@ JD_HD inline void jd_tile_pixels(const JdJob& J, const JdTile& T, int tx, int ty
     }
 }
 
+// the two steps for whatever the job's sampling is (a host program steps these)
+JD_HD inline void jd_tile_blocks(const JdJob& J, JdTile& T, int tx, int ty, int tid) {
+    jd_with_sampling(J, [&](auto g) { jd_tile_blocks_s<decltype(g)::hs, decltype(g)::vs>(J, T, tx, ty, tid); });
+}
+JD_HD inline void jd_tile_pixels(const JdJob& J, const JdTile& T, int tx, int ty, int tid) {
+    jd_with_sampling(J, [&](auto g) { jd_tile_pixels_s<decltype(g)::hs, decltype(g)::vs>(J, T, tx, ty, tid); });
+}
+
 __global__ __launch_bounds__(256) void jd_pixels_kernel(const JdLaunch L) {
     __shared__ JdTile T;
     const JdJob& J = L.job[job_of(L, blockIdx.x, &JdJob::tile_base)];
     const int tile = blockIdx.x - J.tile_base, tx = tile % J.tiles_x, ty = tile / J.tiles_x;
     jd_tile_quant(J, T, threadIdx.x);
     __syncthreads();
-    jd_tile_blocks(J, T, tx, ty, threadIdx.x);
-    __syncthreads();
-    jd_tile_pixels(J, T, tx, ty, threadIdx.x);
+    jd_with_sampling(J, [&](auto g) {                      // one switch per workgroup: each sampling has its own blocks and pixels code
+        jd_tile_blocks_s<decltype(g)::hs, decltype(g)::vs>(J, T, tx, ty, threadIdx.x);
+        __syncthreads();
+        jd_tile_pixels_s<decltype(g)::hs, decltype(g)::vs>(J, T, tx, ty, threadIdx.x);
+    });
 }
 
 __global__ void jd_status_kernel(const JdLaunch L) {

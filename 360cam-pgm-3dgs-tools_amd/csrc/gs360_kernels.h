@@ -391,17 +391,28 @@ hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s);
 // n_tables x 256 symbol counts -> n_tables x 272 bytes (16 BITS + HUFFVAL, zero padded): the table kernel alone
 hipError_t launch_jpeg_huff_tables(const uint32_t* hist, int n_tables, uint8_t* tables, hipStream_t s);
 
-// The MCU grid of an image, for both codecs: 8 x 8 pixels and one block per component, or (4:2:0, colour images only) 16 x 16 pixels
-// and six blocks
-struct JpGrid { int mcu_px, bpm, mw, mh; int64_t mcus() const { return (int64_t)mw * mh; } };
-inline JpGrid jpeg_grid(int H, int W, int C, int sub420) {
+// The MCU grid of an image, for both codecs.  A colour image's luma is sampled hs x vs over 1 x 1 chroma: its MCU is 8 hs x 8 vs pixels
+// and holds hs vs luma blocks in raster order, then Cb, then Cr (hs = vs = 1: one block per component).  A gray image's MCU is one
+// block whatever its sampling factors say.
+struct JpGrid { int mcu_w, mcu_h, bpm, mw, mh, hs, vs; int64_t mcus() const { return (int64_t)mw * mh; } };
+inline JpGrid jpeg_grid_sampled(int H, int W, int C, int hs, int vs) {
     JpGrid g;
-    const bool sub = sub420 && C == 3;
-    g.mcu_px = sub ? 16 : 8;
-    g.bpm = sub ? 6 : C;
-    g.mw = (W + g.mcu_px - 1) / g.mcu_px;
-    g.mh = (H + g.mcu_px - 1) / g.mcu_px;
+    g.hs = C == 3 ? hs : 1;
+    g.vs = C == 3 ? vs : 1;
+    g.mcu_w = 8 * g.hs;
+    g.mcu_h = 8 * g.vs;
+    g.bpm = g.hs * g.vs > 1 ? g.hs * g.vs + 2 : C;
+    g.mw = (W + g.mcu_w - 1) / g.mcu_w;
+    g.mh = (H + g.mcu_h - 1) / g.mcu_h;
     return g;
+}
+// the encoder's two modes: 8 x 8 pixels, or (4:2:0, colour images only) 16 x 16 pixels and six blocks
+inline JpGrid jpeg_grid(int H, int W, int C, int sub420) { return jpeg_grid_sampled(H, W, C, sub420 ? 2 : 1, sub420 ? 2 : 1); }
+// the decoder's: GS360_JPEG_444 / 422 / 420 / 440 / 411 (checked by the caller) -> luma sampling 1x1 / 2x1 / 2x2 / 1x2 / 4x1
+inline JpGrid jd_grid(int H, int W, int C, int subsampling) {
+    const int hs = subsampling == GS360_JPEG_411 ? 4 : (subsampling == GS360_JPEG_422 || subsampling == GS360_JPEG_420) ? 2 : 1;
+    const int vs = (subsampling == GS360_JPEG_440 || subsampling == GS360_JPEG_420) ? 2 : 1;
+    return jpeg_grid_sampled(H, W, C, hs, vs);
 }
 
 // the job of a launch that workgroup (tile, interval) `index` belongs to: the last one whose `base` is <= index
@@ -424,13 +435,12 @@ struct JdLayout {
     int64_t blocks;
     int32_t n_wg, dc_chunks;             // entropy workgroups; DC chunks of the component with the most blocks
 };
-inline JdLayout jd_layout(int H, int W, int C, int sub420, uint32_t n_sub) {
+inline JdLayout jd_layout_grid(const JpGrid& g, uint32_t n_sub) {
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const JpGrid g = jpeg_grid(H, W, C, sub420);
     JdLayout l;
     l.blocks = g.mcus() * g.bpm;
     l.n_wg = (int32_t)((n_sub + kJdWgSubs - 1) / kJdWgSubs);
-    l.dc_chunks = (int32_t)((g.mcus() * (g.bpm == 6 ? 4 : 1) + kJdDcChunk - 1) / kJdDcChunk);
+    l.dc_chunks = (int32_t)((g.mcus() * g.hs * g.vs + kJdDcChunk - 1) / kJdDcChunk);
     l.exits = 256;
     l.sums = l.exits + up((size_t)n_sub * 4);
     l.used = l.sums + up((size_t)n_sub * 4);
@@ -441,6 +451,8 @@ inline JdLayout jd_layout(int H, int W, int C, int sub420, uint32_t n_sub) {
     l.total = l.coef + (size_t)l.blocks * 128;
     return l;
 }
+inline JdLayout jd_layout(int H, int W, int C, int sub420, uint32_t n_sub) { return jd_layout_grid(jpeg_grid(H, W, C, sub420), n_sub); }
+inline JdLayout jd_layout_sub(int H, int W, int C, int subsampling, uint32_t n_sub) { return jd_layout_grid(jd_grid(H, W, C, subsampling), n_sub); }
 struct JdJob {
     const uint8_t* scan;                 // the entropy-coded segment
     const uint4* seg;                    // per restart interval: start, length, first subsequence, first MCU
@@ -449,14 +461,15 @@ struct JdJob {
     uint8_t* out;
     int64_t stride;
     uint32_t n_seg, n_sub, scan_len;
-    int32_t H, W, C, bpm, mw, mh, ri;    // bpm: blocks per MCU (1, 3 or 6); MCU grid; MCUs per restart interval (0: none)
+    int32_t H, W, C, bpm, mw, mh, ri;    // bpm: blocks per MCU (1, 3, 4 or 6); MCU grid; MCUs per restart interval (0: none)
+    int32_t hs, vs;                      // luma sampling: an MCU's first hs x vs blocks are Y, in raster order (JpGrid)
     int32_t wg_base, tile_base, tiles_x; // first entropy workgroup, first reconstruction tile (64 rows x 128 columns), tiles per row
     uint8_t tq[4], td[4], ta[4];         // per component: quantiser, DC table, AC table
     JdLayout lay;
 };
 // everything of a (checked) job but its places in the batch, wg_base and tile_base
 inline void jd_fill_job(JdJob& J, const gs360_jpeg_dec_job& j) {
-    const JpGrid g = jpeg_grid(j.H, j.W, j.C, j.subsampling == GS360_JPEG_420);
+    const JpGrid g = jd_grid(j.H, j.W, j.C, j.subsampling);
     J.scan = (const uint8_t*)j.scan;
     J.seg = (const uint4*)j.segments;
     J.meta = j.tables;
@@ -467,11 +480,11 @@ inline void jd_fill_job(JdJob& J, const gs360_jpeg_dec_job& j) {
     J.n_sub = j.n_subseq;
     J.scan_len = j.scan_len;
     J.H = j.H; J.W = j.W; J.C = j.C;
-    J.bpm = g.bpm; J.mw = g.mw; J.mh = g.mh;
+    J.bpm = g.bpm; J.mw = g.mw; J.mh = g.mh; J.hs = g.hs; J.vs = g.vs;
     J.ri = j.restart_interval;
     J.tiles_x = (j.W + 127) / 128;
     for (int q = 0; q < 4; ++q) { J.tq[q] = j.comp_tq[q] & 3; J.td[q] = j.comp_td[q] & 1; J.ta[q] = j.comp_ta[q] & 1; }
-    J.lay = jd_layout(j.H, j.W, j.C, j.subsampling == GS360_JPEG_420, j.n_subseq);
+    J.lay = jd_layout_grid(g, j.n_subseq);
 }
 struct JdLaunch {
     JdJob job[GS360_MAX_VIEWS];

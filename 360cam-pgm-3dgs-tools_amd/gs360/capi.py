@@ -40,6 +40,9 @@ JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the 
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
 JPEG_444 = 0                         # GS360_JPEG_444 / GS360_JPEG_420: the `subsampling` of gs360_jpeg_scan_sub_u8 (Pillow's numbers)
 JPEG_420 = 2
+JPEG_422 = 1                         # GS360_JPEG_422 / _440 / _411: further `subsampling` values of gs360_jpeg_decode_u8 (decoder only)
+JPEG_440 = 3
+JPEG_411 = 4
 JPEG_DEC_SUBSEQ_BYTES = 128          # GS360_JPEG_DEC_SUBSEQ_BYTES: bytes of a scan one lane of gs360_jpeg_decode_u8 decodes first
 JPEG_DEC_WG_SUBSEQS = 256            # GS360_JPEG_DEC_WG_SUBSEQS: subsequences one workgroup synchronises among themselves
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"

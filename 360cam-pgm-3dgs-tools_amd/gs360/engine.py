@@ -19,8 +19,9 @@ gs360_jpeg_scan_opt_u8 call, which builds every view's own Huffman tables first)
 header + scan + EOI with a plain file write.  The default, `host`, is the path above, unchanged.
 
 GS360_JPEG_DECODER=device does the same for the input side (gs360/jpegdec.py, JPD-SPEC v1): a baseline .jpg / .jpeg still is not
-decoded by Pillow and uploaded as pixels; its scan is uploaded and gs360_jpeg_decode_u8 leaves the frame resident.  Files the device
-path does not take (progressive, 4:2:2, CMYK, cut short ...) and every other format go through imageio.read_image as before.
+decoded by Pillow and uploaded as pixels; its scan is uploaded and gs360_jpeg_decode_u8 leaves the frame resident (gray, 4:4:4, 4:2:2,
+4:2:0, 4:4:0 and 4:1:1 files).  Files the device path does not take (progressive, other sampling factors, CMYK, cut short ...) and
+every other format go through imageio.read_image as before.
 """
 import collections
 import itertools

@@ -3,7 +3,7 @@
 parse() walks a file's marker segments on the host and returns what the device needs: the geometry, the quantiser and Huffman tables
 and where the entropy-coded segment and its restart intervals lie.  decode_device() uploads only those bytes; gs360_jpeg_decode_u8
 (csrc/gs360_jpegdec.hip) decodes the scan with the self-synchronising parallel Huffman scheme, rebuilds the pixels with libjpeg's
-integer arithmetic (islow IDCT, "fancy" h2v2 upsampling, the fixed-point YCbCr -> RGB rows) and leaves an H x W x C uint8 image in
+integer arithmetic (islow IDCT, the upsampling of the file's chroma layout, the fixed-point YCbCr -> RGB rows) and leaves an H x W x C uint8 image in
 device memory, byte for byte what Pillow / libjpeg-turbo return for the file.  Whatever parse() refuses (Unsupported) the host decodes.
 
 Restart markers are found on the host, with vectorised NumPy: the scan's bytes are in host memory anyway before their upload, one
@@ -28,8 +28,16 @@ class Unsupported(ValueError):
     """the file is not one the device path takes (the host decodes it)"""
 
 
+# component sampling bytes (Y, Cb, Cr) -> `subsampling`: what parse() takes by default, and everything the device decodes
+V1_SAMPLINGS = {(0x11, 0x11, 0x11): capi.JPEG_444, (0x22, 0x11, 0x11): capi.JPEG_420}
+DEVICE_SAMPLINGS = dict(V1_SAMPLINGS)
+DEVICE_SAMPLINGS.update({(0x21, 0x11, 0x11): capi.JPEG_422, (0x12, 0x11, 0x11): capi.JPEG_440, (0x41, 0x11, 0x11): capi.JPEG_411})
+# `subsampling` -> the luma sampling (horizontal, vertical) over 1 x 1 chroma
+LUMA_SAMPLING = {capi.JPEG_444: (1, 1), capi.JPEG_422: (2, 1), capi.JPEG_420: (2, 2), capi.JPEG_440: (1, 2), capi.JPEG_411: (4, 1)}
+
+
 class Descriptor:
-    """What parse() found.  H, W, C; subsampling (capi.JPEG_444 / JPEG_420; JPEG_444 for gray); restart (MCUs per restart interval, 0 =
+    """What parse() found.  H, W, C; subsampling (capi.JPEG_444 / JPEG_422 / JPEG_420 / JPEG_440 / JPEG_411; JPEG_444 for gray); restart (MCUs per restart interval, 0 =
     none); quant: uint8 [4][64] in file (zig-zag) order; huff: uint8 [4][272] (DC0, AC0, DC1, AC1: 16 BITS + HUFFVAL, zero padded);
     comp_tq / comp_td / comp_ta: per component the quantiser, DC and AC table it uses; scan_off, scan_len: the entropy-coded segment
     in the file (everything between the SOS header and EOI); segments: uint32 [n][2], start (relative to scan_off) and length of every
@@ -38,17 +46,28 @@ class Descriptor:
                  "segments")
 
     @property
+    def luma_sampling(self):
+        """(hs, vs): an MCU holds hs x vs Y blocks in raster order, then (C = 3) Cb and Cr"""
+        return LUMA_SAMPLING[self.subsampling] if self.C == 3 else (1, 1)
+
+    @property
     def mcu_px(self):
-        return 16 if (self.C == 3 and self.subsampling == capi.JPEG_420) else 8
+        """(height, width) of an MCU in pixels"""
+        hs, vs = self.luma_sampling
+        return 8 * vs, 8 * hs
+
+    mcu_h = property(lambda self: self.mcu_px[0])
+    mcu_w = property(lambda self: self.mcu_px[1])
 
     @property
     def blocks_per_mcu(self):
-        return 6 if self.mcu_px == 16 else self.C
+        hs, vs = self.luma_sampling
+        return hs * vs + 2 if hs * vs > 1 else self.C
 
     @property
     def mcu_grid(self):
-        p = self.mcu_px
-        return (self.H + p - 1) // p, (self.W + p - 1) // p
+        ph, pw = self.mcu_px
+        return (self.H + ph - 1) // ph, (self.W + pw - 1) // pw
 
     @property
     def n_mcu(self):
@@ -77,8 +96,9 @@ def find_segments(scan, restart, n_mcu):
     return np.stack([starts, ends - starts], axis=1).astype(np.uint32)
 
 
-def parse(data):
-    """data: the bytes of a file -> Descriptor, or raises Unsupported(reason)"""
+def parse(data, samplings=V1_SAMPLINGS):
+    """data: the bytes of a file -> Descriptor, or raises Unsupported(reason).  samplings: the component layouts of a colour file to
+    accept, {(Y, Cb, Cr sampling bytes): subsampling}; the default is gray, 4:4:4 and 4:2:0 only, DEVICE_SAMPLINGS all the device takes"""
     data = bytes(data)
     n = len(data)
     if n > MAX_BYTES:
@@ -171,13 +191,11 @@ def parse(data):
         raise Unsupported("empty image (or DNL-defined height)")
     if len(comps) not in (1, 3):
         raise Unsupported(f"{len(comps)} components")
-    sampling = [c[1] for c in comps]
+    sampling = tuple(c[1] for c in comps)
     if len(comps) == 1:
         d.subsampling = capi.JPEG_444        # a single component's sampling factors do not matter: its MCU is one block
-    elif sampling == [0x11, 0x11, 0x11]:
-        d.subsampling = capi.JPEG_444
-    elif sampling == [0x22, 0x11, 0x11]:
-        d.subsampling = capi.JPEG_420
+    elif sampling in samplings:
+        d.subsampling = samplings[sampling]
     else:
         raise Unsupported("sampling factors " + ",".join("%02x" % s for s in sampling))
     if len(comps) == 3 and adobe_transform is not None and adobe_transform != 1:
@@ -276,7 +294,7 @@ class Batch:
         sources = []
         for k, data in enumerate(datas):
             try:
-                d = parse(data)
+                d = parse(data, samplings=DEVICE_SAMPLINGS)
             except Unsupported as exc:
                 self.refused[k] = str(exc)
                 continue

@@ -493,11 +493,15 @@ int gs360_jpeg_scan_sub_u8(gs360_ctx *ctx, const gs360_jpeg_job *jobs, int n_job
 int gs360_jpeg_scan_bound_sub(int H, int W, int C, int restart_interval, int subsampling, size_t *bytes);
 
 /* ---- baseline JPEG files decoded on the device (JPD-SPEC v1) -------------------------------------------
- * The inverse of the scans above for the input side: a baseline sequential JPEG (SOF0, 8 bits, one interleaved scan; gray, 4:4:4 or
- * 4:2:0) becomes an H x W x C uint8 image in device memory (C = 3: R, G, B), byte for byte what libjpeg's default decoder returns
- * (islow IDCT, "fancy" h2v2 upsampling, its fixed-point YCbCr -> RGB tables).  The host parses the header (gs360/jpegdec.py) and hands
- * over, all in device memory: `scan`, the entropy-coded segment (everything between the SOS header and EOI, restart markers
- * included); `segments`, per restart interval four uint32: its first byte in `scan`, its length (marker excluded), the number of
+ * The inverse of the scans above for the input side: a baseline sequential JPEG (SOF0, 8 bits, one interleaved scan; gray, 4:4:4,
+ * 4:2:2, 4:2:0, 4:4:0 or 4:1:1) becomes an H x W x C uint8 image in device memory (C = 3: R, G, B), byte for byte what libjpeg's
+ * default decoder returns (islow IDCT, its "fancy" h2v2 / h2v1 / h1v2 upsampling and plain replication for 4:1:1, its fixed-point
+ * YCbCr -> RGB tables).  `subsampling` names the luma sampling of a C = 3 file whose chroma components are both sampled 1 x 1:
+ * GS360_JPEG_444 1x1, GS360_JPEG_422 2x1 (MCUs of 16 x 8 pixels: Y Y Cb Cr), GS360_JPEG_420 2x2 (16 x 16: Y Y Y Y Cb Cr),
+ * GS360_JPEG_440 1x2 (8 x 16: upper Y, lower Y, Cb, Cr) and GS360_JPEG_411 4x1 (32 x 8: Y Y Y Y Cb Cr); a C = 1 job ignores it
+ * (its MCU is one block).  restart_interval and the segments' first MCUs count those MCUs.  The encoder entry points above take only
+ * GS360_JPEG_444 and GS360_JPEG_420.  The host parses the header (gs360/jpegdec.py) and hands over, all in device memory:
+ * `scan`, the entropy-coded segment (everything between the SOS header and EOI, restart markers included); `segments`, per restart interval four uint32: its first byte in `scan`, its length (marker excluded), the number of
  * subsequences of GS360_JPEG_DEC_SUBSEQ_BYTES bytes all earlier intervals take (each ceil(length / that)), and its first MCU (the
  * records are read as 16-byte vectors: `segments` is 16-byte aligned);
  * `tables`, 4 * GS360_JPEG_TABLE_BYTES bytes (DC0, AC0, DC1, AC1: 16 BITS + HUFFVAL, zero padded) followed by four quantiser tables of
@@ -506,8 +510,11 @@ int gs360_jpeg_scan_bound_sub(int H, int W, int C, int restart_interval, int sub
  * status_dev[k] (device memory) is 0 when job k's stream decoded to exactly its blocks and every interval ended at its last byte,
  * 1 when the decoder met an invalid code and 2 when an interval held fewer or more blocks than it should; `out` then holds no image.
  * A truncated or corrupt stream never makes the device read or write outside the job's buffers.  Asynchronous on `slot`.
- * GS360_ERR_UNSUPPORTED: C not 1 or 3, a subsampling other than GS360_JPEG_444 / GS360_JPEG_420, a table selector above 1 (3 for
+ * GS360_ERR_UNSUPPORTED: C not 1 or 3, a subsampling that is none of the five GS360_JPEG_4xx values, a table selector above 1 (3 for
  * quantisers); GS360_ERR_ARG: sizes of 2^31 bytes or more, a scratch that is too small or misaligned, misaligned segments. */
+#define GS360_JPEG_422 1             /* decoder only (Pillow's number) */
+#define GS360_JPEG_440 3             /* decoder only */
+#define GS360_JPEG_411 4             /* decoder only */
 #define GS360_JPEG_DEC_SUBSEQ_BYTES 128  /* the entropy decoder's unit: one lane decodes one subsequence first */
 #define GS360_JPEG_DEC_WG_SUBSEQS 256    /* subsequences one workgroup synchronises among themselves */
 typedef struct gs360_jpeg_dec_job {
