@@ -141,7 +141,7 @@ int gs360_jpeg_scan_bound_sub(int H, int W, int C, int restart_interval, int sub
     if (int rc = check_jpeg_subsampling(subsampling)) return rc;
     // a block's 64 coefficients cost at most 26 bits each (a 16-bit code and 10 value bits): 208 bytes, twice that when every byte is
     // stuffed; an interval adds at most its marker and one slack byte
-    const JpGrid g = jpeg_grid(H, W, C, subsampling == GS360_JPEG_420);
+    const JpGrid g = jpeg_grid(H, W, C, subsampling);
     const size_t mcus = (size_t)g.mcus();
     const size_t intervals = (mcus + restart_interval - 1) / restart_interval;
     *bytes = mcus * g.bpm * 416 + intervals * 3;
@@ -160,13 +160,14 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
     if (!jobs || !lengths_dev || (optimal && !tables_dev)) return fail(GS360_ERR_ARG, "NULL argument");
     if (quality < 1 || quality > 100) return fail(GS360_ERR_ARG, "quality %d outside 1..100", quality);
     if (int rc = check_jpeg_subsampling(subsampling)) return rc;
+    std::vector<JpGrid> grid(n_jobs);            // each job's MCU grid: checked here, then read by the sizing and the fill
     for (int k = 0; k < n_jobs; ++k) {
         const gs360_jpeg_job& j = jobs[k];
         if (int rc = check_jpeg_geometry(j.H, j.W, j.C, restart_interval)) return rc;
         if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
         if (j.src_stride && j.src_stride < (size_t)j.W * j.C) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
         // the table construction's range: counts in uint32 below libjpeg's 10^9 sentinel, code lengths below 64 before limiting
-        const JpGrid g = jpeg_grid(j.H, j.W, j.C, subsampling == GS360_JPEG_420);
+        const JpGrid& g = grid[k] = jpeg_grid(j.H, j.W, j.C, subsampling);
         if (optimal && g.mcus() * g.bpm * 64 >= 1000000000ll)
             return fail(GS360_ERR_UNSUPPORTED, "job %d: optimal Huffman tables take images below 10^9 coefficients", k);
     }
@@ -188,9 +189,8 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
         int64_t blocks = 0, intervals = 0;
         for (int k = k0; k < std::min(n_jobs, k0 + GS360_MAX_VIEWS); ++k) {
-            const JpGrid g = jpeg_grid(jobs[k].H, jobs[k].W, jobs[k].C, subsampling == GS360_JPEG_420);
-            const int64_t mcus = g.mcus();
-            blocks += mcus * g.bpm;
+            const int64_t mcus = grid[k].mcus();
+            blocks += mcus * grid[k].bpm;
             intervals += (mcus + restart_interval - 1) / restart_interval;
         }
         size_t a, b, d, e;
@@ -212,7 +212,7 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
             J.cap = j.out_capacity;
             J.stride = (int64_t)(j.src_stride ? j.src_stride : (size_t)j.W * j.C);
             J.H = j.H; J.W = j.W; J.C = j.C;
-            const JpGrid g = jpeg_grid(j.H, j.W, j.C, subsampling == GS360_JPEG_420);
+            const JpGrid& g = grid[k0 + k];
             J.bw = g.mw;
             J.bpm = g.bpm;
             J.n_mcu = g.mw * g.mh;
@@ -290,7 +290,7 @@ int gs360_jpeg_decode_scratch(int H, int W, int C, int subsampling, uint32_t n_s
     if (!bytes) return fail(GS360_ERR_ARG, "NULL argument");
     if (int rc = check_jpeg_dec_geometry(H, W, C, subsampling)) return rc;
     if (n_subseq < 1 || n_subseq > (1u << 31) / kJdSubseq) return fail(GS360_ERR_ARG, "n_subseq %u outside 1..2^24", n_subseq);
-    *bytes = jd_layout_sub(H, W, C, subsampling, n_subseq).total;
+    *bytes = jd_layout(H, W, C, subsampling, n_subseq).total;
     return GS360_OK;
 }
 
@@ -314,7 +314,7 @@ int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_job
         // every interval takes at least one subsequence and none crosses an interval
         if (j.n_subseq < 1 || j.n_subseq > (uint64_t)j.scan_len / kJdSubseq + (uint32_t)j.n_segments)
             return fail(GS360_ERR_ARG, "job %d: %u subsequences for %u bytes in %d segments", k, j.n_subseq, j.scan_len, j.n_segments);
-        if (jd_layout_sub(j.H, j.W, j.C, j.subsampling, j.n_subseq).total > j.scratch_bytes)
+        if (jd_layout(j.H, j.W, j.C, j.subsampling, j.n_subseq).total > j.scratch_bytes)
             return fail(GS360_ERR_ARG, "job %d: scratch too small", k);
     }
     HIP_TRY(hipSetDevice(c->device));

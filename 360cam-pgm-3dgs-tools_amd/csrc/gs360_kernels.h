@@ -395,7 +395,11 @@ hipError_t launch_jpeg_huff_tables(const uint32_t* hist, int n_tables, uint8_t* 
 // and holds hs vs luma blocks in raster order, then Cb, then Cr (hs = vs = 1: one block per component).  A gray image's MCU is one
 // block whatever its sampling factors say.
 struct JpGrid { int mcu_w, mcu_h, bpm, mw, mh, hs, vs; int64_t mcus() const { return (int64_t)mw * mh; } };
-inline JpGrid jpeg_grid_sampled(int H, int W, int C, int hs, int vs) {
+// GS360_JPEG_444 / 422 / 420 / 440 / 411 (checked by the caller: the encoder takes _444 and _420) -> luma sampling 1x1 / 2x1 / 2x2 /
+// 1x2 / 4x1
+inline JpGrid jpeg_grid(int H, int W, int C, int subsampling) {
+    const int hs = subsampling == GS360_JPEG_411 ? 4 : (subsampling == GS360_JPEG_422 || subsampling == GS360_JPEG_420) ? 2 : 1;
+    const int vs = (subsampling == GS360_JPEG_440 || subsampling == GS360_JPEG_420) ? 2 : 1;
     JpGrid g;
     g.hs = C == 3 ? hs : 1;
     g.vs = C == 3 ? vs : 1;
@@ -405,14 +409,6 @@ inline JpGrid jpeg_grid_sampled(int H, int W, int C, int hs, int vs) {
     g.mw = (W + g.mcu_w - 1) / g.mcu_w;
     g.mh = (H + g.mcu_h - 1) / g.mcu_h;
     return g;
-}
-// the encoder's two modes: 8 x 8 pixels, or (4:2:0, colour images only) 16 x 16 pixels and six blocks
-inline JpGrid jpeg_grid(int H, int W, int C, int sub420) { return jpeg_grid_sampled(H, W, C, sub420 ? 2 : 1, sub420 ? 2 : 1); }
-// the decoder's: GS360_JPEG_444 / 422 / 420 / 440 / 411 (checked by the caller) -> luma sampling 1x1 / 2x1 / 2x2 / 1x2 / 4x1
-inline JpGrid jd_grid(int H, int W, int C, int subsampling) {
-    const int hs = subsampling == GS360_JPEG_411 ? 4 : (subsampling == GS360_JPEG_422 || subsampling == GS360_JPEG_420) ? 2 : 1;
-    const int vs = (subsampling == GS360_JPEG_440 || subsampling == GS360_JPEG_420) ? 2 : 1;
-    return jpeg_grid_sampled(H, W, C, hs, vs);
 }
 
 // the job of a launch that workgroup (tile, interval) `index` belongs to: the last one whose `base` is <= index
@@ -451,8 +447,7 @@ inline JdLayout jd_layout_grid(const JpGrid& g, uint32_t n_sub) {
     l.total = l.coef + (size_t)l.blocks * 128;
     return l;
 }
-inline JdLayout jd_layout(int H, int W, int C, int sub420, uint32_t n_sub) { return jd_layout_grid(jpeg_grid(H, W, C, sub420), n_sub); }
-inline JdLayout jd_layout_sub(int H, int W, int C, int subsampling, uint32_t n_sub) { return jd_layout_grid(jd_grid(H, W, C, subsampling), n_sub); }
+inline JdLayout jd_layout(int H, int W, int C, int subsampling, uint32_t n_sub) { return jd_layout_grid(jpeg_grid(H, W, C, subsampling), n_sub); }
 struct JdJob {
     const uint8_t* scan;                 // the entropy-coded segment
     const uint4* seg;                    // per restart interval: start, length, first subsequence, first MCU
@@ -469,7 +464,7 @@ struct JdJob {
 };
 // everything of a (checked) job but its places in the batch, wg_base and tile_base
 inline void jd_fill_job(JdJob& J, const gs360_jpeg_dec_job& j) {
-    const JpGrid g = jd_grid(j.H, j.W, j.C, j.subsampling);
+    const JpGrid g = jpeg_grid(j.H, j.W, j.C, j.subsampling);
     J.scan = (const uint8_t*)j.scan;
     J.seg = (const uint4*)j.segments;
     J.meta = j.tables;

@@ -604,38 +604,34 @@ class Context:
                                           len(pairs), out.ptr, points.ptr if points is not None else None, slot), self.L)
 
     # -- JPEG scans of device images (gs360/jpegenc.py) ---------------------------------------
-    @staticmethod
-    def _jpeg_jobs(jobs):
+    def _jpeg_scan(self, fn, jobs, head, lengths, tables, slot):
+        """What the three scan entry points share: the tables buffer's size check, the job array and the call.  head = (quality,
+        restart[, subsampling]); tables = (DeviceBuffer or None,), or () for the entry point without the argument."""
+        for t in tables:
+            if t is not None and t.nbytes < 4 * JPEG_TABLE_BYTES * len(jobs):
+                raise ValueError("tables buffer below 4 x 272 bytes per job")
         arr = (JpegJob * max(len(jobs), 1))()
         for k, (src, H, W, Cn, stride, out, cap) in enumerate(jobs):
             if cap > out.nbytes:
                 raise ValueError("out_capacity larger than the output buffer")
             arr[k] = JpegJob(src.ptr, int(H), int(W), int(Cn), int(stride), out.ptr, int(cap))
-        return arr
+        _check(fn(self.handle, arr, len(jobs), *(int(v) for v in head), lengths.ptr,
+                  *(t.ptr if t is not None else None for t in tables), slot), self.L)
 
     def jpeg_scan_dev(self, jobs, lengths, quality=100, restart=8, slot=0):
         """gs360_jpeg_scan_u8: jobs = iterable of (src DeviceBuffer, H, W, C, src_stride, out DeviceBuffer, out_capacity); lengths =
         DeviceBuffer of len(jobs) uint64 (JPEG_OVERFLOW where a scan exceeded its capacity).  Asynchronous on `slot`."""
-        arr = self._jpeg_jobs(jobs)
-        _check(self.L.gs360_jpeg_scan_u8(self.handle, arr, len(jobs), int(quality), int(restart), lengths.ptr, slot), self.L)
+        self._jpeg_scan(self.L.gs360_jpeg_scan_u8, jobs, (quality, restart), lengths, (), slot)
 
     def jpeg_scan_opt_dev(self, jobs, lengths, tables, quality=100, restart=8, slot=0):
         """gs360_jpeg_scan_opt_u8: jpeg_scan_dev with every image's own optimal Huffman tables; tables = DeviceBuffer of
         len(jobs) * 4 * JPEG_TABLE_BYTES bytes (per image DC0, AC0, DC1, AC1).  Asynchronous on `slot`."""
-        if tables is not None and tables.nbytes < 4 * JPEG_TABLE_BYTES * len(jobs):
-            raise ValueError("tables buffer below 4 x 272 bytes per job")
-        arr = self._jpeg_jobs(jobs)
-        _check(self.L.gs360_jpeg_scan_opt_u8(self.handle, arr, len(jobs), int(quality), int(restart), lengths.ptr,
-                                             tables.ptr if tables is not None else None, slot), self.L)
+        self._jpeg_scan(self.L.gs360_jpeg_scan_opt_u8, jobs, (quality, restart), lengths, (tables,), slot)
 
     def jpeg_scan_sub_dev(self, jobs, lengths, tables=None, quality=100, restart=8, subsampling=JPEG_444, slot=0):
         """gs360_jpeg_scan_sub_u8: jpeg_scan_dev (tables None: the Annex K tables) or jpeg_scan_opt_dev (tables = DeviceBuffer of
         len(jobs) * 4 * JPEG_TABLE_BYTES bytes) with the chroma subsampling JPEG_444 or JPEG_420.  Asynchronous on `slot`."""
-        if tables is not None and tables.nbytes < 4 * JPEG_TABLE_BYTES * len(jobs):
-            raise ValueError("tables buffer below 4 x 272 bytes per job")
-        arr = self._jpeg_jobs(jobs)
-        _check(self.L.gs360_jpeg_scan_sub_u8(self.handle, arr, len(jobs), int(quality), int(restart), int(subsampling), lengths.ptr,
-                                             tables.ptr if tables is not None else None, slot), self.L)
+        self._jpeg_scan(self.L.gs360_jpeg_scan_sub_u8, jobs, (quality, restart, subsampling), lengths, (tables,), slot)
 
     def jpeg_huff_tables_dev(self, hist, n, tables, slot=0):
         """gs360_jpeg_huff_tables: hist = DeviceBuffer of n * 256 uint32 symbol counts -> tables = DeviceBuffer of n * JPEG_TABLE_BYTES

@@ -28,18 +28,7 @@ from .fisheye import SensorCalibration, UndistortTables
 INTERPOLATIONS = {"nearest": 0, "linear": 1, "cubic": 2, "lanczos4": 4}   # cv2.INTER_* values (DF:59-64)
 
 
-_JPEG_RESTART = 8                       # MCUs per restart interval of the device JPEG encoder (the engine's constant)
-
-
-def jpeg_mode_from_env():
-    """-> None (the host codecs write the views) or the device encoder's Huffman mode.  GS360_JPEG_ENCODER = host (default) | device and
-    GS360_JPEG_HUFFMAN = standard (default: the Annex K tables, what cv2 and Pillow write for this tool) | optimal, as in the engine."""
-    if os.environ.get("GS360_JPEG_ENCODER", "host") != "device":
-        return None
-    huffman = os.environ.get("GS360_JPEG_HUFFMAN", "standard")
-    if huffman not in jpegenc.HUFFMAN_MODES:
-        raise ValueError(f"GS360_JPEG_HUFFMAN must be standard or optimal (got {huffman!r})")
-    return huffman
+jpeg_mode_from_env = jpegenc.mode_from_env      # the CLI's name for it: read once per run
 
 
 def engine_interpolation(flag: int) -> int:
@@ -101,7 +90,7 @@ class PairRenderer:
         quality, huffman = jpeg
         with self.ctx.slot_locks[0]:
             files = jpegenc.encode_buffers(self.ctx, [(b, h, w, c) for b, (h, w, c) in zip(bufs, shapes)], quality=int(quality),
-                                           restart=_JPEG_RESTART, slot=0, huffman=huffman, subsampling="4:2:0", raw_capacity=True)
+                                           restart=jpegenc.RESTART, slot=0, huffman=huffman, subsampling="4:2:0", raw_capacity=True)
         self._stats["jpeg_device_images"] += len(files)
         self._stats["jpeg_device_bytes"] += sum(len(f) for f in files)
         return dict(zip(keys, files))

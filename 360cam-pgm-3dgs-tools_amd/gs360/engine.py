@@ -14,8 +14,8 @@ launch, queues all device->pinned-host copies on the same stream and synchronise
 own view in its own thread (the encoders are the end-to-end bound, scripts/bench_cli_e2e.py).
 
 GS360_JPEG_ENCODER=device moves that last step onto the GPU for 8-bit .jpg views: the batch's rendered views are entropy-coded where
-they are (gs360/jpegenc.py, one gs360_jpeg_scan_u8 call on the launch's stream; with GS360_JPEG_HUFFMAN=optimal one
-gs360_jpeg_scan_opt_u8 call, which builds every view's own Huffman tables first), only the scans cross PCIe, and a job writes
+they are (gs360/jpegenc.py, one gs360_jpeg_scan_sub_u8 call on the launch's stream; with GS360_JPEG_HUFFMAN=optimal it builds
+every view's own Huffman tables first), only the scans cross PCIe, and a job writes
 header + scan + EOI with a plain file write.  The default, `host`, is the path above, unchanged.
 
 GS360_JPEG_DECODER=device does the same for the input side (gs360/jpegdec.py, JPD-SPEC v1): a baseline .jpg / .jpeg still is not
@@ -42,7 +42,6 @@ _PREFETCH_FRAMES = int(os.environ.get("GS360_PREFETCH_FRAMES", "8"))      # stil
 _PREFETCH_THREADS = int(os.environ.get("GS360_PREFETCH_THREADS", "4"))    # decoder threads of the read-ahead
 _STALE_RUN_S = float(os.environ.get("GS360_STALE_RUN_S", "30"))            # an earlier run's untouched sources are dropped by the next announce() after this long
 _RECENT_SOURCES = 512                   # sources whose device is remembered after their record is gone (bounded)
-_JPEG_RESTART = 8                       # MCUs per restart interval of the device JPEG encoder (JPG-SPEC v1's default)
 
 
 class _JpegScan:
@@ -353,63 +352,34 @@ class Engine:
         | device and GS360_JPEG_HUFFMAN = standard (default: the Annex K tables) | optimal (every view's own tables, the reference's
         `-huffman optimal`; only meaningful with `device`), read once per job; the device encoder takes the .jpg / .jpeg views nobody
         wants back as arrays."""
-        if want_array or os.environ.get("GS360_JPEG_ENCODER", "host") != "device":
+        if want_array or pathlib.Path(str(job.dst)).suffix.lower() not in (".jpg", ".jpeg"):
             return None
-        if pathlib.Path(str(job.dst)).suffix.lower() not in (".jpg", ".jpeg"):
-            return None
-        huffman = os.environ.get("GS360_JPEG_HUFFMAN", "standard")
-        if huffman not in jpegenc.HUFFMAN_MODES:
-            raise ValueError(f"GS360_JPEG_HUFFMAN must be standard or optimal (got {huffman!r})")
-        return jpegenc.quality_for(job.jpeg_q), huffman
+        huffman = jpegenc.mode_from_env()
+        return None if huffman is None else (jpegenc.quality_for(job.jpeg_q), huffman)
 
-    def _encode_views(self, st, ctx, slot, d_out, h_out, sizes, shapes, C, mode):
-        """(slot lock held, the views' launch queued on `slot`) one gs360_jpeg_scan_u8 call over the rendered views (mode = (quality,
-        "standard")) or one gs360_jpeg_scan_opt_u8 call ((quality, "optimal"): the views' own Huffman tables come back with the lengths,
-        1 088 bytes a view); only the scans' bytes come back, into the views' pinned blocks.  A scan is given the view's raw size; one
-        that needs more (noise at quality 100) is coded again, in the same mode, into a buffer of the bound.  -> [_JpegScan]; h_out[i]
-        is replaced where a larger block was needed."""
+    def _encode_views(self, st, ctx, slot, d_out, h_out, shapes, C, mode):
+        """(slot lock held, the views' launch queued on `slot`) jpegenc.scan_items over the rendered views with the device pool as its
+        allocator: one scan call (mode = (quality, Huffman mode)), a scan is given the view's raw size and one that needs more (noise
+        at quality 100) is coded again into a buffer of the bound.  Only the scans' bytes come back, into the views' pinned blocks.
+        -> [_JpegScan]; h_out[i] is replaced where the scan is longer than the block."""
         quality, huffman = mode
-        optimal = huffman == "optimal"
-        n = len(sizes)
-        tb = 4 * jpegenc.TABLE_BYTES
-        d_scan = [st.take(st.dev_pool, nb, ctx.alloc) for nb in sizes]
-        d_len = st.take(st.dev_pool, 8 * capi.MAX_VIEWS * capi.MAX_FRAMES, ctx.alloc)
-        d_tab = st.take(st.dev_pool, tb * capi.MAX_VIEWS * capi.MAX_FRAMES, ctx.alloc) if optimal else None
-        tables = [None] * n
-
-        def scan(jobs):
-            if optimal:
-                ctx.jpeg_scan_opt_dev(jobs, d_len, d_tab, quality=quality, restart=_JPEG_RESTART, slot=slot)
-                tabs = ctx.download(d_tab, (len(jobs), tb), np.uint8, slot)
-                return [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)], [t.tobytes() for t in tabs]
-            ctx.jpeg_scan_dev(jobs, d_len, quality=quality, restart=_JPEG_RESTART, slot=slot)
-            return [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)], [None] * len(jobs)
+        scans = jpegenc.scan_items(ctx, [(d, h, w, C) for d, (h, w) in zip(d_out, shapes)], lambda nb: st.take(st.dev_pool, nb, ctx.alloc),
+                                   lambda b: st.give(st.dev_pool, b), quality, jpegenc.RESTART, slot, huffman)
         try:
-            if 8 * n > d_len.nbytes:
-                raise capi.Gs360Error(-1, "too many views in one batch for the device JPEG encoder")
-            lengths, tables = scan([(d, h, w, C, 0, o, nb) for d, (h, w), o, nb in zip(d_out, shapes, d_scan, sizes)])
-            for i, length in enumerate(lengths):
-                if length != capi.JPEG_OVERFLOW:
-                    continue
-                h, w = shapes[i]
-                bound = jpegenc.scan_bound(h, w, C, _JPEG_RESTART)
-                st.give(st.dev_pool, d_scan[i])
-                d_scan[i] = st.take(st.dev_pool, bound, ctx.alloc)
-                st.give(st.pin_pool, h_out[i])
-                h_out[i] = st.take(st.pin_pool, bound, ctx.pinned)
-                (lengths[i],), (tables[i],) = scan([(d_out[i], h, w, C, 0, d_scan[i], bound)])
-                if lengths[i] == capi.JPEG_OVERFLOW:
-                    raise capi.Gs360Error(-2, "a JPEG scan exceeded its bound")
             L = ctx.L
-            for d, hb, length in zip(d_scan, h_out, lengths):
-                capi._check(L.gs360_download(ctx.handle, hb.ptr, d.ptr, length, slot), L)
+            for i, (d, length, _tab) in enumerate(scans):
+                if length > h_out[i].nbytes:
+                    larger = st.take(st.pin_pool, d.nbytes, ctx.pinned)
+                    st.give(st.pin_pool, h_out[i])
+                    h_out[i] = larger
+                capi._check(L.gs360_download(ctx.handle, h_out[i].ptr, d.ptr, length, slot), L)
             ctx.sync(slot)
         finally:
-            for d in d_scan + [d_len] + ([d_tab] if optimal else []):
+            for d, _length, _tab in scans:
                 st.give(st.dev_pool, d)
         out = []
-        for hb, length, (h, w), tab in zip(h_out, lengths, shapes, tables):
-            head = jpegenc.header(h, w, C, quality, _JPEG_RESTART, tab)
+        for hb, (_d, length, tab), (h, w) in zip(h_out, scans, shapes):
+            head = jpegenc.header(h, w, C, quality, jpegenc.RESTART, tab)
             out.append(_JpegScan(head, np.frombuffer(hb.view, dtype=np.uint8, count=length)))
             with st.pool_lock:
                 st.stats["jpeg_device_images"] += 1
@@ -438,7 +408,7 @@ class Engine:
             with ctx.slot_locks[slot]:
                 ctx.equirect_views_dev(bufs, W, H, C, views, d_out, slot=slot, interp=interp, flags=flags, dtype=dtype)
                 if encode:
-                    scans = self._encode_views(st, ctx, slot, d_out, h_out, sizes, [(v.height, v.width) for v in views] * len(bufs), C, jpeg)
+                    scans = self._encode_views(st, ctx, slot, d_out, h_out, [(v.height, v.width) for v in views] * len(bufs), C, jpeg)
                 else:
                     for d, hb, n in zip(d_out, h_out, sizes):
                         capi._check(L.gs360_download(ctx.handle, hb.ptr, d.ptr, n, slot), L)

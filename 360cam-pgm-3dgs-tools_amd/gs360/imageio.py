@@ -16,6 +16,8 @@ import zlib
 
 import numpy as np
 
+from . import jpegenc
+
 try:  # Pillow is present in the ROCm image but is not a hard dependency
     from PIL import Image
     Image.MAX_IMAGE_PIXELS = None
@@ -348,8 +350,7 @@ def write_image(path, arr: np.ndarray, jpeg_q: int = None) -> None:
         if ext in (".jpg", ".jpeg"):
             if mode == "RGBA":
                 im = im.convert("RGB")
-            quality = 95 if (jpeg_q is not None and jpeg_q >= 2) else 100
-            im.save(path, "JPEG", quality=quality, subsampling=0, optimize=_JPEG_OPTIMIZE)
+            im.save(path, "JPEG", quality=jpegenc.quality_for(jpeg_q), subsampling=0, optimize=_JPEG_OPTIMIZE)
         elif ext == ".png":
             im.save(path, "PNG", compress_level=3)
         elif ext in (".tif", ".tiff"):

@@ -6,6 +6,7 @@ huffman="optimal" the device builds every image's own tables (gs360_jpeg_scan_op
 header's DHT segments carry those.  It stands in for the reference's image writer at PC:327-338 (ffmpeg's mjpeg encoder behind `-q:v`), which the host path leaves to Pillow.
 """
 import ctypes as ct
+import os
 
 import numpy as np
 
@@ -58,6 +59,19 @@ def _segment(marker, payload):
 TABLE_BYTES = 272            # GS360_JPEG_TABLE_BYTES: 16 BITS + up to 256 HUFFVAL, zero padded
 HUFFMAN_MODES = ("standard", "optimal")
 SUBSAMPLINGS = {"4:4:4": capi.JPEG_444, "4:2:0": capi.JPEG_420}      # -> GS360_JPEG_444 / GS360_JPEG_420 (Pillow's numbers)
+RESTART = 8                  # MCUs per restart interval the engine and the dual-fisheye renderer ask for (JPG-SPEC v1's default)
+
+
+def mode_from_env():
+    """-> None (the host codecs write the views) or the device encoder's Huffman mode.  GS360_JPEG_ENCODER = host (default) | device and
+    GS360_JPEG_HUFFMAN = standard (default: the Annex K tables) | optimal (every image's own tables, the reference's `-huffman
+    optimal`; only meaningful with `device`)."""
+    if os.environ.get("GS360_JPEG_ENCODER", "host") != "device":
+        return None
+    huffman = os.environ.get("GS360_JPEG_HUFFMAN", "standard")
+    if huffman not in HUFFMAN_MODES:
+        raise ValueError(f"GS360_JPEG_HUFFMAN must be standard or optimal (got {huffman!r})")
+    return huffman
 
 
 def _subsampling(name):
@@ -109,11 +123,14 @@ def scan_bound(H, W, C, restart=8, subsampling="4:4:4"):
     return int(n.value)
 
 
-def encode_buffers(ctx, items, quality=100, restart=8, slot=0, huffman="standard", subsampling="4:4:4", raw_capacity=True):
-    """(the caller holds `slot`) items: [(DeviceBuffer, H, W, C)] tight 8-bit device images -> [bytes], one whole JFIF file each.  One
-    gs360_jpeg_scan_sub_u8 call on `slot` encodes them all where they are; the lengths, with "optimal" the tables (1 088 bytes an image)
-    and each scan's bytes come back.  raw_capacity: a scan gets the image's raw size and one that needs more (noise at quality 100) is
-    coded again, in the same mode, into a buffer of the bound; otherwise every scan gets the bound at once."""
+def scan_items(ctx, items, take, give, quality=100, restart=RESTART, slot=0, huffman="standard", subsampling="4:4:4", raw_capacity=True):
+    """(the caller holds `slot`) items: [(DeviceBuffer, H, W, C)] tight 8-bit device images -> [(DeviceBuffer holding the scan, its
+    length, its 4 x 272 table bytes or None)].  One gs360_jpeg_scan_sub_u8 call on `slot` encodes them all where they are; the lengths
+    and, with "optimal", the tables (1 088 bytes an image) come back.  raw_capacity: a scan gets the image's raw size and one that
+    needs more (noise at quality 100) is coded again, alone and in the same mode, into a buffer of the bound; otherwise every scan gets
+    the bound at once.  Device memory comes from take(nbytes) and goes back through give(buffer): everything taken but the scan
+    buffers returned is given back before this returns or raises; those are the caller's to give back.  The length and table
+    buffers are taken at 8 and 1 088 bytes an item, so no batch is too large for them."""
     if huffman not in HUFFMAN_MODES:
         raise ValueError("huffman must be 'standard' or 'optimal'")
     sub = _subsampling(subsampling)
@@ -121,11 +138,11 @@ def encode_buffers(ctx, items, quality=100, restart=8, slot=0, huffman="standard
     if not n:
         return []
     optimal = huffman == "optimal"
-    owned = []
+    taken, kept = [], []
 
-    def alloc(nbytes):
-        owned.append(ctx.alloc(nbytes))
-        return owned[-1]
+    def room(nbytes):
+        taken.append(take(nbytes))
+        return taken[-1]
 
     def run(jobs):
         ctx.jpeg_scan_sub_dev(jobs, d_len, d_tab, quality=quality, restart=restart, subsampling=sub, slot=slot)
@@ -133,9 +150,9 @@ def encode_buffers(ctx, items, quality=100, restart=8, slot=0, huffman="standard
         return [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)], [None if t is None else t.tobytes() for t in tabs]
     try:
         caps = [H * W * C if raw_capacity else scan_bound(H, W, C, restart, subsampling) for _b, H, W, C in items]
-        jobs = [(buf, H, W, C, 0, alloc(cap), cap) for (buf, H, W, C), cap in zip(items, caps)]
-        d_len = alloc(8 * n)
-        d_tab = alloc(4 * TABLE_BYTES * n) if optimal else None
+        jobs = [(buf, H, W, C, 0, room(cap), cap) for (buf, H, W, C), cap in zip(items, caps)]
+        d_len = room(8 * n)
+        d_tab = room(4 * TABLE_BYTES * n) if optimal else None
         lengths, tables = run(jobs)
         for i, length in enumerate(lengths):
             if length != capi.JPEG_OVERFLOW:
@@ -144,18 +161,28 @@ def encode_buffers(ctx, items, quality=100, restart=8, slot=0, huffman="standard
             bound = scan_bound(H, W, C, restart, subsampling)
             if bound <= caps[i]:
                 raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
-            jobs[i] = (buf, H, W, C, 0, alloc(bound), bound)
+            jobs[i] = (buf, H, W, C, 0, room(bound), bound)
             (lengths[i],), (tables[i],) = run([jobs[i]])
             if lengths[i] == capi.JPEG_OVERFLOW:
                 raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
-        files = []
-        for (_b, H, W, C), job, length, tab in zip(items, jobs, lengths, tables):
-            body = ctx.download(job[5], (length,), np.uint8, slot).tobytes()
-            files.append(header(H, W, C, quality, restart, tab, subsampling) + body + EOI)
-        return files
+        kept = [job[5] for job in jobs]
+        return list(zip(kept, lengths, tables))
     finally:
-        for b in owned:
-            ctx.free(b)
+        for b in taken:
+            if not any(b is k for k in kept):
+                give(b)
+
+
+def encode_buffers(ctx, items, quality=100, restart=8, slot=0, huffman="standard", subsampling="4:4:4", raw_capacity=True):
+    """(the caller holds `slot`) items: [(DeviceBuffer, H, W, C)] tight 8-bit device images -> [bytes], one whole JFIF file each:
+    scan_items with the context's own allocator, then each scan's bytes come back and get their header and EOI."""
+    scans = scan_items(ctx, items, ctx.alloc, ctx.free, quality, restart, slot, huffman, subsampling, raw_capacity)
+    try:
+        return [header(H, W, C, quality, restart, tab, subsampling) + ctx.download(d, (length,), np.uint8, slot).tobytes() + EOI
+                for (_b, H, W, C), (d, length, tab) in zip(items, scans)]
+    finally:
+        for d, _length, _tab in scans:
+            ctx.free(d)
 
 
 def encode_device(ctx, images, quality=100, restart=8, slot=0, huffman="standard", subsampling="4:4:4"):

@@ -1,5 +1,6 @@
 """The device JPEG scans (gs360_jpeg_scan_u8, csrc/gs360_jpeg.hip) against the NumPy restatement of JPG-SPEC v1 (tests/jpegenc_np.py):
 every scan and every length byte for byte."""
+import collections
 import io
 
 import numpy as np
@@ -9,6 +10,7 @@ import gs360
 from gs360 import jpegenc
 
 import jpegenc_np as ref
+import jpegopt_np as opt
 
 pytestmark = pytest.mark.gpu
 
@@ -125,6 +127,117 @@ def test_encode_device_files_equal_the_restatement_and_decode_in_pillow(ctx):
         assert im.shape == IMAGES[name].shape, name
         err = np.abs(im.astype(int) - IMAGES[name].astype(int)).mean()
         assert err < 6.0, (name, err)                                   # the picture, not noise (quality >= 95)
+
+
+# ---- the re-code path of jpegenc.scan_items under pool allocators, as the engine configures it -----------------------------------
+def _recode_images():
+    """Gray noise, a photo and RGB noise, and a 3 x 3 gray image.  With optimal tables at quality 95 none of the first three needs more than its
+    raw size (restated scans of 803 / 863 / 4513 bytes against 960 / 3072 / 5883), so without a fourth nothing would be coded again in
+    that mode; an image below one block does in every mode (45 to 79 bytes against 9)."""
+    return [ref.noise_image(24, 40, 1), ref.photo_image(32, 32), ref.noise_image(37, 53, 3), ref.noise_image(3, 3, 1)]
+
+
+_RECODE_REF = {}
+
+
+def recode_reference(huffman, quality):
+    """-> ([whole file], {indices whose restated scan is longer than H * W * C}) of _recode_images(), computed once per mode"""
+    key = (huffman, quality)
+    if key not in _RECODE_REF:
+        files, longer = [], set()
+        for i, im in enumerate(_recode_images()):
+            H, W = im.shape[:2]
+            C = 1 if im.ndim == 2 else 3
+            if huffman == "optimal":
+                scan, tables = opt.scan_optimal(im, quality, jpegenc.RESTART)
+                head = opt.header_optimal(H, W, C, quality, jpegenc.RESTART, tables)
+            else:
+                scan, head = ref.scan(im, quality, jpegenc.RESTART), ref.header(H, W, C, quality, jpegenc.RESTART)
+            files.append(head + scan + b"\xff\xd9")
+            if len(scan) > im.size:
+                longer.add(i)
+        _RECODE_REF[key] = (files, longer)
+    return _RECODE_REF[key]
+
+
+class CountingPool:
+    """the engine's device pool in small: free buffers by size, every take and give counted"""
+
+    def __init__(self, ctx):
+        self.ctx, self.free, self.takes, self.gives = ctx, collections.defaultdict(list), 0, 0
+
+    def take(self, nbytes):
+        self.takes += 1
+        return self.free[nbytes].pop() if self.free[nbytes] else self.ctx.alloc(nbytes)
+
+    def give(self, buf):
+        self.gives += 1
+        self.free[buf.nbytes].append(buf)
+
+    def close(self):
+        for bufs in self.free.values():
+            for b in bufs:
+                self.ctx.free(b)
+
+
+@pytest.mark.parametrize("quality", [100, 95])
+@pytest.mark.parametrize("huffman", ["standard", "optimal"])
+def test_scans_past_their_raw_size_are_coded_again_under_pool_allocators(ctx, huffman, quality):
+    """jpegenc.scan_items as Engine._encode_views calls it (4:4:4, jpegenc.RESTART, raw-size first capacities, taking and giving
+    callables over a pool): the files equal the restatement's, exactly the items whose restated scan exceeds H * W * C were coded
+    again, and everything taken but the returned scan buffers went back."""
+    images = _recode_images()
+    wants, longer = recode_reference(huffman, quality)
+    print(f"{huffman} q={quality}: restated scans longer than the raw size: {sorted(longer)} of {len(images)}")
+    assert 0 < len(longer) < len(images)             # both branches run in every parametrisation
+    pool = CountingPool(ctx)
+    srcs = [ctx.to_device(im) for im in images]
+    items = [(d, im.shape[0], im.shape[1], 1 if im.ndim == 2 else 3) for d, im in zip(srcs, images)]
+    try:
+        with ctx.slot_locks[0]:
+            scans = jpegenc.scan_items(ctx, items, pool.take, pool.give, quality, jpegenc.RESTART, 0, huffman)
+        assert pool.takes == pool.gives + len(scans)
+        assert pool.takes == len(images) + (2 if huffman == "optimal" else 1) + len(longer)
+        recoded = {i for i, ((d, _n, _t), im) in enumerate(zip(scans, images)) if d.nbytes != im.size}
+        assert recoded == longer
+        for i, ((d, n, tab), (_s, H, W, C)) in enumerate(zip(scans, items)):
+            assert d.nbytes == (jpegenc.scan_bound(H, W, C, jpegenc.RESTART) if i in longer else H * W * C), i
+            assert (tab is None) == (huffman == "standard"), i
+            got = jpegenc.header(H, W, C, quality, jpegenc.RESTART, tab) + ctx.download(d, (n,), np.uint8).tobytes() + jpegenc.EOI
+            assert got == wants[i], i
+        for d, _n, _t in scans:
+            pool.give(d)
+        assert pool.takes == pool.gives
+    finally:
+        pool.close()
+        for d in srcs:
+            ctx.free(d)
+
+
+@pytest.mark.parametrize("huffman", ["standard", "optimal"])
+def test_the_engine_replaces_the_pinned_block_of_exactly_the_views_coded_again(huffman):
+    """Engine._encode_views itself, without a render: a device state of its own, hand-made view outputs and pinned blocks.  Its views
+    share one channel count, so the RGB images of the set at quality 100 (the noise is coded again, the photo is not)."""
+    from gs360 import engine
+    wants, longer = recode_reference(huffman, 100)
+    pick = [i for i, im in enumerate(_recode_images()) if im.ndim == 3]
+    images = [_recode_images()[i] for i in pick]
+    assert 0 < len(longer & set(pick)) < len(pick)
+    st = engine._DeviceState(0)
+    try:
+        d_out = [st.ctx.to_device(im) for im in images]
+        blocks = [st.ctx.pinned(im.size) for im in images]
+        h_out = list(blocks)
+        with st.ctx.slot_locks[0]:
+            out = engine.Engine._encode_views(None, st, st.ctx, 0, d_out, h_out, [im.shape[:2] for im in images], 3, (100, huffman))
+        for k, i in enumerate(pick):
+            assert bytes(out[k].header) + out[k].scan.tobytes() + jpegenc.EOI == wants[i], i
+            assert (h_out[k] is not blocks[k]) == (i in longer), i
+            assert h_out[k].nbytes >= out[k].scan.size and (h_out[k].nbytes > blocks[k].nbytes) == (i in longer), i
+        assert st.stats["jpeg_device_images"] == len(pick) and st.stats["jpeg_device_bytes"] == sum(len(wants[i]) for i in pick)
+        assert sum(len(v) for v in st.dev_pool.values()) == len(pick) + (2 if huffman == "optimal" else 1) + len(longer & set(pick))
+    finally:
+        st.ctx.close()
 
 
 def test_argument_errors(ctx):

@@ -1,4 +1,4 @@
-"""The device JPEG decoder's bounds for 4:2:2, 4:4:0 and 4:1:1 files, checked on the CPU: tests/tools/jpegsamp_hostcheck.hip steps the
+"""The device JPEG decoder's bounds for 4:2:2, 4:4:0 and 4:1:1 files, checked on the CPU: tests/tools/jpegdec_hostcheck.hip steps the
 kernels' own stage functions (csrc/gs360_jpegdec.hip) lane by lane on the host, built with AddressSanitizer and
 UndefinedBehaviorSanitizer and with every buffer at its exact size, the scratch by the layout of the file's own sampling.  Valid files
 must give Pillow's pixels with status 0; truncated and corrupted scans must give a status (or the restatement's pixels) and, like the
@@ -29,9 +29,9 @@ def program(tmp_path_factory):
         pytest.skip("no hipcc to build the host check with")
     if os.environ.get("LD_PRELOAD"):
         pytest.skip("a preloaded library and a sanitized program do not go together")
-    exe = tmp_path_factory.mktemp("hostcheck") / "jpegsamp_hostcheck"
+    exe = tmp_path_factory.mktemp("hostcheck") / "jpegdec_hostcheck"
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                    "-Xarch_host", "-fno-sanitize-recover=all", "-o", str(exe), str(ROOT / "tests" / "tools" / "jpegsamp_hostcheck.hip")],
+                    "-Xarch_host", "-fno-sanitize-recover=all", "-o", str(exe), str(ROOT / "tests" / "tools" / "jpegdec_hostcheck.hip")],
                    check=True, capture_output=True, timeout=600)
     return exe
 

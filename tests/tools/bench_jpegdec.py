@@ -1,5 +1,5 @@
 """Device JPEG decode (gs360_jpeg_decode_u8, JPD-SPEC v1) against Pillow on the same files, same host, same run: 16 distinct 7680 x 3840
-4:2:0 quality-92 JPEGs of photo-like frames.
+quality-92 JPEGs of photo-like frames, 4:2:0 unless --subsampling (Pillow's numbers and the binding's) says otherwise.
 
   device  one call over the 16 files (scans, tables and segment records uploaded before), HIP events around it, warm, median of
           `--reps` runs, per frame.  The 16 frames' scratch and outputs are some gigabytes, far beyond the caches, so every run reads
@@ -10,7 +10,14 @@
   pillow  np.asarray(Image.open(...)) of the same bytes, one thread, median per frame
   pcie    bytes per frame that cross PCIe each way on the two paths
 
-    python tests/tools/bench_jpegdec.py [--reps 20] [--frames 16] [--width 7680] [--restart 0] [--out FILE]     (prints one JSON object)
+--subsampling 2 (4:2:0, the default), 0 (4:4:4) and 1 (4:2:2) are written by Pillow.  3 (4:4:0) and 4 (4:1:1) are written by the NumPy
+writer of tests/jpegsamp_np.py, which is far too slow for whole 8K frames: it codes eight MCU rows of the first frame, each as one
+restart interval, and every frame is those eight intervals over and over, frame k starting with row k.  Such a file has a restart
+interval of one MCU row whatever --restart says (give a Pillow-written layout --restart = its MCUs per row to compare like with
+like), and its bytes per frame are those of eight rows, repeated.  The result names the layout when it is not the default.
+
+    python tests/tools/bench_jpegdec.py [--subsampling 2] [--reps 20] [--frames 16] [--width 7680] [--restart 0] [--out FILE]
+    (prints one JSON object)
 """
 import argparse
 import io
@@ -42,15 +49,41 @@ def synth(h, w, k=0):
     return img
 
 
-def bench(reps, frames, width, restart):
+WRITTEN = {3: (1, 2), 4: (4, 1)}      # --subsampling -> luma sampling of the layouts Pillow does not write
+
+
+def written_frames(frames, height, width, hs, vs):
+    """-> [file bytes]: see the module docstring"""
+    import jpegsamp_np as samp
+    rows, mw, mh = 8, -(-width // (8 * hs)), -(-height // (8 * vs))
+    z = samp.coefficients(synth(rows * 8 * vs, width), hs, vs, 92)
+    intervals = [samp.scan(z[r * mw:(r + 1) * mw], hs, vs, 0) for r in range(rows)]
+    head = samp.header(height, width, hs, vs, 92, mw)
+    out = []
+    for k in range(frames):
+        body = b"".join(intervals[(k + r) % rows] + (bytes([0xFF, 0xD0 + (r & 7)]) if r + 1 < mh else b"") for r in range(mh))
+        out.append(head + body + b"\xff\xd9")
+    return out
+
+
+def pillow_frames(frames, height, width, subsampling, restart):
     from PIL import Image
-    height = width // 2
-    files = []
+    out = []
     for k in range(frames):
         b = io.BytesIO()
         kw = {"restart_marker_blocks": restart} if restart else {}
-        Image.fromarray(synth(height, width, k)).save(b, "JPEG", quality=92, subsampling=2, **kw)
-        files.append(b.getvalue())
+        Image.fromarray(synth(height, width, k)).save(b, "JPEG", quality=92, subsampling=subsampling, **kw)
+        out.append(b.getvalue())
+    return out
+
+
+def bench(reps, frames, width, restart, subsampling=2):
+    from PIL import Image
+    height = width // 2
+    if subsampling in WRITTEN:
+        files = written_frames(frames, height, width, *WRITTEN[subsampling])
+    else:
+        files = pillow_frames(frames, height, width, subsampling, restart)
     pillow_ms = []
     for data in files:
         t0 = time.perf_counter()
@@ -81,7 +114,8 @@ def bench(reps, frames, width, restart):
             batch.close()
     raw = height * width * 3
     return {
-        "frames": frames, "width": width, "height": height, "restart": restart, "reps": reps,
+        **({} if subsampling == 2 else {"subsampling": subsampling}),
+        "frames": frames, "width": width, "height": height, "restart": d.restart if subsampling in WRITTEN else restart, "reps": reps,
         "file_bytes_per_frame": int(np.mean([len(f) for f in files])),
         "device_ms_per_frame": statistics.median(ms) / frames, "device_ms_per_call_min": min(ms), "device_ms_per_call_max": max(ms),
         "chain_rounds": rounds, "last_frame_equals_pillow": equal,
@@ -94,13 +128,14 @@ def bench(reps, frames, width, restart):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--subsampling", type=int, default=2, choices=(0, 1, 2, 3, 4))
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--width", type=int, default=7680)
     ap.add_argument("--restart", type=int, default=0)
     ap.add_argument("--out")
     a = ap.parse_args()
-    res = bench(a.reps, a.frames, a.width, a.restart)
+    res = bench(a.reps, a.frames, a.width, a.restart, a.subsampling)
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -1,10 +1,12 @@
-// jpegdec_hostcheck.hip -- the device JPEG decoder's stages (csrc/gs360_jpegdec.hip, JPD-SPEC v1) stepped lane by lane on the host.
-// A CPU-only stand-alone program: it includes the kernels' source, calls the host-callable stage functions in the order and with the
-// lane numbers the kernels use (barriers become loop boundaries), and allocates the scan, the segment table and the scratch at their
-// exact sizes, so that a build with -fsanitize=address,undefined (tests/test_jpegdec_hostcheck.py) turns any read or write outside a
-// buffer into a failure.  The DC scan kernels are stood in for by a serial sum.  Usage: jpegdec_hostcheck IN.bin OUT.bin, IN = 16
-// int32 (H, W, C, subsampling, restart, scan bytes, segments, subsequences, 0, 0, 0, row padding, 0...), 12 table selectors, the
-// scan, the segment records, 4 x 272 Huffman and 4 x 64 quantiser bytes; OUT = the image rows; prints the status.
+// jpegdec_hostcheck.hip -- the device JPEG decoder's stages (csrc/gs360_jpegdec.hip, JPD-SPEC v1) stepped lane by lane on the host,
+// for every chroma layout it takes (gray, 4:4:4, 4:2:2, 4:2:0, 4:4:0, 4:1:1).  A CPU-only stand-alone program: it includes the
+// kernels' source, calls the host-callable stage functions in the order and with the lane numbers the kernels use (barriers become
+// loop boundaries), and allocates the scan, the segment table, the output and the scratch (by the layout of the job's own sampling,
+// jd_layout) at their exact sizes, so that a build with -fsanitize=address,undefined (tests/test_jpegdec_hostcheck.py,
+// tests/test_jpegsamp_hostcheck.py) turns any read or write outside a buffer into a failure.  The DC scan kernels are stood in for by
+// a serial sum over jd_dc_seq's sequences.  Usage: jpegdec_hostcheck IN.bin OUT.bin, IN = 16 int32 (H, W, C, subsampling, restart,
+// scan bytes, segments, subsequences, 0, 0, 0, row padding, 0...), 12 table selectors, the scan, the segment records, 4 x 272 Huffman
+// and 4 x 64 quantiser bytes; OUT = the image rows; prints the status and the sampling.
 #include "../../360cam-pgm-3dgs-tools_amd/csrc/gs360_jpegdec.hip"
 #include <cstdio>
 #include <vector>
@@ -21,7 +23,7 @@ int main(int argc, char** argv) {
     if (fread(sel, 1, 12, f) != 12 || fread(scan.data(), 1, scan_len, f) != (size_t)scan_len ||
         fread(seg.data(), 4, n_seg * 4, f) != (size_t)n_seg * 4 || fread(meta.data(), 1, meta.size(), f) != meta.size()) return 2;
     fclose(f);
-    JdLayout l = jd_layout(H, W, C, sub == GS360_JPEG_420, n_sub);
+    JdLayout l = jd_layout(H, W, C, sub, n_sub);
     std::vector<uint8_t> scratch(l.total);   // exact size: the sanitizer guards its end
     size_t stride = (size_t)W * C + pad;
     std::vector<uint8_t> out(stride * H, 0xA5);
@@ -33,6 +35,7 @@ int main(int argc, char** argv) {
     JdJob J;
     memset(&J, 0, sizeof(J));
     jd_fill_job(J, job);                     // the set-up of gs360_jpeg_decode_u8
+    if (J.lay.total != l.total || J.lay.blocks != (int64_t)J.mw * J.mh * J.bpm) return 3;
     memset(scratch.data() + l.coef, 0, l.blocks * 128);
     memset(scratch.data() + l.dc, 0, l.blocks * 4);
     JdTables* T = new JdTables;
@@ -137,7 +140,7 @@ int main(int argc, char** argv) {
     uint32_t status = hdr->err ? 1u : (hdr->ok != J.n_seg ? 2u : 0u);
     delete T;
     delete TL;
-    printf("status %u rounds %u wg_rounds %d n_sub %u n_wg %d\n", status, rounds, max_rounds_wg, J.n_sub, J.lay.n_wg);
+    printf("status %u rounds %u wg_rounds %d n_sub %u n_wg %d sampling %dx%d bpm %d\n", status, rounds, max_rounds_wg, J.n_sub, J.lay.n_wg, J.hs, J.vs, J.bpm);
     f = fopen(argv[2], "wb"); fwrite(out.data(), 1, out.size(), f); fclose(f);
     return 0;
 }
