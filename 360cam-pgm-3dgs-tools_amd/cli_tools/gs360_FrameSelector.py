@@ -10,13 +10,16 @@ the `Done:` block), its CSV and its moves into <in_dir>/blur.
 What changed underneath: every per-pixel pass runs on the GPU through libgs360hip.so.  `--score_backend ffmpeg` (the default)
 spawns no ffmpeg: it is the edge pass gs360_frame_edge_u8 (FS-EDGE v1); `--score_backend opencv` is
 gs360_frame_stats_u8 (+ gs360_frame_fft_energy with `--fft device`); the optical flow is gs360_frame_flow_u8.  Frames are decoded
-on a thread pool (`--workers`, default: gs360.framescore's own, at most 16) that runs ahead of launches of 16 frames.  The
+on a thread pool (`--workers`, default: gs360.framescore's own, at most 16) that runs ahead of launches of 16 frames; with
+GS360_JPEG_DECODER=device baseline .jpg / .jpeg frames are decoded on the GPU instead, once for the scoring and the flow pass
+(gs360/framesource.py), and one more [INFO] line counts them.  The
 selection itself is gs360/frameselect.py.  8-bit sources only: a 16-bit or float image ends the run with one [ERR] line and exit
 code 1 before anything is moved.  The reference's memory-pressure limiter and its stdin listener are left out.
 
 main(argv, score_records=..., flow_magnitudes=...) replaces the two GPU seams, for tests that replay recorded scores.
 """
 import argparse
+import contextlib
 import csv
 import math
 import os
@@ -28,7 +31,7 @@ _HERE = pathlib.Path(__file__).resolve().parent
 if str(_HERE.parent) not in sys.path:
     sys.path.insert(0, str(_HERE.parent))
 
-from gs360 import frameflow, framescore  # noqa: E402
+from gs360 import frameflow, framescore, framesource, jpegdec  # noqa: E402
 from gs360 import frameselect as fsel  # noqa: E402
 from gs360.capi import Gs360Error  # noqa: E402
 
@@ -157,6 +160,11 @@ def main(argv=None, *, score_records=None, flow_magnitudes=None):
     if args.reselect_csv:
         args.dry_run = True
     scoring_needed = not args.apply_csv and not args.reselect_csv
+    try:
+        device_decoder = jpegdec.device_decoder_enabled()      # GS360_JPEG_DECODER
+    except ValueError as exc:
+        print(f"[ERR] {exc}")
+        sys.exit(1)
     cancel = cancel_event
     try:
         signal.signal(signal.SIGINT, _handle_sigint)
@@ -220,49 +228,55 @@ def main(argv=None, *, score_records=None, flow_magnitudes=None):
     pool = args.workers if manual else None
     print("[INFO] workers: {} (mode={}, auto={})".format(workers, "manual" if manual else "auto", auto_workers))
 
-    if args.apply_csv:
-        apply_csv_path = _resolve(args.in_dir, args.apply_csv)
-        selection_flags = _load_csv("Selection", apply_csv_path, records, scores, brightness_mean_arr, group_score_arr, flow_mag_arr)
-        final_selected = {i for i, flag in enumerate(selection_flags) if flag == 1 and exists(records[i])}
-        initial_selected = set(final_selected)
-        existing_indices = [i for i in range(total) if exists(records[i])]
-    elif args.reselect_csv:
-        reselect_csv_path = _resolve(args.in_dir, args.reselect_csv)
-        selection_flags = _load_csv("Metrics", reselect_csv_path, records, scores, brightness_mean_arr, group_score_arr, flow_mag_arr)
-        existing_indices = [i for i in range(total) if exists(records[i])]
-        if compute_optical_flow:
-            reused_flow = fsel.csv_has_numeric_flow_motion_values(reselect_csv_path)
-            if reused_flow:
-                print("[INFO] reselect CSV already contains numeric flow_motion values; reusing them without recomputation.")
-    else:
-        state = {"done": 0, "pct": -1}
+    # GS360_JPEG_DECODER=device: the gray planes decoded for scoring stay in device memory for the flow pass (gs360/framesource.py)
+    with framesource.open_store() if device_decoder else contextlib.nullcontext():
+        if args.apply_csv:
+            apply_csv_path = _resolve(args.in_dir, args.apply_csv)
+            selection_flags = _load_csv("Selection", apply_csv_path, records, scores, brightness_mean_arr, group_score_arr, flow_mag_arr)
+            final_selected = {i for i, flag in enumerate(selection_flags) if flag == 1 and exists(records[i])}
+            initial_selected = set(final_selected)
+            existing_indices = [i for i in range(total) if exists(records[i])]
+        elif args.reselect_csv:
+            reselect_csv_path = _resolve(args.in_dir, args.reselect_csv)
+            selection_flags = _load_csv("Metrics", reselect_csv_path, records, scores, brightness_mean_arr, group_score_arr, flow_mag_arr)
+            existing_indices = [i for i in range(total) if exists(records[i])]
+            if compute_optical_flow:
+                reused_flow = fsel.csv_has_numeric_flow_motion_values(reselect_csv_path)
+                if reused_flow:
+                    print("[INFO] reselect CSV already contains numeric flow_motion values; reusing them without recomputation.")
+        else:
+            state = {"done": 0, "pct": -1}
 
-        def tick(count):
-            if cancel.is_set():
-                raise _Cancelled()
-            while state["done"] < min(count, n):
-                state["done"] += 1
-                state["pct"] = _progress("Scoring", state["done"], n, state["pct"])
-        try:
-            tuples = score_records(records, args.metric, score_crop_ratio, fsel.MAX_LONG, args.augment_motion, args.ignore_highlights,
-                                   args.score_backend, workers=pool, fft=args.fft, progress=tick)
-            tick(n)
-        except (_Cancelled, KeyboardInterrupt):
-            cancel.set()
-            tuples = None
-        except Gs360Error as exc:
-            print(f"[ERR] {exc}")
-            sys.exit(1)
-        if tuples is not None:
-            scores = [t[0] for t in tuples]
-            brightness_mean_arr = [t[3] for t in tuples]
-            brightness_arr = [t[4] for t in tuples]
-    cancelled = cancel.is_set()
-
-    flow_pairs_total = 0
-    if not cancelled and n > 1 and compute_optical_flow and not reused_flow:
-        flow_pairs_total = flow_magnitudes(records, flow_mag_arr, flow_crop_ratio, pool, "Optical flow")
+            def tick(count):
+                if cancel.is_set():
+                    raise _Cancelled()
+                while state["done"] < min(count, n):
+                    state["done"] += 1
+                    state["pct"] = _progress("Scoring", state["done"], n, state["pct"])
+            try:
+                tuples = score_records(records, args.metric, score_crop_ratio, fsel.MAX_LONG, args.augment_motion, args.ignore_highlights,
+                                       args.score_backend, workers=pool, fft=args.fft, progress=tick)
+                tick(n)
+            except (_Cancelled, KeyboardInterrupt):
+                cancel.set()
+                tuples = None
+            except Gs360Error as exc:
+                print(f"[ERR] {exc}")
+                sys.exit(1)
+            if tuples is not None:
+                scores = [t[0] for t in tuples]
+                brightness_mean_arr = [t[3] for t in tuples]
+                brightness_arr = [t[4] for t in tuples]
         cancelled = cancel.is_set()
+
+        flow_pairs_total = 0
+        if not cancelled and n > 1 and compute_optical_flow and not reused_flow:
+            flow_pairs_total = flow_magnitudes(records, flow_mag_arr, flow_crop_ratio, pool, "Optical flow")
+            cancelled = cancel.is_set()
+    if device_decoder:
+        st = framesource.stats()
+        print("[INFO] JPEG decoder: {} frames decoded on the device, {} fallbacks, {} reused".format(
+            st["device_decoded"], st["fallbacks"], st["reused"]))
 
     if not cancelled and args.metric == "hybrid" and tuples is not None:
         scores = framescore.hybrid_scores(tuples)

@@ -294,7 +294,10 @@ int gs360_jpeg_decode_scratch(int H, int W, int C, int subsampling, uint32_t n_s
     return GS360_OK;
 }
 
-int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_jobs, uint32_t* status_dev, int slot) {
+namespace {
+
+// gs360_jpeg_decode_u8 (gray false: H x W x C out) and gs360_jpeg_decode_gray_u8 (gray true: an H x W plane)
+int jpeg_decode(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_jobs, uint32_t* status_dev, bool gray, int slot) {
     if (int rc = check_ctx_slot(c, slot)) return rc;
     if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
     if (n_jobs == 0) return GS360_OK;
@@ -306,7 +309,7 @@ int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_job
         if (j.scan_len < 1 || j.scan_len > (uint32_t)INT32_MAX) return fail(GS360_ERR_ARG, "job %d: scan of %u bytes outside 1..2^31-1", k, j.scan_len);
         if (j.n_segments < 1 || (uint32_t)j.n_segments > j.scan_len) return fail(GS360_ERR_ARG, "job %d: %d segments for %u bytes", k, j.n_segments, j.scan_len);
         if (j.restart_interval < 0 || j.restart_interval > 65535) return fail(GS360_ERR_ARG, "job %d: restart interval %d outside 0..65535", k, j.restart_interval);
-        if (j.out_stride && j.out_stride < (size_t)j.W * j.C) return fail(GS360_ERR_ARG, "job %d: out_stride below a row", k);
+        if (j.out_stride && j.out_stride < (size_t)j.W * (gray ? 1 : j.C)) return fail(GS360_ERR_ARG, "job %d: out_stride below a row", k);
         if ((uintptr_t)j.scratch % 256) return fail(GS360_ERR_ARG, "job %d: scratch is not 256-byte aligned", k);
         if ((uintptr_t)j.segments % 16) return fail(GS360_ERR_ARG, "job %d: segments is not 16-byte aligned", k);
         for (int q = 0; q < j.C; ++q)
@@ -328,7 +331,7 @@ int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_job
         for (int k = 0; k < L.n_jobs; ++k) {
             const gs360_jpeg_dec_job& j = jobs[k0 + k];
             JdJob& J = L.job[k];
-            jd_fill_job(J, j);
+            jd_fill_job(J, j, gray);
             J.wg_base = (int32_t)wgs;
             J.tile_base = (int32_t)tiles;
             wgs += J.lay.n_wg;
@@ -338,7 +341,17 @@ int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_job
         if (wgs > INT32_MAX || tiles > INT32_MAX) return fail(GS360_ERR_ARG, "JPEG batch too large");
         L.total_wg = (int32_t)wgs;
         L.total_tiles = (int32_t)tiles;
-        HIP_TRY(launch_jpeg_decode(L, s));
+        HIP_TRY(launch_jpeg_decode(L, gray, s));
     }
     return GS360_OK;
+}
+
+}  // namespace
+
+int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_jobs, uint32_t* status_dev, int slot) {
+    return jpeg_decode(c, jobs, n_jobs, status_dev, false, slot);
+}
+
+int gs360_jpeg_decode_gray_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_jobs, uint32_t* status_dev, int slot) {
+    return jpeg_decode(c, jobs, n_jobs, status_dev, true, slot);
 }

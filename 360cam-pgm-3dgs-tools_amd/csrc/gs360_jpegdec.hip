@@ -10,7 +10,8 @@
 // (jd_chain_kernel), and that fixed point is the sequential decoder's state at every subsequence boundary, exactly.  The same kernel
 // sums the blocks completed per subsequence, so the second decode pass (jd_write_kernel) knows every lane's first block and writes the
 // coefficients.  DC differences are summed per component within each segment by a three-step segmented scan (jd_dc_kernel /
-// jd_dc_carry_kernel, both over jd_seg_scan), and jd_pixels_kernel turns 64 x 128 pixel tiles of blocks into pixels.
+// jd_dc_carry_kernel, both over jd_seg_scan), and jd_pixels_kernel turns 64 x 128 pixel tiles of blocks into pixels: RGB (or Y) for
+// gs360_jpeg_decode_u8, one byte of FS-SPEC's gray for gs360_jpeg_decode_gray_u8 (its template parameter).
 //
 // Every loop below is bounded by a launch-time size: symbols of a subsequence (each takes at least one bit), subsequences of a
 // workgroup, workgroups of a file, segments (binary search), chunks of a scan.  No workgroup waits for another one.  Every byte
@@ -580,7 +581,12 @@ JD_HD inline void jd_tile_blocks_s(const JdJob& J, JdTile& T, int tx, int ty, in
 //   by two along one axis ("fancy" h2v1 / h1v2): (3 s + the nearer neighbour + 1 (even pixels) or 2 (odd)) >> 2
 //   by two along both (h2v2): that filter down the columns without its shift, then along the rows: + 8 (even) or 7 (odd), >> 4
 //   by four (h4v1): the sample itself
-template <int kHs, int kVs>
+//   by two along x (h2v1, h2v2) of a plane of one or two samples a row: the sample itself on both axes; libjpeg picks its filters
+//   only for planes more than two samples wide
+// kGray: the output is an H x W plane of FS-SPEC's gray, (4899 R + 9617 G + 1868 B + 8192) >> 14 of the pixel the RGB mode stores
+// (gray_of<3> with red = 0, after libjpeg's colour conversion and its clamps; not the file's Y, which differs by rounding); a
+// C = 1 file's byte is its Y sample in both modes
+template <int kHs, int kVs, bool kGray>
 JD_HD inline void jd_tile_pixels_s(const JdJob& J, const JdTile& T, int tx, int ty, int tid) {
     using G = JdChroma<kHs, kVs>;
     const int x = tid & 127, gx = tx * kTileW + x;
@@ -592,7 +598,7 @@ JD_HD inline void jd_tile_pixels_s(const JdJob& J, const JdTile& T, int tx, int 
     for (int i = 0; i < kTileH / 2; ++i) {
         const int y = (tid >> 7) + 2 * i, gy = ty * kTileH + y;
         if (gy >= J.H) break;
-        uint8_t* o = J.out + (size_t)gy * J.stride + (size_t)gx * J.C;
+        uint8_t* o = J.out + (size_t)gy * J.stride + (size_t)gx * (kGray ? 1 : J.C);
         const int Y = T.plane[0][y * kTileW + x];
         if (kHs * kVs == 1 && J.C == 1) {
             o[0] = (uint8_t)Y;
@@ -601,7 +607,10 @@ JD_HD inline void jd_tile_pixels_s(const JdJob& J, const JdTile& T, int tx, int 
         const int cy = gy / kVs, ny = (gy & 1) ? jd_min(cy + 1, ch - 1) : jd_max(cy - 1, 0);
         const int r0 = (cy - y0) * G::pitch, r1 = (ny - y0) * G::pitch;
         int cb, cr;
-        if (kHs == 2 && kVs == 2) {
+        if (kHs == 2 && cw <= 2) {
+            cb = T.plane[1][r0 + lcx];
+            cr = T.plane[2][r0 + lcx];
+        } else if (kHs == 2 && kVs == 2) {
             const int bias = (gx & 1) ? 7 : 8;
             const int sb = 3 * T.plane[1][r0 + lcx] + T.plane[1][r1 + lcx], sbn = 3 * T.plane[1][r0 + lnx] + T.plane[1][r1 + lnx];
             const int sr = 3 * T.plane[2][r0 + lcx] + T.plane[2][r1 + lcx], srn = 3 * T.plane[2][r0 + lnx] + T.plane[2][r1 + lnx];
@@ -620,9 +629,16 @@ JD_HD inline void jd_tile_pixels_s(const JdJob& J, const JdTile& T, int tx, int 
             cr = T.plane[2][r0 + lcx];
         }
         cb -= 128; cr -= 128;
-        o[0] = (uint8_t)jd_clamp8(Y + ((91881 * cr + 32768) >> 16));
-        o[1] = (uint8_t)jd_clamp8(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
-        o[2] = (uint8_t)jd_clamp8(Y + ((116130 * cb + 32768) >> 16));
+        const uint32_t r = jd_clamp8(Y + ((91881 * cr + 32768) >> 16));
+        const uint32_t g = jd_clamp8(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+        const uint32_t b = jd_clamp8(Y + ((116130 * cb + 32768) >> 16));
+        if (kGray) {
+            o[0] = (uint8_t)((4899 * r + 9617 * g + 1868 * b + 8192) >> 14);
+        } else {
+            o[0] = (uint8_t)r;
+            o[1] = (uint8_t)g;
+            o[2] = (uint8_t)b;
+        }
     }
 }
 
@@ -630,10 +646,12 @@ JD_HD inline void jd_tile_pixels_s(const JdJob& J, const JdTile& T, int tx, int 
 JD_HD inline void jd_tile_blocks(const JdJob& J, JdTile& T, int tx, int ty, int tid) {
     jd_with_sampling(J, [&](auto g) { jd_tile_blocks_s<decltype(g)::hs, decltype(g)::vs>(J, T, tx, ty, tid); });
 }
+template <bool kGray = false>
 JD_HD inline void jd_tile_pixels(const JdJob& J, const JdTile& T, int tx, int ty, int tid) {
-    jd_with_sampling(J, [&](auto g) { jd_tile_pixels_s<decltype(g)::hs, decltype(g)::vs>(J, T, tx, ty, tid); });
+    jd_with_sampling(J, [&](auto g) { jd_tile_pixels_s<decltype(g)::hs, decltype(g)::vs, kGray>(J, T, tx, ty, tid); });
 }
 
+template <bool kGray>
 __global__ __launch_bounds__(256) void jd_pixels_kernel(const JdLaunch L) {
     __shared__ JdTile T;
     const JdJob& J = L.job[job_of(L, blockIdx.x, &JdJob::tile_base)];
@@ -643,7 +661,7 @@ __global__ __launch_bounds__(256) void jd_pixels_kernel(const JdLaunch L) {
     jd_with_sampling(J, [&](auto g) {                      // one switch per workgroup: each sampling has its own blocks and pixels code
         jd_tile_blocks_s<decltype(g)::hs, decltype(g)::vs>(J, T, tx, ty, threadIdx.x);
         __syncthreads();
-        jd_tile_pixels_s<decltype(g)::hs, decltype(g)::vs>(J, T, tx, ty, threadIdx.x);
+        jd_tile_pixels_s<decltype(g)::hs, decltype(g)::vs, kGray>(J, T, tx, ty, threadIdx.x);
     });
 }
 
@@ -656,7 +674,7 @@ __global__ void jd_status_kernel(const JdLaunch L) {
 
 }  // namespace
 
-hipError_t launch_jpeg_decode(const JdLaunch& L, hipStream_t s) {
+hipError_t launch_jpeg_decode(const JdLaunch& L, bool gray, hipStream_t s) {
     for (int k = 0; k < L.n_jobs; ++k) {
         const JdJob& J = L.job[k];
         if (hipError_t e = hipMemsetAsync(J.scratch + J.lay.coef, 0, (size_t)J.lay.blocks * 128, s)) return e;
@@ -668,7 +686,8 @@ hipError_t launch_jpeg_decode(const JdLaunch& L, hipStream_t s) {
     hipLaunchKernelGGL(jd_dc_kernel<false>, dim3(L.max_dc_chunks, L.n_jobs * 3), dim3(256), 0, s, L);
     hipLaunchKernelGGL(jd_dc_carry_kernel, dim3(L.n_jobs * 3), dim3(256), 0, s, L);
     hipLaunchKernelGGL(jd_dc_kernel<true>, dim3(L.max_dc_chunks, L.n_jobs * 3), dim3(256), 0, s, L);
-    hipLaunchKernelGGL(jd_pixels_kernel, dim3(L.total_tiles), dim3(256), 0, s, L);
+    if (gray) hipLaunchKernelGGL(jd_pixels_kernel<true>, dim3(L.total_tiles), dim3(256), 0, s, L);
+    else hipLaunchKernelGGL(jd_pixels_kernel<false>, dim3(L.total_tiles), dim3(256), 0, s, L);
     hipLaunchKernelGGL(jd_status_kernel, dim3(1), dim3(64), 0, s, L);
     return hipGetLastError();
 }

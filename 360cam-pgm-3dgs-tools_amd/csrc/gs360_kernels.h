@@ -462,15 +462,16 @@ struct JdJob {
     uint8_t tq[4], td[4], ta[4];         // per component: quantiser, DC table, AC table
     JdLayout lay;
 };
-// everything of a (checked) job but its places in the batch, wg_base and tile_base
-inline void jd_fill_job(JdJob& J, const gs360_jpeg_dec_job& j) {
+// everything of a (checked) job but its places in the batch, wg_base and tile_base.  gray: `out` is the H x W plane of
+// gs360_jpeg_decode_gray_u8, one byte per pixel
+inline void jd_fill_job(JdJob& J, const gs360_jpeg_dec_job& j, bool gray = false) {
     const JpGrid g = jpeg_grid(j.H, j.W, j.C, j.subsampling);
     J.scan = (const uint8_t*)j.scan;
     J.seg = (const uint4*)j.segments;
     J.meta = j.tables;
     J.scratch = (uint8_t*)j.scratch;
     J.out = (uint8_t*)j.out;
-    J.stride = (int64_t)(j.out_stride ? j.out_stride : (size_t)j.W * j.C);
+    J.stride = (int64_t)(j.out_stride ? j.out_stride : (size_t)j.W * (gray ? 1 : j.C));
     J.n_seg = (uint32_t)j.n_segments;
     J.n_sub = j.n_subseq;
     J.scan_len = j.scan_len;
@@ -487,6 +488,6 @@ struct JdLaunch {
     uint32_t* status;                    // n_jobs
 };
 static_assert(sizeof(JdLaunch) <= 4096, "a launch travels by value as the kernels' argument");
-hipError_t launch_jpeg_decode(const JdLaunch& L, hipStream_t s);
+hipError_t launch_jpeg_decode(const JdLaunch& L, bool gray, hipStream_t s);   // gray: jd_pixels_kernel's output mode
 
 }  // namespace gs360

@@ -35,6 +35,7 @@ EXPORTS = (
     "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
     "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound", "gs360_jpeg_scan_opt_u8", "gs360_jpeg_huff_tables",
     "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub", "gs360_jpeg_decode_u8", "gs360_jpeg_decode_scratch",
+    "gs360_jpeg_decode_gray_u8",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -224,6 +225,7 @@ def load_library(path=None):
         L.gs360_jpeg_scan_sub_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, i, vp, vp, i]
         L.gs360_jpeg_scan_bound_sub.argtypes = [i, i, i, i, i, C.POINTER(C.c_size_t)]
         L.gs360_jpeg_decode_u8.argtypes = [vp, C.POINTER(JpegDecJob), i, vp, i]
+        L.gs360_jpeg_decode_gray_u8.argtypes = [vp, C.POINTER(JpegDecJob), i, vp, i]
         L.gs360_jpeg_decode_scratch.argtypes = [i, i, i, i, u32, C.POINTER(C.c_size_t)]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
@@ -648,6 +650,14 @@ class Context:
             raise ValueError("status buffer below 4 bytes per job")
         arr = (JpegDecJob * max(len(jobs), 1))(*jobs)
         _check(self.L.gs360_jpeg_decode_u8(self.handle, arr, len(jobs), status.ptr, slot), self.L)
+
+    def jpeg_decode_gray_dev(self, jobs, status, slot=0):
+        """gs360_jpeg_decode_gray_u8: as jpeg_decode_dev, but every job's `out` is an H x W plane of FS-SPEC's gray (out_stride 0 or at
+        least W).  Asynchronous on `slot`."""
+        if status.nbytes < 4 * len(jobs):
+            raise ValueError("status buffer below 4 bytes per job")
+        arr = (JpegDecJob * max(len(jobs), 1))(*jobs)
+        _check(self.L.gs360_jpeg_decode_gray_u8(self.handle, arr, len(jobs), status.ptr, slot), self.L)
 
     # -- hot path, host buffers (synchronous) -----------------------------------------------
     def equirect_views(self, src, views, slot=0, interp=INTERP_LINEAR, flags=0):

@@ -105,10 +105,13 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
         if shapes[a] == shapes[b] and dev[0] == dev[1]:
             groups.setdefault(shapes[a] + (dev[0],), []).append(k)
             continue
-        if any(dev):
+        # a device frame beside a host frame (a file the device JPEG decoder left to the host): a packed gray plane pairs with the
+        # host frame's gray; any other device frame has no host twin to convert
+        if any(dv and (shapes[f][2] != 1 or frames[f].stride not in (0, shapes[f][1])) for f, dv in zip((a, b), dev)):
             raise ValueError("a pair of device frames must share the channel count")
-        for f in (a, b):
-            gray.setdefault(f, _host_gray(frames[f], red_index))
+        for f, dv in zip((a, b), dev):
+            if not dv:
+                gray.setdefault(f, _host_gray(frames[f], red_index))
         groups.setdefault(shapes[a][:2] + (1, False, "gray"), []).append(k)
     for key, ks in groups.items():
         H, W, Cn = key[:3]
@@ -116,7 +119,7 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
         idx = sorted({f for k in ks for f in pairs[k]})
         local = {f: i for i, f in enumerate(idx)}
         x0, y0, cw, ch, sw, sh = flow_geometry(H, W, crop_ratio)
-        with framescore.device_frames(ctx, [gray[f] if use_gray else frames[f] for f in idx]) as (bufs, stride, alloc):
+        with framescore.device_frames(ctx, [gray.get(f, frames[f]) if use_gray else frames[f] for f in idx]) as (bufs, stride, alloc):
             out = alloc(len(ks) * RECORD_DTYPE.itemsize)
             pbuf = alloc(len(ks) * capi.FLOW_MAX_CORNERS * POINT_DTYPE.itemsize) if with_points else None
             with ctx.slot_locks[0]:
@@ -141,13 +144,15 @@ def flow_arrays(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0):
 
 def _compute_pair_flow_magnitude(prev_path, curr_path, crop_ratio, mask_mode="none"):
     """Drop-in for the reference's _compute_pair_flow_magnitude (FS:1283-1337, Lucas-Kanade) on the GPU."""
-    a = _decode(prev_path)
-    if a is None:
-        return None
-    b = _decode(curr_path)
-    if b is None:
-        return None
-    return flow_arrays(None, [a, b], [(0, 1)], crop_ratio, mask_mode)[0]
+    with framescore._source(lambda p: _decode(p)) as src:
+        read = (lambda p: src.read([p])[0]) if src else _decode
+        a = read(prev_path)
+        if a is None:
+            return None
+        b = read(curr_path)
+        if b is None:
+            return None
+        return flow_arrays(None, [a, b], [(0, 1)], crop_ratio, mask_mode)[0]
 
 
 def _record_exists(record):
@@ -242,21 +247,34 @@ def _compute_flow_magnitudes(records, flow_mag_arr, flow_crop_ratio, workers, la
 
     completed = 0
     last_pct = -1
-    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as ex, framescore._source(decode) as src:
         futs = {}
+        resolved = {}                            # device decoder: record -> its frames, once the decode calls are queued
 
         def submit(chunk):
             for l, r in chunk:
                 for k in (l, r):
                     if k not in futs:
-                        futs[k] = [ex.submit(decode, p) for p in records[k].get("file_paths", [])]
+                        futs[k] = [ex.submit(src.load if src else decode, p) for p in records[k].get("file_paths", [])]
+
+        def frames_of(chunk):
+            if not src:
+                return {k: [f.result() for f in futs[k]] for lr in chunk for k in lr}
+            new = [k for k in dict.fromkeys(k for lr in chunk for k in lr) if k not in resolved]
+            flat = [(k, p, f.result()) for k in new for p, f in zip(records[k].get("file_paths", []), futs[k])]
+            got = src.resolve([p for _, p, _ in flat], [item for _, _, item in flat])    # one run of decode calls for the chunk
+            for k in new:
+                resolved[k] = []
+            for (k, _, _), fr in zip(flat, got):
+                resolved[k].append(fr)
+            return {k: resolved[k] for lr in chunk for k in lr}
         submit(chunks[0])
         for ci, chunk in enumerate(chunks):
             if cancel_event.is_set():
                 break
             if ci + 1 < len(chunks):
                 submit(chunks[ci + 1])           # decode ahead while this chunk runs on the GPU
-            images = {k: [f.result() for f in futs[k]] for lr in chunk for k in lr}
+            images = frames_of(chunk)
             jobs, per, ok = _chunk_values(ctx, records, chunk, images)
             for mode, (frames, _, prs, dest) in jobs.items():
                 for (pos, j), v in zip(dest, flow_arrays(ctx, frames, prs, flow_crop_ratio, mode)):
@@ -272,4 +290,6 @@ def _compute_flow_magnitudes(records, flow_mag_arr, flow_crop_ratio, workers, la
             keep = {k for lr in (chunks[ci + 1] if ci + 1 < len(chunks) else []) for k in lr}
             for k in [k for k in futs if k not in keep]:
                 del futs[k]                      # a record's images live until its last chunk
+                if src:
+                    src.release(resolved.pop(k, []))
     return completed

@@ -14,6 +14,9 @@ is gs360_frame_edge_u8 (FS-EDGE v1) with the branch logic of FS:875-896 here; no
 score_files batch frames GS360_MAX_FRAMES per launch; hybrid_scores is the main
 flow's per-run normalisation of the hybrid features (FS:2363-2392).
 
+The path-based seams decode with imageio (Pillow) on the host; with GS360_JPEG_DECODER=device they read through
+gs360/framesource.py instead, which decodes baseline JPEG files on the GPU into gray planes (DeviceFrames with C = 1).
+
 8-bit sources only: 16-bit and float images raise Gs360Error (GS360_ERR_UNSUPPORTED), as does max_long > 0.
 """
 import collections
@@ -25,7 +28,7 @@ import threading
 
 import numpy as np
 
-from . import capi, imageio
+from . import capi, imageio, jpegdec
 
 HYBRID_LAPVAR_WEIGHT = 0.6        # FS:311-315 (the code's weights; the docstring's 0.2 is not what runs)
 HYBRID_TENENGRAD_WEIGHT = 0.3
@@ -407,6 +410,28 @@ def decode(fp):
     return a
 
 
+def _source(decode_file, keep=False):
+    """The pass's reader as a context: None under GS360_JPEG_DECODER=host (the default; the caller then decodes as ever), else
+    gs360/framesource.py's Reader, which decodes baseline JPEG files on the device into gray DeviceFrames and hands every other file
+    to decode_file.  keep: what it decodes may stay in an open framesource store."""
+    if not jpegdec.device_decoder_enabled():
+        return contextlib.nullcontext()
+    from . import framesource             # (imports this module)
+    return framesource.Reader(default_context(), decode_file, keep=keep)
+
+
+def _host_frames(paths, ex, window):
+    """(index, decode(path)) for every path, in order: decoding runs on the pool `ex`, at most `window` files ahead"""
+    futs = collections.deque()
+    nxt = 0
+    while nxt < len(paths) or futs:
+        while nxt < len(paths) and len(futs) < window:
+            futs.append((nxt, ex.submit(decode, paths[nxt])))
+            nxt += 1
+        k, fut = futs.popleft()
+        yield k, fut.result()
+
+
 def _check_max_long(max_long):
     if max_long and max_long > 0:
         raise capi.Gs360Error(-4, "max_long > 0 is not implemented (the reference CLI runs with MAX_LONG = 0)")
@@ -434,9 +459,7 @@ def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_high
     out = [None] * len(paths)
     workers = workers or min(16, os.cpu_count() or 1)
     window = 2 * capi.MAX_FRAMES
-    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as ex:
-        futs = collections.deque()
-        nxt = 0
+    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as ex, _source(lambda fp: decode(fp), keep=True) as src:
         pending = []                      # (index, image) decoded, not yet scored
         done = [0]
 
@@ -450,16 +473,13 @@ def score_files(paths, metric, crop_ratio, max_long, augment_motion, ignore_high
                 imgs = [a for _, a in pending]
                 res = edge_arrays(ctx, imgs, crop_ratio) if edge else \
                     score_arrays(ctx, imgs, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, fft=fft)
+                if src:
+                    src.release(imgs)
                 for (k, _), r in zip(pending, res):
                     out[k] = r
                 finished(len(pending))
                 pending.clear()
-        while nxt < len(paths) or futs:
-            while nxt < len(paths) and len(futs) < window:
-                futs.append((nxt, ex.submit(decode, paths[nxt])))
-                nxt += 1
-            k, fut = futs.popleft()
-            a = fut.result()
+        for k, a in (src.frames(paths, ex, window) if src else _host_frames(paths, ex, window)):
             if a is None:
                 out[k] = FAILED
                 finished(1)
@@ -477,10 +497,11 @@ def score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_high
     """Drop-in for the reference's score_one_file (FS:902-1044) on the GPU.  fft: as score_arrays."""
     fft = fft_mode(fft)
     _check_max_long(max_long)
-    a = decode(fp)
-    if a is None:
-        return FAILED
-    return score_arrays(None, [a], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, fft=fft)[0]
+    with _source(lambda p: decode(p)) as src:
+        a = src.read([fp])[0] if src else decode(fp)
+        if a is None:
+            return FAILED
+        return score_arrays(None, [a], metric, crop_ratio, augment_motion, ignore_highlights, mask_mode, fft=fft)[0]
 
 
 def score_one_file_ffmpeg(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode="none"):
@@ -489,10 +510,11 @@ def score_one_file_ffmpeg(fp, metric, crop_ratio, max_long, augment_motion, igno
     if mask_mode == "fisheye_circle":
         return score_one_file(fp, metric, crop_ratio, max_long, augment_motion, ignore_highlights, mask_mode=mask_mode)
     _check_max_long(max_long)
-    a = decode(fp)
-    if a is None:
-        return FAILED
-    return edge_arrays(None, [a], crop_ratio)[0]
+    with _source(lambda p: decode(p)) as src:
+        a = src.read([fp])[0] if src else decode(fp)
+        if a is None:
+            return FAILED
+        return edge_arrays(None, [a], crop_ratio)[0]
 
 
 def record_mask_mode(record):

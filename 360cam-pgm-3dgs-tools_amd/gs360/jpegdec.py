@@ -5,6 +5,8 @@ and where the entropy-coded segment and its restart intervals lie.  decode_devic
 (csrc/gs360_jpegdec.hip) decodes the scan with the self-synchronising parallel Huffman scheme, rebuilds the pixels with libjpeg's
 integer arithmetic (islow IDCT, the upsampling of the file's chroma layout, the fixed-point YCbCr -> RGB rows) and leaves an H x W x C uint8 image in
 device memory, byte for byte what Pillow / libjpeg-turbo return for the file.  Whatever parse() refuses (Unsupported) the host decodes.
+With gray=True the call is gs360_jpeg_decode_gray_u8 and the result an H x W plane of FS-SPEC's gray of those pixels, which is all the
+FrameSelector's passes read (gs360/framesource.py).  prepare() is the part of a decode that needs neither a device nor a lock.
 
 Restart markers are found on the host, with vectorised NumPy: the scan's bytes are in host memory anyway before their upload, one
 comparison pass over them costs less than their PCIe copy, and the device then gets every segment's start, length and first
@@ -272,13 +274,31 @@ class Decoded:
         self.buf, self.shape, self.stride, self.status, self.reason = buf, shape, stride, status, reason
 
 
+class Prepared:
+    """The host-only part of one file's decode: its bytes, parse()'s Descriptor, the segment table, the subsequence count and the
+    scratch the device needs.  prepare() makes it without touching a device or a lock, so that a pool thread can; Batch takes it in
+    place of the file's bytes."""
+    __slots__ = ("data", "d", "seg", "n_sub", "nscr")
+
+    def __init__(self, data, d, seg, n_sub, nscr):
+        self.data, self.d, self.seg, self.n_sub, self.nscr = data, d, seg, n_sub, nscr
+
+
+def prepare(data):
+    """data: the bytes of a file -> Prepared, or raises Unsupported(reason) as parse() does"""
+    d = parse(data, samplings=DEVICE_SAMPLINGS)
+    seg, n_sub = segment_table(d)
+    return Prepared(data, d, seg, n_sub, scratch_bytes(d, n_sub))
+
+
 class Batch:
     """The device side of one decode call: per accepted file its scan, segment table and tables uploaded, scratch and output
-    allocated.  run() queues gs360_jpeg_decode_u8 (as often as wanted: the bench times it); close() frees everything but the outputs
-    handed out."""
+    allocated.  datas: per file its bytes, or what prepare() made of them (then only allocations and uploads happen here).  gray: the
+    outputs are H x (W + pad) planes and run() queues gs360_jpeg_decode_gray_u8.  run() queues gs360_jpeg_decode_u8 (as often as
+    wanted: the bench times it); close() frees everything but the outputs handed out."""
 
-    def __init__(self, ctx, datas, slot=0, pad=0, guard=0):
-        self.ctx, self.slot = ctx, slot
+    def __init__(self, ctx, datas, slot=0, pad=0, guard=0, gray=False):
+        self.ctx, self.slot, self.gray = ctx, slot, bool(gray)
         self.refused = {}                # index in datas -> reason
         self.items = []                  # (index in datas, Descriptor, out buffer, scratch buffer, scratch bytes, stride)
         self.jobs, self.owned = [], []
@@ -294,15 +314,14 @@ class Batch:
         sources = []
         for k, data in enumerate(datas):
             try:
-                d = parse(data, samplings=DEVICE_SAMPLINGS)
+                p = data if isinstance(data, Prepared) else prepare(data)
             except Unsupported as exc:
                 self.refused[k] = str(exc)
                 continue
-            seg, n_sub = segment_table(d)
-            scan = np.frombuffer(data, np.uint8, d.scan_len, d.scan_off)
+            d, seg, n_sub, nscr = p.d, p.seg, p.n_sub, p.nscr
+            scan = np.frombuffer(p.data, np.uint8, d.scan_len, d.scan_off)
             meta = np.concatenate([d.huff.reshape(-1), d.quant.reshape(-1)])
-            stride = d.W * d.C + int(pad)
-            nscr = scratch_bytes(d, n_sub)
+            stride = d.W * (1 if self.gray else d.C) + int(pad)
             b_scan, b_seg, b_meta, b_scr, b_out = (self._alloc(n) for n in (scan.nbytes, seg.nbytes, meta.nbytes, nscr + guard, d.H * stride + guard))
             for b, a in ((b_scan, scan), (b_seg, seg), (b_meta, meta)):
                 ctx.upload(b, a, slot, sync=False)
@@ -325,7 +344,7 @@ class Batch:
     def run(self):
         """queues the decode on the slot (asynchronous)"""
         if self.jobs:
-            self.ctx.jpeg_decode_dev(self.jobs, self.d_status, slot=self.slot)
+            (self.ctx.jpeg_decode_gray_dev if self.gray else self.ctx.jpeg_decode_dev)(self.jobs, self.d_status, slot=self.slot)
 
     def status(self):
         """-> [status code per accepted file]; waits for the slot"""
@@ -347,20 +366,21 @@ class Batch:
         self.owned = []
 
 
-def decode_device(ctx, datas, slot=0):
-    """datas: the bytes of JPEG files -> [Decoded], one gs360_jpeg_decode_u8 call on `slot` for all the files parse() accepts.  Only
+def decode_device(ctx, datas, slot=0, gray=False):
+    """datas: the bytes of JPEG files (or prepare()'s results) -> [Decoded], one gs360_jpeg_decode_u8 call on `slot` for all the files
+    parse() accepts; gray: one gs360_jpeg_decode_gray_u8 call, the results are H x W planes of shape (H, W, 1).  Only
     the scans, the tables and the segment records are uploaded.  A file the device path did not take (parse() refused it, or the device
     reports a status != 0) has buf = None: the caller decodes it on the host.  The caller owns the buffers it gets."""
     results = [None] * len(datas)
     with ctx.slot_locks[slot]:
-        batch = Batch(ctx, datas, slot)  # (frees what it allocated if it fails half way)
+        batch = Batch(ctx, datas, slot, gray=gray)  # (frees what it allocated if it fails half way)
         try:
             for k, reason in batch.refused.items():
                 results[k] = Decoded(None, None, 0, -1, reason)
             batch.run()
             for (k, d, b_out, _scr, _n, stride), code in zip(batch.items, batch.status()):
                 buf = batch.release(b_out) if code == 0 else None
-                results[k] = Decoded(buf, (d.H, d.W, d.C), stride, code, "" if code == 0 else "device status %d" % code)
+                results[k] = Decoded(buf, (d.H, d.W, 1 if gray else d.C), stride, code, "" if code == 0 else "device status %d" % code)
         finally:
             batch.close()
     return results

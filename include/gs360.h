@@ -36,7 +36,7 @@ extern "C" {
 /* 2 (round 6): + gs360_ctx_set_option / _get_option / gs360_device_pci_bus_id (added in round 5 without a bump), the table_stage* options; the
  * library no longer reads GS360_RING, GS360_XCD_GROUP, GS360_EQ_PERSIST, GS360_TABLE_PERSIST, GS360_LANCZOS_TABLE, GS360_TABLE_ROWS from
  * the environment (context options of the same names do that: INTEGRATION.md section 2.1).  A binding checks gs360_abi_version() first.
- * Entry points added since (frame statistics, JPEG scans, gs360_jpeg_decode_u8 / gs360_jpeg_decode_scratch) only add symbols and leave
+ * Entry points added since (frame statistics, JPEG scans, gs360_jpeg_decode_u8 / gs360_jpeg_decode_gray_u8 / gs360_jpeg_decode_scratch) only add symbols and leave
  * every existing signature and struct alone, so the number stays. */
 #define GS360_ABI_VERSION 2
 
@@ -532,6 +532,12 @@ typedef struct gs360_jpeg_dec_job {
 } gs360_jpeg_dec_job;
 int gs360_jpeg_decode_u8(gs360_ctx *ctx, const gs360_jpeg_dec_job *jobs, int n_jobs, uint32_t *status_dev, int slot);
 int gs360_jpeg_decode_scratch(int H, int W, int C, int subsampling, uint32_t n_subseq, size_t *bytes);
+/* The same decode with a gray result, for consumers that never look at colour (the FrameSelector's passes): same jobs, scratch,
+ * status codes and argument checks, but `out` is an H x W uint8 plane (out_stride 0 = tight, else at least W).  For a C = 3 job each
+ * byte is (4899 R + 9617 G + 1868 B + 8192) >> 14 of the pixel gs360_jpeg_decode_u8 writes for the same file (FS-SPEC's gray, taken
+ * after libjpeg's colour conversion and its clamps: not the file's Y plane, which differs from it by rounding); for a C = 1 job it is
+ * the Y sample. */
+int gs360_jpeg_decode_gray_u8(gs360_ctx *ctx, const gs360_jpeg_dec_job *jobs, int n_jobs, uint32_t *status_dev, int slot);
 
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
