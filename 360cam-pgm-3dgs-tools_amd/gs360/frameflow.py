@@ -84,7 +84,9 @@ def _host_gray(fr, red_index):
 def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, with_points=False):
     """One gs360_frame_flow record per pair (a structured array of RECORD_DTYPE) for uint8 frames (H x W or H x W x C ndarrays, RGB(A)
     order unless red_index = 2, or framescore.DeviceFrames) and pairs of (prev, curr) indices into frames; a pair of frames of
-    different sizes gets n_corners = -1.  with_points: also the FlowPoint records, len(pairs) x FLOW_MAX_CORNERS (POINT_DTYPE)."""
+    different sizes gets n_corners = -1.  Every DeviceFrame is read with its own row stride: pairs go to the device grouped by
+    shape, kind and stride, and a pair of DeviceFrames of two strides runs on packed copies of both.  with_points: also the
+    FlowPoint records, len(pairs) x FLOW_MAX_CORNERS (POINT_DTYPE)."""
     frames = list(frames)
     pairs = [(int(a), int(b)) for a, b in pairs]
     for a, b in pairs:
@@ -95,15 +97,24 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
     pts = np.zeros((len(pairs), capi.FLOW_MAX_CORNERS), POINT_DTYPE) if with_points else None
     ctx = ctx or framescore.default_context()
     flags = capi.FS_CIRCLE if mask_mode == "fisheye_circle" else 0
-    groups = {}                           # (H, W, C, on device) -> pair positions
+    groups = {}                           # (H, W, C, on device, row stride, which frames) -> pair positions: one device call each
     gray = {}                             # frame index -> host gray, for pairs whose frames differ only in channels
+    packed = {}                           # frame index -> packed host copy, for pairs of device frames of different row strides
     for k, (a, b) in enumerate(pairs):
         if shapes[a][:2] != shapes[b][:2]:
             recs[k]["n_corners"] = -1
             continue
         dev = isinstance(frames[a], framescore.DeviceFrame), isinstance(frames[b], framescore.DeviceFrame)
-        if shapes[a] == shapes[b] and dev[0] == dev[1]:
-            groups.setdefault(shapes[a] + (dev[0],), []).append(k)
+        strides = framescore.row_stride(frames[a]), framescore.row_stride(frames[b])
+        if shapes[a] == shapes[b] and dev[0] == dev[1] and strides[0] == strides[1]:
+            groups.setdefault(shapes[a] + (dev[0], strides[0], "own"), []).append(k)
+            continue
+        if shapes[a] == shapes[b] and dev[0] and dev[1]:
+            # the entry point takes one stride per call: such a pair (no producer makes one today) runs on packed copies
+            for f in (a, b):
+                if f not in packed:
+                    packed[f] = framescore.host_copy(ctx, frames[f])
+            groups.setdefault(shapes[a] + (False, shapes[a][1] * shapes[a][2], "packed"), []).append(k)
             continue
         # a device frame beside a host frame (a file the device JPEG decoder left to the host): a packed gray plane pairs with the
         # host frame's gray; any other device frame has no host twin to convert
@@ -112,14 +123,15 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
         for f, dv in zip((a, b), dev):
             if not dv:
                 gray.setdefault(f, _host_gray(frames[f], red_index))
-        groups.setdefault(shapes[a][:2] + (1, False, "gray"), []).append(k)
+        groups.setdefault(shapes[a][:2] + (1, False, shapes[a][1], "gray"), []).append(k)
     for key, ks in groups.items():
         H, W, Cn = key[:3]
-        use_gray = len(key) == 5
+        use_gray = key[5] == "gray"
         idx = sorted({f for k in ks for f in pairs[k]})
         local = {f: i for i, f in enumerate(idx)}
         x0, y0, cw, ch, sw, sh = flow_geometry(H, W, crop_ratio)
-        with framescore.device_frames(ctx, [gray.get(f, frames[f]) if use_gray else frames[f] for f in idx]) as (bufs, stride, alloc):
+        own = {"own": {}, "gray": gray, "packed": packed}[key[5]]
+        with framescore.device_frames(ctx, [own.get(f, frames[f]) for f in idx]) as (bufs, stride, alloc):
             out = alloc(len(ks) * RECORD_DTYPE.itemsize)
             pbuf = alloc(len(ks) * capi.FLOW_MAX_CORNERS * POINT_DTYPE.itemsize) if with_points else None
             with ctx.slot_locks[0]:

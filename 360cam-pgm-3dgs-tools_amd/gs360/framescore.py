@@ -47,7 +47,9 @@ DEFAULT_FFT = "host"              # where score_* compute the fft term when thei
 FFT_DTYPE = capi.record_dtype(capi.FrameFft)
 EDGE_FIELDS = tuple(n for n, _ in capi.FrameEdge._fields_)
 
-DeviceFrame = collections.namedtuple("DeviceFrame", "buf H W C stride")   # an H x W x C uint8 frame already in device memory
+# An H x W x C uint8 frame already in device memory.  stride: bytes from one row to the next, 0 = packed rows (W * C).  Every frame
+# keeps its own: frames of one shape and different strides never share a launch (the C entry points take one stride per call).
+DeviceFrame = collections.namedtuple("DeviceFrame", "buf H W C stride")
 DeviceFrame.__new__.__defaults__ = (0,)
 
 
@@ -293,22 +295,43 @@ def frame_shape(fr):
     return a.shape
 
 
+def row_stride(fr):
+    """A frame's row stride in bytes, normalised: a DeviceFrame's own (its 0 = packed rows, W * C), a host frame's packed W * C
+    (host frames are uploaded contiguous)."""
+    H, W, Cn = frame_shape(fr)
+    return (int(fr.stride) or W * Cn) if isinstance(fr, DeviceFrame) else W * Cn
+
+
+def host_copy(ctx, fr):
+    """A DeviceFrame's pixels as a packed H x W x C host ndarray: one download of its rows, the padding dropped."""
+    H, W, Cn = frame_shape(fr)
+    stride = row_stride(fr)
+    with ctx.slot_locks[0]:
+        flat = ctx.download(fr.buf, ((H - 1) * stride + W * Cn,), np.uint8)
+    rows = np.lib.stride_tricks.as_strided(flat, (H, W * Cn), (stride, 1))
+    return np.ascontiguousarray(rows).reshape(H, W, Cn)
+
+
 @contextlib.contextmanager
 def device_frames(ctx, frames):
     """Device buffers of one launch's frames: a DeviceFrame's own buffer, a host frame uploaded.  Yields (bufs, stride, alloc):
-    stride is the DeviceFrames' row stride (0 = packed rows), alloc(nbytes) allocates an output buffer.  Whatever was uploaded or
-    allocated is freed on exit."""
+    stride is the row stride all the frames share (0 = packed rows), alloc(nbytes) allocates an output buffer.  Frames of different
+    row strides cannot share a launch: ValueError before anything is uploaded.  Whatever was uploaded or allocated is freed on
+    exit."""
     owned = []
 
     def alloc(nbytes):
         owned.append(ctx.alloc(nbytes))
         return owned[-1]
     try:
+        strides = {row_stride(fr) for fr in frames}
+        if len(strides) > 1:
+            raise ValueError(f"frames of row strides {sorted(strides)} in one launch: group them by stride")
         bufs, stride = [], 0
         for fr in frames:
             if isinstance(fr, DeviceFrame):
                 bufs.append(fr.buf)
-                stride = fr.stride
+                stride = 0 if row_stride(fr) == fr.W * fr.C else row_stride(fr)
             else:
                 owned.append(ctx.to_device(np.ascontiguousarray(fr)))
                 bufs.append(owned[-1])
@@ -319,12 +342,13 @@ def device_frames(ctx, frames):
 
 
 def _batches(frames, shapes):
-    """(i, j) index ranges of one launch each: consecutive frames of one size and one kind, GS360_MAX_FRAMES at most."""
+    """(i, j) index ranges of one launch each: consecutive frames of one size, one kind and one row stride, GS360_MAX_FRAMES at
+    most."""
+    kinds = [(shape, isinstance(fr, DeviceFrame), row_stride(fr)) for fr, shape in zip(frames, shapes)]
     i = 0
     while i < len(frames):
         j = i + 1
-        while j < len(frames) and j - i < capi.MAX_FRAMES and shapes[j] == shapes[i] \
-                and isinstance(frames[j], DeviceFrame) == isinstance(frames[i], DeviceFrame):
+        while j < len(frames) and j - i < capi.MAX_FRAMES and kinds[j] == kinds[i]:
             j += 1
         yield i, j
         i = j
@@ -361,8 +385,8 @@ def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_
 
 def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode="none", red_index=0, fft=None):
     """9-tuples for a sequence of frames: uint8 ndarrays (H x W or H x W x C, RGB(A) order unless red_index = 2) or DeviceFrames
-    already in device memory (decoded video frames, gs360/video.py).  Consecutive frames of one size share a launch of up to
-    GS360_MAX_FRAMES frames.  ctx None = the process's default context.  fft: where the fft / hybrid metrics' FFT runs, "host" or
+    already in device memory (decoded video frames, gs360/video.py).  Consecutive frames of one size, and for DeviceFrames one row
+    stride, share a launch of up to GS360_MAX_FRAMES frames.  ctx None = the process's default context.  fft: where the fft / hybrid metrics' FFT runs, "host" or
     "device" (None = DEFAULT_FFT); with "device" no plane leaves the GPU."""
     fft = fft_mode(fft)
     frames = list(frames)

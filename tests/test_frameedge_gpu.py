@@ -5,6 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import frame_layouts as layouts
 import frameedge_np as enp
 from gs360 import framescore
 
@@ -29,23 +30,16 @@ def _frame(rng, H, W, C, kind):
     return np.ascontiguousarray(np.repeat(g[:, :, None], C, axis=2) ^ (np.arange(C, dtype=np.uint8) * 17))
 
 
-def _run(ctx, frames, band, red_index=0, pad=0):
-    """The records of one call; pad > 0 uploads every frame with `pad` bytes of filler after each row and passes the stride."""
+def _run(ctx, frames, band, red_index=0, pad=0, window=None):
+    """The records of one call; pad > 0 uploads every frame with `pad` bytes of filler after each row and passes the stride,
+    window = (parent_h, parent_w, row, col) places every frame inside a parent image (frame_layouts.upload)."""
     H, W = frames[0].shape[:2]
-    Cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
-    stride = 0
-    if pad:
-        stride = W * Cn + pad
-        rows = [np.full((H, stride), 0xA5, np.uint8) for _ in frames]
-        for r, f in zip(rows, frames):
-            r[:, :W * Cn] = f.reshape(H, W * Cn)
-        bufs = [ctx.to_device(r) for r in rows]
-    else:
-        bufs = [ctx.to_device(f) for f in frames]
+    Cn = layouts.channels(frames[0])
+    objs, stride, bufs = layouts.upload(ctx, frames, pad, window)
     out = ctx.alloc(len(frames) * 24)
     try:
         ctx.memset(out, 0x5A)                          # the call clears the records itself
-        ctx.frame_edge_dev(bufs, H, W, Cn, band, out, red_index=red_index, stride=stride)
+        ctx.frame_edge_dev(objs, H, W, Cn, band, out, red_index=red_index, stride=stride)
         ctx.sync(0)
         recs = ctx.download(out, (len(frames), 3), np.int64)
     finally:
@@ -173,3 +167,36 @@ def test_device_frames_take_the_edge_pass_without_a_round_trip(ctx):
     finally:
         ctx.free(buf)
     assert got == [enp.score(img, 0.8)]
+
+
+@pytest.mark.parametrize("pad", [1, 2, 3])
+def test_maximal_staging_on_odd_strides(ctx, pad):
+    H, W, C = layouts.MAXIMAL
+    layouts.check_maximal_staging(pad)
+    img = _frame(np.random.default_rng(514 + pad), H, W, C, "noise")
+    assert _run(ctx, [img], layouts.MAXIMAL_BAND, pad=pad)[0] == enp.frame_edge(img, *layouts.MAXIMAL_BAND)
+
+
+@pytest.mark.parametrize("C", [1, 3, 4])
+def test_windows_of_a_parent_image(ctx, C):
+    """A 37 x 515 window at row 5 of a 64 x 640 parent: the band and the mirrored halo are the window's own."""
+    H, W, PH, PW, row = 37, 515, 64, 640, 5
+    col = layouts.window_column(9, PW * C, row, C)
+    for kind in ("noise", "ramp"):
+        img = _frame(np.random.default_rng(515 + C), H, W, C, kind)
+        for crop in (0.8, 1.0):
+            band = framescore.edge_band_rows(H, crop)
+            assert _run(ctx, [img], band, window=(PH, PW, row, col))[0] == enp.frame_edge(img, *band), (kind, crop)
+
+
+def test_device_frames_of_three_strides_in_one_call(ctx):
+    """DeviceFrames of one shape stored packed (stride 0 and W*C) and with 8 filler bytes a row: each is read with its own stride."""
+    rng = np.random.default_rng(61)
+    frames = [_frame(rng, 61, 90, 3, ("noise", "ramp", "vstep")[k % 3]) for k in range(6)]
+    dev, bufs = layouts.mixed_strides(ctx, frames)
+    try:
+        got = framescore.edge_arrays(ctx, dev, 0.8)
+    finally:
+        for b in bufs:
+            ctx.free(b)
+    assert got == framescore.edge_arrays(ctx, frames, 0.8) == [enp.score(f, 0.8) for f in frames]

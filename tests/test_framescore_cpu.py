@@ -6,6 +6,7 @@ import pathlib
 import re
 import subprocess
 import tempfile
+import threading
 
 import numpy as np
 import pytest
@@ -13,7 +14,7 @@ import pytest
 import framescore_np as fnp
 import gs360
 from conftest import ROOT
-from gs360 import capi, framescore
+from gs360 import capi, frameflow, framescore
 
 HEADER = (ROOT / "include" / "gs360.h").read_text()
 
@@ -172,6 +173,97 @@ def test_unsupported_sources_fail_before_any_gpu_work():
 def test_unreadable_file_gives_the_reference_failure_tuple(tmp_path):
     assert framescore.score_one_file(str(tmp_path / "missing.png"), "hybrid", 0.8, 0, True, False) == \
         (None, 0.0, 0.0, 0.0, 1.0, None, None, None, 1.0)
+
+
+# ---- DeviceFrames keep their own row stride -------------------------------------------------------------------------------
+class _Buf:
+    def __init__(self, ptr, nbytes):
+        self.ptr, self.nbytes = ptr, nbytes
+
+
+class _RecordingCtx:
+    """A context without a device: it records (pointers, stride) of every frame_*_dev call and answers every download with
+    records of ones (zeros would divide by n = 0 in the finish layer) or, for bytes, zeros."""
+
+    def __init__(self):
+        self.slot_locks = [threading.Lock()]
+        self.launches = []
+        self.next_ptr = 0x1000
+
+    def alloc(self, nbytes):
+        self.next_ptr += 0x100000
+        return _Buf(self.next_ptr, int(nbytes))
+
+    def to_device(self, array):
+        return self.alloc(np.ascontiguousarray(array).nbytes)
+
+    def free(self, buf):
+        pass
+
+    def download(self, buf, shape, dtype=np.uint8):
+        return np.zeros(shape, dtype) if np.dtype(dtype) == np.uint8 else np.ones(shape, dtype)
+
+    def _launch(self, frames, H, W, Cn, stride):
+        self.launches.append(([b.ptr for b in frames], int(stride) or W * Cn))
+
+    def frame_stats_dev(self, frames, H, W, Cn, band, stats, stride=0, **kw):
+        self._launch(frames, H, W, Cn, stride)
+
+    def frame_edge_dev(self, frames, H, W, Cn, band, out, red_index=0, stride=0, slot=0):
+        self._launch(frames, H, W, Cn, stride)
+
+    def frame_flow_dev(self, frames, H, W, Cn, crop, small_w, small_h, pairs, out, stride=0, **kw):
+        self._launch(frames, H, W, Cn, stride)
+        self.launches[-1] += ([tuple(p) for p in pairs],)
+
+
+def _mixed_stride_frames(ctx, H, W, Cn):
+    """Six DeviceFrames of one shape whose strides are 0, W*C and W*C + 8, interleaved, and {pointer: normalised stride}."""
+    frames = [framescore.DeviceFrame(ctx.alloc(H * (W * Cn + 8)), H, W, Cn, s) for s in (0, W * Cn, W * Cn + 8, 0, W * Cn + 8, W * Cn)]
+    return frames, {fr.buf.ptr: fr.stride or W * Cn for fr in frames}
+
+
+def _assert_own_strides(ctx, own, W, Cn):
+    """Every launch reads each DeviceFrame with that frame's stride (0 and W*C are the same) and each uploaded copy packed."""
+    for launch in ctx.launches:
+        for p in launch[0]:
+            want = own.get(p, W * Cn)
+            assert launch[1] == want, f"frame at {p:#x} launched with stride {launch[1]}, its own is {want}"
+
+
+def test_device_frames_of_one_shape_are_launched_with_their_own_strides():
+    H, W, Cn = 61, 90, 3
+    for run in (lambda c, fr: framescore.score_arrays(c, fr, "lapvar", 0.8, False, True),
+                lambda c, fr: framescore.edge_arrays(c, fr, 0.8)):
+        ctx = _RecordingCtx()
+        frames, own = _mixed_stride_frames(ctx, H, W, Cn)
+        assert len(run(ctx, frames)) == len(frames)
+        _assert_own_strides(ctx, own, W, Cn)
+        assert sorted(p for launch in ctx.launches for p in launch[0]) == sorted(own)      # every frame once, none copied
+        assert [len(launch[0]) for launch in ctx.launches] == [2, 1, 1, 1, 1]              # runs of one stride: 0 and W*C share
+    ctx = _RecordingCtx()
+    frames, own = _mixed_stride_frames(ctx, H, W, Cn)
+    pairs = [(0, 1), (1, 2), (2, 0), (2, 4), (3, 5), (4, 4)]
+    recs = frameflow.flow_records(ctx, frames, pairs, 1.0)
+    assert len(recs) == len(pairs)
+    _assert_own_strides(ctx, own, W, Cn)
+    assert sum(len(launch[2]) for launch in ctx.launches) == len(pairs)                    # every pair ran, once
+    by_ptrs = {tuple(launch[0]): launch for launch in ctx.launches}
+    # pairs of one stride stay on the device: (0,1) and (3,5) together (0 = W*C), (2,4) and (4,4) together
+    assert by_ptrs[tuple(frames[k].buf.ptr for k in (0, 1, 3, 5))][2] == [(0, 1), (2, 3)]
+    assert by_ptrs[tuple(frames[k].buf.ptr for k in (2, 4))][2] == [(0, 1), (1, 1)]
+
+
+def test_device_frames_refuses_a_mixture_of_strides():
+    ctx = _RecordingCtx()
+    frames, _ = _mixed_stride_frames(ctx, 8, 10, 1)
+    with pytest.raises(ValueError):
+        with framescore.device_frames(ctx, frames):
+            pass
+    with framescore.device_frames(ctx, frames[:2] + [np.zeros((8, 10), np.uint8)]) as (bufs, stride, _alloc):
+        assert len(bufs) == 3 and stride in (0, 10)
+    with framescore.device_frames(ctx, [frames[2], frames[4]]) as (bufs, stride, _alloc):
+        assert stride == 18
 
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------
