@@ -209,7 +209,7 @@ def _write_image(path: pathlib.Path, image, jpeg_quality: Optional[int]):
     """cv2.imwrite stand-in: arrays here are in file channel order already (decoded and encoded by the same codec)."""
     from gs360 import imageio
     path.parent.mkdir(parents=True, exist_ok=True)
-    if isinstance(image, bytes):                              # a whole file from the device encoder (GS360_JPEG_ENCODER=device)
+    if isinstance(image, bytes):                              # a whole file from a device encoder (GS360_JPEG_ENCODER / GS360_PNG_ENCODER=device)
         path.write_bytes(image)
         return
     if path.suffix.lower() in (".jpg", ".jpeg") and imageio.Image is not None:
@@ -479,14 +479,16 @@ def main() -> None:
             processed += 2
     else:
         from gs360 import capi, hostmem, imageio, jpegdec
-        from gs360.dualfisheye import DeviceImage, PairRenderer, jpeg_mode_from_env
+        from gs360.dualfisheye import DeviceImage, PairRenderer, jpeg_mode_from_env, png_mode_from_env
         try:
             huffman = jpeg_mode_from_env()                # GS360_JPEG_ENCODER / GS360_JPEG_HUFFMAN, read once per run
+            device_png = png_mode_from_env()              # GS360_PNG_ENCODER
             device_decoder = jpegdec.device_decoder_enabled()      # GS360_JPEG_DECODER
         except ValueError as exc:
             _die("[ERR] {}".format(exc), 1)
         jpeg_views = (_jpeg_quality(jpeg_q), huffman) if huffman and persp_ext in (".jpg", ".jpeg") else None
         jpeg_masks = (_jpeg_quality(jpeg_q), huffman) if huffman and mask_ext in (".jpg", ".jpeg") else None
+        png_views, png_masks = device_png and persp_ext == ".png", device_png and mask_ext == ".png"
         n_dev = capi.device_count()
         if n_dev <= 0:
             _die("[ERR] no MI355X visible: the gs360 engine has no CPU fallback", 2)
@@ -528,7 +530,8 @@ def main() -> None:
                 raise
             res = r.render_pair(img_x, img_y, sx, sy, interpolation=interpolation, mask_outside_model=bool(args.mask_outside_model),
                                 mask_value=mask_value, mask_x=mx, mask_y=my, want_fisheye=write_fisheye, want_perspective=write_persp,
-                                color_stage=stage, want_color=save_color, jpeg_views=jpeg_views, jpeg_masks=jpeg_masks)
+                                color_stage=stage, want_color=save_color, jpeg_views=jpeg_views, jpeg_masks=jpeg_masks,
+                                png_views=png_views, png_masks=png_masks)
             names = {"color": [], "fisheye": [], "persp": [], "mask": []}
             if save_color:
                 for key, p in (("X", x_path), ("Y", y_path)):

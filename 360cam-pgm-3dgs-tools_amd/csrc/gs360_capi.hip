@@ -156,7 +156,7 @@ int gs360_ctx_destroy(gs360_ctx* c) {
         for (int k = 0; k < kEventsPerSlot; ++k)
             if (c->event[s][k]) (void)hipEventDestroy(c->event[s][k]);
         for (void* p : {c->stage[s].d_src, c->stage[s].d_dst, c->stage[s].d_aux, c->stage[s].d_maskbits, c->stage[s].d_fft, c->stage[s].d_flow,
-                        c->stage[s].d_jpeg})
+                        c->stage[s].d_jpeg, c->stage[s].d_png})
             if (p) (void)hipFree(p);
         if (c->stream[s]) (void)hipStreamDestroy(c->stream[s]);
     }

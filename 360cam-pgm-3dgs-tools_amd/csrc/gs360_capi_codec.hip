@@ -1,6 +1,6 @@
 // gs360_capi_codec.hip -- image-codec entry points of libgs360hip.so (include/gs360.h): PNG scanline unfiltering and TIFF LZW strip
 // decoding for the Python-side codec (gs360/imageio.py; host only, no GPU involved), and the glue of the device JPEG scans
-// (gs360_jpeg.hip) and of the device JPEG decoder (gs360_jpegdec.hip).
+// (gs360_jpeg.hip), of the device JPEG decoder (gs360_jpegdec.hip) and of the device PNG encoder (gs360_png.hip).
 #include "gs360_capi_internal.h"
 
 using namespace gs360;
@@ -354,4 +354,121 @@ int gs360_jpeg_decode_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_job
 
 int gs360_jpeg_decode_gray_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int n_jobs, uint32_t* status_dev, int slot) {
     return jpeg_decode(c, jobs, n_jobs, status_dev, true, slot);
+}
+
+// ---- PNG deflate streams on the device (PNG-SPEC v1; kernels in gs360_png.hip) --------------------------------------------
+namespace {
+
+int check_png_geometry(int H, int W, int C, int bytes_per_sample) {
+    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(GS360_ERR_ARG, "the PNG encoder's sides are 1..65535 (got %d x %d)", W, H);
+    if (C != 1 && C != 3 && C != 4) return fail(GS360_ERR_UNSUPPORTED, "the PNG encoder takes C = 1, 3 or 4 (got %d)", C);
+    if (bytes_per_sample != 1 && bytes_per_sample != 2)
+        return fail(GS360_ERR_UNSUPPORTED, "the PNG encoder takes 1 or 2 bytes per sample (got %d)", bytes_per_sample);
+    return 0;
+}
+
+inline size_t png_filtered(int H, int W, int C, int bps) { return (size_t)H * (1 + (size_t)W * C * bps); }
+inline size_t png_chunks(size_t n) { return (n + kPnChunk - 1) / kPnChunk; }
+
+}  // namespace
+
+int gs360_png_bound(int H, int W, int C, int bytes_per_sample, size_t* bytes) {
+    if (!bytes) return fail(GS360_ERR_ARG, "NULL argument");
+    if (int rc = check_png_geometry(H, W, C, bytes_per_sample)) return rc;
+    // a literal costs at most 15 bits, a match of three or more bytes at most 15 + 5 + 15 + 13: two bytes per filtered byte; a chunk
+    // adds its header (168 bytes), the end of block and the stored block (7 bytes)
+    const size_t n = png_filtered(H, W, C, bytes_per_sample);
+    *bytes = 2 * n + png_chunks(n) * 176;
+    return GS360_OK;
+}
+
+int gs360_png_deflate(gs360_ctx* c, const gs360_png_job* jobs, int n_jobs, uint64_t* lengths_dev, uint32_t* adler_dev, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
+    if (n_jobs == 0) return GS360_OK;
+    if (!jobs || !lengths_dev || !adler_dev) return fail(GS360_ERR_ARG, "NULL argument");
+    for (int k = 0; k < n_jobs; ++k) {
+        const gs360_png_job& j = jobs[k];
+        if (int rc = check_png_geometry(j.H, j.W, j.C, j.bytes_per_sample)) return rc;
+        if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
+        if (j.src_stride && j.src_stride < (size_t)j.W * j.C * j.bytes_per_sample) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
+        if (j.bytes_per_sample == 2 && (((uintptr_t)j.src | j.src_stride) & 1)) return fail(GS360_ERR_ARG, "job %d: 16-bit rows are not 2-byte aligned", k);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream[slot];
+    Staging& st = c->stage[slot];
+    // scratch of a launch batch, sized for the call's largest batch before the first launch: the filtered streams, then per chunk its
+    // length, offset, code tables and segment offsets
+    auto layout = [](size_t filt, size_t chunks, size_t* len_at, size_t* off_at, size_t* codes_at, size_t* seg_at) {
+        *len_at = round_up(filt + 4, 256);
+        *off_at = round_up(*len_at + chunks * 4, 256);
+        *codes_at = *off_at + chunks * 8;
+        *seg_at = *codes_at + chunks * 320 * 4;
+        return *seg_at + chunks * kPnThreads * 4;
+    };
+    size_t need = 0;
+    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
+        size_t filt = 0, chunks = 0, a, b, d, e;
+        for (int k = k0; k < std::min(n_jobs, k0 + GS360_MAX_VIEWS); ++k) {
+            const size_t n = png_filtered(jobs[k].H, jobs[k].W, jobs[k].C, jobs[k].bytes_per_sample);
+            filt += round_up(n + 4, 256);
+            chunks += png_chunks(n);
+        }
+        need = std::max(need, layout(filt, chunks, &a, &b, &d, &e));
+    }
+    if (int rc = ensure(&st.d_png, &st.png_cap, need)) return rc;
+    size_t chunks_before = 0;                             // adler_dev: two words per chunk, the jobs' chunks in job order
+    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
+        PnLaunch L;
+        std::memset(&L, 0, sizeof(L));
+        L.n_jobs = std::min(GS360_MAX_VIEWS, n_jobs - k0);
+        size_t filt = 0;
+        int64_t rows = 0, chunks = 0;
+        for (int k = 0; k < L.n_jobs; ++k) {
+            const gs360_png_job& j = jobs[k0 + k];
+            PnJob& J = L.job[k];
+            J.src = (const uint8_t*)j.src;
+            J.out = (uint8_t*)j.out;
+            J.cap = j.out_capacity;
+            J.bpp = j.C * j.bytes_per_sample;
+            J.Wb = j.W * J.bpp;
+            J.stride = (int64_t)(j.src_stride ? j.src_stride : (size_t)J.Wb);
+            J.H = j.H;
+            J.swap = j.bytes_per_sample == 2;
+            J.n = (int64_t)png_filtered(j.H, j.W, j.C, j.bytes_per_sample);
+            J.filt_base = (int64_t)filt;
+            J.row_base = (int32_t)rows; J.chunk_base = (int32_t)chunks;
+            J.n_chunks = (int32_t)png_chunks((size_t)J.n);
+            const int cand[3] = {1, J.bpp, 1 + J.Wb};
+            for (int q = 0; q < 3; ++q) {
+                const int d = cand[q];
+                if (d > 32768 || (q > 0 && d == cand[q - 1])) continue;            // (bpp = 1 repeats the first: the earlier one wins every tie)
+                J.dist[q] = d;
+                const uint32_t x = (uint32_t)d - 1;                                // RFC 1951 3.2.5
+                const int e = x < 4 ? 0 : 30 - __builtin_clz(x);                   // floor(log2(x)) - 1
+                J.dsym[q] = (uint8_t)(x < 4 ? x : 2 * e + 2 + ((x >> e) & 1));
+                J.dbits[q] = (uint8_t)e;
+                J.dval[q] = (uint16_t)(x & ((1u << e) - 1));
+            }
+            filt += round_up((size_t)J.n + 4, 256);
+            rows += j.H;
+            chunks += J.n_chunks;
+        }
+        if (rows > INT32_MAX || chunks > INT32_MAX) return fail(GS360_ERR_ARG, "PNG batch too large");
+        L.total_rows = (int32_t)rows;
+        L.total_chunks = (int32_t)chunks;
+        size_t len_at, off_at, codes_at, seg_at;
+        if (layout(filt, (size_t)chunks, &len_at, &off_at, &codes_at, &seg_at) > st.png_cap) return fail(GS360_ERR_ARG, "PNG scratch layout");
+        uint8_t* base = (uint8_t*)st.d_png;
+        L.filt = base;
+        L.chunk_len = (uint32_t*)(base + len_at);
+        L.chunk_off = (uint64_t*)(base + off_at);
+        L.codes = (uint32_t*)(base + codes_at);
+        L.seg_off = (uint32_t*)(base + seg_at);
+        L.lengths = lengths_dev + k0;
+        L.adler = adler_dev + 2 * chunks_before;
+        chunks_before += (size_t)chunks;
+        HIP_TRY(launch_png_deflate(L, s));
+    }
+    return GS360_OK;
 }

@@ -53,6 +53,7 @@ struct Staging {  // per-slot device staging used by the *_host conveniences
     void* d_fft = nullptr; size_t fft_cap = 0;             // row-pass spectra and partial sums of one frame-FFT launch
     void* d_flow = nullptr; size_t flow_cap = 0;           // resident frame-flow states, batch work areas and pair points
     void* d_jpeg = nullptr; size_t jpeg_cap = 0;           // coefficients, quantiser table and interval records of one JPEG batch
+    void* d_png = nullptr; size_t png_cap = 0;             // filtered streams and chunk records of one PNG batch
 };
 
 }  // namespace gs360

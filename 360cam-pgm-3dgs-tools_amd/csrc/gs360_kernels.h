@@ -391,6 +391,38 @@ hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s);
 // n_tables x 256 symbol counts -> n_tables x 272 bytes (16 BITS + HUFFVAL, zero padded): the table kernel alone
 hipError_t launch_jpeg_huff_tables(const uint32_t* hist, int n_tables, uint8_t* tables, hipStream_t s);
 
+// PNG deflate streams (gs360_png.hip, PNG-SPEC v1 in DESIGN.md): one batch of up to GS360_MAX_VIEWS images.  Scratch of the batch: the
+// filtered stream of every image (H rows of 1 + Wb bytes, each image's 256-byte aligned), and per chunk of kPnChunk filtered bytes its
+// coded length, its offset in the image's stream, its two code tables and its segments' first bits.
+constexpr int kPnChunk = 65536;          // filtered bytes of one dynamic-Huffman block
+constexpr int kPnSegment = 512;          // bytes one lane parses: no match crosses a segment's end
+constexpr int kPnThreads = kPnChunk / kPnSegment;
+constexpr int kPnLitLen = 286, kPnDist = 30, kPnSyms = kPnLitLen + kPnDist;
+struct PnJob {
+    const uint8_t* src;
+    uint8_t* out;
+    uint64_t cap;
+    int64_t stride, filt_base, n;        // row stride in bytes; the image's filtered stream in the scratch; its length H * (1 + Wb)
+    int32_t H, Wb, bpp, swap;            // Wb: bytes of a row; swap: 1 for 16-bit samples (stored little-endian, written big-endian)
+    int32_t row_base, chunk_base, n_chunks, pad;
+    int32_t dist[3];                     // the candidate distances 1, bpp, 1 + Wb; 0: a repeat of an earlier one, or above 32768
+    uint8_t dsym[3], dbits[3];           // their distance symbols and extra bits ...
+    uint16_t dval[3];                    // ... and the extra bits' values
+};
+struct PnLaunch {
+    PnJob job[GS360_MAX_VIEWS];
+    int32_t n_jobs, total_rows, total_chunks, pad;
+    uint8_t* filt;
+    uint32_t* chunk_len;                 // total_chunks
+    uint64_t* chunk_off;
+    uint32_t* codes;                     // total_chunks x 320: (bit-reversed code << 5) | length, 286 literal/length then 30 distance symbols
+    uint32_t* seg_off;                   // total_chunks x kPnThreads: a segment's first bit in its chunk's bytes
+    uint64_t* lengths;                   // n_jobs: the streams' lengths, UINT64_MAX where one exceeds its capacity
+    uint32_t* adler;                     // total_chunks x 2: the chunks' Adler-32 partial sums (the caller's buffer)
+};
+static_assert(sizeof(PnLaunch) <= 4096, "a launch travels by value as the kernels' argument");
+hipError_t launch_png_deflate(const PnLaunch& L, hipStream_t s);
+
 // The MCU grid of an image, for both codecs.  A colour image's luma is sampled hs x vs over 1 x 1 chroma: its MCU is 8 hs x 8 vs pixels
 // and holds hs vs luma blocks in raster order, then Cb, then Cr (hs = vs = 1: one block per component).  A gray image's MCU is one
 // block whatever its sampling factors say.

@@ -35,7 +35,7 @@ EXPORTS = (
     "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
     "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound", "gs360_jpeg_scan_opt_u8", "gs360_jpeg_huff_tables",
     "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub", "gs360_jpeg_decode_u8", "gs360_jpeg_decode_scratch",
-    "gs360_jpeg_decode_gray_u8",
+    "gs360_jpeg_decode_gray_u8", "gs360_png_deflate", "gs360_png_bound",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -46,6 +46,8 @@ JPEG_440 = 3
 JPEG_411 = 4
 JPEG_DEC_SUBSEQ_BYTES = 128          # GS360_JPEG_DEC_SUBSEQ_BYTES: bytes of a scan one lane of gs360_jpeg_decode_u8 decodes first
 JPEG_DEC_WG_SUBSEQS = 256            # GS360_JPEG_DEC_WG_SUBSEQS: subsequences one workgroup synchronises among themselves
+PNG_OVERFLOW = 0xFFFFFFFFFFFFFFFF    # a stream length of gs360_png_deflate: the stream did not fit its out_capacity
+PNG_CHUNK = 65536                    # PNG-SPEC v1: filtered bytes per deflate block (and per pair of Adler-32 partial sums)
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
@@ -91,6 +93,12 @@ class JpegJob(C.Structure):
     """gs360_jpeg_job: one image of a batched JPEG scan call (device pointers)."""
     _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("src_stride", C.c_size_t),
                 ("out", C.c_void_p), ("out_capacity", C.c_size_t)]
+
+
+class PngJob(C.Structure):
+    """gs360_png_job: one image of a batched PNG deflate call (device pointers)."""
+    _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("bytes_per_sample", C.c_int32),
+                ("src_stride", C.c_size_t), ("out", C.c_void_p), ("out_capacity", C.c_size_t)]
 
 
 class JpegDecJob(C.Structure):
@@ -227,6 +235,8 @@ def load_library(path=None):
         L.gs360_jpeg_decode_u8.argtypes = [vp, C.POINTER(JpegDecJob), i, vp, i]
         L.gs360_jpeg_decode_gray_u8.argtypes = [vp, C.POINTER(JpegDecJob), i, vp, i]
         L.gs360_jpeg_decode_scratch.argtypes = [i, i, i, i, u32, C.POINTER(C.c_size_t)]
+        L.gs360_png_deflate.argtypes = [vp, C.POINTER(PngJob), i, vp, vp, i]
+        L.gs360_png_bound.argtypes = [i, i, i, i, C.POINTER(C.c_size_t)]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -641,6 +651,24 @@ class Context:
         if hist.nbytes < 1024 * n or tables.nbytes < JPEG_TABLE_BYTES * n:
             raise ValueError("histogram or tables buffer too small for n tables")
         _check(self.L.gs360_jpeg_huff_tables(self.handle, hist.ptr, int(n), tables.ptr, slot), self.L)
+
+    # -- PNG deflate streams of device images (gs360/pngenc.py) -------------------------------
+    def png_deflate_dev(self, jobs, lengths, adler, slot=0):
+        """gs360_png_deflate: jobs = iterable of (src DeviceBuffer or device address, H, W, C, bytes_per_sample, src_stride, out
+        DeviceBuffer, out_capacity); lengths = DeviceBuffer of len(jobs) uint64 (PNG_OVERFLOW where a stream exceeded its capacity);
+        adler = DeviceBuffer of two uint32 per chunk of PNG_CHUNK filtered bytes, the jobs' chunks in job order.  Asynchronous on
+        `slot`."""
+        jobs = list(jobs)
+        arr = (PngJob * max(len(jobs), 1))()
+        chunks = 0
+        for k, (src, H, W, Cn, bps, stride, out, cap) in enumerate(jobs):
+            if cap > out.nbytes:
+                raise ValueError("out_capacity larger than the output buffer")
+            chunks += -(-(int(H) * (1 + int(W) * int(Cn) * int(bps))) // PNG_CHUNK)
+            arr[k] = PngJob(src.ptr if isinstance(src, DeviceBuffer) else int(src), int(H), int(W), int(Cn), int(bps), int(stride), out.ptr, int(cap))
+        if lengths.nbytes < 8 * len(jobs) or adler.nbytes < 8 * chunks:
+            raise ValueError("lengths or adler buffer too small")
+        _check(self.L.gs360_png_deflate(self.handle, arr, len(jobs), lengths.ptr, adler.ptr, slot), self.L)
 
     # -- JPEG files decoded into device images (gs360/jpegdec.py) ------------------------------
     def jpeg_decode_dev(self, jobs, status, slot=0):

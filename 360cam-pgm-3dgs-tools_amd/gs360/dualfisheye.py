@@ -14,7 +14,9 @@ turns them off (A/B).
 The reference writes every view with cv2.imwrite(path, image, [IMWRITE_JPEG_QUALITY, q]) (DF:1826-1840): libjpeg's defaults, 2 x 2 chroma
 subsampling and the Annex K Huffman tables.  With GS360_JPEG_ENCODER=device (jpeg_mode_from_env, read once per run by the CLI) the 8-bit
 .jpg views of a pair are entropy-coded where the remap left them ("JPG-SPEC v1, 4:2:0", gs360/jpegenc.py: one gs360_jpeg_scan_sub_u8
-call on the pair's slot) and only the scans cross PCIe; render_pair then returns whole files instead of arrays.
+call on the pair's slot) and only the scans cross PCIe; render_pair then returns whole files instead of arrays.  GS360_PNG_ENCODER=device
+(png_mode_from_env) does the same for the .png views and .png masks, 8- and 16-bit (PNG-SPEC v1, gs360/pngenc.py: one gs360_png_deflate
+call), in place of cv2.imwrite's PNG writer.
 """
 import os
 import threading
@@ -22,13 +24,15 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import capi, jpegenc
+from . import capi, jpegenc, pngenc
 from .fisheye import SensorCalibration, UndistortTables
 
 INTERPOLATIONS = {"nearest": 0, "linear": 1, "cubic": 2, "lanczos4": 4}   # cv2.INTER_* values (DF:59-64)
 
 
 jpeg_mode_from_env = jpegenc.mode_from_env      # the CLI's name for it: read once per run
+png_mode_from_env = pngenc.mode_from_env
+_PNG = "png"                                    # _collect's `jpeg` for views the device PNG encoder writes
 
 
 def engine_interpolation(flag: int) -> int:
@@ -58,6 +62,7 @@ class PairRenderer:
         self._plans = {}                    # (kind, id, nearest) -> map plan handle
         self.use_plans = os.environ.get("GS360_MAP_PLANS", "1") not in ("0", "off", "no")
         self._stats = {"jpeg_device_images": 0, "jpeg_device_bytes": 0}
+        self._png_stats = {"png_device_images": 0, "png_device_bytes": 0}
         self.dev_undistort = {}
         for sid, u in (undistort or {}).items():
             self.dev_undistort[sid] = (ctx.to_device(u.map_x), ctx.to_device(u.map_y),
@@ -81,10 +86,23 @@ class PairRenderer:
         with self.lock:
             return dict(self._stats)
 
+    def png_stats(self):
+        """png_device_images / png_device_bytes: the same counts for the device PNG encoder (render_pair's png_views / png_masks)"""
+        with self.lock:
+            return dict(self._png_stats)
+
     def _collect(self, keys, bufs, shapes, dtype, jpeg):
         """(the views' launch queued on slot 0) -> {key: array}, or with `jpeg` = (quality, huffman) and 8-bit gray or RGB views
         {key: bytes}: whole 4:2:0 JFIF files, encoded from the device buffers before they are freed.  A scan gets the view's raw size;
-        one that needs more is coded again, in the same mode, into a buffer of the bound."""
+        one that needs more is coded again, in the same mode, into a buffer of the bound.  `jpeg` = _PNG: whole PNG files in the same
+        way, for views of either depth and 1, 3 or 4 channels."""
+        if jpeg == _PNG:
+            esz = np.dtype(dtype).itemsize
+            with self.ctx.slot_locks[0]:
+                files = pngenc.encode_buffers(self.ctx, [(b, h, w, c, esz, 0) for b, (h, w, c) in zip(bufs, shapes)], slot=0, raw_capacity=True)
+            self._png_stats["png_device_images"] += len(files)
+            self._png_stats["png_device_bytes"] += sum(len(f) for f in files)
+            return dict(zip(keys, files))
         if jpeg is None or np.dtype(dtype) != np.uint8 or any(c not in (1, 3) for _h, _w, c in shapes):
             return {k: self.ctx.download(b, shape, dtype=dtype, slot=0) for k, b, shape in zip(keys, bufs, shapes)}
         quality, huffman = jpeg
@@ -167,7 +185,8 @@ class PairRenderer:
                     interpolation: int, mask_outside_model: bool, mask_value: int,
                     mask_x: Optional[np.ndarray] = None, mask_y: Optional[np.ndarray] = None,
                     want_fisheye: bool = False, want_perspective: bool = True,
-                    color_stage=None, want_color: bool = False, jpeg_views=None, jpeg_masks=None):
+                    color_stage=None, want_color: bool = False, jpeg_views=None, jpeg_masks=None, png_views: bool = False,
+                    png_masks: bool = False):
         """-> dict(perspective={view_id: img}, masks={view_id: img}, fisheye={'X': img, 'Y': img}, color={'X','Y'})
 
         `jpeg_views` = None | (quality, huffman): when set and the views are 8-bit with C = 1 or 3, the perspective entries are not
@@ -175,11 +194,15 @@ class PairRenderer:
         every entry is a whole JFIF file (bytes: header + scan + EOI), what cv2.imwrite writes at DF:1826-1840 up to the DCT's rounding.
         `jpeg_masks`: the same for the mask entries, whose files carry their own extension (--perspective-mask-ext).  16-bit and
         four-channel views, the undistorted-fisheye and the colour-corrected outputs stay arrays.
+        `png_views` / `png_masks`: the perspective / mask entries are whole PNG files from the device encoder (gs360_png_deflate; any
+        depth and channel count), in place of `jpeg_views` / `jpeg_masks`.
 
         `color_stage` (gs360.color.ColorStage) converts both lens images on the device right after the upload, i.e.
         before every resampling step, as load_prepared_input_image does on the host (DF:728-743); `want_color`
         returns the converted images (the --save-color-corrected-output files, DF:1953-1959)."""
         interp = engine_interpolation(interpolation)
+        jpeg_views = _PNG if png_views else jpeg_views
+        jpeg_masks = _PNG if png_masks else jpeg_masks
         out = {"perspective": {}, "masks": {}, "fisheye": {}, "color": {}}
         with self.lock:
             imgs = {"X": _hwc(image_x), "Y": _hwc(image_y)}

@@ -22,6 +22,10 @@ GS360_JPEG_DECODER=device does the same for the input side (gs360/jpegdec.py, JP
 decoded by Pillow and uploaded as pixels; its scan is uploaded and gs360_jpeg_decode_u8 leaves the frame resident (gray, 4:4:4, 4:2:2,
 4:2:0, 4:4:0 and 4:1:1 files).  Files the device path does not take (progressive, other sampling factors, CMYK, cut short ...) and
 every other format go through imageio.read_image as before.
+
+GS360_PNG_ENCODER=device is the same step for `.png` views, 8- and 16-bit (gs360/pngenc.py, PNG-SPEC v1): one gs360_png_deflate call
+on the launch's stream filters and deflates the batch's views where they are, only the compressed bytes and 8 bytes of checksum per
+64 KiB cross PCIe, and a job writes the PNG framing around them.  The default, `host`, writes every file exactly as before.
 """
 import collections
 import itertools
@@ -32,7 +36,7 @@ import time
 
 import numpy as np
 
-from . import capi, hostmem, imageio, jpegdec, jpegenc, video
+from . import capi, hostmem, imageio, jpegdec, jpegenc, pngenc, video
 from .jobspec import JobSpec
 
 _FRAME_CACHE_BYTES = int(os.environ.get("GS360_FRAME_CACHE_MB", "4096")) << 20
@@ -61,8 +65,37 @@ class _JpegScan:
             f.write(jpegenc.EOI)
 
 
+class _PngStream:
+    """A view the device encoded (GS360_PNG_ENCODER=device): its geometry, the deflate stream, which aliases pinned host memory, and
+    the filtered scanlines' Adler-32."""
+    __slots__ = ("geometry", "stream", "adler")
+
+    def __init__(self, geometry, stream, adler):
+        self.geometry = geometry            # (H, W, C, bytes per sample)
+        self.stream = stream
+        self.adler = adler
+
+    def write(self, path):
+        path = pathlib.Path(path)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_bytes(pngenc.assemble(*self.geometry, self.stream, self.adler))
+
+
+def _fetch_coded(st, ctx, slot, coded, h_out):
+    """(slot lock held) coded: [(DeviceBuffer, length)] -> the bytes in the views' pinned blocks, one synchronisation; h_out[i] is
+    replaced by a block of the device buffer's size where the bytes are longer than the block"""
+    L = ctx.L
+    for i, (d, length) in enumerate(coded):
+        if length > h_out[i].nbytes:
+            larger = st.take(st.pin_pool, d.nbytes, ctx.pinned)
+            st.give(st.pin_pool, h_out[i])
+            h_out[i] = larger
+        capi._check(L.gs360_download(ctx.handle, h_out[i].ptr, d.ptr, length, slot), L)
+    ctx.sync(slot)
+
+
 def _write_view(path, arr, jpeg_q):
-    if isinstance(arr, _JpegScan):
+    if isinstance(arr, (_JpegScan, _PngStream)):
         arr.write(path)
     else:
         imageio.write_image(path, arr, jpeg_q=jpeg_q)
@@ -366,14 +399,7 @@ class Engine:
         scans = jpegenc.scan_items(ctx, [(d, h, w, C) for d, (h, w) in zip(d_out, shapes)], lambda nb: st.take(st.dev_pool, nb, ctx.alloc),
                                    lambda b: st.give(st.dev_pool, b), quality, jpegenc.RESTART, slot, huffman)
         try:
-            L = ctx.L
-            for i, (d, length, _tab) in enumerate(scans):
-                if length > h_out[i].nbytes:
-                    larger = st.take(st.pin_pool, d.nbytes, ctx.pinned)
-                    st.give(st.pin_pool, h_out[i])
-                    h_out[i] = larger
-                capi._check(L.gs360_download(ctx.handle, h_out[i].ptr, d.ptr, length, slot), L)
-            ctx.sync(slot)
+            _fetch_coded(st, ctx, slot, [(d, length) for d, length, _tab in scans], h_out)
         finally:
             for d, _length, _tab in scans:
                 st.give(st.dev_pool, d)
@@ -386,11 +412,40 @@ class Engine:
                 st.stats["jpeg_device_bytes"] += len(head) + length + len(jpegenc.EOI)
         return out
 
+    @staticmethod
+    def _png_mode(job: JobSpec, want_array=False):
+        """-> None (the host codecs write the view) or ("png",): GS360_PNG_ENCODER = host (default) | device, read once per job; the
+        device encoder takes the .png views, 8- and 16-bit, nobody wants back as arrays."""
+        if want_array or pathlib.Path(str(job.dst)).suffix.lower() != ".png":
+            return None
+        return ("png",) if pngenc.mode_from_env() else None
+
+    def _encode_png_views(self, st, ctx, slot, d_out, h_out, shapes, C, esz):
+        """(slot lock held, the views' launch queued on `slot`) pngenc.deflate_items over the rendered views with the device pool as its
+        allocator: one gs360_png_deflate call, a stream is given about the view's raw size and one that needs more (noise) is coded again
+        into a buffer of the bound.  Only the streams' bytes come back, into the views' pinned blocks.  -> [_PngStream]; h_out[i] is
+        replaced where the stream is longer than the block."""
+        streams = pngenc.deflate_items(ctx, [(d, h, w, C, esz, 0) for d, (h, w) in zip(d_out, shapes)],
+                                       lambda nb: st.take(st.dev_pool, nb, ctx.alloc), lambda b: st.give(st.dev_pool, b), slot)
+        try:
+            _fetch_coded(st, ctx, slot, [(d, length) for d, length, _adler in streams], h_out)
+        finally:
+            for d, _length, _adler in streams:
+                st.give(st.dev_pool, d)
+        out = []
+        for hb, (_d, length, adler), (h, w) in zip(h_out, streams, shapes):
+            out.append(_PngStream((h, w, C, esz), np.frombuffer(hb.view, dtype=np.uint8, count=length), adler))
+            with st.pool_lock:
+                st.stats["png_device_images"] += 1
+                st.stats["png_device_bytes"] += length + 6 + 57             # zlib header and Adler-32; signature, IHDR, IDAT framing, IEND
+        return out
+
     def _launch_batch(self, st: _DeviceState, buf, H, W, C, views, interp, flags, dtype=np.uint8, jpeg=None):
         """One batched launch for `views` of one resident frame -- or of a WINDOW of resident frames (`buf` a list: the frames of a video
         the view jobs walk together, PC:746-749, PC:1049-1078; ring families reach the source-major kernel from four frames per call).
         Returns [(array aliasing pinned memory, PinnedBuffer)] per view; for a window a list of those, one per frame.  With `jpeg` (a
-        (quality, Huffman mode) pair) and an 8-bit gray or RGB frame the views are encoded where they are and the arrays are _JpegScan objects."""
+        (quality, Huffman mode) pair) and an 8-bit gray or RGB frame the views are encoded where they are and the arrays are _JpegScan
+        objects; with `jpeg` = ("png",) (_png_mode) they are _PngStream objects, for any frame."""
         with st.lock:
             slot = next(st.slot_cycle)
         ctx, L = st.ctx, st.ctx.L
@@ -401,13 +456,16 @@ class Engine:
         sizes = [v.height * v.width * C * esz for v in views] * len(bufs)           # frame-major, as gs360_equirect_views_u8 writes them
         d_out = [st.take(st.dev_pool, n, ctx.alloc) for n in sizes]
         h_out = [st.take(st.pin_pool, n, ctx.pinned) for n in sizes]
-        encode = jpeg is not None and np.dtype(dtype) == np.uint8 and C in (1, 3)
+        png = jpeg == ("png",)
+        encode = png or (jpeg is not None and np.dtype(dtype) == np.uint8 and C in (1, 3))
         scans = None
         t0 = time.perf_counter()
         try:
             with ctx.slot_locks[slot]:
                 ctx.equirect_views_dev(bufs, W, H, C, views, d_out, slot=slot, interp=interp, flags=flags, dtype=dtype)
-                if encode:
+                if png:
+                    scans = self._encode_png_views(st, ctx, slot, d_out, h_out, [(v.height, v.width) for v in views] * len(bufs), C, esz)
+                elif encode:
                     scans = self._encode_views(st, ctx, slot, d_out, h_out, [(v.height, v.width) for v in views] * len(bufs), C, jpeg)
                 else:
                     for d, hb, n in zip(d_out, h_out, sizes):
@@ -440,7 +498,7 @@ class Engine:
         """Render `view` of the frame identified by `fkey`, coalesced with the other views of that frame that arrive
         within the linger window.  get_frame() -> (DeviceBuffer, H, W, C, dtype) is called by the batch leader only.
         Returns (array, release): the array aliases pinned host memory until release() is called.  `jpeg`: the device encoder's
-        quality and Huffman mode for this view (_jpeg_mode); views that differ in either do not share a batch."""
+        quality and Huffman mode for this view (_jpeg_mode), or ("png",) (_png_mode); views that differ in it do not share a batch."""
         key = (fkey, interp, flags) if jpeg is None else (fkey, interp, flags, "jpeg") + tuple(jpeg)
         with st.batch_cond:
             b = st.open_batches.get(key)
@@ -619,7 +677,7 @@ class Engine:
         of the view when want_array is set (the result itself lives in pooled pinned memory), else None."""
         view, flags = self._view_for(job)
         interp = self._interp_for(job)
-        jpeg = self._jpeg_mode(job, want_array)
+        jpeg = self._jpeg_mode(job, want_array) or self._png_mode(job, want_array)
         rec = self._job_touches(job.src)
         try:
             st = self.states[rec.dev]
@@ -645,9 +703,11 @@ class Engine:
 
     def stats(self):
         """Counters since start: batched launches, views, seconds the launch+copy sections held a stream; jpeg_device_images /
-        jpeg_device_bytes: views the device encoder wrote (GS360_JPEG_ENCODER=device) and their files' bytes; device_decoded_frames /
-        device_decode_fallbacks: .jpg stills the device decoder took (GS360_JPEG_DECODER=device) and those it left to the host."""
-        total = collections.Counter(jpeg_device_images=0, jpeg_device_bytes=0, device_decoded_frames=0, device_decode_fallbacks=0)
+        jpeg_device_bytes: views the device encoder wrote (GS360_JPEG_ENCODER=device) and their files' bytes; png_device_images /
+        png_device_bytes: the same for GS360_PNG_ENCODER=device; device_decoded_frames / device_decode_fallbacks: .jpg stills the device
+        decoder took (GS360_JPEG_DECODER=device) and those it left to the host."""
+        total = collections.Counter(jpeg_device_images=0, jpeg_device_bytes=0, png_device_images=0, png_device_bytes=0,
+                                    device_decoded_frames=0, device_decode_fallbacks=0)
         for st in self.states:
             total.update(st.stats)
         return dict(total)
@@ -678,7 +738,7 @@ class Engine:
         """All frames of one view of a video; returns the number of frames written."""
         view, flags = self._view_for(job)
         interp = self._interp_for(job)
-        jpeg = self._jpeg_mode(job)
+        jpeg = self._jpeg_mode(job) or self._png_mode(job)
         sess, token = self._video_session(plan, stop_event, register_proc)
         written = 0
         try:

@@ -539,6 +539,33 @@ int gs360_jpeg_decode_scratch(int H, int W, int C, int subsampling, uint32_t n_s
  * the Y sample. */
 int gs360_jpeg_decode_gray_u8(gs360_ctx *ctx, const gs360_jpeg_dec_job *jobs, int n_jobs, uint32_t *status_dev, int slot);
 
+/* ---- PNG deflate streams of device-resident images (PNG-SPEC v1) ---------------------------------------
+ * The PNG writer behind `.png` views and masks (the host path: Pillow at compress_level 3 for 8 bits, gs360/imageio.py's filter-0
+ * writer for 16).  For every job an H x W x C image (C = 1, 3 or 4; bytes_per_sample 1 = uint8, 2 = uint16 in host byte order; row
+ * stride src_stride bytes, 0 = tight; the buffer rules of the memory section apply) becomes the raw deflate stream of its filtered
+ * scanlines: per row the PNG filter with the smallest sum of |residual as int8| (ties to the lower type), 16-bit samples big-endian;
+ * the filtered stream in chunks of 65 536 bytes, each one dynamic-Huffman block followed by an empty stored block (so every chunk
+ * starts on a byte; the last stored block carries BFINAL); matches only at the distances 1, bpp and 1 + W * bpp, inside segments of
+ * 512 bytes, greedy; code lengths limited to 15 bits; a fixed code-length code.  The bytes are a function of the pixels alone
+ * (tests/pngenc_np.py restates them).  `out` receives the stream (no zlib header, no Adler-32, no PNG chunks: gs360/pngenc.py builds
+ * those), lengths_dev[k] (device memory) its length; a stream longer than out_capacity gets the length UINT64_MAX and none of it is
+ * written.  adler_dev (device memory) receives two uint32 per chunk of 65 536 filtered bytes, the jobs' chunks in job order (job k has
+ * ceil(H * (1 + W * C * bytes_per_sample) / 65 536)): the sum of the chunk's bytes and the sum of (n - i) * byte i over its n bytes,
+ * both mod 65 521, which the host folds into the stream's Adler-32.  n_jobs may exceed GS360_MAX_VIEWS (split internally); the jobs
+ * of a call may differ in size, C and depth.  Asynchronous on `slot`.
+ * Errors: GS360_ERR_ARG for sides outside 1..65535, NULL pointers, a stride below a row, odd 16-bit addresses or strides;
+ * GS360_ERR_UNSUPPORTED for other C or bytes_per_sample.
+ * gs360_png_bound (host only): *bytes = a capacity no stream of such an image exceeds (two bytes per filtered byte + 176 per chunk). */
+typedef struct gs360_png_job {
+    const void *src;       /* H x W x C uint8 or uint16 */
+    int32_t H, W, C, bytes_per_sample;
+    size_t src_stride;     /* bytes; 0 = tight */
+    void *out;             /* the deflate stream */
+    size_t out_capacity;
+} gs360_png_job;
+int gs360_png_deflate(gs360_ctx *ctx, const gs360_png_job *jobs, int n_jobs, uint64_t *lengths_dev, uint32_t *adler_dev, int slot);
+int gs360_png_bound(int H, int W, int C, int bytes_per_sample, size_t *bytes);
+
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
                                  const gs360_view *views, int n_views,
