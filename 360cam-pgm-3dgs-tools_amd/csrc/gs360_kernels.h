@@ -522,4 +522,37 @@ struct JdLaunch {
 static_assert(sizeof(JdLaunch) <= 4096, "a launch travels by value as the kernels' argument");
 hipError_t launch_jpeg_decode(const JdLaunch& L, bool gray, hipStream_t s);   // gray: jd_pixels_kernel's output mode
 
+// Segmentation-mask finishing (gs360_maskmorph.hip, MSK-SPEC v1 in DESIGN.md): one step of the chain over a batch of up to
+// GS360_MAX_VIEWS masks.  A mask lives as a bit plane (bit x & 31 of dword x >> 5, pw = ceil(W / 32) dwords per row, bits at columns
+// >= W zero); the glue fills the fields a step reads and gives a job that skips the step no tiles.
+constexpr int kMkThreads = 256;
+constexpr int kMkTileW = 32, kMkTileR = 32;              // a morph tile: output dwords x output rows
+constexpr int kMkMaxElem = 1025;                         // largest element side (p = 512)
+constexpr int kMkMaxHalo = kMkMaxElem / 2 / 32 + 2;      // staged dwords left and right of a tile: reach / 32 + 2
+constexpr int kMkStageW = kMkTileW + 2 * kMkMaxHalo, kMkStageRows = 96;   // the LDS band: 96 rows of at most 68 dwords
+constexpr int kMkFinishRows = 32;                        // rows of a workgroup of the counting pass
+constexpr int kMkCompIn = 1, kMkCompOut = 2;             // morph flags: complement the plane read / written, inside the image
+struct MkJob {
+    const uint8_t *src, *add, *img;      // raw mask (null: all clear), manual add layer (null: none), H x W x 3 image (compose kinds)
+    uint8_t* dst;
+    int64_t src_stride, add_stride, img_stride, dst_stride;
+    const uint32_t* in;                  // the plane a step reads ...
+    uint32_t* out;                       // ... and writes (pack, finish: the one plane they work on)
+    const int32_t* spans;                // morph: kh x (j1, j2), device memory
+    int32_t H, W, pw, thresh;
+    int32_t kh, ax, ay, halo;            // morph: element rows, anchor, staged halo dwords (reach / 32 + 2)
+    int32_t f, s, kind, invert;          // edge fuse: strip width and vertical spread of the side seeds; output kind and polarity
+    int32_t tile_base, tiles_x, flags, pad;
+};
+struct MkLaunch {
+    MkJob job[GS360_MAX_VIEWS];
+    int32_t n_jobs, total_tiles, phase, pad;
+    uint32_t* counts;                    // n_jobs: set pixels of the finished masks (the caller's buffer)
+};
+static_assert(sizeof(MkLaunch) <= 4096, "a launch travels by value as the kernels' argument");
+hipError_t launch_mask_pack_bits(const MkLaunch& L, hipStream_t s);   // mk_pack_kernel
+hipError_t launch_mask_morph(const MkLaunch& L, hipStream_t s);       // mk_morph_kernel: one dilate or erode
+hipError_t launch_mask_fuse(const MkLaunch& L, hipStream_t s);        // mk_fuse_kernel, phase 0 (copy) or 1 (the strips' fills)
+hipError_t launch_mask_finish(const MkLaunch& L, hipStream_t s);      // mk_finish_kernel, phase 0 (add layer, count) or 1 (output)
+
 }  // namespace gs360

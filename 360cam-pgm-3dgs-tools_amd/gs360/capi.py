@@ -35,7 +35,7 @@ EXPORTS = (
     "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
     "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound", "gs360_jpeg_scan_opt_u8", "gs360_jpeg_huff_tables",
     "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub", "gs360_jpeg_decode_u8", "gs360_jpeg_decode_scratch",
-    "gs360_jpeg_decode_gray_u8", "gs360_png_deflate", "gs360_png_bound",
+    "gs360_jpeg_decode_gray_u8", "gs360_png_deflate", "gs360_png_bound", "gs360_mask_finish_u8", "gs360_mask_finish_scratch",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -48,6 +48,10 @@ JPEG_DEC_SUBSEQ_BYTES = 128          # GS360_JPEG_DEC_SUBSEQ_BYTES: bytes of a s
 JPEG_DEC_WG_SUBSEQS = 256            # GS360_JPEG_DEC_WG_SUBSEQS: subsequences one workgroup synchronises among themselves
 PNG_OVERFLOW = 0xFFFFFFFFFFFFFFFF    # a stream length of gs360_png_deflate: the stream did not fit its out_capacity
 PNG_CHUNK = 65536                    # PNG-SPEC v1: filtered bytes per deflate block (and per pair of Adler-32 partial sums)
+MASK_OUT_MASK, MASK_OUT_RGBA, MASK_OUT_KEEP, MASK_OUT_REMOVE = 0, 1, 2, 3   # GS360_MASK_OUT_*: the `kind` of gs360_mask_finish_u8
+MASK_MAX_SIDE = 32768                # GS360_MASK_MAX_SIDE / GS360_MASK_MAX_ELEMENT: the largest mask side and element side
+MASK_MAX_ELEMENT = 1025
+MASK_MAX_FUSE = 1024                 # GS360_MASK_MAX_FUSE: the largest edge-fuse strip (and spread)
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
@@ -99,6 +103,16 @@ class PngJob(C.Structure):
     """gs360_png_job: one image of a batched PNG deflate call (device pointers)."""
     _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("bytes_per_sample", C.c_int32),
                 ("src_stride", C.c_size_t), ("out", C.c_void_p), ("out_capacity", C.c_size_t)]
+
+
+class MaskJob(C.Structure):
+    """gs360_mask_job: one mask of a batched finishing call (device pointers; the element rows are host arrays)."""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_size_t), ("add", C.c_void_p), ("add_stride", C.c_size_t),
+                ("image", C.c_void_p), ("image_stride", C.c_size_t), ("dst", C.c_void_p), ("dst_stride", C.c_size_t),
+                ("H", C.c_int32), ("W", C.c_int32), ("thresh", C.c_int32), ("close_kw", C.c_int32), ("close_kh", C.c_int32),
+                ("expand_kw", C.c_int32), ("expand_kh", C.c_int32), ("fuse", C.c_int32), ("spread", C.c_int32),
+                ("kind", C.c_int32), ("invert", C.c_int32), ("pad", C.c_int32),
+                ("close_rows", C.c_void_p), ("expand_rows", C.c_void_p)]
 
 
 class JpegDecJob(C.Structure):
@@ -237,6 +251,8 @@ def load_library(path=None):
         L.gs360_jpeg_decode_scratch.argtypes = [i, i, i, i, u32, C.POINTER(C.c_size_t)]
         L.gs360_png_deflate.argtypes = [vp, C.POINTER(PngJob), i, vp, vp, i]
         L.gs360_png_bound.argtypes = [i, i, i, i, C.POINTER(C.c_size_t)]
+        L.gs360_mask_finish_scratch.argtypes = [C.POINTER(MaskJob), i, C.POINTER(C.c_size_t)]
+        L.gs360_mask_finish_u8.argtypes = [vp, C.POINTER(MaskJob), i, vp, sz, vp, i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -669,6 +685,25 @@ class Context:
         if lengths.nbytes < 8 * len(jobs) or adler.nbytes < 8 * chunks:
             raise ValueError("lengths or adler buffer too small")
         _check(self.L.gs360_png_deflate(self.handle, arr, len(jobs), lengths.ptr, adler.ptr, slot), self.L)
+
+    # -- segmentation masks finished on the device (gs360/maskfinish.py) -----------------------
+    def mask_finish_scratch(self, jobs):
+        """gs360_mask_finish_scratch: jobs = sequence of MaskJob -> the bytes of scratch one gs360_mask_finish_u8 call on them needs"""
+        n = C.c_size_t(0)
+        arr = (MaskJob * max(len(jobs), 1))(*jobs)
+        _check(self.L.gs360_mask_finish_scratch(arr, len(jobs), C.byref(n)), self.L)
+        return int(n.value)
+
+    def mask_finish_dev(self, jobs, scratch, counts, slot=0, scratch_bytes=None):
+        """gs360_mask_finish_u8: jobs = sequence of MaskJob (gs360/maskfinish.py fills them), scratch = DeviceBuffer of
+        mask_finish_scratch(jobs) bytes, counts = DeviceBuffer of len(jobs) uint32.  The kernels are asynchronous on `slot`."""
+        if counts.nbytes < 4 * len(jobs):
+            raise ValueError("counts buffer below 4 bytes per job")
+        nbytes = scratch.nbytes if scratch_bytes is None else int(scratch_bytes)
+        if nbytes > scratch.nbytes:
+            raise ValueError("scratch_bytes larger than the scratch buffer")
+        arr = (MaskJob * max(len(jobs), 1))(*jobs)
+        _check(self.L.gs360_mask_finish_u8(self.handle, arr, len(jobs), scratch.ptr, nbytes, counts.ptr, slot), self.L)
 
     # -- JPEG files decoded into device images (gs360/jpegdec.py) ------------------------------
     def jpeg_decode_dev(self, jobs, status, slot=0):

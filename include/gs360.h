@@ -566,6 +566,60 @@ typedef struct gs360_png_job {
 int gs360_png_deflate(gs360_ctx *ctx, const gs360_png_job *jobs, int n_jobs, uint64_t *lengths_dev, uint32_t *adler_dev, int slot);
 int gs360_png_bound(int H, int W, int C, int bytes_per_sample, size_t *bytes);
 
+/* ---- finishing segmentation masks on the device (MSK-SPEC v1) ------------------------------------------
+ * What gs360_SegmentationMaskTool.py runs on every image after the network (SEG:680-781), on device-resident data: threshold the raw
+ * H x W uint8 mask (`value > thresh`; src NULL = no detection, all clear), close it (dilate, then erode), dilate it, fuse it to the
+ * frame edges, OR in the manual add layer (`value > 0`; NULL = none), count the set pixels and write the output.  All steps work on a
+ * bit image and are exact; tests/maskfinish_np.py restates them.
+ *   elements  given as DATA: `rows` is a HOST array of kh pairs (j1, j2), the half-open span of set columns of element row i, the
+ *             anchor is (kw / 2, kh / 2); kh = 0 skips the step.  Dilate ORs, erode ANDs over the offsets (i - kh / 2, j - kw / 2);
+ *             pixels outside the image never contribute to a dilate and never restrict an erode.  gs360/maskfinish.py's
+ *             structuring_rows builds cv2.getStructuringElement(MORPH_ELLIPSE)'s rows.
+ *   fuse      f = fuse (0 skips), s = spread: in every column with a set row among rows [0, f) the rows above the topmost one are
+ *             set, likewise below the lowest one of rows [H - f, H); the mask's columns [0, f) and [W - f, W), each spread s rows
+ *             up and down, set per row the columns left of the leftmost (right of the rightmost) one.  All four read the mask as it
+ *             enters the step.
+ *   output    GS360_MASK_OUT_MASK: H x W, `invert ? 0 : 255` where set, else the other; _RGBA: H x W x 4, the image's RGB and that
+ *             value as alpha; _KEEP / _REMOVE: H x W x 3, the image where set / not set, zero elsewhere.  A mask without a set pixel
+ *             takes the reference's `mask is None` branches: alpha 0 everywhere, the image unchanged.  `image` is H x W x 3 and
+ *             needed by all kinds but _MASK.  Strides in bytes, 0 = tight.
+ * counts_dev (device memory) receives each job's number of set pixels.  scratch_dev: device memory of at least
+ * gs360_mask_finish_scratch's bytes for the same jobs, 256-byte aligned; the call stages the element rows into it and waits for that
+ * copy, the kernels are asynchronous on `slot`.  n_jobs may exceed GS360_MAX_VIEWS (split internally); the jobs of a call may differ
+ * in everything.
+ * Errors: GS360_ERR_UNSUPPORTED for a side above 32768, an element side above 1025, fuse or spread above 1024 (a lane of the side
+ * strips reads 2 spread + 1 rows of fuse / 32 dwords); GS360_ERR_ARG for NULL or inconsistent
+ * pointers, a stride below a row, a span outside its element, fuse > min(H, W), an unknown kind, a scratch that is too small.
+ * Nothing is written then. */
+#define GS360_MASK_OUT_MASK 0
+#define GS360_MASK_OUT_RGBA 1
+#define GS360_MASK_OUT_KEEP 2
+#define GS360_MASK_OUT_REMOVE 3
+#define GS360_MASK_MAX_SIDE 32768
+#define GS360_MASK_MAX_ELEMENT 1025
+#define GS360_MASK_MAX_FUSE 1024
+typedef struct gs360_mask_job {
+    const void *src;            /* H x W uint8 raw mask, or NULL */
+    size_t src_stride;
+    const void *add;            /* H x W uint8 manual add layer, or NULL */
+    size_t add_stride;
+    const void *image;          /* H x W x 3 uint8, or NULL for GS360_MASK_OUT_MASK */
+    size_t image_stride;
+    void *dst;
+    size_t dst_stride;
+    int32_t H, W, thresh;
+    int32_t close_kw, close_kh;
+    int32_t expand_kw, expand_kh;
+    int32_t fuse, spread;
+    int32_t kind, invert;
+    int32_t pad;
+    const int32_t *close_rows;  /* host memory: close_kh x (j1, j2) */
+    const int32_t *expand_rows; /* host memory: expand_kh x (j1, j2) */
+} gs360_mask_job;
+int gs360_mask_finish_scratch(const gs360_mask_job *jobs, int n_jobs, size_t *bytes);
+int gs360_mask_finish_u8(gs360_ctx *ctx, const gs360_mask_job *jobs, int n_jobs, void *scratch_dev, size_t scratch_bytes,
+                         uint32_t *counts_dev, int slot);
+
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
                                  const gs360_view *views, int n_views,
