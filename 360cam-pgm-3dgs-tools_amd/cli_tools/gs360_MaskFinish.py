@@ -10,9 +10,12 @@ manual layer is), or there are none and the manual layers of --manual-mask-dir (
 
 Outputs: `<stem>.png` (mask, alpha), `<stem>_cutout.png`, `<stem>_<mode>.png` (SEG:740-781), written by the device PNG encoder with
 GS360_PNG_ENCODER=device, else by gs360/imageio.py.  Every image is looked at before the first one is finished, so a run that ends
-with an [ERR] line has written nothing.  Not built, and refused with one [ERR] line each: --mode inpaint (Telea inpainting),
---include_shadow (the contour-filtered shadow estimate), 16-bit images in the compose modes, --edge-fuse-pixels above an image's
-shorter side or above 1024, an expansion above 512 pixels, an image side above 32768.
+with an [ERR] line has written nothing.  --include_shadow adds the reference's shadow estimate (SEG:499-558, MSK-SHADOW v1) between
+the close and the expansion when the environment says GS360_MASK_SHADOW=device; the estimate is not pinned against cv2 yet, so
+without that variable the flag is refused as before.  It reads the images in every mode.  Not built, and refused with one [ERR]
+line each: --mode inpaint (Telea inpainting), --include_shadow without GS360_MASK_SHADOW=device, 16-bit images in the compose modes
+and with the shadow estimate, --edge-fuse-pixels above an image's shorter side or above 1024, an expansion above 512 pixels, an image
+side above 32768.
 """
 import argparse
 import sys
@@ -41,7 +44,9 @@ def create_arg_parser():
                     help="what to write: the mask (target black), the image with the mask as alpha, the cutout, or the image with the "
                          "target kept / blacked out; inpaint is not built")
     ap.add_argument("--close", type=int, default=5, help="side of the ellipse that closes small holes first (1 or less: no closing)")
-    ap.add_argument("--include_shadow", action="store_true", help="not built: ends the run with an [ERR] line")
+    ap.add_argument("--include_shadow", action="store_true",
+                    help="add the estimated cast shadow to the mask; runs with GS360_MASK_SHADOW=device in the environment, else ends "
+                         "the run with an [ERR] line")
     ap.add_argument("--mask-expand-mode", type=str, choices=["pixels", "percent"], default="pixels",
                     help="grow the mask by --mask-expand-pixels, or by --mask-expand-percent of the image's longer side")
     ap.add_argument("--mask-expand-pixels", type=int, default=15, help="growth in pixels (mode pixels)")
@@ -80,9 +85,9 @@ def read_layer(path, size):
         return ((np.asarray(gray) > LAYER_THRESH) * np.uint8(255)).astype(np.uint8)
 
 
-def survey(images, params, kind, mode):
-    """every image's (W, H) and, for the compose modes, whether it is an 8-bit image -> (sizes, None) or (None, the reason this
-    build does not take the run)"""
+def survey(images, params, kind, mode, shadow=False):
+    """every image's (W, H) and, for the compose modes and the shadow estimate, whether it is an 8-bit image -> (sizes, None) or
+    (None, the reason this build does not take the run)"""
     from PIL import Image
     from gs360 import capi, maskfinish
     sizes = []
@@ -91,6 +96,8 @@ def survey(images, params, kind, mode):
             sizes.append(im.size)                         # the header alone: the mask mode never reads pixels
             if kind != "mask" and im.mode.startswith("I"):
                 return None, f"{path.name}: 16-bit images are not built for --mode {mode}"
+            if shadow and im.mode.startswith("I"):
+                return None, f"{path.name}: 16-bit images are not built for --include_shadow"
     try:
         jobs, _rows = maskfinish.build_jobs([(h, w) for w, h in sizes], params, kind)
     except ValueError as exc:
@@ -120,7 +127,13 @@ def main(argv=None):
     if args.mode == "inpaint":
         return fail("--mode inpaint is not built: Telea inpainting is not part of this tool")
     if args.include_shadow:
-        return fail("--include_shadow is not built: the contour-filtered shadow estimate is not part of this tool")
+        from gs360 import maskfinish
+        try:
+            on_device = maskfinish.shadow_mode_from_env()
+        except ValueError as exc:
+            return fail(str(exc))
+        if not on_device:
+            return fail("--include_shadow is not built: the contour-filtered shadow estimate is not part of this tool")
 
     input_dir = Path(args.input_dir)
     if not input_dir.is_dir():
@@ -153,7 +166,7 @@ def main(argv=None):
     kind, invert, suffix = OUTPUTS[args.mode]
     params = maskfinish.Params(close=args.close, expand_mode=args.mask_expand_mode, expand_pixels=args.mask_expand_pixels,
                                expand_percent=args.mask_expand_percent, edge_fuse_pixels=args.edge_fuse_pixels, thresh=LAYER_THRESH)
-    sizes, reason = survey(images, params, kind, args.mode)
+    sizes, reason = survey(images, params, kind, args.mode, args.include_shadow)
     if reason:
         return fail(reason)
     device_png = pngenc.mode_from_env()
@@ -167,13 +180,16 @@ def main(argv=None):
                 adds = [read_layer(manual_dir / f"{maskfinish.manual_key(p)}__add.png", size) if manual_dir is not None else None
                         for p, size in batch]
                 pixels = None
-                if kind != "mask":
+                if kind != "mask" or args.include_shadow:
                     pixels = []
                     for p, _size in batch:
                         with Image.open(p) as im:
                             pixels.append(np.asarray(im.convert("RGB")))
                 with ctx.slot_locks[0]:
-                    items, _counts = maskfinish.finish_device(ctx, masks, params, adds, pixels, kind, invert)
+                    if args.include_shadow:
+                        items, _counts = maskfinish.finish_with_shadow_device(ctx, masks, params, None, adds, pixels, kind, invert)
+                    else:
+                        items, _counts = maskfinish.finish_device(ctx, masks, params, adds, pixels, kind, invert)
                     try:
                         if device_png:
                             files = pngenc.encode_buffers(ctx, items)

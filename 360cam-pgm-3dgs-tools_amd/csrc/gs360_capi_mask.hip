@@ -1,5 +1,5 @@
-// gs360_capi_mask.hip -- the mask-finishing entry points of libgs360hip.so (include/gs360.h; MSK-SPEC v1):
-// validation, the scratch layout and the launch sequence of the kernels in gs360_maskmorph.hip.
+// gs360_capi_mask.hip -- the mask-finishing entry points of libgs360hip.so (include/gs360.h; MSK-SPEC v1 and MSK-SHADOW v1, DESIGN.md
+// section 14): validation, the scratch layout and the launch sequence of the kernels in gs360_maskmorph.hip and gs360_maskshadow.hip.
 #include "gs360_capi_internal.h"
 
 using namespace gs360;
@@ -7,7 +7,8 @@ using namespace gs360;
 namespace {
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline size_t plane_bytes(const gs360_mask_job& j) { return round_up((size_t)j.H * ((size_t)(j.W + 31) / 32) * 4, 256); }
+inline size_t plane_bytes(int H, int W) { return round_up((size_t)H * ((size_t)(W + 31) / 32) * 4, 256); }
+inline size_t plane_bytes(const gs360_mask_job& j) { return plane_bytes(j.H, j.W); }
 inline size_t rows_bytes(int kh) { return round_up((size_t)kh * 8, 256); }
 
 // the largest |column offset| an element reaches, or -1 for a span outside the element
@@ -71,18 +72,19 @@ int check_jobs(const gs360_mask_job* jobs, int n_jobs, size_t* need) {
 }
 
 // row tiles of a job: workgroups of `px` pixels by `rows` rows
-int64_t row_tiles(MkJob& J, int px, int rows) {
+template <class Job>
+int64_t row_tiles(Job& J, int px, int rows) {
     J.tiles_x = (J.W + px - 1) / px;
     return (int64_t)J.tiles_x * ((J.H + rows - 1) / rows);
 }
 
 // one step over the batch: `tiles_of(k, J)` sets the step's fields of job k and returns its tiles (0: the job skips the step); the
 // jobs' tiles are numbered in job order
-template <class Tiles>
-int run_step(MkLaunch& L, hipError_t (*launch)(const MkLaunch&, hipStream_t), hipStream_t s, Tiles tiles_of) {
+template <class Launch, class Fn, class Tiles>
+int run_step(Launch& L, Fn launch, hipStream_t s, Tiles tiles_of) {
     int64_t tiles = 0;
     for (int k = 0; k < L.n_jobs; ++k) {
-        MkJob& J = L.job[k];
+        auto& J = L.job[k];
         J.tile_base = (int32_t)tiles;
         J.tiles_x = 1;
         tiles += tiles_of(k, J);
@@ -184,5 +186,260 @@ int gs360_mask_finish_u8(gs360_ctx* c, const gs360_mask_job* jobs, int n_jobs, v
                 })) return rc;
         }
     }
+    return GS360_OK;
+}
+
+// ---- the shadow estimate (MSK-SHADOW v1): gs360_maskshadow.hip's kernels around the morph kernel above ---------------------------
+namespace {
+
+// a job's area of the scratch; it depends on H and W alone, so both calls and the caller find a job's planes in the same place
+enum { kShP, kShC0, kShC1, kShC2, kShClean, kShSat, kShT0, kShT1, kShPlanes };
+constexpr size_t kShHead = 256;                           // the call's error word, in front of the first job's area
+struct ShadowArea {
+    size_t plane, gray, mid, area, weights, sdiv, rows[4], total;   // rows: close, near, shadow close, open
+};
+ShadowArea shadow_area(int H, int W) {
+    ShadowArea a;
+    size_t at = kShPlanes * plane_bytes(H, W);
+    a.plane = plane_bytes(H, W);
+    a.gray = at; at += round_up((size_t)H * ((size_t)(W + 31) / 32) * 32, 256);
+    a.mid = at; at += round_up((size_t)H * W * 4, 256);
+    a.area = at; at += round_up((size_t)H * W * 4, 256);
+    a.weights = at; at += round_up((size_t)(kMsMaxR + 1) * 4, 256);
+    a.sdiv = at; at += 1024;
+    for (int e = 0; e < 4; ++e) { a.rows[e] = at; at += rows_bytes(GS360_MASK_MAX_ELEMENT); }
+    a.total = at;
+    return a;
+}
+
+int check_shadow_job(int k, const gs360_shadow_job& j, bool merge) {
+    if (j.H < 1 || j.W < 1) return fail(GS360_ERR_ARG, "job %d: image of %d x %d", k, j.W, j.H);
+    if (j.H > GS360_MASK_MAX_SIDE || j.W > GS360_MASK_MAX_SIDE)
+        return fail(GS360_ERR_UNSUPPORTED, "job %d: image sides are 1..%d (got %d x %d)", k, GS360_MASK_MAX_SIDE, j.W, j.H);
+    if ((int64_t)j.H * j.W > GS360_SHADOW_MAX_PIXELS)
+        return fail(GS360_ERR_UNSUPPORTED, "job %d: %d x %d is above 2^30 pixels (labels are 32-bit, areas are doubled)", k, j.W, j.H);
+    if (j.radius < 0) return fail(GS360_ERR_ARG, "job %d: filter radius %d", k, j.radius);
+    if (j.radius > GS360_SHADOW_MAX_RADIUS) return fail(GS360_ERR_UNSUPPORTED, "job %d: filter radius %d above %d", k, j.radius, GS360_SHADOW_MAX_RADIUS);
+    if ((j.src_stride && j.src_stride < (size_t)j.W) || (j.image_stride && j.image_stride < (size_t)j.W * 3) || (j.dst_stride && j.dst_stride < (size_t)j.W))
+        return fail(GS360_ERR_ARG, "job %d: a stride below a row", k);
+    if (!merge) {
+        if (!j.image || !j.weights || !j.sdiv) return fail(GS360_ERR_ARG, "job %d: NULL image, weights or divisor table", k);
+        if (j.thresh < 0 || j.thresh > 255) return fail(GS360_ERR_ARG, "job %d: thresh %d outside 0..255", k, j.thresh);
+        return check_element(k, "close", j.close_kw, j.close_kh, j.close_rows);
+    }
+    if (!j.dst) return fail(GS360_ERR_ARG, "job %d: NULL output", k);
+    if (j.near_kh < 1 || j.sclose_kh < 1 || j.open_kh < 1) return fail(GS360_ERR_ARG, "job %d: the merge needs its three elements", k);
+    if (int rc = check_element(k, "near", j.near_kw, j.near_kh, j.near_rows)) return rc;
+    if (int rc = check_element(k, "shadow close", j.sclose_kw, j.sclose_kh, j.sclose_rows)) return rc;
+    return check_element(k, "open", j.open_kw, j.open_kh, j.open_rows);
+}
+
+int check_shadow_jobs(const gs360_shadow_job* jobs, int n_jobs, bool merge, size_t* need) {
+    if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
+    if (n_jobs && !jobs) return fail(GS360_ERR_ARG, "NULL argument");
+    *need = kShHead;
+    for (int k = 0; k < n_jobs; ++k) {
+        if (int rc = check_shadow_job(k, jobs[k], merge)) return rc;
+        *need += shadow_area(jobs[k].H, jobs[k].W).total;
+    }
+    return 0;
+}
+
+int check_shadow_call(gs360_ctx* c, const gs360_shadow_job* jobs, int n_jobs, bool merge, void* scratch_dev, size_t scratch_bytes,
+                      uint32_t* counts_dev, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    size_t need = 0;
+    if (int rc = check_shadow_jobs(jobs, n_jobs, merge, &need)) return rc;
+    if (n_jobs == 0) return 0;
+    if (!scratch_dev || !counts_dev) return fail(GS360_ERR_ARG, "NULL argument");
+    if ((uintptr_t)scratch_dev % 256) return fail(GS360_ERR_ARG, "scratch is not 256-byte aligned");
+    if (scratch_bytes < need) return fail(GS360_ERR_ARG, "scratch of %zu bytes below the %zu the jobs need", scratch_bytes, need);
+    return 0;
+}
+
+// the jobs [k0, k0 + n) of a call as one launch of either family; base[k]: the job's area of the scratch
+struct ShadowBatch {
+    MkLaunch mk;
+    MsLaunch ms;
+    uint8_t* base[GS360_MAX_VIEWS];
+    ShadowArea area[GS360_MAX_VIEWS];
+    uint32_t* plane(int k, int which) const { return (uint32_t*)(base[k] + (size_t)which * area[k].plane); }
+    const int32_t* rows(int k, int e) const { return (const int32_t*)(base[k] + area[k].rows[e]); }
+};
+void shadow_batch(ShadowBatch& B, const gs360_shadow_job* jobs, int n, uint8_t* at, uint32_t* counts, uint32_t* err) {
+    std::memset(&B.mk, 0, sizeof(B.mk));
+    std::memset(&B.ms, 0, sizeof(B.ms));
+    B.mk.n_jobs = B.ms.n_jobs = n;
+    B.mk.counts = B.ms.counts = counts;
+    B.ms.err = err;
+    for (int k = 0; k < n; ++k) {
+        const gs360_shadow_job& j = jobs[k];
+        B.base[k] = at;
+        B.area[k] = shadow_area(j.H, j.W);
+        at += B.area[k].total;
+        MkJob& K = B.mk.job[k];
+        K.src = (const uint8_t*)j.src;
+        K.src_stride = (int64_t)(j.src_stride ? j.src_stride : (size_t)j.W);
+        K.H = j.H; K.W = j.W; K.pw = (j.W + 31) / 32; K.thresh = j.thresh;
+        MsJob& S = B.ms.job[k];
+        S.img = (const uint8_t*)j.image; S.dst = (uint8_t*)j.dst;
+        S.img_stride = (int64_t)(j.image_stride ? j.image_stride : (size_t)j.W * 3);
+        S.dst_stride = (int64_t)(j.dst_stride ? j.dst_stride : (size_t)j.W);
+        S.gray = B.base[k] + B.area[k].gray;
+        S.mid = (float*)(B.base[k] + B.area[k].mid); S.lab = (int32_t*)S.mid;
+        S.area = (uint32_t*)(B.base[k] + B.area[k].area);
+        S.k = (const float*)(B.base[k] + B.area[k].weights); S.sdiv = (const int32_t*)(B.base[k] + B.area[k].sdiv);
+        S.H = j.H; S.W = j.W; S.pw = K.pw; S.r = j.radius;
+        S.t = j.t; S.delta_min = j.delta_min; S.sat_max = j.sat_max;
+        S.th2 = (uint32_t)std::min<int64_t>(2 * (int64_t)std::max(1, j.min_area), UINT32_MAX);
+    }
+}
+// one dilate or erode of every job of the batch: plane `from` -> plane `to` by element e of the job's staged rows
+int shadow_morph(ShadowBatch& B, hipStream_t s, int from, int to, int e, const int* kw, const int* kh, const int* halo, int flags) {
+    return run_step(B.mk, launch_mask_morph, s, [&](int k, MkJob& J) -> int64_t {
+        J.in = B.plane(k, from); J.out = B.plane(k, to);
+        J.spans = B.rows(k, e); J.kh = kh[k]; J.ax = kw[k] / 2; J.ay = kh[k] / 2; J.halo = halo[k]; J.flags = flags;
+        if (!kh[k]) return 0;
+        J.tiles_x = (J.pw + kMkTileW - 1) / kMkTileW;
+        return (int64_t)J.tiles_x * ((J.H + kMkTileR - 1) / kMkTileR);
+    });
+}
+// one step of gs360_maskshadow.hip over the batch
+template <class Tiles>
+int shadow_step(ShadowBatch& B, hipStream_t s, MsStep step, Tiles tiles_of) {
+    return run_step(B.ms, [step](const MsLaunch& L, hipStream_t st) { return launch_mask_shadow(step, L, st); }, s, tiles_of);
+}
+int64_t items_tiles(int64_t items) { return (items + kMsThreads - 1) / kMsThreads; }
+
+// labels of plane `which` (or of its complement) of every job: init, merge with connectivity `conn`, flatten
+int shadow_label(ShadowBatch& B, hipStream_t s, int which, int conn, int flags) {
+    B.ms.conn = conn;
+    for (MsStep step : {kMsLabelInit, kMsLabelMerge, kMsLabelFlatten})
+        if (int rc = shadow_step(B, s, step, [&](int k, MsJob& J) {
+                J.a = B.plane(k, which); J.flags = flags;
+                return items_tiles((int64_t)J.H * J.pw);
+            })) return rc;
+    return 0;
+}
+
+}  // namespace
+
+int gs360_mask_shadow_scratch(const gs360_shadow_job* jobs, int n_jobs, size_t* bytes) {
+    if (!bytes) return fail(GS360_ERR_ARG, "NULL argument");
+    size_t need = 0;
+    if (int rc = check_shadow_jobs(jobs, n_jobs, false, &need)) return rc;
+    *bytes = need;
+    return GS360_OK;
+}
+
+int gs360_mask_shadow_candidates_u8(gs360_ctx* c, const gs360_shadow_job* jobs, int n_jobs, void* scratch_dev, size_t scratch_bytes,
+                                    uint32_t* counts_dev, int slot) {
+    if (int rc = check_shadow_call(c, jobs, n_jobs, false, scratch_dev, scratch_bytes, counts_dev, slot)) return rc;
+    if (n_jobs == 0) return GS360_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream[slot];
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_jobs * sizeof(uint32_t), s));
+    uint8_t* at = (uint8_t*)scratch_dev + kShHead;
+    for (int k = 0; k < n_jobs; ++k) {                    // the host tables of every job
+        const gs360_shadow_job& j = jobs[k];
+        const ShadowArea a = shadow_area(j.H, j.W);
+        HIP_TRY(hipMemcpyAsync(at + a.weights, j.weights, (size_t)(j.radius + 1) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(at + a.sdiv, j.sdiv, 1024, hipMemcpyHostToDevice, s));
+        if (j.close_kh) HIP_TRY(hipMemcpyAsync(at + a.rows[0], j.close_rows, (size_t)j.close_kh * 8, hipMemcpyHostToDevice, s));
+        at += a.total;
+    }
+    HIP_TRY(hipStreamSynchronize(s));                     // the caller's tables are read
+    at = (uint8_t*)scratch_dev + kShHead;
+    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
+        const int n = std::min(GS360_MAX_VIEWS, n_jobs - k0);
+        ShadowBatch B;
+        shadow_batch(B, jobs + k0, n, at, counts_dev + k0, (uint32_t*)scratch_dev);
+        int kw[GS360_MAX_VIEWS], kh[GS360_MAX_VIEWS], halo[GS360_MAX_VIEWS];
+        for (int k = 0; k < n; ++k) {
+            const gs360_shadow_job& j = jobs[k0 + k];
+            kw[k] = j.close_kw; kh[k] = j.close_kh;
+            halo[k] = kh[k] ? element_reach(j.close_rows, kw[k], kh[k]) / 32 + 2 : 0;
+            at += B.area[k].total;
+        }
+        // P: MSK-SPEC steps 0-1 (pack, close); a job without a close packs straight into P
+        if (int rc = run_step(B.mk, launch_mask_pack_bits, s, [&](int k, MkJob& J) { J.out = B.plane(k, kh[k] ? kShT0 : kShP); return row_tiles(J, 4 * kMkThreads, 1); })) return rc;
+        if (int rc = shadow_morph(B, s, kShT0, kShT1, 0, kw, kh, halo, 0)) return rc;
+        if (int rc = shadow_morph(B, s, kShT1, kShP, 0, kw, kh, halo, kMkCompIn | kMkCompOut)) return rc;
+        B.mk.phase = 0;                                   // count(P): the finishing chain's counting pass without an add layer
+        if (int rc = run_step(B.mk, launch_mask_finish, s, [&](int k, MkJob& J) { J.out = B.plane(k, kShP); return row_tiles(J, 4 * kMkThreads, kMkFinishRows); })) return rc;
+        if (int rc = shadow_step(B, s, kMsPixel, [&](int k, MsJob& J) { J.out = B.plane(k, kShSat); return row_tiles(J, 4 * kMsThreads, 1); })) return rc;
+        if (int rc = shadow_step(B, s, kMsBlurRows, [&](int, MsJob& J) { return row_tiles(J, kMsRowSeg, 1); })) return rc;
+        if (int rc = shadow_step(B, s, kMsBlurCols, [&](int k, MsJob& J) {
+                J.a = B.plane(k, kShSat); J.out = B.plane(k, kShC0);
+                return row_tiles(J, kMsColW, kMsColRows);
+            })) return rc;
+    }
+    return GS360_OK;
+}
+
+int gs360_mask_shadow_merge_u8(gs360_ctx* c, const gs360_shadow_job* jobs, int n_jobs, void* scratch_dev, size_t scratch_bytes,
+                               uint32_t* counts_dev, int slot) {
+    if (int rc = check_shadow_call(c, jobs, n_jobs, true, scratch_dev, scratch_bytes, counts_dev, slot)) return rc;
+    if (n_jobs == 0) return GS360_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream[slot];
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_jobs * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(scratch_dev, 0, kShHead, s));
+    uint8_t* at = (uint8_t*)scratch_dev + kShHead;
+    for (int k = 0; k < n_jobs; ++k) {                    // the three elements of every job
+        const gs360_shadow_job& j = jobs[k];
+        const ShadowArea a = shadow_area(j.H, j.W);
+        HIP_TRY(hipMemcpyAsync(at + a.rows[1], j.near_rows, (size_t)j.near_kh * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(at + a.rows[2], j.sclose_rows, (size_t)j.sclose_kh * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(at + a.rows[3], j.open_rows, (size_t)j.open_kh * 8, hipMemcpyHostToDevice, s));
+        at += a.total;
+    }
+    HIP_TRY(hipStreamSynchronize(s));                     // the caller's element rows are read
+    at = (uint8_t*)scratch_dev + kShHead;
+    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
+        const int n = std::min(GS360_MAX_VIEWS, n_jobs - k0);
+        ShadowBatch B;
+        shadow_batch(B, jobs + k0, n, at, counts_dev + k0, (uint32_t*)scratch_dev);
+        int kw[3][GS360_MAX_VIEWS], kh[3][GS360_MAX_VIEWS], halo[3][GS360_MAX_VIEWS];
+        for (int k = 0; k < n; ++k) {
+            const gs360_shadow_job& j = jobs[k0 + k];
+            const int w[3] = {j.near_kw, j.sclose_kw, j.open_kw}, h[3] = {j.near_kh, j.sclose_kh, j.open_kh};
+            const int32_t* rows[3] = {j.near_rows, j.sclose_rows, j.open_rows};
+            for (int e = 0; e < 3; ++e) { kw[e][k] = w[e]; kh[e][k] = h[e]; halo[e][k] = element_reach(rows[e], w[e], h[e]) / 32 + 2; }
+            at += B.area[k].total;
+        }
+        auto clear_area = [&]() {
+            for (int k = 0; k < n; ++k) HIP_TRY(hipMemsetAsync(B.ms.job[k].area, 0, (size_t)B.ms.job[k].H * B.ms.job[k].W * 4, s));
+            return 0;
+        };
+        const int both = kMkCompIn | kMkCompOut;
+        if (int rc = shadow_morph(B, s, kShP, kShT0, 1, kw[0], kh[0], halo[0], 0)) return rc;                  // step 4: the near region
+        if (int rc = shadow_step(B, s, kMsLogic, [&](int k, MsJob& J) {
+                J.a = B.plane(k, kShC0); J.b = B.plane(k, kShT0); J.c = B.plane(k, kShP); J.out = B.plane(k, kShC1);
+                return items_tiles((int64_t)J.H * J.pw);
+            })) return rc;
+        if (int rc = shadow_morph(B, s, kShC1, kShT0, 2, kw[1], kh[1], halo[1], 0)) return rc;                 // step 5: close ...
+        if (int rc = shadow_morph(B, s, kShT0, kShT1, 2, kw[1], kh[1], halo[1], both)) return rc;
+        if (int rc = shadow_morph(B, s, kShT1, kShT0, 3, kw[2], kh[2], halo[2], both)) return rc;              // ... and open
+        if (int rc = shadow_morph(B, s, kShT0, kShC2, 3, kw[2], kh[2], halo[2], 0)) return rc;
+        if (int rc = clear_area()) return rc;                                                                  // step 6: O, G = ~O in T1
+        if (int rc = shadow_label(B, s, kShC2, 4, kMsComplement)) return rc;
+        if (int rc = shadow_step(B, s, kMsBorder, [&](int, MsJob& J) { return items_tiles(2 * (int64_t)J.W + 2 * (int64_t)J.H); })) return rc;
+        if (int rc = shadow_step(B, s, kMsFill, [&](int k, MsJob& J) { J.out = B.plane(k, kShT1); return row_tiles(J, kMsThreads, 1); })) return rc;
+        if (int rc = clear_area()) return rc;
+        if (int rc = shadow_label(B, s, kShT1, 8, 0)) return rc;
+        if (int rc = shadow_step(B, s, kMsArea, [&](int k, MsJob& J) {
+                J.a = B.plane(k, kShT1);
+                return J.H < 2 ? 0 : items_tiles((int64_t)J.pw * ((J.H - 1 + kMsAreaRows - 1) / kMsAreaRows));
+            })) return rc;
+        if (int rc = shadow_step(B, s, kMsSelect, [&](int k, MsJob& J) {                                       // steps 6-7: clean, M and its count
+                J.a = B.plane(k, kShT1); J.b = B.plane(k, kShP); J.out = B.plane(k, kShClean);
+                return row_tiles(J, 4 * kMsThreads, kMsSelectRows);
+            })) return rc;
+    }
+    uint32_t err = 0;                                     // a label walk past its bound: the result is not to be used
+    HIP_TRY(hipMemcpyAsync(&err, scratch_dev, sizeof(err), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err) return fail(GS360_ERR_INTERNAL, "a label walk ran past its bound");
     return GS360_OK;
 }

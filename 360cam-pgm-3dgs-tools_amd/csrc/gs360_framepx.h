@@ -1,12 +1,12 @@
 // gs360_framepx.h -- FS-SPEC's per-pixel steps, shared by the FrameSelector passes (gs360_framescore.hip, gs360_framefft.hip,
-// gs360_frameflow.hip).  Private to those files.
+// gs360_frameflow.hip).  Private to those files; gs360_maskshadow.hip takes gray_of from here, the library's one 8-bit gray.
 #pragma once
 #include "gs360_kernels.h"
 
 namespace gs360 {
 
 template <int C>
-__device__ __forceinline__ int gray_of(const uint8_t* p, int red) {
+__host__ __device__ __forceinline__ int gray_of(const uint8_t* p, int red) {
     if constexpr (C == 1) {
         return p[0];
     } else {

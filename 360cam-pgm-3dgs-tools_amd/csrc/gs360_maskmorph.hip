@@ -22,15 +22,9 @@
 // (MK_HD) so that tests/tools/maskmorph_hostcheck.hip can step it under a sanitizer.
 #include "gs360_kernels.h"
 
-#define MK_HD __host__ __device__
-
 namespace gs360 {
 namespace {
 
-MK_HD inline uint32_t mk_colmask(int W, int w) {         // the columns of dword w that lie inside the image
-    const int left = W - 32 * w;
-    return left >= 32 ? 0xffffffffu : left <= 0 ? 0u : (0xffffffffu >> (32 - left));
-}
 MK_HD inline int mk_ctz(uint32_t v) { return __builtin_ctz(v); }
 MK_HD inline int mk_clz(uint32_t v) { return __builtin_clz(v); }
 
@@ -228,13 +222,7 @@ __device__ __forceinline__ void mk_row_tile(const MkJob& J, int t, int* y, int* 
     *y = t / J.tiles_x;
     *x0 = (t - *y * J.tiles_x) * kMkThreads;
 }
-// eight neighbouring lanes' nibbles as the dword of the plane they cover (in all eight lanes)
-__device__ __forceinline__ uint32_t mk_gather8(uint32_t nib) {
-    uint32_t v = nib << (4 * (threadIdx.x & 7));
-    v |= __shfl_xor(v, 1, 64); v |= __shfl_xor(v, 2, 64); v |= __shfl_xor(v, 4, 64);
-    return v;
-}
-// ... stored by the first of them
+// eight lanes' dword of the plane (mk_gather8, gs360_kernels.h), stored by the first of them
 __device__ __forceinline__ void mk_store_word(const MkJob& J, int y, int x, uint32_t word) {
     if ((threadIdx.x & 7) == 0 && (x >> 5) < J.pw) J.out[(int64_t)y * J.pw + (x >> 5)] = word;
 }

@@ -36,6 +36,7 @@ EXPORTS = (
     "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound", "gs360_jpeg_scan_opt_u8", "gs360_jpeg_huff_tables",
     "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub", "gs360_jpeg_decode_u8", "gs360_jpeg_decode_scratch",
     "gs360_jpeg_decode_gray_u8", "gs360_png_deflate", "gs360_png_bound", "gs360_mask_finish_u8", "gs360_mask_finish_scratch",
+    "gs360_mask_shadow_scratch", "gs360_mask_shadow_candidates_u8", "gs360_mask_shadow_merge_u8",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -52,6 +53,9 @@ MASK_OUT_MASK, MASK_OUT_RGBA, MASK_OUT_KEEP, MASK_OUT_REMOVE = 0, 1, 2, 3   # GS
 MASK_MAX_SIDE = 32768                # GS360_MASK_MAX_SIDE / GS360_MASK_MAX_ELEMENT: the largest mask side and element side
 MASK_MAX_ELEMENT = 1025
 MASK_MAX_FUSE = 1024                 # GS360_MASK_MAX_FUSE: the largest edge-fuse strip (and spread)
+SHADOW_MAX_PIXELS = 1 << 30          # GS360_SHADOW_MAX_PIXELS / GS360_SHADOW_MAX_RADIUS: the shadow estimate's largest image and filter radius
+SHADOW_MAX_RADIUS = 255
+ERR_INTERNAL = -6                    # GS360_ERR_INTERNAL: a kernel's own bound was exceeded
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
@@ -113,6 +117,18 @@ class MaskJob(C.Structure):
                 ("expand_kw", C.c_int32), ("expand_kh", C.c_int32), ("fuse", C.c_int32), ("spread", C.c_int32),
                 ("kind", C.c_int32), ("invert", C.c_int32), ("pad", C.c_int32),
                 ("close_rows", C.c_void_p), ("expand_rows", C.c_void_p)]
+
+
+class ShadowJob(C.Structure):
+    """gs360_shadow_job: one image of the two shadow-estimate calls (device pointers; the tables and element rows are host arrays)."""
+    _fields_ = [("image", C.c_void_p), ("image_stride", C.c_size_t), ("src", C.c_void_p), ("src_stride", C.c_size_t),
+                ("dst", C.c_void_p), ("dst_stride", C.c_size_t),
+                ("H", C.c_int32), ("W", C.c_int32), ("thresh", C.c_int32), ("close_kw", C.c_int32), ("close_kh", C.c_int32),
+                ("radius", C.c_int32), ("sat_max", C.c_int32), ("min_area", C.c_int32), ("t", C.c_float), ("delta_min", C.c_float),
+                ("near_kw", C.c_int32), ("near_kh", C.c_int32), ("sclose_kw", C.c_int32), ("sclose_kh", C.c_int32),
+                ("open_kw", C.c_int32), ("open_kh", C.c_int32),
+                ("close_rows", C.c_void_p), ("weights", C.c_void_p), ("sdiv", C.c_void_p),
+                ("near_rows", C.c_void_p), ("sclose_rows", C.c_void_p), ("open_rows", C.c_void_p)]
 
 
 class JpegDecJob(C.Structure):
@@ -253,6 +269,9 @@ def load_library(path=None):
         L.gs360_png_bound.argtypes = [i, i, i, i, C.POINTER(C.c_size_t)]
         L.gs360_mask_finish_scratch.argtypes = [C.POINTER(MaskJob), i, C.POINTER(C.c_size_t)]
         L.gs360_mask_finish_u8.argtypes = [vp, C.POINTER(MaskJob), i, vp, sz, vp, i]
+        L.gs360_mask_shadow_scratch.argtypes = [C.POINTER(ShadowJob), i, C.POINTER(C.c_size_t)]
+        L.gs360_mask_shadow_candidates_u8.argtypes = [vp, C.POINTER(ShadowJob), i, vp, sz, vp, i]
+        L.gs360_mask_shadow_merge_u8.argtypes = [vp, C.POINTER(ShadowJob), i, vp, sz, vp, i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -704,6 +723,32 @@ class Context:
             raise ValueError("scratch_bytes larger than the scratch buffer")
         arr = (MaskJob * max(len(jobs), 1))(*jobs)
         _check(self.L.gs360_mask_finish_u8(self.handle, arr, len(jobs), scratch.ptr, nbytes, counts.ptr, slot), self.L)
+
+    def mask_shadow_scratch(self, jobs):
+        """gs360_mask_shadow_scratch: jobs = sequence of ShadowJob -> the bytes of scratch the two shadow calls on them share"""
+        n = C.c_size_t(0)
+        arr = (ShadowJob * max(len(jobs), 1))(*jobs)
+        _check(self.L.gs360_mask_shadow_scratch(arr, len(jobs), C.byref(n)), self.L)
+        return int(n.value)
+
+    def _mask_shadow_call(self, fn, jobs, scratch, counts, slot, scratch_bytes):
+        if counts.nbytes < 4 * len(jobs):
+            raise ValueError("counts buffer below 4 bytes per job")
+        nbytes = scratch.nbytes if scratch_bytes is None else int(scratch_bytes)
+        if nbytes > scratch.nbytes:
+            raise ValueError("scratch_bytes larger than the scratch buffer")
+        arr = (ShadowJob * max(len(jobs), 1))(*jobs)
+        _check(fn(self.handle, arr, len(jobs), scratch.ptr, nbytes, counts.ptr, slot), self.L)
+
+    def mask_shadow_candidates_dev(self, jobs, scratch, counts, slot=0, scratch_bytes=None):
+        """gs360_mask_shadow_candidates_u8: leaves P and C0 in `scratch` and count(P) per job in `counts` (DeviceBuffers);
+        asynchronous on `slot`"""
+        self._mask_shadow_call(self.L.gs360_mask_shadow_candidates_u8, jobs, scratch, counts, slot, scratch_bytes)
+
+    def mask_shadow_merge_dev(self, jobs, scratch, counts, slot=0, scratch_bytes=None):
+        """gs360_mask_shadow_merge_u8 on the scratch the candidates call left: M into every job's dst, count(M) into `counts`;
+        returns when the kernels are done"""
+        self._mask_shadow_call(self.L.gs360_mask_shadow_merge_u8, jobs, scratch, counts, slot, scratch_bytes)
 
     # -- JPEG files decoded into device images (gs360/jpegdec.py) ------------------------------
     def jpeg_decode_dev(self, jobs, status, slot=0):

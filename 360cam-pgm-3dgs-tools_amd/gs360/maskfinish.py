@@ -4,8 +4,15 @@ What gs360_SegmentationMaskTool.py runs on every image after the network (SEG:68
 larger one, fuse to the frame edges, OR in the manual add layer, count, and write the mask or compose it with the image.  The raw masks
 come from any segmenter (or none: manual layers alone); the network itself is not part of this package.  One gs360_mask_finish_u8 call
 (csrc/gs360_maskmorph.hip) finishes a batch; the elements reach the kernels as data, built here by structuring_rows.
+
+With the shadow estimate (MSK-SHADOW v1, SEG:499-558 between the close and the expansion) two more calls come first
+(csrc/gs360_maskshadow.hip): gs360_mask_shadow_candidates_u8 leaves the person plane, its count and the shadow candidates on the device,
+the host turns the count into element sizes (shadow_sizes), and gs360_mask_shadow_merge_u8 writes M = person | shadow, which the
+finishing call then reads from device memory.  The Gaussian's weights and the saturation divisors are data as well.
 """
+import dataclasses
 import math
+import os
 import pathlib
 from dataclasses import dataclass
 
@@ -103,6 +110,59 @@ class Params:
     thresh: int = 0
 
 
+@dataclass
+class ShadowParams:
+    """estimate_shadow_mask's parameters and their defaults (SEG:63-71)"""
+    t: float = 0.82
+    sigma: float = 21
+    near_px: int = 25
+    min_area: int = 160
+    delta_min: float = 12
+    sat_max: int = 115
+
+
+SHADOW_MAX_NEAR, SHADOW_NEAR_SCALE, SHADOW_CLOSE_SCALE = 128, 0.2, 0.2      # SEG:69-71
+
+
+def shadow_mode_from_env():
+    """-> True when --include_shadow runs the device estimate.  GS360_MASK_SHADOW = off (default: the flag is refused as before;
+    the estimate's parity with cv2 is not pinned) | device."""
+    mode = os.environ.get("GS360_MASK_SHADOW", "off")
+    if mode not in ("off", "device"):
+        raise ValueError(f"GS360_MASK_SHADOW must be off or device (got {mode!r})")
+    return mode == "device"
+
+
+def gaussian_weights(sigma):
+    """-> the float32 kernel cv2.GaussianBlur(float image, (0, 0), sigma) filters with along either axis, all ksize of it:
+    ksize = rint(8 sigma + 1) | 1 (OpenCV's rule for a source that is not 8-bit), exp(-x^2 / (2 sigma^2)) in double, divided by the
+    double sum, rounded to float32.  The kernels take the half from the centre outward."""
+    sigma = float(sigma)
+    if not sigma > 0:
+        raise ValueError(f"sigma must be positive (got {sigma})")
+    ksize = _rint(sigma * 8 + 1) | 1
+    x = np.arange(ksize, dtype=np.float64) - (ksize - 1) * 0.5
+    k = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    return (k / k.sum()).astype(np.float32)
+
+
+def sat_div_table():
+    """-> the 256 int32 divisors of cv2's 8-bit RGB2HSV saturation, S = (d sdiv[v] + 2048) >> 12: sdiv[0] = 0,
+    sdiv[i] = rint(1044480 / i) in double, a tie to the even one"""
+    t = np.zeros(256, np.int32)
+    t[1:] = np.rint(1044480.0 / np.arange(1, 256, dtype=np.float64)).astype(np.int32)
+    return t
+
+
+def shadow_sizes(count, near_px=25):
+    """person pixels -> (k, close_k): the sides of the near-region ellipse and of the closing ellipse, in the reference's own
+    expressions (SEG:527-540)"""
+    n = max(1, int(count))
+    near = int(max(int(near_px), min(SHADOW_MAX_NEAR, math.sqrt(n) * SHADOW_NEAR_SCALE)))
+    k = max(3, near | 1)
+    return k, max(5, int(round(k * SHADOW_CLOSE_SCALE)) | 1)
+
+
 def _rows_array(kw, kh, cache):
     if (kw, kh) not in cache:
         cache[(kw, kh)] = np.ascontiguousarray(structuring_rows(kw, kh)[0], dtype=np.int32)
@@ -137,34 +197,44 @@ def build_jobs(shapes, params, kind="mask", invert=True):
     return jobs, cache
 
 
+def _device_plane(ctx, a, shape, what, owned, slot):
+    """-> the device address of a uint8 array of `shape`: a DeviceBuffer's own, else that of a fresh upload, which joins `owned`"""
+    if isinstance(a, capi.DeviceBuffer):
+        return a.ptr
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    if a.shape != shape:
+        raise ValueError(f"{what} of shape {a.shape}, expected {shape}")
+    owned.append(ctx.to_device(a, slot))
+    return owned[-1].ptr
+
+
 def finish_device(ctx, masks, params=None, adds=None, images=None, kind="mask", invert=True, slot=0):
-    """(the caller holds `slot`) masks: per image an H x W uint8 ndarray or an (H, W) tuple (no detection: all clear) ->
+    """(the caller holds `slot`) masks: per image an H x W uint8 ndarray, an (H, W) tuple (no detection: all clear) or an
+    (H, W, DeviceBuffer) tuple (a mask that is on the device already) ->
     ([(DeviceBuffer, H, W, C, 1, 0)] outputs left on the device, in pngenc's item form, counts as a uint32 array).  adds: None or
-    per image None / an H x W uint8 layer (set where > 0); images: per image an H x W x 3 uint8 array, needed by every kind but
-    "mask".  The output buffers are the caller's to free."""
+    per image None / an H x W uint8 layer (set where > 0); images: per image an H x W x 3 uint8 array or a DeviceBuffer holding
+    one, needed by every kind but "mask".  The output buffers are the caller's to free; buffers that came in stay the caller's."""
     params = params or Params()
     n = len(masks)
     adds = list(adds) if adds is not None else [None] * n
     images = list(images) if images is not None else [None] * n
     if len(adds) != n or len(images) != n:
         raise ValueError("one add layer and one image per mask (or None)")
-    shapes = [tuple(m) if isinstance(m, tuple) else np.asarray(m).shape[:2] for m in masks]
+    shapes = [tuple(m[:2]) if isinstance(m, tuple) else np.asarray(m).shape[:2] for m in masks]
     jobs, keep = build_jobs(shapes, params, kind, invert)
     if not n:
         return [], np.zeros(0, np.uint32)
     owned, outs = [], []
 
     def plane(a, shape, what):
-        a = np.ascontiguousarray(a, dtype=np.uint8)
-        if a.shape != shape:
-            raise ValueError(f"{what} of shape {a.shape}, expected {shape}")
-        owned.append(ctx.to_device(a, slot))
-        return owned[-1].ptr
+        return _device_plane(ctx, a, shape, what, owned, slot)
     try:
         C = _CHANNELS[kind]
         for j, m, a, im, (H, W) in zip(jobs, masks, adds, images, shapes):
             if not isinstance(m, tuple):
                 j.src = plane(m, (H, W), "mask")
+            elif len(m) == 3:
+                j.src = m[2].ptr
             if a is not None:
                 j.add = plane(a, (H, W), "add layer")
             if kind != "mask":
@@ -194,6 +264,109 @@ def finish(ctx, masks, params=None, adds=None, images=None, kind="mask", invert=
     """finish_device with the outputs brought back: -> ([H x W (kind "mask") or H x W x C uint8 arrays], counts)"""
     with ctx.slot_locks[slot]:
         items, counts = finish_device(ctx, masks, params, adds, images, kind, invert, slot)
+        try:
+            return [ctx.download(o, (H, W) if C == 1 else (H, W, C), np.uint8, slot) for o, H, W, C, _b, _s in items], counts
+        finally:
+            for it in items:
+                ctx.free(it[0])
+
+
+def shadow_device(ctx, masks, images, params=None, shadow=None, slot=0):
+    """(the caller holds `slot`) the person masks of finish_device (ndarrays or (H, W) tuples) and their H x W x 3 uint8 images
+    (ndarrays or DeviceBuffers) -> ([DeviceBuffer of H x W bytes, 0 / 255] M = closed person mask | shadow estimate, counts of M as a
+    uint32 array).  params: the finishing Params (close and thresh are used here); shadow: ShadowParams.  The buffers are the
+    caller's to free."""
+    params, shadow = params or Params(), shadow or ShadowParams()
+    n = len(masks)
+    if len(images) != n:
+        raise ValueError("one image per mask")
+    if not n:
+        return [], np.zeros(0, np.uint32)
+    shapes = [tuple(m[:2]) if isinstance(m, tuple) else np.asarray(m).shape[:2] for m in masks]
+    weights, sdiv, cache = gaussian_weights(shadow.sigma), sat_div_table(), {}
+    half = np.ascontiguousarray(weights[len(weights) // 2:])
+    close = max(1, int(params.close))
+    owned, outs, jobs = [], [], []
+
+    def plane(a, shape, what):
+        return _device_plane(ctx, a, shape, what, owned, slot)
+
+    def element(j, name, k):
+        setattr(j, name + "_kw", k)
+        setattr(j, name + "_kh", k)
+        if k <= capi.MASK_MAX_ELEMENT:                   # (beyond: the call answers GS360_ERR_UNSUPPORTED before it reads the rows)
+            setattr(j, name + "_rows", _rows_array(k, k, cache).ctypes.data)
+    try:
+        for m, im, (H, W) in zip(masks, images, shapes):
+            j = capi.ShadowJob()
+            j.H, j.W, j.thresh = int(H), int(W), int(params.thresh)
+            j.radius, j.weights, j.sdiv = len(half) - 1, half.ctypes.data, sdiv.ctypes.data
+            j.t, j.delta_min, j.sat_max = float(shadow.t), float(shadow.delta_min), int(shadow.sat_max)
+            j.min_area = max(1, min(int(shadow.min_area), 2 ** 31 - 1))
+            if close > 1:
+                element(j, "close", close)
+            if not isinstance(m, tuple):
+                j.src = plane(m, (H, W), "mask")
+            elif len(m) == 3:
+                j.src = m[2].ptr
+            j.image = plane(im, (H, W, 3), "image")
+            outs.append(ctx.alloc(H * W))
+            j.dst = outs[-1].ptr
+            jobs.append(j)
+        scratch = ctx.alloc(ctx.mask_shadow_scratch(jobs))
+        owned.append(scratch)
+        d_counts = ctx.alloc(4 * n)
+        owned.append(d_counts)
+        ctx.mask_shadow_candidates_dev(jobs, scratch, d_counts, slot)
+        person = ctx.download(d_counts, (n,), np.uint32, slot)
+        for j, count in zip(jobs, person):               # the count -> size rule stays on the host
+            k, close_k = shadow_sizes(int(count), shadow.near_px)
+            element(j, "near", k)
+            element(j, "sclose", close_k)
+            element(j, "open", 3)
+        ctx.mask_shadow_merge_dev(jobs, scratch, d_counts, slot)
+        counts = ctx.download(d_counts, (n,), np.uint32, slot)
+        del cache
+        return outs, counts
+    except BaseException:
+        for o in outs:
+            ctx.free(o)
+        raise
+    finally:
+        for b in owned:
+            ctx.free(b)
+
+
+def finish_with_shadow_device(ctx, masks, params=None, shadow=None, adds=None, images=None, kind="mask", invert=True, slot=0):
+    """finish_device with the shadow estimate between the close and the expansion (the reference's --include_shadow): the images are
+    needed by every kind.  M stays on the device between the two stages, and so do the images."""
+    params = params or Params()
+    if images is None:
+        raise ValueError("the shadow estimate needs the images")
+    n = len(masks)
+    shapes = [tuple(m[:2]) if isinstance(m, tuple) else np.asarray(m).shape[:2] for m in masks]
+    d_images, merged = [], []
+    try:
+        for im, (H, W) in zip(images, shapes):
+            a = np.ascontiguousarray(im, dtype=np.uint8)
+            if a.shape != (H, W, 3):
+                raise ValueError(f"image of shape {a.shape}, expected {(H, W, 3)}")
+            d_images.append(ctx.to_device(a, slot))
+        if len(d_images) != n:
+            raise ValueError("one image per mask")
+        merged, _counts = shadow_device(ctx, masks, d_images, params, shadow, slot)
+        rest = dataclasses.replace(params, close=1, thresh=0)        # M is closed and holds 0 / 255
+        return finish_device(ctx, [(H, W, m) for (H, W), m in zip(shapes, merged)], rest, adds, d_images if kind != "mask" else None,
+                             kind, invert, slot)
+    finally:
+        for b in d_images + merged:
+            ctx.free(b)
+
+
+def finish_with_shadow(ctx, masks, params=None, shadow=None, adds=None, images=None, kind="mask", invert=True, slot=0):
+    """finish_with_shadow_device with the outputs brought back: -> ([H x W (kind "mask") or H x W x C uint8 arrays], counts)"""
+    with ctx.slot_locks[slot]:
+        items, counts = finish_with_shadow_device(ctx, masks, params, shadow, adds, images, kind, invert, slot)
         try:
             return [ctx.download(o, (H, W) if C == 1 else (H, W, C), np.uint8, slot) for o, H, W, C, _b, _s in items], counts
         finally:

@@ -46,7 +46,8 @@ typedef enum gs360_status {
     GS360_ERR_HIP = -2,         /* a HIP runtime call failed; text in gs360_last_error */
     GS360_ERR_NODEV = -3,       /* no usable GPU */
     GS360_ERR_UNSUPPORTED = -4, /* valid request this build does not implement */
-    GS360_ERR_NOMEM = -5
+    GS360_ERR_NOMEM = -5,
+    GS360_ERR_INTERNAL = -6     /* a kernel's own bound was exceeded (a defect): the call's results are not to be used */
 } gs360_status;
 
 /* values equal cv2.INTER_NEAREST / INTER_LINEAR / INTER_CUBIC / INTER_LANCZOS4 (DF:59-64) */
@@ -619,6 +620,56 @@ typedef struct gs360_mask_job {
 int gs360_mask_finish_scratch(const gs360_mask_job *jobs, int n_jobs, size_t *bytes);
 int gs360_mask_finish_u8(gs360_ctx *ctx, const gs360_mask_job *jobs, int n_jobs, void *scratch_dev, size_t scratch_bytes,
                          uint32_t *counts_dev, int slot);
+
+/* ---- the shadow estimate in front of the finishing chain (MSK-SHADOW v1) -------------------------------
+ * estimate_shadow_mask of gs360_SegmentationMaskTool.py (SEG:499-558) between the close and the expansion (SEG:707-724), on
+ * device-resident data, in two calls because the element sizes of the second depend on a count the first one leaves:
+ *   candidates  P = the raw mask packed at `thresh` and closed (MSK-SPEC steps 0-1); gray (the library's one 8-bit gray), the gray
+ *               filtered by the separable symmetric filter `weights` (HOST array of radius + 1 float32, centre outward; border
+ *               BORDER_REFLECT_101; row pass then column pass in float32, s = k[0] v(c), s = s + k[i] (v(c - i) + v(c + i)), every
+ *               operation rounded on its own) = illum; C0 = gray / (illum + 1e-6f) < t && illum - gray >= delta_min &&
+ *               S <= sat_max with cv2's 8-bit RGB2HSV S = (d sdiv[v] + 2048) >> 12 (`sdiv`: HOST array of 256 int32).
+ *               counts_dev[k] = count(P).  gs360/maskfinish.py's gaussian_weights and sat_div_table build the two tables.
+ *   merge       C1 = C0 & dilate(P, near) & ~P; C2 = open(close(C1, shadow close), open); G = the outermost 8-connected
+ *               components of C2 with everything they enclose; clean = the components of G whose doubled area (2 per 2 x 2 cell
+ *               of pixel centres with four corners in G, 1 with three) is >= 2 max(1, min_area); M = P | clean goes to dst as
+ *               H x W bytes of 0 / 255 and counts_dev[k] = count(M).  The three elements are given as MSK-SPEC's rows (HOST).
+ * Both calls take the same jobs (the merge reads H, W, dst, min_area and its elements, the candidates everything else) and the same
+ * scratch_dev: device memory of at least gs360_mask_shadow_scratch's bytes, 256-byte aligned, kept between the two calls.  Its
+ * layout is fixed so that a test can look at every stage: 256 bytes, then one area per job in job order whose size is what
+ * gs360_mask_shadow_scratch gives for that job alone minus 256; an area begins with the bit planes P, C0, C1, C2, clean, each
+ * H x ceil(W / 32) dwords rounded up to 256 bytes.  n_jobs may exceed GS360_MAX_VIEWS.  The candidates stage their tables and wait
+ * for that copy, the kernels are asynchronous on `slot`; the merge returns when its kernels are done.
+ * Errors: GS360_ERR_UNSUPPORTED for a side above 32768, more than 2^30 pixels (labels are 32-bit, areas are doubled), a radius
+ * above 255, an element side above 1025; GS360_ERR_ARG as for gs360_mask_finish_u8; GS360_ERR_INTERNAL when a label walk ran past
+ * its bound of H W steps (a defect, never data). */
+#define GS360_SHADOW_MAX_PIXELS (1 << 30)
+#define GS360_SHADOW_MAX_RADIUS 255
+typedef struct gs360_shadow_job {
+    const void *image;          /* H x W x 3 uint8 RGB */
+    size_t image_stride;
+    const void *src;            /* H x W uint8 raw mask, or NULL */
+    size_t src_stride;
+    void *dst;                  /* merge: M, H x W uint8 */
+    size_t dst_stride;
+    int32_t H, W;
+    int32_t thresh;
+    int32_t close_kw, close_kh; /* 0 x 0: no close */
+    int32_t radius;             /* of the filter: `weights` has radius + 1 entries */
+    int32_t sat_max;
+    int32_t min_area;           /* merge */
+    float t, delta_min;
+    int32_t near_kw, near_kh, sclose_kw, sclose_kh, open_kw, open_kh;   /* merge */
+    const int32_t *close_rows;  /* host memory: close_kh x (j1, j2) */
+    const float *weights;       /* host memory */
+    const int32_t *sdiv;        /* host memory */
+    const int32_t *near_rows, *sclose_rows, *open_rows;                 /* merge; host memory */
+} gs360_shadow_job;
+int gs360_mask_shadow_scratch(const gs360_shadow_job *jobs, int n_jobs, size_t *bytes);
+int gs360_mask_shadow_candidates_u8(gs360_ctx *ctx, const gs360_shadow_job *jobs, int n_jobs, void *scratch_dev, size_t scratch_bytes,
+                                    uint32_t *counts_dev, int slot);
+int gs360_mask_shadow_merge_u8(gs360_ctx *ctx, const gs360_shadow_job *jobs, int n_jobs, void *scratch_dev, size_t scratch_bytes,
+                               uint32_t *counts_dev, int slot);
 
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
