@@ -37,6 +37,7 @@ EXPORTS = (
     "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub", "gs360_jpeg_decode_u8", "gs360_jpeg_decode_scratch",
     "gs360_jpeg_decode_gray_u8", "gs360_png_deflate", "gs360_png_bound", "gs360_mask_finish_u8", "gs360_mask_finish_scratch",
     "gs360_mask_shadow_scratch", "gs360_mask_shadow_candidates_u8", "gs360_mask_shadow_merge_u8",
+    "gs360_voxel_scratch", "gs360_cloud_bounds_f32", "gs360_voxel_count_f32", "gs360_voxel_pick_f32",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -55,6 +56,10 @@ MASK_MAX_ELEMENT = 1025
 MASK_MAX_FUSE = 1024                 # GS360_MASK_MAX_FUSE: the largest edge-fuse strip (and spread)
 SHADOW_MAX_PIXELS = 1 << 30          # GS360_SHADOW_MAX_PIXELS / GS360_SHADOW_MAX_RADIUS: the shadow estimate's largest image and filter radius
 SHADOW_MAX_RADIUS = 255
+VOXEL_FIRST, VOXEL_CENTER, VOXEL_CENTROID, VOXEL_SEGMENTS = 0, 1, 2, 3   # GS360_VOXEL_*: the `strategy` of gs360_voxel_pick_f32
+VOXEL_MAX_POINTS = (1 << 31) - 1     # GS360_VOXEL_MAX_POINTS: indices are 32-bit on the device
+ERR_ARG = -1                         # GS360_ERR_ARG / GS360_ERR_UNSUPPORTED
+ERR_UNSUPPORTED = -4
 ERR_INTERNAL = -6                    # GS360_ERR_INTERNAL: a kernel's own bound was exceeded
 FS_CIRCLE = 0x1       # gs360_frame_stats_u8 flags: mask_mode "fisheye_circle"
 FS_HIGHLIGHTS = 0x2   # ignore_highlights
@@ -272,6 +277,11 @@ def load_library(path=None):
         L.gs360_mask_shadow_scratch.argtypes = [C.POINTER(ShadowJob), i, C.POINTER(C.c_size_t)]
         L.gs360_mask_shadow_candidates_u8.argtypes = [vp, C.POINTER(ShadowJob), i, vp, sz, vp, i]
         L.gs360_mask_shadow_merge_u8.argtypes = [vp, C.POINTER(ShadowJob), i, vp, sz, vp, i]
+        i64 = C.c_int64
+        L.gs360_voxel_scratch.argtypes = [vp, i64, C.POINTER(C.c_size_t)]
+        L.gs360_cloud_bounds_f32.argtypes = [vp, vp, i64, vp, sz, C.POINTER(C.c_float), i]
+        L.gs360_voxel_count_f32.argtypes = [vp, vp, i64, C.POINTER(C.c_float), C.c_double, vp, sz, C.POINTER(i64), i]
+        L.gs360_voxel_pick_f32.argtypes = [vp, vp, i64, C.POINTER(C.c_float), C.c_double, i, vp, sz, vp, vp, vp, C.POINTER(i64), i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -751,6 +761,37 @@ class Context:
         self._mask_shadow_call(self.L.gs360_mask_shadow_merge_u8, jobs, scratch, counts, slot, scratch_bytes)
 
     # -- JPEG files decoded into device images (gs360/jpegdec.py) ------------------------------
+    # -- voxel downsampling of a resident point cloud (gs360/pointcloud.py) -----------------------
+    def voxel_scratch(self, n):
+        """gs360_voxel_scratch: the bytes of scratch the bounds, count and pick calls on a cloud of n points share"""
+        nbytes = C.c_size_t(0)
+        _check(self.L.gs360_voxel_scratch(self.handle, int(n), C.byref(nbytes)), self.L)
+        return int(nbytes.value)
+
+    def cloud_bounds_dev(self, xyz, n, scratch, slot=0):
+        """gs360_cloud_bounds_f32: xyz = DeviceBuffer of n x 3 float32 -> float32[6], the per-axis minimum then maximum"""
+        out = (C.c_float * 6)()
+        _check(self.L.gs360_cloud_bounds_f32(self.handle, xyz.ptr, int(n), scratch.ptr, scratch.nbytes, out, slot), self.L)
+        return np.array(out, dtype=np.float32)
+
+    def voxel_count_dev(self, xyz, n, minmax, voxel, scratch, slot=0):
+        """gs360_voxel_count_f32: the number of occupied voxels of edge float32(voxel) on the grid at minmax[:3]"""
+        mm = (C.c_float * 6)(*[float(v) for v in minmax])
+        count = C.c_int64(0)
+        _check(self.L.gs360_voxel_count_f32(self.handle, xyz.ptr, int(n), mm, float(voxel), scratch.ptr, scratch.nbytes, C.byref(count), slot),
+               self.L)
+        return int(count.value)
+
+    def voxel_pick_dev(self, xyz, n, minmax, voxel, strategy, scratch, pick=None, order=None, starts=None, slot=0):
+        """gs360_voxel_pick_f32 -> k; pick / order / starts = DeviceBuffers of n uint32 (or None) that receive the representatives, the
+        indices in stable key order and the segment starts"""
+        mm = (C.c_float * 6)(*[float(v) for v in minmax])
+        k = C.c_int64(0)
+        ptr = [b.ptr if b is not None else None for b in (pick, order, starts)]
+        _check(self.L.gs360_voxel_pick_f32(self.handle, xyz.ptr, int(n), mm, float(voxel), int(strategy), scratch.ptr, scratch.nbytes,
+                                           ptr[0], ptr[1], ptr[2], C.byref(k), slot), self.L)
+        return int(k.value)
+
     def jpeg_decode_dev(self, jobs, status, slot=0):
         """gs360_jpeg_decode_u8: jobs = sequence of JpegDecJob (device pointers; gs360/jpegdec.py fills them), status = DeviceBuffer of
         len(jobs) uint32.  Asynchronous on `slot`."""

@@ -671,6 +671,37 @@ int gs360_mask_shadow_candidates_u8(gs360_ctx *ctx, const gs360_shadow_job *jobs
 int gs360_mask_shadow_merge_u8(gs360_ctx *ctx, const gs360_shadow_job *jobs, int n_jobs, void *scratch_dev, size_t scratch_bytes,
                                uint32_t *counts_dev, int slot);
 
+/* ---- voxel downsampling of a resident point cloud (VOX-SPEC v1) ----------------------------------------
+ * gs360_PlyOptimizer.py's compute_point_cloud_stats, _unique_voxel_count and voxel_downsample_by_size (PLY:110-128, 747-862) on a
+ * DEVICE array of n x 3 float32 (16-byte aligned) that stays where it is from call to call:
+ *   bounds   minmax[0..2] = the per-axis minimum, minmax[3..5] = the maximum (HOST array of six floats).
+ *   count    the number of occupied voxels of edge (float) voxel on the grid that starts at minmax[0..2].
+ *   pick     *k = that number; pick_dev[0 .. k) = per voxel, in the lexicographic order of the (x, y, z) keys, the original index of
+ *            its representative: GS360_VOXEL_FIRST the smallest index, _CENTER / _CENTROID the point nearest the voxel's centre / the
+ *            float64 centroid (ties: the smallest index).  order_dev (n) and starts_dev (k of its n entries), when not NULL, receive
+ *            the indices in stable key order and where each voxel's segment starts in them; GS360_VOXEL_SEGMENTS writes only these
+ *            two (the caller draws its own representative) and takes pick_dev = NULL.  All three are DEVICE arrays of n uint32.
+ * minmax is what the bounds call returned for this cloud.  Keys are k_a = floorf((x_a - min_a) / (float) voxel) in float32, as the
+ * reference computes them on its float32 arrays.  Count and pick share scratch_dev: device memory of at least gs360_voxel_scratch's
+ * bytes, 256-byte aligned.  Every call returns when its result is there.
+ * Errors: GS360_ERR_ARG for n < 1, NULL or misaligned pointers, a scratch that is too small, voxel <= 0, a cloud with non-finite
+ * coordinates (bounds), a point outside minmax (count, pick); GS360_ERR_UNSUPPORTED for n >= 2^31 and for a voxel so small that the
+ * three keys' bit lengths sum to more than 64 or that one key needs more than 63 (the caller counts such a grid on the host);
+ * GS360_ERR_INTERNAL when a segment list left its bound (a defect, never data). */
+#define GS360_VOXEL_MAX_POINTS 2147483647LL
+#define GS360_VOXEL_FIRST 0
+#define GS360_VOXEL_CENTER 1
+#define GS360_VOXEL_CENTROID 2
+#define GS360_VOXEL_SEGMENTS 3
+int gs360_voxel_scratch(gs360_ctx *ctx, int64_t n, size_t *bytes);
+int gs360_cloud_bounds_f32(gs360_ctx *ctx, const float *xyz_dev, int64_t n, void *scratch_dev, size_t scratch_bytes, float *minmax,
+                           int slot);
+int gs360_voxel_count_f32(gs360_ctx *ctx, const float *xyz_dev, int64_t n, const float *minmax, double voxel, void *scratch_dev,
+                          size_t scratch_bytes, int64_t *count, int slot);
+int gs360_voxel_pick_f32(gs360_ctx *ctx, const float *xyz_dev, int64_t n, const float *minmax, double voxel, int strategy,
+                         void *scratch_dev, size_t scratch_bytes, uint32_t *pick_dev, uint32_t *order_dev, uint32_t *starts_dev,
+                         int64_t *k, int slot);
+
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
                                  const gs360_view *views, int n_views,
