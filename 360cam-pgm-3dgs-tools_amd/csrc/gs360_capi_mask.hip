@@ -1,6 +1,8 @@
 // gs360_capi_mask.hip -- the mask-finishing entry points of libgs360hip.so (include/gs360.h; MSK-SPEC v1 and MSK-SHADOW v1, DESIGN.md
 // section 14): validation, the scratch layout and the launch sequence of the kernels in gs360_maskmorph.hip and gs360_maskshadow.hip.
+// Every grid is sized by the function of gs360_maskplane.h that bounds its kernel.
 #include "gs360_capi_internal.h"
+#include "gs360_maskplane.h"
 
 using namespace gs360;
 
@@ -10,17 +12,8 @@ inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline size_t plane_bytes(int H, int W) { return round_up((size_t)H * ((size_t)(W + 31) / 32) * 4, 256); }
 inline size_t plane_bytes(const gs360_mask_job& j) { return plane_bytes(j.H, j.W); }
 inline size_t rows_bytes(int kh) { return round_up((size_t)kh * 8, 256); }
-
-// the largest |column offset| an element reaches, or -1 for a span outside the element
-int element_reach(const int32_t* rows, int kw, int kh) {
-    int reach = 0;
-    for (int i = 0; i < kh; ++i) {
-        const int j1 = rows[2 * i], j2 = rows[2 * i + 1];
-        if (j1 < 0 || j2 < j1 || j2 > kw) return -1;
-        if (j2 > j1) reach = std::max({reach, std::abs(j1 - kw / 2), std::abs(j2 - 1 - kw / 2)});
-    }
-    return reach;
-}
+inline int64_t stride_or(size_t stride, size_t row) { return (int64_t)(stride ? stride : row); }
+inline int out_channels(int kind) { return kind == GS360_MASK_OUT_MASK ? 1 : kind == GS360_MASK_OUT_RGBA ? 4 : 3; }
 
 int check_element(int k, const char* name, int kw, int kh, const int32_t* rows) {
     if (kh == 0) return 0;
@@ -28,7 +21,18 @@ int check_element(int k, const char* name, int kw, int kh, const int32_t* rows) 
     if (kw > GS360_MASK_MAX_ELEMENT || kh > GS360_MASK_MAX_ELEMENT)
         return fail(GS360_ERR_UNSUPPORTED, "job %d: %s element of %d x %d above %d", k, name, kw, kh, GS360_MASK_MAX_ELEMENT);
     if (!rows) return fail(GS360_ERR_ARG, "job %d: %s element without rows", k, name);
-    if (element_reach(rows, kw, kh) < 0) return fail(GS360_ERR_ARG, "job %d: %s element has a span outside its %d columns", k, name, kw);
+    if (mk_element_halo(rows, kw, kh) < 0) return fail(GS360_ERR_ARG, "job %d: %s element has a span outside its %d columns", k, name, kw);
+    return 0;
+}
+
+// a checked element of a job as the morph kernel takes it (a job without it has kh == 0); its rows are staged at `dev`
+struct Element {
+    int kw, kh, halo;                    // halo: at most kMkMaxHalo, check_element bounds kw
+    const int32_t* rows;                 // device memory
+};
+Element element_of(int kw, int kh, const int32_t* rows, const void* dev) { return {kw, kh, mk_element_halo(rows, kw, kh), (const int32_t*)dev}; }
+int stage_rows(void* dev, const int32_t* rows, int kh, hipStream_t s) {
+    if (kh) HIP_TRY(hipMemcpyAsync(dev, rows, (size_t)kh * 8, hipMemcpyHostToDevice, s));
     return 0;
 }
 
@@ -39,9 +43,8 @@ int check_job(int k, const gs360_mask_job& j) {
     if (j.kind < GS360_MASK_OUT_MASK || j.kind > GS360_MASK_OUT_REMOVE) return fail(GS360_ERR_ARG, "job %d: unknown output kind %d", k, j.kind);
     if (!j.dst) return fail(GS360_ERR_ARG, "job %d: NULL output", k);
     if (j.kind != GS360_MASK_OUT_MASK && !j.image) return fail(GS360_ERR_ARG, "job %d: output kind %d needs the image", k, j.kind);
-    const size_t out_c = j.kind == GS360_MASK_OUT_MASK ? 1 : j.kind == GS360_MASK_OUT_RGBA ? 4 : 3;
     if ((j.src_stride && j.src_stride < (size_t)j.W) || (j.add_stride && j.add_stride < (size_t)j.W) ||
-        (j.image_stride && j.image_stride < (size_t)j.W * 3) || (j.dst_stride && j.dst_stride < (size_t)j.W * out_c))
+        (j.image_stride && j.image_stride < (size_t)j.W * 3) || (j.dst_stride && j.dst_stride < (size_t)j.W * out_channels(j.kind)))
         return fail(GS360_ERR_ARG, "job %d: a stride below a row", k);
     if (j.thresh < 0 || j.thresh > 255) return fail(GS360_ERR_ARG, "job %d: thresh %d outside 0..255", k, j.thresh);
     if (int rc = check_element(k, "close", j.close_kw, j.close_kh, j.close_rows)) return rc;
@@ -71,12 +74,22 @@ int check_jobs(const gs360_mask_job* jobs, int n_jobs, size_t* need) {
     return 0;
 }
 
-// row tiles of a job: workgroups of `px` pixels by `rows` rows
-template <class Job>
-int64_t row_tiles(Job& J, int px, int rows) {
-    J.tiles_x = (J.W + px - 1) / px;
-    return (int64_t)J.tiles_x * ((J.H + rows - 1) / rows);
+// what every call with jobs in it does between its jobs' checks, which gave `need`, and its first copy: the buffers' checks, the
+// slot's stream, the counts cleared
+int begin_call(gs360_ctx* c, int slot, int n_jobs, const void* scratch_dev, size_t scratch_bytes, size_t need, uint32_t* counts_dev,
+               hipStream_t* s) {
+    if (!scratch_dev || !counts_dev) return fail(GS360_ERR_ARG, "NULL argument");
+    if ((uintptr_t)scratch_dev % 256) return fail(GS360_ERR_ARG, "scratch is not 256-byte aligned");
+    if (scratch_bytes < need) return fail(GS360_ERR_ARG, "scratch of %zu bytes below the %zu the jobs need", scratch_bytes, need);
+    HIP_TRY(hipSetDevice(c->device));
+    *s = c->stream[slot];
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_jobs * sizeof(uint32_t), *s));
+    return 0;
 }
+
+// row tiles of a job: workgroups of t.w pixels by t.h rows
+template <class Job>
+int64_t row_tiles(Job& J, MkTile t) { return mk_tiles(J, J.W, t); }
 
 // one step over the batch: `tiles_of(k, J)` sets the step's fields of job k and returns its tiles (0: the job skips the step); the
 // jobs' tiles are numbered in job order
@@ -92,6 +105,74 @@ int run_step(Launch& L, Fn launch, hipStream_t s, Tiles tiles_of) {
     }
     L.total_tiles = (int32_t)tiles;
     HIP_TRY(launch(L, s));
+    return 0;
+}
+
+// one dilate or erode over the batch: plane from(k) -> plane to(k) by el[k]; a job without the element skips the step
+template <class From, class To>
+int morph_step(MkLaunch& L, hipStream_t s, From from, To to, const Element* el, int flags) {
+    return run_step(L, launch_mask_morph, s, [&](int k, MkJob& J) -> int64_t {
+        const Element& e = el[k];
+        if (!e.kh) return 0;
+        J.in = from(k); J.out = to(k);
+        J.spans = e.rows; J.kh = e.kh; J.ax = e.kw / 2; J.ay = e.kh / 2; J.halo = e.halo; J.flags = flags;
+        return mk_tiles(J, J.pw, kMkMorphTile);
+    });
+}
+
+// the jobs [k0, k0 + n) of a finishing call as one launch: two planes per job, the one that holds the mask so far is cur[k]
+struct FinishBatch {
+    MkLaunch mk;
+    uint32_t* plane[GS360_MAX_VIEWS][2];
+    int cur[GS360_MAX_VIEWS];
+    Element close[GS360_MAX_VIEWS], expand[GS360_MAX_VIEWS];
+    uint32_t* held(int k) const { return plane[k][cur[k]]; }
+    uint32_t* other(int k) const { return plane[k][cur[k] ^ 1]; }
+};
+int finish_batch(FinishBatch& B, const gs360_mask_job* jobs, int n, uint8_t* at, uint32_t* counts, hipStream_t s) {
+    std::memset(&B.mk, 0, sizeof(B.mk));
+    B.mk.n_jobs = n;
+    B.mk.counts = counts;
+    for (int k = 0; k < n; ++k) {
+        const gs360_mask_job& j = jobs[k];
+        MkJob& J = B.mk.job[k];
+        J.src = (const uint8_t*)j.src; J.add = (const uint8_t*)j.add; J.img = (const uint8_t*)j.image; J.dst = (uint8_t*)j.dst;
+        J.src_stride = stride_or(j.src_stride, (size_t)j.W);
+        J.add_stride = stride_or(j.add_stride, (size_t)j.W);
+        J.img_stride = stride_or(j.image_stride, (size_t)j.W * 3);
+        J.dst_stride = stride_or(j.dst_stride, (size_t)j.W * out_channels(j.kind));
+        J.H = j.H; J.W = j.W; J.pw = (j.W + 31) / 32; J.thresh = j.thresh;
+        J.f = j.fuse; J.s = j.spread; J.kind = j.kind; J.invert = j.invert != 0;
+        B.cur[k] = 0;
+        B.plane[k][0] = (uint32_t*)at; at += plane_bytes(j);
+        B.plane[k][1] = (uint32_t*)at; at += plane_bytes(j);
+        B.close[k] = element_of(j.close_kw, j.close_kh, j.close_rows, at);
+        if (int rc = stage_rows(at, j.close_rows, j.close_kh, s)) return rc;
+        at += rows_bytes(j.close_kh);
+        B.expand[k] = element_of(j.expand_kw, j.expand_kh, j.expand_rows, at);
+        if (int rc = stage_rows(at, j.expand_rows, j.expand_kh, s)) return rc;
+        at += rows_bytes(j.expand_kh);
+    }
+    HIP_TRY(hipStreamSynchronize(s));                     // the caller's element rows are read; the earlier batch is done with the scratch
+    return 0;
+}
+// both go from the held plane into the other one, which the jobs that took the step hold afterwards
+int finish_morph(FinishBatch& B, hipStream_t s, const Element* el, int flags) {
+    if (int rc = morph_step(B.mk, s, [&](int k) { return B.held(k); }, [&](int k) { return B.other(k); }, el, flags)) return rc;
+    for (int k = 0; k < B.mk.n_jobs; ++k) B.cur[k] ^= el[k].kh != 0;
+    return 0;
+}
+// the edge fuse of the jobs that have strips: the copy, then the fills
+int finish_fuse(FinishBatch& B, hipStream_t s) {
+    for (int phase = 0; phase < 2; ++phase) {
+        B.mk.phase = phase;
+        if (int rc = run_step(B.mk, launch_mask_fuse, s, [&](int k, MkJob& J) -> int64_t {
+                if (!J.f) return 0;
+                J.in = B.held(k); J.out = B.other(k);
+                return mk_item_tiles(phase ? mk_fuse_items(J) : mk_plane_items(J));
+            })) return rc;
+    }
+    for (int k = 0; k < B.mk.n_jobs; ++k) B.cur[k] ^= B.mk.job[k].f != 0;
     return 0;
 }
 
@@ -111,78 +192,21 @@ int gs360_mask_finish_u8(gs360_ctx* c, const gs360_mask_job* jobs, int n_jobs, v
     size_t need = 0;
     if (int rc = check_jobs(jobs, n_jobs, &need)) return rc;
     if (n_jobs == 0) return GS360_OK;
-    if (!scratch_dev || !counts_dev) return fail(GS360_ERR_ARG, "NULL argument");
-    if ((uintptr_t)scratch_dev % 256) return fail(GS360_ERR_ARG, "scratch is not 256-byte aligned");
-    if (scratch_bytes < need) return fail(GS360_ERR_ARG, "scratch of %zu bytes below the %zu the jobs need", scratch_bytes, need);
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream[slot];
-    HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_jobs * sizeof(uint32_t), s));
+    hipStream_t s;
+    if (int rc = begin_call(c, slot, n_jobs, scratch_dev, scratch_bytes, need, counts_dev, &s)) return rc;
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
-        MkLaunch L;
-        std::memset(&L, 0, sizeof(L));
-        L.n_jobs = std::min(GS360_MAX_VIEWS, n_jobs - k0);
-        L.counts = counts_dev + k0;
-        uint32_t* plane[GS360_MAX_VIEWS][2];
-        const int32_t* spans[GS360_MAX_VIEWS][2];
-        int halo[GS360_MAX_VIEWS][2], cur[GS360_MAX_VIEWS] = {};
-        uint8_t* at = (uint8_t*)scratch_dev;
-        for (int k = 0; k < L.n_jobs; ++k) {
-            const gs360_mask_job& j = jobs[k0 + k];
-            MkJob& J = L.job[k];
-            J.src = (const uint8_t*)j.src; J.add = (const uint8_t*)j.add; J.img = (const uint8_t*)j.image; J.dst = (uint8_t*)j.dst;
-            const int out_c = j.kind == GS360_MASK_OUT_MASK ? 1 : j.kind == GS360_MASK_OUT_RGBA ? 4 : 3;
-            J.src_stride = (int64_t)(j.src_stride ? j.src_stride : (size_t)j.W);
-            J.add_stride = (int64_t)(j.add_stride ? j.add_stride : (size_t)j.W);
-            J.img_stride = (int64_t)(j.image_stride ? j.image_stride : (size_t)j.W * 3);
-            J.dst_stride = (int64_t)(j.dst_stride ? j.dst_stride : (size_t)j.W * out_c);
-            J.H = j.H; J.W = j.W; J.pw = (j.W + 31) / 32; J.thresh = j.thresh;
-            J.f = j.fuse; J.s = j.spread; J.kind = j.kind; J.invert = j.invert != 0;
-            plane[k][0] = (uint32_t*)at; at += plane_bytes(j);
-            plane[k][1] = (uint32_t*)at; at += plane_bytes(j);
-            const int kh[2] = {j.close_kh, j.expand_kh}, kw[2] = {j.close_kw, j.expand_kw};
-            const int32_t* host[2] = {j.close_rows, j.expand_rows};
-            for (int e = 0; e < 2; ++e) {
-                spans[k][e] = (const int32_t*)at;
-                halo[k][e] = kh[e] ? element_reach(host[e], kw[e], kh[e]) / 32 + 2 : 0;   // at most kMkMaxHalo: check_element bounds kw
-                if (kh[e]) HIP_TRY(hipMemcpyAsync(at, host[e], (size_t)kh[e] * 8, hipMemcpyHostToDevice, s));
-                at += rows_bytes(kh[e]);
-            }
-        }
-        HIP_TRY(hipStreamSynchronize(s));                 // the caller's element rows are read; the earlier batch is done with the scratch
-        auto flip = [&](int k, MkJob& J) { J.in = plane[k][cur[k]]; J.out = plane[k][cur[k] ^ 1]; };
-        auto morph = [&](int e, int flags) {              // element e (0 close, 1 expand) over the jobs that have one
-            int rc = run_step(L, launch_mask_morph, s, [&](int k, MkJob& J) -> int64_t {
-                const gs360_mask_job& j = jobs[k0 + k];
-                const int kh = e ? j.expand_kh : j.close_kh, kw = e ? j.expand_kw : j.close_kw;
-                if (!kh) return 0;
-                flip(k, J);
-                J.spans = spans[k][e]; J.kh = kh; J.ax = kw / 2; J.ay = kh / 2; J.halo = halo[k][e]; J.flags = flags;
-                J.tiles_x = (J.pw + kMkTileW - 1) / kMkTileW;
-                return (int64_t)J.tiles_x * ((J.H + kMkTileR - 1) / kMkTileR);
-            });
-            for (int k = 0; k < L.n_jobs; ++k) cur[k] ^= (e ? jobs[k0 + k].expand_kh : jobs[k0 + k].close_kh) != 0;
-            return rc;
-        };
-        if (int rc = run_step(L, launch_mask_pack_bits, s, [&](int k, MkJob& J) { J.out = plane[k][0]; return row_tiles(J, 4 * kMkThreads, 1); })) return rc;
-        if (int rc = morph(0, 0)) return rc;                                  // close: dilate ...
-        if (int rc = morph(0, kMkCompIn | kMkCompOut)) return rc;             // ... then erode
-        if (int rc = morph(1, 0)) return rc;                                  // expand
-        for (int phase = 0; phase < 2; ++phase) {                             // edge fuse: copy, then the fills
-            L.phase = phase;
-            if (int rc = run_step(L, launch_mask_fuse, s, [&](int k, MkJob& J) -> int64_t {
-                    if (!J.f) return 0;
-                    flip(k, J);
-                    const int64_t items = phase ? 2 * (int64_t)J.pw + 2 * (int64_t)J.H : (int64_t)J.H * J.pw;
-                    return (items + kMkThreads - 1) / kMkThreads;
-                })) return rc;
-        }
-        for (int k = 0; k < L.n_jobs; ++k) cur[k] ^= L.job[k].f != 0;
-        for (int phase = 0; phase < 2; ++phase) {                             // add layer and count, then the output
-            L.phase = phase;
-            if (int rc = run_step(L, launch_mask_finish, s, [&](int k, MkJob& J) {
-                    J.out = plane[k][cur[k]];
-                    if (!phase) return row_tiles(J, 4 * kMkThreads, kMkFinishRows);
-                    return row_tiles(J, J.kind == GS360_MASK_OUT_MASK ? 4 * kMkThreads : kMkThreads, 1);
+        FinishBatch B;
+        if (int rc = finish_batch(B, jobs + k0, std::min(GS360_MAX_VIEWS, n_jobs - k0), (uint8_t*)scratch_dev, counts_dev + k0, s)) return rc;
+        if (int rc = run_step(B.mk, launch_mask_pack_bits, s, [&](int k, MkJob& J) { J.out = B.held(k); return row_tiles(J, kMkPackTile); })) return rc;
+        if (int rc = finish_morph(B, s, B.close, 0)) return rc;                          // close: dilate ...
+        if (int rc = finish_morph(B, s, B.close, kMkCompIn | kMkCompOut)) return rc;     // ... then erode
+        if (int rc = finish_morph(B, s, B.expand, 0)) return rc;                         // expand
+        if (int rc = finish_fuse(B, s)) return rc;
+        for (int phase = 0; phase < 2; ++phase) {                                        // add layer and count, then the output
+            B.mk.phase = phase;
+            if (int rc = run_step(B.mk, launch_mask_finish, s, [&](int k, MkJob& J) {
+                    J.out = B.held(k);
+                    return row_tiles(J, phase ? mk_output_tile(J.kind) : kMkCountTile);
                 })) return rc;
         }
     }
@@ -194,9 +218,10 @@ namespace {
 
 // a job's area of the scratch; it depends on H and W alone, so both calls and the caller find a job's planes in the same place
 enum { kShP, kShC0, kShC1, kShC2, kShClean, kShSat, kShT0, kShT1, kShPlanes };
+enum { kShElClose, kShElNear, kShElSclose, kShElOpen, kShElements };
 constexpr size_t kShHead = 256;                           // the call's error word, in front of the first job's area
 struct ShadowArea {
-    size_t plane, gray, mid, area, weights, sdiv, rows[4], total;   // rows: close, near, shadow close, open
+    size_t plane, gray, mid, area, weights, sdiv, rows[kShElements], total;
 };
 ShadowArea shadow_area(int H, int W) {
     ShadowArea a;
@@ -207,7 +232,7 @@ ShadowArea shadow_area(int H, int W) {
     a.area = at; at += round_up((size_t)H * W * 4, 256);
     a.weights = at; at += round_up((size_t)(kMsMaxR + 1) * 4, 256);
     a.sdiv = at; at += 1024;
-    for (int e = 0; e < 4; ++e) { a.rows[e] = at; at += rows_bytes(GS360_MASK_MAX_ELEMENT); }
+    for (int e = 0; e < kShElements; ++e) { a.rows[e] = at; at += rows_bytes(GS360_MASK_MAX_ELEMENT); }
     a.total = at;
     return a;
 }
@@ -245,17 +270,16 @@ int check_shadow_jobs(const gs360_shadow_job* jobs, int n_jobs, bool merge, size
     return 0;
 }
 
-int check_shadow_call(gs360_ctx* c, const gs360_shadow_job* jobs, int n_jobs, bool merge, void* scratch_dev, size_t scratch_bytes,
-                      uint32_t* counts_dev, int slot) {
-    if (int rc = check_ctx_slot(c, slot)) return rc;
-    size_t need = 0;
-    if (int rc = check_shadow_jobs(jobs, n_jobs, merge, &need)) return rc;
-    if (n_jobs == 0) return 0;
-    if (!scratch_dev || !counts_dev) return fail(GS360_ERR_ARG, "NULL argument");
-    if ((uintptr_t)scratch_dev % 256) return fail(GS360_ERR_ARG, "scratch is not 256-byte aligned");
-    if (scratch_bytes < need) return fail(GS360_ERR_ARG, "scratch of %zu bytes below the %zu the jobs need", scratch_bytes, need);
-    return 0;
-}
+// a job's four elements as the caller gives them, by kShEl... index; the candidates take the first, the merge the other three
+struct ShadowElements {
+    int kw[kShElements], kh[kShElements];
+    const int32_t* rows[kShElements];
+    explicit ShadowElements(const gs360_shadow_job& j)
+        : kw{j.close_kw, j.near_kw, j.sclose_kw, j.open_kw}, kh{j.close_kh, j.near_kh, j.sclose_kh, j.open_kh},
+          rows{j.close_rows, j.near_rows, j.sclose_rows, j.open_rows} {}
+    static int first(bool merge) { return merge ? kShElNear : kShElClose; }
+    static int end(bool merge) { return merge ? kShElements : kShElNear; }
+};
 
 // the jobs [k0, k0 + n) of a call as one launch of either family; base[k]: the job's area of the scratch
 struct ShadowBatch {
@@ -263,10 +287,11 @@ struct ShadowBatch {
     MsLaunch ms;
     uint8_t* base[GS360_MAX_VIEWS];
     ShadowArea area[GS360_MAX_VIEWS];
+    Element el[kShElements][GS360_MAX_VIEWS];             // those of the call
     uint32_t* plane(int k, int which) const { return (uint32_t*)(base[k] + (size_t)which * area[k].plane); }
-    const int32_t* rows(int k, int e) const { return (const int32_t*)(base[k] + area[k].rows[e]); }
 };
-void shadow_batch(ShadowBatch& B, const gs360_shadow_job* jobs, int n, uint8_t* at, uint32_t* counts, uint32_t* err) {
+// fills B from the jobs at *at of the scratch and moves *at behind them
+void shadow_batch(ShadowBatch& B, const gs360_shadow_job* jobs, int n, bool merge, uint8_t** at, uint32_t* counts, uint32_t* err) {
     std::memset(&B.mk, 0, sizeof(B.mk));
     std::memset(&B.ms, 0, sizeof(B.ms));
     B.mk.n_jobs = B.ms.n_jobs = n;
@@ -274,17 +299,17 @@ void shadow_batch(ShadowBatch& B, const gs360_shadow_job* jobs, int n, uint8_t* 
     B.ms.err = err;
     for (int k = 0; k < n; ++k) {
         const gs360_shadow_job& j = jobs[k];
-        B.base[k] = at;
+        B.base[k] = *at;
         B.area[k] = shadow_area(j.H, j.W);
-        at += B.area[k].total;
+        *at += B.area[k].total;
         MkJob& K = B.mk.job[k];
         K.src = (const uint8_t*)j.src;
-        K.src_stride = (int64_t)(j.src_stride ? j.src_stride : (size_t)j.W);
+        K.src_stride = stride_or(j.src_stride, (size_t)j.W);
         K.H = j.H; K.W = j.W; K.pw = (j.W + 31) / 32; K.thresh = j.thresh;
         MsJob& S = B.ms.job[k];
         S.img = (const uint8_t*)j.image; S.dst = (uint8_t*)j.dst;
-        S.img_stride = (int64_t)(j.image_stride ? j.image_stride : (size_t)j.W * 3);
-        S.dst_stride = (int64_t)(j.dst_stride ? j.dst_stride : (size_t)j.W);
+        S.img_stride = stride_or(j.image_stride, (size_t)j.W * 3);
+        S.dst_stride = stride_or(j.dst_stride, (size_t)j.W);
         S.gray = B.base[k] + B.area[k].gray;
         S.mid = (float*)(B.base[k] + B.area[k].mid); S.lab = (int32_t*)S.mid;
         S.area = (uint32_t*)(B.base[k] + B.area[k].area);
@@ -292,33 +317,60 @@ void shadow_batch(ShadowBatch& B, const gs360_shadow_job* jobs, int n, uint8_t* 
         S.H = j.H; S.W = j.W; S.pw = K.pw; S.r = j.radius;
         S.t = j.t; S.delta_min = j.delta_min; S.sat_max = j.sat_max;
         S.th2 = (uint32_t)std::min<int64_t>(2 * (int64_t)std::max(1, j.min_area), UINT32_MAX);
+        const ShadowElements el(j);
+        for (int e = el.first(merge); e < el.end(merge); ++e) B.el[e][k] = element_of(el.kw[e], el.kh[e], el.rows[e], B.base[k] + B.area[k].rows[e]);
     }
 }
-// one dilate or erode of every job of the batch: plane `from` -> plane `to` by element e of the job's staged rows
-int shadow_morph(ShadowBatch& B, hipStream_t s, int from, int to, int e, const int* kw, const int* kh, const int* halo, int flags) {
-    return run_step(B.mk, launch_mask_morph, s, [&](int k, MkJob& J) -> int64_t {
-        J.in = B.plane(k, from); J.out = B.plane(k, to);
-        J.spans = B.rows(k, e); J.kh = kh[k]; J.ax = kw[k] / 2; J.ay = kh[k] / 2; J.halo = halo[k]; J.flags = flags;
-        if (!kh[k]) return 0;
-        J.tiles_x = (J.pw + kMkTileW - 1) / kMkTileW;
-        return (int64_t)J.tiles_x * ((J.H + kMkTileR - 1) / kMkTileR);
-    });
+// one dilate or erode of every job of the batch: plane `from` -> plane `to` by element e
+int shadow_morph(ShadowBatch& B, hipStream_t s, int from, int to, int e, int flags) {
+    return morph_step(B.mk, s, [&](int k) { return B.plane(k, from); }, [&](int k) { return B.plane(k, to); }, B.el[e], flags);
 }
 // one step of gs360_maskshadow.hip over the batch
 template <class Tiles>
 int shadow_step(ShadowBatch& B, hipStream_t s, MsStep step, Tiles tiles_of) {
     return run_step(B.ms, [step](const MsLaunch& L, hipStream_t st) { return launch_mask_shadow(step, L, st); }, s, tiles_of);
 }
-int64_t items_tiles(int64_t items) { return (items + kMsThreads - 1) / kMsThreads; }
-
 // labels of plane `which` (or of its complement) of every job: init, merge with connectivity `conn`, flatten
 int shadow_label(ShadowBatch& B, hipStream_t s, int which, int conn, int flags) {
     B.ms.conn = conn;
     for (MsStep step : {kMsLabelInit, kMsLabelMerge, kMsLabelFlatten})
         if (int rc = shadow_step(B, s, step, [&](int k, MsJob& J) {
                 J.a = B.plane(k, which); J.flags = flags;
-                return items_tiles((int64_t)J.H * J.pw);
+                return mk_item_tiles(mk_plane_items(J));
             })) return rc;
+    return 0;
+}
+
+// either call: the checks, the caller's tables and elements staged in every job's area and read, then `steps(B, s)` per batch
+template <class Steps>
+int shadow_call(gs360_ctx* c, const gs360_shadow_job* jobs, int n_jobs, bool merge, void* scratch_dev, size_t scratch_bytes,
+                uint32_t* counts_dev, int slot, hipStream_t* s, Steps steps) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    size_t need = 0;
+    if (int rc = check_shadow_jobs(jobs, n_jobs, merge, &need)) return rc;
+    if (n_jobs == 0) return 0;
+    if (int rc = begin_call(c, slot, n_jobs, scratch_dev, scratch_bytes, need, counts_dev, s)) return rc;
+    if (merge) HIP_TRY(hipMemsetAsync(scratch_dev, 0, kShHead, *s));
+    uint8_t* at = (uint8_t*)scratch_dev + kShHead;
+    for (int k = 0; k < n_jobs; ++k) {
+        const gs360_shadow_job& j = jobs[k];
+        const ShadowArea a = shadow_area(j.H, j.W);
+        const ShadowElements el(j);
+        for (int e = el.first(merge); e < el.end(merge); ++e)
+            if (int rc = stage_rows(at + a.rows[e], el.rows[e], el.kh[e], *s)) return rc;
+        if (!merge) {
+            HIP_TRY(hipMemcpyAsync(at + a.weights, j.weights, (size_t)(j.radius + 1) * 4, hipMemcpyHostToDevice, *s));
+            HIP_TRY(hipMemcpyAsync(at + a.sdiv, j.sdiv, 1024, hipMemcpyHostToDevice, *s));
+        }
+        at += a.total;
+    }
+    HIP_TRY(hipStreamSynchronize(*s));                    // the caller's tables and element rows are read
+    at = (uint8_t*)scratch_dev + kShHead;
+    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
+        ShadowBatch B;
+        shadow_batch(B, jobs + k0, std::min(GS360_MAX_VIEWS, n_jobs - k0), merge, &at, counts_dev + k0, (uint32_t*)scratch_dev);
+        if (int rc = steps(B, *s)) return rc;
+    }
     return 0;
 }
 
@@ -334,109 +386,55 @@ int gs360_mask_shadow_scratch(const gs360_shadow_job* jobs, int n_jobs, size_t* 
 
 int gs360_mask_shadow_candidates_u8(gs360_ctx* c, const gs360_shadow_job* jobs, int n_jobs, void* scratch_dev, size_t scratch_bytes,
                                     uint32_t* counts_dev, int slot) {
-    if (int rc = check_shadow_call(c, jobs, n_jobs, false, scratch_dev, scratch_bytes, counts_dev, slot)) return rc;
-    if (n_jobs == 0) return GS360_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream[slot];
-    HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_jobs * sizeof(uint32_t), s));
-    uint8_t* at = (uint8_t*)scratch_dev + kShHead;
-    for (int k = 0; k < n_jobs; ++k) {                    // the host tables of every job
-        const gs360_shadow_job& j = jobs[k];
-        const ShadowArea a = shadow_area(j.H, j.W);
-        HIP_TRY(hipMemcpyAsync(at + a.weights, j.weights, (size_t)(j.radius + 1) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(at + a.sdiv, j.sdiv, 1024, hipMemcpyHostToDevice, s));
-        if (j.close_kh) HIP_TRY(hipMemcpyAsync(at + a.rows[0], j.close_rows, (size_t)j.close_kh * 8, hipMemcpyHostToDevice, s));
-        at += a.total;
-    }
-    HIP_TRY(hipStreamSynchronize(s));                     // the caller's tables are read
-    at = (uint8_t*)scratch_dev + kShHead;
-    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
-        const int n = std::min(GS360_MAX_VIEWS, n_jobs - k0);
-        ShadowBatch B;
-        shadow_batch(B, jobs + k0, n, at, counts_dev + k0, (uint32_t*)scratch_dev);
-        int kw[GS360_MAX_VIEWS], kh[GS360_MAX_VIEWS], halo[GS360_MAX_VIEWS];
-        for (int k = 0; k < n; ++k) {
-            const gs360_shadow_job& j = jobs[k0 + k];
-            kw[k] = j.close_kw; kh[k] = j.close_kh;
-            halo[k] = kh[k] ? element_reach(j.close_rows, kw[k], kh[k]) / 32 + 2 : 0;
-            at += B.area[k].total;
-        }
+    hipStream_t stream;
+    return shadow_call(c, jobs, n_jobs, false, scratch_dev, scratch_bytes, counts_dev, slot, &stream, [](ShadowBatch& B, hipStream_t s) {
+        const Element* close = B.el[kShElClose];
         // P: MSK-SPEC steps 0-1 (pack, close); a job without a close packs straight into P
-        if (int rc = run_step(B.mk, launch_mask_pack_bits, s, [&](int k, MkJob& J) { J.out = B.plane(k, kh[k] ? kShT0 : kShP); return row_tiles(J, 4 * kMkThreads, 1); })) return rc;
-        if (int rc = shadow_morph(B, s, kShT0, kShT1, 0, kw, kh, halo, 0)) return rc;
-        if (int rc = shadow_morph(B, s, kShT1, kShP, 0, kw, kh, halo, kMkCompIn | kMkCompOut)) return rc;
+        if (int rc = run_step(B.mk, launch_mask_pack_bits, s, [&](int k, MkJob& J) { J.out = B.plane(k, close[k].kh ? kShT0 : kShP); return row_tiles(J, kMkPackTile); })) return rc;
+        if (int rc = shadow_morph(B, s, kShT0, kShT1, kShElClose, 0)) return rc;
+        if (int rc = shadow_morph(B, s, kShT1, kShP, kShElClose, kMkCompIn | kMkCompOut)) return rc;
         B.mk.phase = 0;                                   // count(P): the finishing chain's counting pass without an add layer
-        if (int rc = run_step(B.mk, launch_mask_finish, s, [&](int k, MkJob& J) { J.out = B.plane(k, kShP); return row_tiles(J, 4 * kMkThreads, kMkFinishRows); })) return rc;
-        if (int rc = shadow_step(B, s, kMsPixel, [&](int k, MsJob& J) { J.out = B.plane(k, kShSat); return row_tiles(J, 4 * kMsThreads, 1); })) return rc;
-        if (int rc = shadow_step(B, s, kMsBlurRows, [&](int, MsJob& J) { return row_tiles(J, kMsRowSeg, 1); })) return rc;
-        if (int rc = shadow_step(B, s, kMsBlurCols, [&](int k, MsJob& J) {
-                J.a = B.plane(k, kShSat); J.out = B.plane(k, kShC0);
-                return row_tiles(J, kMsColW, kMsColRows);
-            })) return rc;
-    }
-    return GS360_OK;
+        if (int rc = run_step(B.mk, launch_mask_finish, s, [&](int k, MkJob& J) { J.out = B.plane(k, kShP); return row_tiles(J, kMkCountTile); })) return rc;
+        if (int rc = shadow_step(B, s, kMsPixel, [&](int k, MsJob& J) { J.out = B.plane(k, kShSat); return row_tiles(J, kMsPixelTile); })) return rc;
+        if (int rc = shadow_step(B, s, kMsBlurRows, [&](int, MsJob& J) { return row_tiles(J, kMsRowsTile); })) return rc;
+        return shadow_step(B, s, kMsBlurCols, [&](int k, MsJob& J) {
+            J.a = B.plane(k, kShSat); J.out = B.plane(k, kShC0);
+            return row_tiles(J, kMsColsTile);
+        });
+    });
 }
 
 int gs360_mask_shadow_merge_u8(gs360_ctx* c, const gs360_shadow_job* jobs, int n_jobs, void* scratch_dev, size_t scratch_bytes,
                                uint32_t* counts_dev, int slot) {
-    if (int rc = check_shadow_call(c, jobs, n_jobs, true, scratch_dev, scratch_bytes, counts_dev, slot)) return rc;
-    if (n_jobs == 0) return GS360_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream[slot];
-    HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_jobs * sizeof(uint32_t), s));
-    HIP_TRY(hipMemsetAsync(scratch_dev, 0, kShHead, s));
-    uint8_t* at = (uint8_t*)scratch_dev + kShHead;
-    for (int k = 0; k < n_jobs; ++k) {                    // the three elements of every job
-        const gs360_shadow_job& j = jobs[k];
-        const ShadowArea a = shadow_area(j.H, j.W);
-        HIP_TRY(hipMemcpyAsync(at + a.rows[1], j.near_rows, (size_t)j.near_kh * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(at + a.rows[2], j.sclose_rows, (size_t)j.sclose_kh * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(at + a.rows[3], j.open_rows, (size_t)j.open_kh * 8, hipMemcpyHostToDevice, s));
-        at += a.total;
-    }
-    HIP_TRY(hipStreamSynchronize(s));                     // the caller's element rows are read
-    at = (uint8_t*)scratch_dev + kShHead;
-    for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
-        const int n = std::min(GS360_MAX_VIEWS, n_jobs - k0);
-        ShadowBatch B;
-        shadow_batch(B, jobs + k0, n, at, counts_dev + k0, (uint32_t*)scratch_dev);
-        int kw[3][GS360_MAX_VIEWS], kh[3][GS360_MAX_VIEWS], halo[3][GS360_MAX_VIEWS];
-        for (int k = 0; k < n; ++k) {
-            const gs360_shadow_job& j = jobs[k0 + k];
-            const int w[3] = {j.near_kw, j.sclose_kw, j.open_kw}, h[3] = {j.near_kh, j.sclose_kh, j.open_kh};
-            const int32_t* rows[3] = {j.near_rows, j.sclose_rows, j.open_rows};
-            for (int e = 0; e < 3; ++e) { kw[e][k] = w[e]; kh[e][k] = h[e]; halo[e][k] = element_reach(rows[e], w[e], h[e]) / 32 + 2; }
-            at += B.area[k].total;
-        }
-        auto clear_area = [&]() {
-            for (int k = 0; k < n; ++k) HIP_TRY(hipMemsetAsync(B.ms.job[k].area, 0, (size_t)B.ms.job[k].H * B.ms.job[k].W * 4, s));
-            return 0;
-        };
-        const int both = kMkCompIn | kMkCompOut;
-        if (int rc = shadow_morph(B, s, kShP, kShT0, 1, kw[0], kh[0], halo[0], 0)) return rc;                  // step 4: the near region
-        if (int rc = shadow_step(B, s, kMsLogic, [&](int k, MsJob& J) {
-                J.a = B.plane(k, kShC0); J.b = B.plane(k, kShT0); J.c = B.plane(k, kShP); J.out = B.plane(k, kShC1);
-                return items_tiles((int64_t)J.H * J.pw);
-            })) return rc;
-        if (int rc = shadow_morph(B, s, kShC1, kShT0, 2, kw[1], kh[1], halo[1], 0)) return rc;                 // step 5: close ...
-        if (int rc = shadow_morph(B, s, kShT0, kShT1, 2, kw[1], kh[1], halo[1], both)) return rc;
-        if (int rc = shadow_morph(B, s, kShT1, kShT0, 3, kw[2], kh[2], halo[2], both)) return rc;              // ... and open
-        if (int rc = shadow_morph(B, s, kShT0, kShC2, 3, kw[2], kh[2], halo[2], 0)) return rc;
-        if (int rc = clear_area()) return rc;                                                                  // step 6: O, G = ~O in T1
-        if (int rc = shadow_label(B, s, kShC2, 4, kMsComplement)) return rc;
-        if (int rc = shadow_step(B, s, kMsBorder, [&](int, MsJob& J) { return items_tiles(2 * (int64_t)J.W + 2 * (int64_t)J.H); })) return rc;
-        if (int rc = shadow_step(B, s, kMsFill, [&](int k, MsJob& J) { J.out = B.plane(k, kShT1); return row_tiles(J, kMsThreads, 1); })) return rc;
-        if (int rc = clear_area()) return rc;
-        if (int rc = shadow_label(B, s, kShT1, 8, 0)) return rc;
-        if (int rc = shadow_step(B, s, kMsArea, [&](int k, MsJob& J) {
-                J.a = B.plane(k, kShT1);
-                return J.H < 2 ? 0 : items_tiles((int64_t)J.pw * ((J.H - 1 + kMsAreaRows - 1) / kMsAreaRows));
-            })) return rc;
-        if (int rc = shadow_step(B, s, kMsSelect, [&](int k, MsJob& J) {                                       // steps 6-7: clean, M and its count
+    hipStream_t s;
+    if (int rc = shadow_call(c, jobs, n_jobs, true, scratch_dev, scratch_bytes, counts_dev, slot, &s, [](ShadowBatch& B, hipStream_t s) {
+            auto clear_area = [&]() {
+                for (int k = 0; k < B.ms.n_jobs; ++k) HIP_TRY(hipMemsetAsync(B.ms.job[k].area, 0, (size_t)B.ms.job[k].H * B.ms.job[k].W * 4, s));
+                return 0;
+            };
+            const int both = kMkCompIn | kMkCompOut;
+            if (int rc = shadow_morph(B, s, kShP, kShT0, kShElNear, 0)) return rc;                             // step 4: the near region
+            if (int rc = shadow_step(B, s, kMsLogic, [&](int k, MsJob& J) {
+                    J.a = B.plane(k, kShC0); J.b = B.plane(k, kShT0); J.c = B.plane(k, kShP); J.out = B.plane(k, kShC1);
+                    return mk_item_tiles(mk_plane_items(J));
+                })) return rc;
+            if (int rc = shadow_morph(B, s, kShC1, kShT0, kShElSclose, 0)) return rc;                          // step 5: close ...
+            if (int rc = shadow_morph(B, s, kShT0, kShT1, kShElSclose, both)) return rc;
+            if (int rc = shadow_morph(B, s, kShT1, kShT0, kShElOpen, both)) return rc;                         // ... and open
+            if (int rc = shadow_morph(B, s, kShT0, kShC2, kShElOpen, 0)) return rc;
+            if (int rc = clear_area()) return rc;                                                              // step 6: O, G = ~O in T1
+            if (int rc = shadow_label(B, s, kShC2, 4, kMsComplement)) return rc;
+            if (int rc = shadow_step(B, s, kMsBorder, [&](int, MsJob& J) { return mk_item_tiles(ms_border_items(J)); })) return rc;
+            if (int rc = shadow_step(B, s, kMsFill, [&](int k, MsJob& J) { J.out = B.plane(k, kShT1); return row_tiles(J, kMsFillTile); })) return rc;
+            if (int rc = clear_area()) return rc;
+            if (int rc = shadow_label(B, s, kShT1, 8, 0)) return rc;
+            if (int rc = shadow_step(B, s, kMsArea, [&](int k, MsJob& J) { J.a = B.plane(k, kShT1); return mk_item_tiles(ms_area_items(J)); })) return rc;
+            return shadow_step(B, s, kMsSelect, [&](int k, MsJob& J) {                                         // steps 6-7: clean, M and its count
                 J.a = B.plane(k, kShT1); J.b = B.plane(k, kShP); J.out = B.plane(k, kShClean);
-                return row_tiles(J, 4 * kMsThreads, kMsSelectRows);
-            })) return rc;
-    }
+                return row_tiles(J, kMsSelectTile);
+            });
+        })) return rc;
+    if (n_jobs == 0) return GS360_OK;
     uint32_t err = 0;                                     // a label walk past its bound: the result is not to be used
     HIP_TRY(hipMemcpyAsync(&err, scratch_dev, sizeof(err), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

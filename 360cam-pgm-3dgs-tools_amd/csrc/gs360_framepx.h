@@ -1,5 +1,5 @@
 // gs360_framepx.h -- FS-SPEC's per-pixel steps, shared by the FrameSelector passes (gs360_framescore.hip, gs360_framefft.hip,
-// gs360_frameflow.hip).  Private to those files; gs360_maskshadow.hip takes gray_of from here, the library's one 8-bit gray.
+// gs360_frameflow.hip).  Private to those files; the mask kernels (gs360_maskplane.h) take gray_of, the library's one 8-bit gray, and wave_sum from here.
 #pragma once
 #include "gs360_kernels.h"
 

@@ -522,86 +522,7 @@ struct JdLaunch {
 static_assert(sizeof(JdLaunch) <= 4096, "a launch travels by value as the kernels' argument");
 hipError_t launch_jpeg_decode(const JdLaunch& L, bool gray, hipStream_t s);   // gray: jd_pixels_kernel's output mode
 
-// Segmentation-mask finishing (gs360_maskmorph.hip, MSK-SPEC v1 in DESIGN.md): one step of the chain over a batch of up to
-// GS360_MAX_VIEWS masks.  A mask lives as a bit plane (bit x & 31 of dword x >> 5, pw = ceil(W / 32) dwords per row, bits at columns
-// >= W zero); the glue fills the fields a step reads and gives a job that skips the step no tiles.
-constexpr int kMkThreads = 256;
-constexpr int kMkTileW = 32, kMkTileR = 32;              // a morph tile: output dwords x output rows
-constexpr int kMkMaxElem = 1025;                         // largest element side (p = 512)
-constexpr int kMkMaxHalo = kMkMaxElem / 2 / 32 + 2;      // staged dwords left and right of a tile: reach / 32 + 2
-constexpr int kMkStageW = kMkTileW + 2 * kMkMaxHalo, kMkStageRows = 96;   // the LDS band: 96 rows of at most 68 dwords
-constexpr int kMkFinishRows = 32;                        // rows of a workgroup of the counting pass
-constexpr int kMkCompIn = 1, kMkCompOut = 2;             // morph flags: complement the plane read / written, inside the image
-#define MK_HD __host__ __device__
-MK_HD inline uint32_t mk_colmask(int W, int w) {         // the columns of dword w that lie inside the image
-    const int left = W - 32 * w;
-    return left >= 32 ? 0xffffffffu : left <= 0 ? 0u : (0xffffffffu >> (32 - left));
-}
-// eight neighbouring lanes' nibbles as the dword of the plane they cover (in all eight lanes)
-__device__ __forceinline__ uint32_t mk_gather8(uint32_t nib) {
-    uint32_t v = nib << (4 * (threadIdx.x & 7));
-    v |= __shfl_xor(v, 1, 64); v |= __shfl_xor(v, 2, 64); v |= __shfl_xor(v, 4, 64);
-    return v;
-}
-struct MkJob {
-    const uint8_t *src, *add, *img;      // raw mask (null: all clear), manual add layer (null: none), H x W x 3 image (compose kinds)
-    uint8_t* dst;
-    int64_t src_stride, add_stride, img_stride, dst_stride;
-    const uint32_t* in;                  // the plane a step reads ...
-    uint32_t* out;                       // ... and writes (pack, finish: the one plane they work on)
-    const int32_t* spans;                // morph: kh x (j1, j2), device memory
-    int32_t H, W, pw, thresh;
-    int32_t kh, ax, ay, halo;            // morph: element rows, anchor, staged halo dwords (reach / 32 + 2)
-    int32_t f, s, kind, invert;          // edge fuse: strip width and vertical spread of the side seeds; output kind and polarity
-    int32_t tile_base, tiles_x, flags, pad;
-};
-struct MkLaunch {
-    MkJob job[GS360_MAX_VIEWS];
-    int32_t n_jobs, total_tiles, phase, pad;
-    uint32_t* counts;                    // n_jobs: set pixels of the finished masks (the caller's buffer)
-};
-static_assert(sizeof(MkLaunch) <= 4096, "a launch travels by value as the kernels' argument");
-hipError_t launch_mask_pack_bits(const MkLaunch& L, hipStream_t s);   // mk_pack_kernel
-hipError_t launch_mask_morph(const MkLaunch& L, hipStream_t s);       // mk_morph_kernel: one dilate or erode
-hipError_t launch_mask_fuse(const MkLaunch& L, hipStream_t s);        // mk_fuse_kernel, phase 0 (copy) or 1 (the strips' fills)
-hipError_t launch_mask_finish(const MkLaunch& L, hipStream_t s);      // mk_finish_kernel, phase 0 (add layer, count) or 1 (output)
-
-// The shadow estimate in front of the finishing chain (gs360_maskshadow.hip, MSK-SHADOW v1 in DESIGN.md section 14): one step over a
-// batch of up to GS360_MAX_VIEWS images.  Bit planes are MSK-SPEC's; the gray plane has 32 pw bytes per row, the float plane of the
-// row pass W floats (the labels take its place later), `area` one dword per pixel (root flags, then doubled areas).
-constexpr int kMsThreads = 256;
-constexpr int kMsOut = 8;                                // neighbouring outputs of one lane of the two blur passes
-constexpr int kMsMaxR = 255;                             // largest filter radius
-constexpr int kMsRowSeg = kMsThreads * kMsOut;           // outputs of a workgroup of the row pass
-constexpr int kMsColW = 64, kMsColRows = 128;            // a column-pass tile: a wave's 64 columns x 4 waves' 32 rows
-constexpr int kMsAreaRows = 16, kMsSelectRows = 8;       // cell rows of an area lane, rows of a select workgroup
-constexpr int kMsComplement = 1;                         // label flag: the plane's complement (inside the image) is labelled
-struct MsJob {
-    const uint8_t* img;                  // H x W x 3
-    uint8_t *gray, *dst;                 // gray plane; M as H x W bytes of 0 / 255
-    float* mid;                          // the row pass's result
-    int32_t* lab;                        // labels: a set pixel's root index y W + x, -1 elsewhere
-    uint32_t* area;
-    const float* k;                      // r + 1 weights, centre outward (device memory)
-    const int32_t* sdiv;                 // 256 saturation divisors (device memory)
-    const uint32_t *a, *b, *c;           // the planes a step reads ...
-    uint32_t *out, *out2;                // ... and writes
-    int64_t img_stride, dst_stride;
-    int32_t H, W, pw, r;
-    float t, delta_min;
-    int32_t sat_max;
-    uint32_t th2;                        // 2 max(1, min_area)
-    int32_t tile_base, tiles_x, flags, pad;
-};
-struct MsLaunch {
-    MsJob job[GS360_MAX_VIEWS];
-    int32_t n_jobs, total_tiles, conn, pad;              // conn: 4 or 8 (label merge)
-    uint32_t* counts;                    // n_jobs: set pixels of M
-    uint32_t* err;                       // one word: set when a label walk ran past its bound
-};
-static_assert(sizeof(MsLaunch) <= 4096, "a launch travels by value as the kernels' argument");
-enum MsStep { kMsPixel, kMsBlurRows, kMsBlurCols, kMsLogic, kMsLabelInit, kMsLabelMerge, kMsLabelFlatten, kMsBorder, kMsFill, kMsArea, kMsSelect };
-hipError_t launch_mask_shadow(MsStep step, const MsLaunch& L, hipStream_t s);
+// The mask families (gs360_maskmorph.hip, gs360_maskshadow.hip) keep their jobs, launches and shared steps in gs360_maskplane.h.
 
 // Voxel downsampling of a resident point cloud (gs360_voxel.hip, VOX-SPEC v1 in DESIGN.md section 15).  The glue sorts the packed
 // keys between `keys` and `heads`; everything else of a count or a pick is one of these steps.

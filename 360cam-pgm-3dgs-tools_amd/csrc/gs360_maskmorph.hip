@@ -19,32 +19,23 @@
 //            writes the mask (four pixels per lane) or composes RGBA / keep / remove (one), and takes the
 //            empty-mask branches from the count
 // Every loop is bounded by H, W, kh or the strip; there are no waits between workgroups.  The per-lane arithmetic is host-callable
-// (MK_HD) so that tests/tools/maskmorph_hostcheck.hip can step it under a sanitizer.
-#include "gs360_kernels.h"
+// (MK_HD) so that tests/tools/maskmorph_hostcheck.hip can step it under a sanitizer.  The steps on a plane that the shadow estimate
+// shares (a bit, a nibble, the 4-byte group load and store, the gathered word, the count tail, the atomics) and every step's launch
+// geometry are gs360_maskplane.h's; this file holds the morph, fuse and compose arithmetic.
+#include "gs360_maskplane.h"
 
 namespace gs360 {
 namespace {
 
-MK_HD inline int mk_ctz(uint32_t v) { return __builtin_ctz(v); }
-MK_HD inline int mk_clz(uint32_t v) { return __builtin_clz(v); }
-
 // ---- pack ------------------------------------------------------------------------------------------------------------------------
 // four pixels of a byte plane from column x (a multiple of 4) on as a nibble: bit k = `value > thresh`; clear at columns >= W and for a
-// plane that is not there.  An aligned group inside the row is one dword load.
+// plane that is not there
 MK_HD inline uint32_t mk_nibble(const uint8_t* plane, int64_t stride, int W, int thresh, int y, int x) {
     if (!plane || x >= W) return 0;
-    const uint8_t* p = plane + (int64_t)y * stride + x;
-    uint32_t v = 0;
-    if (x + 4 <= W && ((uintptr_t)p & 3) == 0) __builtin_memcpy(&v, __builtin_assume_aligned(p, 4), 4);
-    else
-        for (int k = 0; k < 4 && x + k < W; ++k) v |= (uint32_t)p[k] << (8 * k);
+    const uint32_t v = mk_load4(plane + (int64_t)y * stride + x, x, W);
     uint32_t nib = 0;
     for (int k = 0; k < 4; ++k) nib |= (uint32_t)((int)((v >> (8 * k)) & 255u) > thresh) << k;
     return nib;
-}
-// the same four columns of a bit plane's row
-MK_HD inline uint32_t mk_plane_nibble(const uint32_t* plane, int pw, int y, int x) {
-    return (x >> 5) < pw ? (plane[(int64_t)y * pw + (x >> 5)] >> (x & 31)) & 15u : 0u;
 }
 
 // ---- morph -----------------------------------------------------------------------------------------------------------------------
@@ -131,14 +122,7 @@ MK_HD inline void mk_morph_store(const MkJob& J, int y0, int w0, int lane, const
 }
 
 // ---- fuse ------------------------------------------------------------------------------------------------------------------------
-MK_HD inline void mk_or(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicOr(p, v);
-#else
-    *p |= v;
-#endif
-}
-// item q of a job's fills: dword columns of the top strip, of the bottom strip, rows of the left strip, of the right strip
+// item q of a job's fills (mk_fuse_items); integer atomic ORs, which commute
 MK_HD inline void mk_fuse_item(const MkJob& J, int q) {
     const int pw = J.pw, H = J.H, W = J.W, f = J.f, s = J.s;
     if (q < 2 * pw) {                                     // rows 0 .. y_min (top) or y_max .. H - 1 (bottom) of every column with a set row
@@ -150,7 +134,7 @@ MK_HD inline void mk_fuse_item(const MkJob& J, int q) {
         uint32_t seen = 0;
         for (int k = 0, y = y_first; k < f; ++k, y += step) {
             const uint32_t cur = J.in[(int64_t)y * pw + w], fill = any & ~seen & ~cur;
-            if (fill) mk_or(J.out + (int64_t)y * pw + w, fill);
+            if (fill) mk_atomic_or(J.out + (int64_t)y * pw + w, fill);
             seen |= cur;
         }
         return;
@@ -171,22 +155,20 @@ MK_HD inline void mk_fuse_item(const MkJob& J, int q) {
         if (!v) continue;
         uint32_t* row = J.out + (int64_t)y * pw;
         if (left) {
-            for (int u = 0; u < w; ++u) mk_or(row + u, 0xffffffffu);
-            mk_or(row + w, 0xffffffffu >> (31 - mk_ctz(v)));
+            for (int u = 0; u < w; ++u) mk_atomic_or(row + u, 0xffffffffu);
+            mk_atomic_or(row + w, 0xffffffffu >> (31 - mk_ctz(v)));
         } else {
-            mk_or(row + w, (0xffffffffu << (31 - mk_clz(v))) & mk_colmask(W, w));
-            for (int u = w + 1; u < pw; ++u) mk_or(row + u, mk_colmask(W, u));
+            mk_atomic_or(row + w, (0xffffffffu << (31 - mk_clz(v))) & mk_colmask(W, w));
+            for (int u = w + 1; u < pw; ++u) mk_atomic_or(row + u, mk_colmask(W, u));
         }
         return;
     }
 }
-MK_HD inline int mk_fuse_items(const MkJob& J) { return 2 * J.pw + 2 * J.H; }
 
 // ---- finish ----------------------------------------------------------------------------------------------------------------------
-MK_HD inline bool mk_bit(const MkJob& J, int y, int x) { return (J.out[(int64_t)y * J.pw + (x >> 5)] >> (x & 31)) & 1u; }
 // pixel (y, x) of the output; count: the mask's set pixels (zero takes the reference's `mask is None` branches)
 MK_HD inline void mk_compose(const MkJob& J, int y, int x, uint32_t count) {
-    const bool m = mk_bit(J, y, x);
+    const bool m = mk_bit(J.out, J.pw, y, x);
     const uint8_t on = J.invert ? 0 : 255, off = J.invert ? 255 : 0;
     if (J.kind == GS360_MASK_OUT_MASK) {
         J.dst[(int64_t)y * J.dst_stride + x] = m ? on : off;
@@ -205,41 +187,29 @@ MK_HD inline void mk_compose(const MkJob& J, int y, int x, uint32_t count) {
     o[0] = keep ? r : 0; o[1] = keep ? g : 0; o[2] = keep ? b : 0;
 }
 
-// GS360_MASK_OUT_MASK, four pixels from column x (a multiple of 4) on: one dword store where the group is aligned and inside the row
+// GS360_MASK_OUT_MASK, four pixels from column x (a multiple of 4) on
 MK_HD inline void mk_compose_mask4(const MkJob& J, int y, int x) {
     if (x >= J.W) return;
     const uint32_t nib = mk_plane_nibble(J.out, J.pw, y, x), on = J.invert ? 0u : 255u, off = 255u - on;
     uint32_t v = 0;
     for (int k = 0; k < 4; ++k) v |= (((nib >> k) & 1u) ? on : off) << (8 * k);
-    uint8_t* p = J.dst + (int64_t)y * J.dst_stride + x;
-    if (x + 4 <= J.W && ((uintptr_t)p & 3) == 0) __builtin_memcpy(__builtin_assume_aligned(p, 4), &v, 4);
-    else
-        for (int k = 0; k < 4 && x + k < J.W; ++k) p[k] = (uint8_t)(v >> (8 * k));
-}
-
-// a workgroup's row segment (pack, finish): tile t of the job -> (row or band of rows, the workgroup's first lane among the row's)
-__device__ __forceinline__ void mk_row_tile(const MkJob& J, int t, int* y, int* x0) {
-    *y = t / J.tiles_x;
-    *x0 = (t - *y * J.tiles_x) * kMkThreads;
-}
-// eight lanes' dword of the plane (mk_gather8, gs360_kernels.h), stored by the first of them
-__device__ __forceinline__ void mk_store_word(const MkJob& J, int y, int x, uint32_t word) {
-    if ((threadIdx.x & 7) == 0 && (x >> 5) < J.pw) J.out[(int64_t)y * J.pw + (x >> 5)] = word;
+    mk_store4(J.dst + (int64_t)y * J.dst_stride + x, x, J.W, v);
 }
 
 __global__ void __launch_bounds__(kMkThreads) mk_pack_kernel(const MkLaunch L) {
     const MkJob& J = L.job[job_of(L, blockIdx.x, &MkJob::tile_base)];
-    int y, l0;
-    mk_row_tile(J, blockIdx.x - J.tile_base, &y, &l0);
-    const int x = 4 * (l0 + threadIdx.x);                // four pixels per lane, 1024 per workgroup
-    mk_store_word(J, y, x, mk_gather8(mk_nibble(J.src, J.src_stride, J.W, J.thresh, y, x)));
+    int y, tx;
+    mk_tile_of(J, &y, &tx);
+    const int x = tx * kMkPackTile.w + 4 * threadIdx.x;
+    mk_store_word(J.out, J.pw, y, x, mk_gather8(mk_nibble(J.src, J.src_stride, J.W, J.thresh, y, x)));
 }
 
 __global__ void __launch_bounds__(kMkThreads) mk_morph_kernel(const MkLaunch L) {
     __shared__ uint32_t stage[kMkStageRows * kMkStageW];
     const MkJob& J = L.job[job_of(L, blockIdx.x, &MkJob::tile_base)];
-    const int t = blockIdx.x - J.tile_base, ty = t / J.tiles_x, tx = t - ty * J.tiles_x;
-    const int w0 = tx * kMkTileW, y0 = ty * kMkTileR;
+    int ty, tx;
+    mk_tile_of(J, &ty, &tx);
+    const int w0 = tx * kMkMorphTile.w, y0 = ty * kMkMorphTile.h;
     MkAcc acc = {0, 0, 0, 0};
     for (int i0 = 0; i0 < J.kh; i0 += kMkBand) {
         __syncthreads();
@@ -252,52 +222,41 @@ __global__ void __launch_bounds__(kMkThreads) mk_morph_kernel(const MkLaunch L) 
 
 __global__ void __launch_bounds__(kMkThreads) mk_fuse_kernel(const MkLaunch L) {
     const MkJob& J = L.job[job_of(L, blockIdx.x, &MkJob::tile_base)];
-    const int64_t q = (int64_t)(blockIdx.x - J.tile_base) * kMkThreads + threadIdx.x;
+    const int64_t q = mk_item_of(J);
     if (L.phase == 0) {
-        if (q < (int64_t)J.H * J.pw) J.out[q] = J.in[q];
+        if (q < mk_plane_items(J)) J.out[q] = J.in[q];
     } else if (q < mk_fuse_items(J)) {
         mk_fuse_item(J, (int)q);
     }
 }
 
 __global__ void __launch_bounds__(kMkThreads) mk_finish_kernel(const MkLaunch L) {
-    __shared__ uint32_t wg_count;
     const int j = job_of(L, blockIdx.x, &MkJob::tile_base);
     const MkJob& J = L.job[j];
-    int y, l0;
-    mk_row_tile(J, blockIdx.x - J.tile_base, &y, &l0);
+    int y, tx;
+    mk_tile_of(J, &y, &tx);
     if (L.phase == 1) {                                   // the mask: four pixels per lane; the compose kinds: one
-        if (J.kind == GS360_MASK_OUT_MASK) mk_compose_mask4(J, y, 4 * (l0 + threadIdx.x));
-        else if (l0 + threadIdx.x < J.W) mk_compose(J, y, l0 + threadIdx.x, L.counts[j]);
+        const int lane = tx * kMkThreads + threadIdx.x;   // mk_output_tile: mk_output_px pixels for each of the row's lanes
+        if (J.kind == GS360_MASK_OUT_MASK) mk_compose_mask4(J, y, mk_output_px(GS360_MASK_OUT_MASK) * lane);
+        else if (lane < J.W) mk_compose(J, y, lane, L.counts[j]);
         return;
     }
-    // phase 0: four pixels per lane and a band of kMkFinishRows rows per workgroup, so that a mask costs few atomics on its one counter
-    if (threadIdx.x == 0) wg_count = 0;
-    __syncthreads();
-    const int x = 4 * (l0 + threadIdx.x), y1 = min(J.H, (y + 1) * kMkFinishRows);
+    // phase 0: four pixels per lane and a band of rows per workgroup
+    const int x = tx * kMkCountTile.w + 4 * threadIdx.x, y1 = min(J.H, (y + 1) * kMkCountTile.h);
     uint32_t n = 0;
-    for (y *= kMkFinishRows; y < y1; ++y) {
+    for (y *= kMkCountTile.h; y < y1; ++y) {
         const uint32_t nib = mk_plane_nibble(J.out, J.pw, y, x) | mk_nibble(J.add, J.add_stride, J.W, 0, y, x);
-        if (J.add) mk_store_word(J, y, x, mk_gather8(nib));   // (the shuffles wait for the eight lanes' reads of the dword)
+        if (J.add) mk_store_word(J.out, J.pw, y, x, mk_gather8(nib));   // (the shuffles wait for the eight lanes' reads of the dword)
         n += (uint32_t)__popc(nib);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&wg_count, n);
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_count) atomicAdd(L.counts + j, wg_count);
+    mk_count_tail(n, L.counts + j);
 }
 
 }  // namespace
 
-#define MK_LAUNCH(kernel)                                                                        \
-    if (L.total_tiles <= 0) return hipSuccess;                                                   \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)L.total_tiles), dim3(kMkThreads), 0, s, L);        \
-    return hipGetLastError();
-hipError_t launch_mask_pack_bits(const MkLaunch& L, hipStream_t s) { MK_LAUNCH(mk_pack_kernel) }
-hipError_t launch_mask_morph(const MkLaunch& L, hipStream_t s) { MK_LAUNCH(mk_morph_kernel) }
-hipError_t launch_mask_fuse(const MkLaunch& L, hipStream_t s) { MK_LAUNCH(mk_fuse_kernel) }
-hipError_t launch_mask_finish(const MkLaunch& L, hipStream_t s) { MK_LAUNCH(mk_finish_kernel) }
-#undef MK_LAUNCH
+hipError_t launch_mask_pack_bits(const MkLaunch& L, hipStream_t s) { return mk_launch(mk_pack_kernel, L, s); }
+hipError_t launch_mask_morph(const MkLaunch& L, hipStream_t s) { return mk_launch(mk_morph_kernel, L, s); }
+hipError_t launch_mask_fuse(const MkLaunch& L, hipStream_t s) { return mk_launch(mk_fuse_kernel, L, s); }
+hipError_t launch_mask_finish(const MkLaunch& L, hipStream_t s) { return mk_launch(mk_finish_kernel, L, s); }
 
 }  // namespace gs360

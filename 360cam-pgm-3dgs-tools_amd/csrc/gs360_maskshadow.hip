@@ -2,7 +2,9 @@
 //
 // Reference: gs360_SegmentationMaskTool.py's estimate_shadow_mask (SEG:499-558): pixels much darker than a wide Gaussian of the gray
 // image, of low saturation, near the person mask, cleaned by a close and an open, kept per outer contour of enough area and filled.
-// The morphology is gs360_maskmorph.hip's mk_morph_kernel (launched by the glue); this file holds the rest:
+// The morphology is gs360_maskmorph.hip's mk_morph_kernel (launched by the glue); the steps on a plane that both files share (a bit,
+// the 4-byte group store, the gathered word, the ballot as two dwords, the count tail, the atomics) and every step's launch geometry
+// are gs360_maskplane.h's; this file holds the rest:
 //
 //   pixel     four pixels per lane: gray (gray_of) as one dword of the gray plane, `S <= sat_max` (cv2's 8-bit RGB2HSV, the divisor
 //             table is DATA) as a nibble; eight lanes' nibbles are shuffled into a dword of the plane, as mk_pack_kernel packs
@@ -25,19 +27,14 @@
 //
 // Floating point is taken op by op (the library is built with -ffp-contract=off; no fma here).  The per-lane arithmetic is
 // host-callable (MK_HD) so that tests/tools/maskshadow_hostcheck.hip can step it under a sanitizer.
-#include "gs360_framepx.h"
+#include "gs360_maskplane.h"
 
 #pragma clang fp contract(off)
 
 namespace gs360 {
 namespace {
 
-MK_HD inline int ms_lo(int a, int b) { return a < b ? a : b; }
-MK_HD inline int ms_hi(int a, int b) { return a > b ? a : b; }
-MK_HD inline int ms_ctz(uint32_t v) { return __builtin_ctz(v); }
-MK_HD inline int ms_popc(uint32_t v) { return __builtin_popcount(v); }
 MK_HD inline int64_t ms_gray_pitch(const MsJob& J) { return 32 * (int64_t)J.pw; }
-MK_HD inline bool ms_plane_bit(const uint32_t* plane, int pw, int y, int x) { return (plane[(int64_t)y * pw + (x >> 5)] >> (x & 31)) & 1u; }
 
 // ---- pixel -----------------------------------------------------------------------------------------------------------------------
 // four pixels from column x (a multiple of 4) on: their grays as the bytes of a dword, `S <= sat_max` as a nibble; zero at columns >= W
@@ -52,7 +49,7 @@ MK_HD inline void ms_pixel4(const MsJob& J, int y, int x, uint32_t* gray4, uint3
     for (int k = 0; k < 4 && x + k < J.W; ++k) {
         uint8_t px[3];
         for (int c = 0; c < 3; ++c) px[c] = (uint8_t)(w[(3 * k + c) >> 2] >> (8 * ((3 * k + c) & 3)));
-        const int v = ms_hi(ms_hi(px[0], px[1]), px[2]), d = v - ms_lo(ms_lo(px[0], px[1]), px[2]);
+        const int v = mk_hi(mk_hi(px[0], px[1]), px[2]), d = v - mk_lo(mk_lo(px[0], px[1]), px[2]);
         const int S = (d * J.sdiv[v] + 2048) >> 12;
         *gray4 |= (uint32_t)gray_of<3>(px, 0) << (8 * k);
         *nib |= (uint32_t)(S <= J.sat_max) << k;
@@ -92,7 +89,7 @@ MK_HD inline int ms_round_up8(int v) { return (v + 7) & ~7; }
 
 // the row pass: a workgroup's segment of row y from column x0 (a multiple of kMsRowSeg) on
 MK_HD inline int ms_skew(int e) { return e + (e >> 5); }
-MK_HD inline int ms_rows_len(const MsJob& J, int x0) { return ms_lo(kMsRowSeg, ms_round_up8(J.W - x0)); }      // outputs computed
+MK_HD inline int ms_rows_len(const MsJob& J, int x0) { return mk_lo(kMsRowSeg, ms_round_up8(J.W - x0)); }      // outputs computed
 constexpr int kMsRowStage = kMsRowSeg + 2 * kMsMaxR + (kMsRowSeg + 2 * kMsMaxR) / 32 + 1;
 MK_HD inline void ms_rows_stage(const MsJob& J, int y, int x0, int lane, float* stage) {
     const int n = ms_rows_len(J, x0) + 2 * J.r;
@@ -109,7 +106,7 @@ MK_HD inline void ms_rows_lane(const MsJob& J, int y, int x0, int lane, const fl
 }
 
 // the column pass: a workgroup's tile of kMsColW columns from x0 and kMsColRows rows from y0
-MK_HD inline int ms_cols_rows(const MsJob& J, int y0) { return ms_lo(kMsColRows, ms_round_up8(J.H - y0)) + 2 * J.r; }   // staged rows
+MK_HD inline int ms_cols_rows(const MsJob& J, int y0) { return mk_lo(kMsColRows, ms_round_up8(J.H - y0)) + 2 * J.r; }   // staged rows
 MK_HD inline void ms_cols_stage(const MsJob& J, int y0, int x0, int lane, float* stage) {
     const int n = ms_cols_rows(J, y0) * kMsColW;
     for (int idx = lane; idx < n; idx += kMsThreads) {
@@ -121,7 +118,7 @@ MK_HD inline void ms_cols_stage(const MsJob& J, int y0, int x0, int lane, float*
 MK_HD inline bool ms_candidate(const MsJob& J, int y, int x, float illum) {
     const float g = (float)J.gray[(int64_t)y * ms_gray_pitch(J) + x];
     const float ratio = g / (illum + 1e-6f), delta = illum - g;
-    return ratio < J.t && delta >= J.delta_min && ms_plane_bit(J.a, J.pw, y, x);
+    return ratio < J.t && delta >= J.delta_min && mk_bit(J.a, J.pw, y, x);
 }
 // lane's column, rows c0 .. c0 + 7 of the tile (c0 = 32 wave + 8 chunk, below H - y0) -> bit j: the candidate test of row y0 + c0 + j
 MK_HD inline uint32_t ms_cols_lane(const MsJob& J, int y0, int x0, int lane, int c0, const float* stage) {
@@ -136,29 +133,6 @@ MK_HD inline uint32_t ms_cols_lane(const MsJob& J, int y0, int x0, int lane, int
 
 // ---- labels ----------------------------------------------------------------------------------------------------------------------
 MK_HD inline void ms_fail(uint32_t* err) { *err = 1u; }
-MK_HD inline int32_t ms_load(const int32_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    return *p;
-#endif
-}
-MK_HD inline int32_t ms_atomic_min(int32_t* p, int32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicMin(p, v);
-#else
-    const int32_t old = *p;
-    if (v < old) *p = v;
-    return old;
-#endif
-}
-MK_HD inline void ms_add(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicAdd(p, v);
-#else
-    *p += v;
-#endif
-}
 // dword w of row y of the plane that is labelled; zero outside it
 MK_HD inline uint32_t ms_label_bits(const MsJob& J, int y, int w) {
     if (y < 0 || w < 0 || w >= J.pw) return 0;
@@ -170,7 +144,7 @@ MK_HD inline uint32_t ms_label_bits(const MsJob& J, int y, int w) {
 MK_HD inline int32_t ms_root(const MsJob& J, int32_t x, uint32_t* err) {
     const int32_t bound = J.H * J.W;
     for (int32_t n = 0; n < bound; ++n) {
-        const int32_t p = ms_load(J.lab + x);
+        const int32_t p = mk_atomic_load(J.lab + x);
         if (p == x) return x;
         if ((uint32_t)p >= (uint32_t)bound) break;
         x = p;
@@ -186,7 +160,7 @@ MK_HD inline void ms_unite(const MsJob& J, int32_t a, int32_t b, uint32_t* err) 
         a = ms_root(J, a, err); b = ms_root(J, b, err);
         if (a == b) return;
         if (a < b) { const int32_t t = a; a = b; b = t; }
-        const int32_t old = ms_atomic_min(J.lab + a, b);
+        const int32_t old = mk_atomic_min(J.lab + a, b);
         if (old == a) return;
         a = old;
     }
@@ -194,7 +168,7 @@ MK_HD inline void ms_unite(const MsJob& J, int32_t a, int32_t b, uint32_t* err) 
 }
 // item q = dword (y, w): a set pixel's label is the index of the first pixel of its run inside the dword, any other pixel's -1
 MK_HD inline void ms_label_init(const MsJob& J, int64_t q) {
-    const int y = (int)(q / J.pw), w = (int)(q - (int64_t)y * J.pw), nx = ms_lo(32, J.W - 32 * w);
+    const int y = (int)(q / J.pw), w = (int)(q - (int64_t)y * J.pw), nx = mk_lo(32, J.W - 32 * w);
     const uint32_t m = ms_label_bits(J, y, w);
     const int32_t base = y * J.W + 32 * w;
     int start = 0;
@@ -217,11 +191,11 @@ MK_HD inline void ms_label_merge(const MsJob& J, int64_t q, uint32_t* err) {
     const int32_t base = y * W + 32 * w;
     if ((cur & 1u) && cl) ms_unite(J, base, base - 1, err);
     const uint32_t v = cur & up;
-    for (uint32_t m = v & ~((v << 1) | (cl & ul)); m; m &= m - 1) ms_unite(J, base + ms_ctz(m), base + ms_ctz(m) - W, err);
+    for (uint32_t m = v & ~((v << 1) | (cl & ul)); m; m &= m - 1) ms_unite(J, base + mk_ctz(m), base + mk_ctz(m) - W, err);
     if (CONN == 8) {
         const uint32_t curm1 = (cur << 1) | cl, curp1 = (cur >> 1) | (cr << 31), upm1 = (up << 1) | ul, upp1 = (up >> 1) | (ur << 31);
-        for (uint32_t m = cur & upm1 & ~up & ~curm1; m; m &= m - 1) ms_unite(J, base + ms_ctz(m), base + ms_ctz(m) - W - 1, err);
-        for (uint32_t m = cur & upp1 & ~up & ~curp1; m; m &= m - 1) ms_unite(J, base + ms_ctz(m), base + ms_ctz(m) - W + 1, err);
+        for (uint32_t m = cur & upm1 & ~up & ~curm1; m; m &= m - 1) ms_unite(J, base + mk_ctz(m), base + mk_ctz(m) - W - 1, err);
+        for (uint32_t m = cur & upp1 & ~up & ~curp1; m; m &= m - 1) ms_unite(J, base + mk_ctz(m), base + mk_ctz(m) - W + 1, err);
     }
 }
 // item q = dword (y, w): the pixels of a run inside the dword still name the run's first pixel (only roots are ever relinked), so one
@@ -230,15 +204,14 @@ MK_HD inline void ms_label_flatten(const MsJob& J, int64_t q, uint32_t* err) {
     const int y = (int)(q / J.pw), w = (int)(q - (int64_t)y * J.pw);
     const int32_t base = y * J.W + 32 * w;
     for (uint32_t m = ms_label_bits(J, y, w); m;) {
-        const int s = ms_ctz(m);
+        const int s = mk_ctz(m);
         const uint32_t run = m & ~(m + (1u << s));       // the carry runs through the run that starts at bit s
         const int32_t root = ms_root(J, base + s, err);
-        for (uint32_t b = run; b; b &= b - 1) J.lab[base + ms_ctz(b)] = root;
+        for (uint32_t b = run; b; b &= b - 1) J.lab[base + mk_ctz(b)] = root;
         m &= ~run;
     }
 }
-// item q = a pixel of the four border lines: the root of a labelled one is flagged (equal stores, in any order)
-MK_HD inline int64_t ms_border_items(const MsJob& J) { return 2 * (int64_t)J.W + 2 * (int64_t)J.H; }
+// item q = a pixel of the four border lines (ms_border_items): the root of a labelled one is flagged (equal stores, in any order)
 MK_HD inline void ms_border(const MsJob& J, int64_t q) {
     const int W = J.W, H = J.H;
     const int64_t p = q < W ? q : q < 2 * W ? (int64_t)(H - 1) * W + (q - W) : q < 2 * W + H ? (q - 2 * W) * W : (q - 2 * W - H) * W + W - 1;
@@ -252,13 +225,12 @@ MK_HD inline bool ms_fill_bit(const MsJob& J, int y, int x) {
 }
 
 // ---- area ------------------------------------------------------------------------------------------------------------------------
-// item q = (band of kMsAreaRows cell rows, dword column w).  Cell (y, x) has the corners (y, x), (y, x + 1), (y + 1, x), (y + 1, x + 1);
+// item q (ms_area_items) = (band of kMsAreaRows cell rows, dword column w).  Cell (y, x) has the corners (y, x), (y, x + 1), (y + 1, x), (y + 1, x + 1);
 // it adds 2 with four corners in G and 1 with three.  Neighbouring contributing cells share a set corner or two vertically adjacent
 // ones, so a run of them has one root: one lookup per run, one atomic whenever the root changes.
-MK_HD inline int64_t ms_area_items(const MsJob& J) { return J.H < 2 ? 0 : (int64_t)J.pw * ((J.H - 1 + kMsAreaRows - 1) / kMsAreaRows); }
 MK_HD inline void ms_area_lane(const MsJob& J, int64_t q, uint32_t* err) {
     const int band = (int)(q / J.pw), w = (int)(q - (int64_t)band * J.pw), pw = J.pw;
-    const int y1 = ms_lo((band + 1) * kMsAreaRows, J.H - 1);
+    const int y1 = mk_lo((band + 1) * kMsAreaRows, J.H - 1);
     int32_t root = -1;
     uint32_t sum = 0;
     for (int y = band * kMsAreaRows; y < y1; ++y) {
@@ -269,22 +241,22 @@ MK_HD inline void ms_area_lane(const MsJob& J, int64_t q, uint32_t* err) {
         const uint32_t three = (a & a1 & b & ~b1) | (a & a1 & ~b & b1) | (a & ~a1 & b & b1) | (~a & a1 & b & b1);
         uint32_t todo = four | three;
         while (todo) {
-            const int s = ms_ctz(todo);
+            const int s = mk_ctz(todo);
             const uint32_t gap = ~(todo >> s);
-            const int n = gap ? ms_ctz(gap) : 32;
+            const int n = gap ? mk_ctz(gap) : 32;
             const uint32_t run = (n >= 32 ? 0xffffffffu : (1u << n) - 1u) << s;
             const int32_t at = (((a >> s) & 1u) ? y : y + 1) * J.W + 32 * w + s;      // a set corner of the run's first cell
             const int32_t l = J.lab[at];
             if (l < 0) { ms_fail(err); return; }
             if (l != root) {
-                if (sum) ms_add(J.area + root, sum);
+                if (sum) mk_atomic_add(J.area + root, sum);
                 root = l; sum = 0;
             }
-            sum += 2u * (uint32_t)ms_popc(four & run) + (uint32_t)ms_popc(three & run);
+            sum += 2u * (uint32_t)mk_popc(four & run) + (uint32_t)mk_popc(three & run);
             todo &= ~run;
         }
     }
-    if (sum) ms_add(J.area + root, sum);
+    if (sum) mk_atomic_add(J.area + root, sum);
 }
 
 // ---- select ----------------------------------------------------------------------------------------------------------------------
@@ -294,15 +266,12 @@ MK_HD inline void ms_select4(const MsJob& J, int y, int x, uint32_t* clean, uint
     if (x >= J.W) return;
     uint32_t v = 0;
     for (int k = 0; k < 4 && x + k < J.W; ++k) {
-        const bool c = ms_plane_bit(J.a, J.pw, y, x + k) && J.area[J.lab[(int64_t)y * J.W + x + k]] >= J.th2;
-        const bool m = c || ms_plane_bit(J.b, J.pw, y, x + k);
+        const bool c = mk_bit(J.a, J.pw, y, x + k) && J.area[J.lab[(int64_t)y * J.W + x + k]] >= J.th2;
+        const bool m = c || mk_bit(J.b, J.pw, y, x + k);
         *clean |= (uint32_t)c << k; *merged |= (uint32_t)m << k;
         v |= (m ? 255u : 0u) << (8 * k);
     }
-    uint8_t* p = J.dst + (int64_t)y * J.dst_stride + x;
-    if (x + 4 <= J.W && ((uintptr_t)p & 3) == 0) __builtin_memcpy(__builtin_assume_aligned(p, 4), &v, 4);
-    else
-        for (int k = 0; k < 4 && x + k < J.W; ++k) p[k] = (uint8_t)(v >> (8 * k));
+    mk_store4(J.dst + (int64_t)y * J.dst_stride + x, x, J.W, v);
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
@@ -310,75 +279,63 @@ __device__ __forceinline__ const MsJob& ms_job(const MsLaunch& L, int* j) {
     *j = job_of(L, blockIdx.x, &MsJob::tile_base);
     return L.job[*j];
 }
-// a workgroup's row segment: tile t of the job -> (row or band of rows, the tile's index along x)
-__device__ __forceinline__ void ms_row_tile(const MsJob& J, int* y, int* tx) {
-    const int t = blockIdx.x - J.tile_base;
-    *y = t / J.tiles_x;
-    *tx = t - *y * J.tiles_x;
-}
-// the item of a lane of the kernels that number their work along one axis
-__device__ __forceinline__ int64_t ms_item(const MsJob& J) { return (int64_t)(blockIdx.x - J.tile_base) * kMsThreads + threadIdx.x; }
 
 __global__ void __launch_bounds__(kMsThreads) ms_pixel_kernel(const MsLaunch L) {
     int j, y, tx;
     const MsJob& J = ms_job(L, &j);
-    ms_row_tile(J, &y, &tx);
-    const int x = 4 * (tx * kMsThreads + threadIdx.x);   // four pixels per lane, 1024 per workgroup
+    mk_tile_of(J, &y, &tx);
+    const int x = tx * kMsPixelTile.w + 4 * threadIdx.x;
     uint32_t gray4, nib;
     ms_pixel4(J, y, x, &gray4, &nib);
     const uint32_t word = mk_gather8(nib);
     if (x >= 32 * J.pw) return;
     *(uint32_t*)(J.gray + (int64_t)y * ms_gray_pitch(J) + x) = gray4;
-    if ((threadIdx.x & 7) == 0) J.out[(int64_t)y * J.pw + (x >> 5)] = word;
+    mk_store_word(J.out, J.pw, y, x, word);
 }
 
 __global__ void __launch_bounds__(kMsThreads) ms_blur_rows_kernel(const MsLaunch L) {
     __shared__ float stage[kMsRowStage];
     int j, y, tx;
     const MsJob& J = ms_job(L, &j);
-    ms_row_tile(J, &y, &tx);
-    ms_rows_stage(J, y, tx * kMsRowSeg, threadIdx.x, stage);
+    mk_tile_of(J, &y, &tx);
+    ms_rows_stage(J, y, tx * kMsRowsTile.w, threadIdx.x, stage);
     __syncthreads();
-    ms_rows_lane(J, y, tx * kMsRowSeg, threadIdx.x, stage);
+    ms_rows_lane(J, y, tx * kMsRowsTile.w, threadIdx.x, stage);
 }
 
 __global__ void __launch_bounds__(kMsThreads) ms_blur_cols_kernel(const MsLaunch L) {
     extern __shared__ float ms_cols_stage_lds[];         // (kMsColRows + 2 r) rows of kMsColW floats, r the launch's largest
     int j, ty, tx;
     const MsJob& J = ms_job(L, &j);
-    ms_row_tile(J, &ty, &tx);
-    const int y0 = ty * kMsColRows, x0 = tx * kMsColW;
+    mk_tile_of(J, &ty, &tx);
+    const int y0 = ty * kMsColsTile.h, x0 = tx * kMsColsTile.w;
     ms_cols_stage(J, y0, x0, threadIdx.x, ms_cols_stage_lds);
     __syncthreads();
-    const int wave = threadIdx.x / kMsColW, lane = threadIdx.x & (kMsColW - 1);
+    const int wave = threadIdx.x / kMsColW, x = x0 + (threadIdx.x & (kMsColW - 1));
     for (int chunk = 0; chunk < kMsColRows / 4 / kMsOut; ++chunk) {
         const int c0 = wave * (kMsColRows / 4) + chunk * kMsOut;
         if (y0 + c0 >= J.H) break;                        // (the same for the whole wave)
         const uint32_t bits = ms_cols_lane(J, y0, x0, threadIdx.x, c0, ms_cols_stage_lds);
-        for (int k = 0; k < kMsOut && y0 + c0 + k < J.H; ++k) {
-            const unsigned long long row = __ballot((bits >> k) & 1u);
-            const int w = (x0 >> 5) + (lane >> 5);
-            if ((lane & 31) == 0 && w < J.pw) J.out[(int64_t)(y0 + c0 + k) * J.pw + w] = (uint32_t)(row >> (lane & 32));
-        }
+        for (int k = 0; k < kMsOut && y0 + c0 + k < J.H; ++k) mk_store_ballot(J.out, J.pw, y0 + c0 + k, x, (bits >> k) & 1u);
     }
 }
 
 __global__ void __launch_bounds__(kMsThreads) ms_logic_kernel(const MsLaunch L) {
     int j;
     const MsJob& J = ms_job(L, &j);
-    const int64_t q = ms_item(J);
-    if (q < (int64_t)J.H * J.pw) J.out[q] = J.a[q] & J.b[q] & ~J.c[q];
+    const int64_t q = mk_item_of(J);
+    if (q < mk_plane_items(J)) J.out[q] = J.a[q] & J.b[q] & ~J.c[q];
 }
 
 template <int STEP>
 __global__ void __launch_bounds__(kMsThreads) ms_label_kernel(const MsLaunch L) {
     int j;
     const MsJob& J = ms_job(L, &j);
-    const int64_t q = ms_item(J);
-    if (STEP == 0) { if (q < (int64_t)J.H * J.pw) ms_label_init(J, q); }
-    else if (STEP == 4) { if (q < (int64_t)J.H * J.pw) ms_label_merge<4>(J, q, L.err); }
-    else if (STEP == 8) { if (q < (int64_t)J.H * J.pw) ms_label_merge<8>(J, q, L.err); }
-    else if (STEP == 1) { if (q < (int64_t)J.H * J.pw) ms_label_flatten(J, q, L.err); }
+    const int64_t q = mk_item_of(J);
+    if (STEP == 0) { if (q < mk_plane_items(J)) ms_label_init(J, q); }
+    else if (STEP == 4) { if (q < mk_plane_items(J)) ms_label_merge<4>(J, q, L.err); }
+    else if (STEP == 8) { if (q < mk_plane_items(J)) ms_label_merge<8>(J, q, L.err); }
+    else if (STEP == 1) { if (q < mk_plane_items(J)) ms_label_flatten(J, q, L.err); }
     else if (STEP == 2) { if (q < ms_border_items(J)) ms_border(J, q); }
     else if (q < ms_area_items(J)) ms_area_lane(J, q, L.err);
 }
@@ -386,64 +343,49 @@ __global__ void __launch_bounds__(kMsThreads) ms_label_kernel(const MsLaunch L) 
 __global__ void __launch_bounds__(kMsThreads) ms_fill_kernel(const MsLaunch L) {
     int j, y, tx;
     const MsJob& J = ms_job(L, &j);
-    ms_row_tile(J, &y, &tx);
-    const int x = tx * kMsThreads + threadIdx.x, lane = threadIdx.x & 63;
-    const unsigned long long row = __ballot(x < J.W && ms_fill_bit(J, y, x));
-    if ((lane & 31) == 0 && (x >> 5) < J.pw) J.out[(int64_t)y * J.pw + (x >> 5)] = (uint32_t)(row >> (lane & 32));
+    mk_tile_of(J, &y, &tx);
+    const int x = tx * kMsFillTile.w + threadIdx.x;
+    mk_store_ballot(J.out, J.pw, y, x, x < J.W && ms_fill_bit(J, y, x));
 }
 
 __global__ void __launch_bounds__(kMsThreads) ms_select_kernel(const MsLaunch L) {
-    __shared__ uint32_t wg_count;
     int j, band, tx;
     const MsJob& J = ms_job(L, &j);
-    ms_row_tile(J, &band, &tx);
-    if (threadIdx.x == 0) wg_count = 0;
-    __syncthreads();
-    const int x = 4 * (tx * kMsThreads + threadIdx.x), y1 = min(J.H, (band + 1) * kMsSelectRows);
+    mk_tile_of(J, &band, &tx);
+    const int x = tx * kMsSelectTile.w + 4 * threadIdx.x, y1 = min(J.H, (band + 1) * kMsSelectTile.h);
     uint32_t n = 0;
-    for (int y = band * kMsSelectRows; y < y1; ++y) {
+    for (int y = band * kMsSelectTile.h; y < y1; ++y) {
         uint32_t clean, merged;
         ms_select4(J, y, x, &clean, &merged);
-        const uint32_t word = mk_gather8(clean);
-        if ((threadIdx.x & 7) == 0 && (x >> 5) < J.pw) J.out[(int64_t)y * J.pw + (x >> 5)] = word;
+        mk_store_word(J.out, J.pw, y, x, mk_gather8(clean));
         n += (uint32_t)__popc(merged);
     }
-    n = wave_sum(n);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&wg_count, n);
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_count) atomicAdd(L.counts + j, wg_count);
+    mk_count_tail(n, L.counts + j);
 }
 
 }  // namespace
 
 hipError_t launch_mask_shadow(MsStep step, const MsLaunch& L, hipStream_t s) {
-    if (L.total_tiles <= 0) return hipSuccess;
-    const dim3 grid((unsigned)L.total_tiles), block(kMsThreads);
     switch (step) {
-    case kMsPixel: hipLaunchKernelGGL(ms_pixel_kernel, grid, block, 0, s, L); break;
-    case kMsBlurRows: hipLaunchKernelGGL(ms_blur_rows_kernel, grid, block, 0, s, L); break;
+    case kMsPixel: return mk_launch(ms_pixel_kernel, L, s);
+    case kMsBlurRows: return mk_launch(ms_blur_rows_kernel, L, s);
     case kMsBlurCols: {
         int r = 0;
         for (int k = 0; k < L.n_jobs; ++k) r = L.job[k].r > r ? L.job[k].r : r;
         const size_t lds = (size_t)(kMsColRows + 2 * r) * kMsColW * sizeof(float);    // at most 163 328 bytes of the CU's 160 KiB
         hipError_t e = hipFuncSetAttribute((const void*)ms_blur_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ms_blur_cols_kernel, grid, block, lds, s, L);
-        break;
+        return e != hipSuccess ? e : mk_launch(ms_blur_cols_kernel, L, s, lds);
     }
-    case kMsLogic: hipLaunchKernelGGL(ms_logic_kernel, grid, block, 0, s, L); break;
-    case kMsLabelInit: hipLaunchKernelGGL(ms_label_kernel<0>, grid, block, 0, s, L); break;
-    case kMsLabelMerge:
-        if (L.conn == 8) hipLaunchKernelGGL(ms_label_kernel<8>, grid, block, 0, s, L);
-        else hipLaunchKernelGGL(ms_label_kernel<4>, grid, block, 0, s, L);
-        break;
-    case kMsLabelFlatten: hipLaunchKernelGGL(ms_label_kernel<1>, grid, block, 0, s, L); break;
-    case kMsBorder: hipLaunchKernelGGL(ms_label_kernel<2>, grid, block, 0, s, L); break;
-    case kMsFill: hipLaunchKernelGGL(ms_fill_kernel, grid, block, 0, s, L); break;
-    case kMsArea: hipLaunchKernelGGL(ms_label_kernel<3>, grid, block, 0, s, L); break;
-    case kMsSelect: hipLaunchKernelGGL(ms_select_kernel, grid, block, 0, s, L); break;
+    case kMsLogic: return mk_launch(ms_logic_kernel, L, s);
+    case kMsLabelInit: return mk_launch(ms_label_kernel<0>, L, s);
+    case kMsLabelMerge: return L.conn == 8 ? mk_launch(ms_label_kernel<8>, L, s) : mk_launch(ms_label_kernel<4>, L, s);
+    case kMsLabelFlatten: return mk_launch(ms_label_kernel<1>, L, s);
+    case kMsBorder: return mk_launch(ms_label_kernel<2>, L, s);
+    case kMsFill: return mk_launch(ms_fill_kernel, L, s);
+    case kMsArea: return mk_launch(ms_label_kernel<3>, L, s);
+    case kMsSelect: return mk_launch(ms_select_kernel, L, s);
     }
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 }  // namespace gs360

@@ -169,6 +169,14 @@ def _rows_array(kw, kh, cache):
     return cache[(kw, kh)]
 
 
+def set_element(j, name, k, cache):
+    """the k x k ellipse as element `name` (close, expand, near, sclose, open) of job j; cache keeps the rows alive"""
+    setattr(j, name + "_kw", k)
+    setattr(j, name + "_kh", k)
+    if k <= capi.MASK_MAX_ELEMENT:                       # (beyond: the call answers GS360_ERR_UNSUPPORTED before it reads the rows)
+        setattr(j, name + "_rows", _rows_array(k, k, cache).ctypes.data)
+
+
 def build_jobs(shapes, params, kind="mask", invert=True):
     """shapes: [(H, W)] -> ([capi.MaskJob] with everything but the pointers and strides filled, the host arrays they point into).
     Raises ValueError for an unknown kind and for edge_fuse_pixels > min(H, W) (the reference's slices turn negative there)."""
@@ -186,13 +194,9 @@ def build_jobs(shapes, params, kind="mask", invert=True):
         j.H, j.W, j.thresh = H, W, int(params.thresh)
         j.fuse, j.spread, j.kind, j.invert = f, s, KINDS[kind], 1 if invert else 0
         if close > 1:
-            j.close_kw = j.close_kh = close
-            if close <= capi.MASK_MAX_ELEMENT:
-                j.close_rows = _rows_array(close, close, cache).ctypes.data
+            set_element(j, "close", close, cache)
         if p > 0:
-            j.expand_kw = j.expand_kh = 2 * p + 1
-            if p <= MAX_EXPAND:                          # (beyond: the call answers GS360_ERR_UNSUPPORTED before it reads the rows)
-                j.expand_rows = _rows_array(2 * p + 1, 2 * p + 1, cache).ctypes.data
+            set_element(j, "expand", 2 * p + 1, cache)
         jobs.append(j)
     return jobs, cache
 
@@ -208,6 +212,28 @@ def _device_plane(ctx, a, shape, what, owned, slot):
     return owned[-1].ptr
 
 
+def _shapes(masks):
+    """[(H, W)] of masks given as arrays, (H, W) or (H, W, DeviceBuffer)"""
+    return [tuple(m[:2]) if isinstance(m, tuple) else np.asarray(m).shape[:2] for m in masks]
+
+
+def _source_plane(ctx, j, m, shape, owned, slot):
+    """job j's raw mask: an array is uploaded, a DeviceBuffer is taken as it is, a bare shape leaves it NULL (all clear)"""
+    if not isinstance(m, tuple):
+        j.src = _device_plane(ctx, m, shape, "mask", owned, slot)
+    elif len(m) == 3:
+        j.src = m[2].ptr
+
+
+def _download_and_free(ctx, items, slot):
+    """finish_device's items brought back as H x W (one channel) or H x W x C arrays; their buffers are freed"""
+    try:
+        return [ctx.download(o, (H, W) if C == 1 else (H, W, C), np.uint8, slot) for o, H, W, C, _b, _s in items]
+    finally:
+        for it in items:
+            ctx.free(it[0])
+
+
 def finish_device(ctx, masks, params=None, adds=None, images=None, kind="mask", invert=True, slot=0):
     """(the caller holds `slot`) masks: per image an H x W uint8 ndarray, an (H, W) tuple (no detection: all clear) or an
     (H, W, DeviceBuffer) tuple (a mask that is on the device already) ->
@@ -220,27 +246,21 @@ def finish_device(ctx, masks, params=None, adds=None, images=None, kind="mask", 
     images = list(images) if images is not None else [None] * n
     if len(adds) != n or len(images) != n:
         raise ValueError("one add layer and one image per mask (or None)")
-    shapes = [tuple(m[:2]) if isinstance(m, tuple) else np.asarray(m).shape[:2] for m in masks]
+    shapes = _shapes(masks)
     jobs, keep = build_jobs(shapes, params, kind, invert)
     if not n:
         return [], np.zeros(0, np.uint32)
     owned, outs = [], []
-
-    def plane(a, shape, what):
-        return _device_plane(ctx, a, shape, what, owned, slot)
     try:
         C = _CHANNELS[kind]
         for j, m, a, im, (H, W) in zip(jobs, masks, adds, images, shapes):
-            if not isinstance(m, tuple):
-                j.src = plane(m, (H, W), "mask")
-            elif len(m) == 3:
-                j.src = m[2].ptr
+            _source_plane(ctx, j, m, (H, W), owned, slot)
             if a is not None:
-                j.add = plane(a, (H, W), "add layer")
+                j.add = _device_plane(ctx, a, (H, W), "add layer", owned, slot)
             if kind != "mask":
                 if im is None:
                     raise ValueError(f"kind {kind!r} needs the images")
-                j.image = plane(im, (H, W, 3), "image")
+                j.image = _device_plane(ctx, im, (H, W, 3), "image", owned, slot)
             outs.append(ctx.alloc(H * W * C))
             j.dst = outs[-1].ptr
         scratch = ctx.alloc(max(ctx.mask_finish_scratch(jobs), 256))
@@ -264,11 +284,7 @@ def finish(ctx, masks, params=None, adds=None, images=None, kind="mask", invert=
     """finish_device with the outputs brought back: -> ([H x W (kind "mask") or H x W x C uint8 arrays], counts)"""
     with ctx.slot_locks[slot]:
         items, counts = finish_device(ctx, masks, params, adds, images, kind, invert, slot)
-        try:
-            return [ctx.download(o, (H, W) if C == 1 else (H, W, C), np.uint8, slot) for o, H, W, C, _b, _s in items], counts
-        finally:
-            for it in items:
-                ctx.free(it[0])
+        return _download_and_free(ctx, items, slot), counts
 
 
 def shadow_device(ctx, masks, images, params=None, shadow=None, slot=0):
@@ -282,20 +298,12 @@ def shadow_device(ctx, masks, images, params=None, shadow=None, slot=0):
         raise ValueError("one image per mask")
     if not n:
         return [], np.zeros(0, np.uint32)
-    shapes = [tuple(m[:2]) if isinstance(m, tuple) else np.asarray(m).shape[:2] for m in masks]
+    shapes = _shapes(masks)
     weights, sdiv, cache = gaussian_weights(shadow.sigma), sat_div_table(), {}
     half = np.ascontiguousarray(weights[len(weights) // 2:])
     close = max(1, int(params.close))
     owned, outs, jobs = [], [], []
 
-    def plane(a, shape, what):
-        return _device_plane(ctx, a, shape, what, owned, slot)
-
-    def element(j, name, k):
-        setattr(j, name + "_kw", k)
-        setattr(j, name + "_kh", k)
-        if k <= capi.MASK_MAX_ELEMENT:                   # (beyond: the call answers GS360_ERR_UNSUPPORTED before it reads the rows)
-            setattr(j, name + "_rows", _rows_array(k, k, cache).ctypes.data)
     try:
         for m, im, (H, W) in zip(masks, images, shapes):
             j = capi.ShadowJob()
@@ -304,12 +312,9 @@ def shadow_device(ctx, masks, images, params=None, shadow=None, slot=0):
             j.t, j.delta_min, j.sat_max = float(shadow.t), float(shadow.delta_min), int(shadow.sat_max)
             j.min_area = max(1, min(int(shadow.min_area), 2 ** 31 - 1))
             if close > 1:
-                element(j, "close", close)
-            if not isinstance(m, tuple):
-                j.src = plane(m, (H, W), "mask")
-            elif len(m) == 3:
-                j.src = m[2].ptr
-            j.image = plane(im, (H, W, 3), "image")
+                set_element(j, "close", close, cache)
+            _source_plane(ctx, j, m, (H, W), owned, slot)
+            j.image = _device_plane(ctx, im, (H, W, 3), "image", owned, slot)
             outs.append(ctx.alloc(H * W))
             j.dst = outs[-1].ptr
             jobs.append(j)
@@ -321,9 +326,9 @@ def shadow_device(ctx, masks, images, params=None, shadow=None, slot=0):
         person = ctx.download(d_counts, (n,), np.uint32, slot)
         for j, count in zip(jobs, person):               # the count -> size rule stays on the host
             k, close_k = shadow_sizes(int(count), shadow.near_px)
-            element(j, "near", k)
-            element(j, "sclose", close_k)
-            element(j, "open", 3)
+            set_element(j, "near", k, cache)
+            set_element(j, "sclose", close_k, cache)
+            set_element(j, "open", 3, cache)
         ctx.mask_shadow_merge_dev(jobs, scratch, d_counts, slot)
         counts = ctx.download(d_counts, (n,), np.uint32, slot)
         del cache
@@ -344,14 +349,11 @@ def finish_with_shadow_device(ctx, masks, params=None, shadow=None, adds=None, i
     if images is None:
         raise ValueError("the shadow estimate needs the images")
     n = len(masks)
-    shapes = [tuple(m[:2]) if isinstance(m, tuple) else np.asarray(m).shape[:2] for m in masks]
+    shapes = _shapes(masks)
     d_images, merged = [], []
     try:
         for im, (H, W) in zip(images, shapes):
-            a = np.ascontiguousarray(im, dtype=np.uint8)
-            if a.shape != (H, W, 3):
-                raise ValueError(f"image of shape {a.shape}, expected {(H, W, 3)}")
-            d_images.append(ctx.to_device(a, slot))
+            _device_plane(ctx, im, (H, W, 3), "image", d_images, slot)
         if len(d_images) != n:
             raise ValueError("one image per mask")
         merged, _counts = shadow_device(ctx, masks, d_images, params, shadow, slot)
@@ -367,8 +369,4 @@ def finish_with_shadow(ctx, masks, params=None, shadow=None, adds=None, images=N
     """finish_with_shadow_device with the outputs brought back: -> ([H x W (kind "mask") or H x W x C uint8 arrays], counts)"""
     with ctx.slot_locks[slot]:
         items, counts = finish_with_shadow_device(ctx, masks, params, shadow, adds, images, kind, invert, slot)
-        try:
-            return [ctx.download(o, (H, W) if C == 1 else (H, W, C), np.uint8, slot) for o, H, W, C, _b, _s in items], counts
-        finally:
-            for it in items:
-                ctx.free(it[0])
+        return _download_and_free(ctx, items, slot), counts

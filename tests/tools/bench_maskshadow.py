@@ -34,13 +34,6 @@ H, W, N = 3840, 7680, 16
 PARAMS, SHADOW = maskfinish.Params(thresh=127), maskfinish.ShadowParams()
 
 
-def element(j, name, k, cache):
-    rows = cache.setdefault(k, np.ascontiguousarray(maskfinish.structuring_rows(k, k)[0], dtype=np.int32))
-    setattr(j, name + "_kw", k)
-    setattr(j, name + "_kh", k)
-    setattr(j, name + "_rows", rows.ctypes.data)
-
-
 def bench(ctx, d_images, d_masks, first, reps, device_only):
     w = maskfinish.gaussian_weights(SHADOW.sigma)
     half, sdiv, cache = np.ascontiguousarray(w[len(w) // 2:]), maskfinish.sat_div_table(), {}
@@ -51,7 +44,7 @@ def bench(ctx, d_images, d_masks, first, reps, device_only):
         j.H, j.W, j.thresh, j.image, j.src, j.dst = H, W, PARAMS.thresh, img.ptr, src.ptr, out.ptr
         j.radius, j.weights, j.sdiv = len(half) - 1, half.ctypes.data, sdiv.ctypes.data
         j.t, j.delta_min, j.sat_max, j.min_area = SHADOW.t, SHADOW.delta_min, SHADOW.sat_max, SHADOW.min_area
-        element(j, "close", PARAMS.close, cache)
+        maskfinish.set_element(j, "close", PARAMS.close, cache)
         jobs.append(j)
     scratch, counts = ctx.alloc(ctx.mask_shadow_scratch(jobs)), ctx.alloc(4 * N)
 
@@ -62,9 +55,9 @@ def bench(ctx, d_images, d_masks, first, reps, device_only):
         person = ctx.download(counts, (N,), np.uint32)
         for j, n in zip(jobs, person):
             k, close_k = maskfinish.shadow_sizes(int(n), SHADOW.near_px)
-            element(j, "near", k, cache)
-            element(j, "sclose", close_k, cache)
-            element(j, "open", 3, cache)
+            maskfinish.set_element(j, "near", k, cache)
+            maskfinish.set_element(j, "sclose", close_k, cache)
+            maskfinish.set_element(j, "open", 3, cache)
         ctx.event_record(0, 2)
         ctx.mask_shadow_merge_dev(jobs, scratch, counts)
         ctx.event_record(0, 3)

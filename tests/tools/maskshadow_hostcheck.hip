@@ -1,46 +1,19 @@
 // maskshadow_hostcheck.hip -- the shadow estimate's arithmetic (csrc/gs360_maskshadow.hip, MSK-SHADOW v1) stepped lane by lane on the
 // host.  A CPU-only stand-alone program: it includes the kernels' sources, calls the host-callable per-lane functions in the order and
-// with the tile, row and item numbers the kernels use (a barrier becomes the end of a lane loop, a ballot a loop over the wave's lanes,
-// lanes one after another are one valid schedule of the label kernels), and allocates every plane, table and staged tile at its exact
+// with the tile, row and item numbers the kernels use (mask_hoststep.h and the geometry of csrc/gs360_maskplane.h; a ballot is a loop over
+// the wave's lanes, lanes one after another are one valid schedule of the label kernels), and allocates every plane, table and staged tile at its exact
 // size, so that a build with -fsanitize=address,undefined (tests/test_maskshadow_hostcheck.py) turns any read or write outside a
 // buffer into a failure.  Usage: maskshadow_hostcheck IN.bin OUT.bin; IN = 16 int32 (H, W, thresh, close kw, kh, radius, sat_max,
 // min_area, near kw, kh, shadow-close kw, kh, open kw, kh, has raw, 0), t and delta_min (float32), the four elements' rows (pairs of
 // int32), radius + 1 weights (float32), 256 divisors (int32), the raw mask, the image; OUT = P, C0, C1, C2, clean (a byte of 0 / 1
 // per pixel) and M (0 / 255).  Prints count(P), count(M) and the error word.
-#include "../../360cam-pgm-3dgs-tools_amd/csrc/gs360_maskmorph.hip"
+#include "mask_hoststep.h"
 #include "../../360cam-pgm-3dgs-tools_amd/csrc/gs360_maskshadow.hip"
-#include <cstdio>
-#include <cstring>
-#include <vector>
-using namespace gs360;
-typedef std::vector<uint32_t> Plane;
-
-static bool read_all(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
-
-// mk_morph_kernel over every tile of the plane, as tests/tools/maskmorph_hostcheck.hip steps it
-static void morph(MkJob J, const Plane& in, Plane& out, const std::vector<int32_t>& rows, int kw, int kh, int flags) {
-    int reach = 0;
-    for (int i = 0; i < kh; ++i)
-        if (rows[2 * i + 1] > rows[2 * i]) reach = std::max({reach, std::abs(rows[2 * i] - kw / 2), std::abs(rows[2 * i + 1] - 1 - kw / 2)});
-    J.in = in.data(); J.out = out.data(); J.spans = rows.data();
-    J.kh = kh; J.ax = kw / 2; J.ay = kh / 2; J.halo = reach / 32 + 2; J.flags = flags;
-    for (int y0 = 0; y0 < J.H; y0 += kMkTileR)
-        for (int w0 = 0; w0 < J.pw; w0 += kMkTileW) {
-            std::vector<MkAcc> acc(kMkThreads, MkAcc{0, 0, 0, 0});
-            for (int i0 = 0; i0 < kh; i0 += kMkBand) {
-                if (mk_band_dwords(J, i0) > kMkStageRows * kMkStageW) exit(4);
-                Plane stage(mk_band_dwords(J, i0));
-                for (int lane = 0; lane < kMkThreads; ++lane) mk_morph_stage(J, y0, w0, i0, lane, stage.data());
-                for (int lane = 0; lane < kMkThreads; ++lane) mk_morph_band(J, w0, i0, lane, stage.data(), acc[lane]);
-            }
-            for (int lane = 0; lane < kMkThreads; ++lane) mk_morph_store(J, y0, w0, lane, acc[lane]);
-        }
-}
 
 // the three label kernels over plane `a` (or its complement)
 static void label(MsJob& J, const Plane& a, int conn, int flags, uint32_t* err) {
     J.a = a.data(); J.flags = flags;
-    const int64_t dwords = (int64_t)J.H * J.pw;
+    const int64_t dwords = mk_plane_items(J);
     for (int64_t q = 0; q < dwords; ++q) ms_label_init(J, q);
     for (int64_t q = 0; q < dwords; ++q) conn == 8 ? ms_label_merge<8>(J, q, err) : ms_label_merge<4>(J, q, err);
     for (int64_t q = 0; q < dwords; ++q) ms_label_flatten(J, q, err);
@@ -48,7 +21,7 @@ static void label(MsJob& J, const Plane& a, int conn, int flags, uint32_t* err) 
 
 static void put_plane(std::vector<uint8_t>& out, const Plane& p, int H, int W, int pw) {
     for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) out.push_back(ms_plane_bit(p.data(), pw, y, x));
+        for (int x = 0; x < W; ++x) out.push_back(mk_bit(p.data(), pw, y, x));
 }
 
 int main(int argc, char** argv) {
@@ -94,35 +67,26 @@ int main(int argc, char** argv) {
 
     // mk_pack_kernel, the close
     Plane& packed = kh[0] ? T0 : P;
-    const int lanes4 = (W + 4 * kMkThreads - 1) / (4 * kMkThreads) * kMkThreads;
-    for (int y = 0; y < H; ++y)
-        for (int l0 = 0; l0 < lanes4; l0 += 8) {
-            uint32_t word = 0;
-            for (int l = 0; l < 8; ++l) word |= mk_nibble(K.src, K.src_stride, W, K.thresh, y, 4 * (l0 + l)) << (4 * l);
-            if (l0 / 8 < pw) packed[(size_t)y * pw + l0 / 8] = word;
-        }
+    step_words(H, W, kMkPackTile, [&](int y, int x) { return mk_nibble(K.src, K.src_stride, W, K.thresh, y, x); },
+               [&](int y, int w, uint32_t word) { packed[(size_t)y * pw + w] = word; });
     if (kh[0]) {
         morph(K, T0, T1, rows[0], kw[0], kh[0], 0);
         morph(K, T1, P, rows[0], kw[0], kh[0], kMkCompIn | kMkCompOut);
     }
-    for (uint32_t v : P) count_p += (uint32_t)__builtin_popcount(v);
+    for (uint32_t v : P) count_p += (uint32_t)mk_popc(v);
 
-    // ms_pixel_kernel: a lane's four pixels, eight lanes' nibbles as a dword
-    for (int y = 0; y < H; ++y)
-        for (int l0 = 0; l0 < lanes4; l0 += 8) {
-            uint32_t word = 0;
-            for (int l = 0; l < 8; ++l) {
-                const int x = 4 * (l0 + l);
-                uint32_t gray4, nib;
-                ms_pixel4(J, y, x, &gray4, &nib);
-                word |= nib << (4 * l);
-                if (x < 32 * pw) memcpy(gray.data() + (size_t)y * 32 * pw + x, &gray4, 4);
-            }
-            if (l0 / 8 < pw) sat[(size_t)y * pw + l0 / 8] = word;
-        }
+    // ms_pixel_kernel
+    step_words(H, W, kMsPixelTile,
+               [&](int y, int x) {
+                   uint32_t gray4, nib;
+                   ms_pixel4(J, y, x, &gray4, &nib);
+                   if (x < 32 * pw) memcpy(gray.data() + (size_t)y * 32 * pw + x, &gray4, 4);
+                   return nib;
+               },
+               [&](int y, int w, uint32_t word) { sat[(size_t)y * pw + w] = word; });
     // ms_blur_rows_kernel: stage, barrier, outputs
     for (int y = 0; y < H; ++y)
-        for (int x0 = 0; x0 < W; x0 += kMsRowSeg) {
+        for (int x0 = 0; x0 < W; x0 += kMsRowsTile.w) {
             const int floats = ms_skew(ms_rows_len(J, x0) + 2 * r - 1) + 1;
             if (floats > kMsRowStage) return 4;               // the kernel's LDS array
             std::vector<float> stage(floats, -1.0f);
@@ -131,8 +95,8 @@ int main(int argc, char** argv) {
         }
     // ms_blur_cols_kernel: stage, barrier, per wave and chunk the lanes' bits and the ballot
     J.a = sat.data();
-    for (int y0 = 0; y0 < H; y0 += kMsColRows)
-        for (int x0 = 0; x0 < W; x0 += kMsColW) {
+    for (int y0 = 0; y0 < H; y0 += kMsColsTile.h)
+        for (int x0 = 0; x0 < W; x0 += kMsColsTile.w) {
             if (ms_cols_rows(J, y0) > kMsColRows + 2 * r) return 4;   // the launch's dynamic LDS
             std::vector<float> stage((size_t)ms_cols_rows(J, y0) * kMsColW, -1.0f);
             for (int lane = 0; lane < kMsThreads; ++lane) ms_cols_stage(J, y0, x0, lane, stage.data());
@@ -162,27 +126,25 @@ int main(int argc, char** argv) {
     label(J, C2, 4, kMsComplement, &err);
     for (int64_t q = 0; q < ms_border_items(J); ++q) ms_border(J, q);
     for (int y = 0; y < H; ++y)
-        for (int w = 0; w < pw; ++w) {
-            uint32_t word = 0;
-            for (int b = 0; b < 32 && 32 * w + b < W; ++b) word |= (uint32_t)ms_fill_bit(J, y, 32 * w + b) << b;
-            T1[(size_t)y * pw + w] = word;
-        }
+        for (int x0 = 0; x0 < W; x0 += kMsFillTile.w)
+            for (int x = x0; x < x0 + kMsThreads; x += 32) {                          // half a wave's ballot
+                uint32_t word = 0;
+                for (int b = 0; b < 32; ++b) word |= (uint32_t)(x + b < W && ms_fill_bit(J, y, x + b)) << b;
+                if ((x >> 5) < pw) T1[(size_t)y * pw + (x >> 5)] = word;
+            }
     // the components of G, their areas, the selection
     std::fill(area.begin(), area.end(), 0u);
     label(J, T1, 8, 0, &err);
     for (int64_t q = 0; q < ms_area_items(J); ++q) ms_area_lane(J, q, &err);
     J.a = T1.data(); J.b = P.data();
-    for (int y = 0; y < H; ++y)
-        for (int l0 = 0; l0 < lanes4; l0 += 8) {
-            uint32_t word = 0;
-            for (int l = 0; l < 8; ++l) {
-                uint32_t c, m;
-                ms_select4(J, y, 4 * (l0 + l), &c, &m);
-                word |= c << (4 * l);
-                count_m += (uint32_t)__builtin_popcount(m);
-            }
-            if (l0 / 8 < pw) clean[(size_t)y * pw + l0 / 8] = word;
-        }
+    step_words(H, W, kMsSelectTile,
+               [&](int y, int x) {
+                   uint32_t c, m;
+                   ms_select4(J, y, x, &c, &m);
+                   count_m += (uint32_t)mk_popc(m);
+                   return c;
+               },
+               [&](int y, int w, uint32_t word) { clean[(size_t)y * pw + w] = word; });
 
     std::vector<uint8_t> out;
     for (const Plane* p : {&P, &C0, &C1, &C2, &clean}) put_plane(out, *p, H, W, pw);
