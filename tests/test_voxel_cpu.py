@@ -1,13 +1,15 @@
 """VOX-SPEC v1 on the CPU: the NumPy restatement (tests/voxel_np.py) against what the reference recorded
 (tests/golden/plyopt_goldens.npz), the key layout at the 64-bit boundary, the host path of gs360/pointcloud.py, its PLY reader and
 writer, its sky points and colour conversions."""
+import re
 import struct
 
 import numpy as np
 import pytest
 
+import voxel_cases
 import voxel_np
-from conftest import GOLDEN
+from conftest import GOLDEN, PKG
 from gs360 import pointcloud
 
 CLOUDS = ("mix", "long")
@@ -83,6 +85,14 @@ def test_key_layout_around_64_bits(bits, packed):
     distinct = np.unique(xyz, axis=0).shape[0]
     assert count == distinct == np.unique(voxel_np.triple_keys(xyz, minmax, 1.0), axis=0).shape[0]
     assert pointcloud._host_unique_count(xyz, 1.0, minmax[:3]) == distinct
+
+
+def test_the_cases_know_the_kernels_constants():
+    """tests/voxel_cases.py sizes its clouds by the tile, scan and bounds constants of csrc/gs360_kernels.h"""
+    text = (PKG / "csrc" / "gs360_kernels.h").read_text()
+    value = lambda name: int(re.search(rf"constexpr int {name} = (\d+);", text).group(1))
+    got = (voxel_cases.TILE, voxel_cases.SCAN_THREADS, voxel_cases.BOUND_BLOCKS, voxel_cases.BOUND_THREADS, voxel_cases.LANE_MAX)
+    assert got == tuple(value(n) for n in ("kVxTile", "kVxScanThreads", "kVxBoundBlocks", "kVxThreads", "kVxLaneMax"))
 
 
 def test_a_grid_of_1e9_per_unit_takes_the_host_path(gold):

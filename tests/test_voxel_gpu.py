@@ -16,7 +16,7 @@ def gold():
     return np.load(GOLDEN / "plyopt_goldens.npz")
 
 
-def check(ctx, xyz, voxels, slot=0):
+def check(ctx, xyz, voxels, slot=0, strategies=STRATEGIES):
     """every device result on `xyz` at every voxel size against the restatement"""
     xyz = np.ascontiguousarray(xyz, dtype=np.float32)
     minmax = voxel_np.bounds(xyz)
@@ -26,7 +26,7 @@ def check(ctx, xyz, voxels, slot=0):
             assert voxel_np.layout(minmax, voxel) is not None, "this case is meant for the device path"
             want_k, _packed = voxel_np.unique_count(xyz, voxel, minmax)
             assert cloud.unique_count(voxel) == want_k, voxel
-            for how in STRATEGIES:
+            for how in strategies:
                 got = cloud.downsample_by_size(voxel, how)
                 assert got.dtype == np.int64 and np.array_equal(got, voxel_np.pick(xyz, voxel, how, minmax)), (voxel, how)
             got = cloud.downsample_by_size(voxel, "random")

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import voxel_cases
 import voxel_np
 from conftest import GOLDEN, ROOT
 
@@ -67,6 +68,25 @@ def test_layout_edges(program, tmp_path):
     check(program, tmp_path, flat, 1.0)                                                        # no x bits: shift 48
     cube = np.concatenate([rng.uniform(0.0, 1.0, size=(100, 3)), [[0.0, 0.0, 0.0], [1.0, 1.0, 1.0]]])
     check(program, tmp_path, cube, 1.0)                                                        # the maximum on the upper face
+
+
+@pytest.mark.parametrize("bits", voxel_cases.PACKED_LAYOUTS, ids=lambda b: "+".join(map(str, b)))
+def test_packed_layouts_up_to_64_bits(program, tmp_path, bits):
+    """the lattices of tests/test_voxel_edges_gpu.py; from 0 + 32 + 32 on the x keys' shift is 64, which vx_point_key and vx_center
+    must not carry out"""
+    xyz = voxel_cases.lattice(bits)
+    assert voxel_np.layout(voxel_np.bounds(xyz), 1.0) == list(bits)
+    check(program, tmp_path, xyz, 1.0)
+
+
+def test_squared_distances_at_the_edges_of_float32(program, tmp_path):
+    """subnormal squares are told apart; among infinite ones a lane keeps its first point"""
+    xyz, members = voxel_cases.subnormal_cloud(23, seed=23)
+    assert voxel_np.pick(xyz, 1.0, "centroid")[0] not in (members[0], members[-1])
+    check(program, tmp_path, xyz, 1.0)
+    xyz, corner, _mixed = voxel_cases.overflow_cloud(20, seed=20)
+    assert voxel_np.pick(xyz, 1e20, "center")[0] == voxel_np.pick(xyz, 1e20, "centroid")[0] == corner[0]
+    check(program, tmp_path, xyz, 1e20)
 
 
 def test_points_outside_the_bounds_are_counted_not_read_past(program, tmp_path):

@@ -77,9 +77,22 @@ def pick(xyz, voxel, representative, minmax=None):
     """the pick index per voxel, in key order (int64)"""
     xyz = np.asarray(xyz, dtype=np.float32)
     minmax = bounds(xyz) if minmax is None else minmax
-    ks, order, starts, bits = segments(xyz, voxel, minmax)
     if representative == "first":
+        _ks, order, starts, _bits = segments(xyz, voxel, minmax)
         return order[starts]
+    order, starts, gid, dist2 = distances(xyz, voxel, representative, minmax)
+    low = np.minimum.reduceat(dist2, starts)
+    hits = np.flatnonzero(dist2 == low[gid])               # the first minimum of every segment
+    _g, first = np.unique(gid[hits], return_index=True)
+    return order[hits[first]]
+
+
+def distances(xyz, voxel, representative, minmax=None):
+    """-> (the indices in stable key order, the segment starts, the segment of every sorted position, its float32 squared distance
+    to its voxel's `center` or `centroid`)"""
+    xyz = np.asarray(xyz, dtype=np.float32)
+    minmax = bounds(xyz) if minmax is None else minmax
+    ks, order, starts, bits = segments(xyz, voxel, minmax)
     n, k = xyz.shape[0], starts.size
     lens = np.diff(np.r_[starts, n])
     gid = np.repeat(np.arange(k), lens)
@@ -101,10 +114,7 @@ def pick(xyz, voxel, representative, minmax=None):
         d = xyz[order] - targets[gid]
         dist2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
     assert dist2.dtype == np.float32
-    low = np.minimum.reduceat(dist2, starts)
-    hits = np.flatnonzero(dist2 == low[gid])               # the first minimum of every segment
-    _g, first = np.unique(gid[hits], return_index=True)
-    return order[hits[first]]
+    return order, starts, gid, dist2
 
 
 def downsample_ply_bytes(xyz, rgb, idx):
