@@ -12,11 +12,70 @@ struct gs360_color_plan {
     void* d_cube = nullptr;     // uint32[2^24]: the stage evaluated for every 8-bit pixel (NULL with GS360_COLOR_CUBE=0)
 };
 
+struct gs360_color_plan16 {
+    int device = 0;
+    gs360::Color16Launch L;
+    float* d_lut = nullptr;
+    float* d_thr = nullptr;
+    void* d_bins = nullptr;
+};
+
+// what both creates check first
+static int check_create(gs360_ctx* c, bool have_args, int lut_size) {
+    if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
+    if (!have_args) return fail(GS360_ERR_ARG, "NULL argument");
+    if (lut_size < 2 || lut_size > 256) return fail(GS360_ERR_ARG, "LUT size %d outside [2,256]", lut_size);
+    return GS360_OK;
+}
+
+// Release a plan's device memory and the plan itself (create's failure path and destroy); the first hipFree error, if any.
+template <typename Plan>
+static hipError_t release_plan(Plan* p, std::initializer_list<void*> mem) {
+    hipError_t e = hipSuccess;
+    for (void* d : mem)
+        if (d) { const hipError_t f = hipFree(d); if (e == hipSuccess) e = f; }
+    delete p;
+    return e;
+}
+static hipError_t release_plan(gs360_color_plan* p) { return release_plan(p, {p->d_rtab, p->d_tables, p->d_cube}); }
+static hipError_t release_plan(gs360_color_plan16* p) { return release_plan(p, {p->d_lut, p->d_thr, p->d_bins}); }
+
+template <typename Plan>
+static int destroy_plan(gs360_ctx* c, Plan* p) {
+    if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
+    if (!p) return GS360_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(release_plan(p));
+    return GS360_OK;
+}
+
+// What both apply calls check, for samples of `bytes` bytes.  Fills the image record, default strides included; an empty image is
+// GS360_OK with the record left without a source.
+static int check_apply(gs360_ctx* c, const int* plan_device, const void* src, int H, int W, int C, size_t src_stride, int red_index,
+                       void* dst, size_t dst_stride, int slot, int bytes, ColorImage& I) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (!plan_device || !src || !dst) return fail(GS360_ERR_ARG, "NULL argument");
+    if (*plan_device != c->device) return fail(GS360_ERR_ARG, "colour plan belongs to device %d, ctx is device %d", *plan_device, c->device);
+    if (C != 3 && C != 4) return fail(GS360_ERR_ARG, "the LUT stage needs 3 or 4 channels (got %d)", C);   // DF:693-697
+    if (red_index != 0 && red_index != 2) return fail(GS360_ERR_ARG, "red_index must be 0 (RGB) or 2 (BGR)");
+    if (H < 0 || W < 0) return fail(GS360_ERR_ARG, "bad size");
+    if (H == 0 || W == 0) return GS360_OK;
+    if (H > 65535) return fail(GS360_ERR_UNSUPPORTED, "image height %d above 65535", H);
+    const size_t row = (size_t)W * C * bytes;
+    if (src_stride == 0) src_stride = row;
+    if (dst_stride == 0) dst_stride = row;
+    const bool short_row = src_stride < row || dst_stride < row;
+    if (bytes == 1 && short_row) return fail(GS360_ERR_ARG, "stride smaller than a row");
+    if (bytes == 2 && (short_row || ((src_stride | dst_stride) & 1))) return fail(GS360_ERR_ARG, "16-bit images need even strides of at least one row");
+    HIP_TRY(hipSetDevice(c->device));
+    I = ColorImage{src, dst, H, W, red_index, (int64_t)src_stride, (int64_t)dst_stride};
+    return GS360_OK;
+}
+
 int gs360_color_plan_create(gs360_ctx* c, const float* lut, int lut_size, const float* level_pos,
                             const float* out_thresholds, gs360_color_plan** out) {
-    if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
-    if (!lut || !level_pos || !out_thresholds || !out) return fail(GS360_ERR_ARG, "NULL argument");
-    if (lut_size < 2 || lut_size > 256) return fail(GS360_ERR_ARG, "LUT size %d outside [2,256]", lut_size);
+    if (int rc = check_create(c, lut && level_pos && out_thresholds && out, lut_size)) return rc;
     const int nmax = lut_size - 1;
     for (int i = 0; i < 768; ++i)   // positions index the table: refuse anything that would read outside it
         if (!(level_pos[i] >= 0.0f && level_pos[i] <= (float)nmax))
@@ -63,64 +122,29 @@ int gs360_color_plan_create(gs360_ctx* c, const float* lut, int lut_size, const 
         p->d_rtab = nullptr;
     }
     if (e != hipSuccess) {
-        if (p->d_rtab) (void)hipFree(p->d_rtab);
-        if (p->d_tables) (void)hipFree(p->d_tables);
-        if (p->d_cube) (void)hipFree(p->d_cube);
-        delete p;
+        (void)release_plan(p);
         return fail(e == hipErrorOutOfMemory ? GS360_ERR_NOMEM : GS360_ERR_HIP, "colour plan setup failed: %s", hipGetErrorString(e));
     }
     *out = p;
     return GS360_OK;
 }
 
-int gs360_color_plan_destroy(gs360_ctx* c, gs360_color_plan* p) {
-    if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
-    if (!p) return GS360_OK;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (p->d_rtab) HIP_TRY(hipFree(p->d_rtab));
-    if (p->d_tables) HIP_TRY(hipFree(p->d_tables));
-    if (p->d_cube) HIP_TRY(hipFree(p->d_cube));
-    delete p;
-    return GS360_OK;
-}
+int gs360_color_plan_destroy(gs360_ctx* c, gs360_color_plan* p) { return destroy_plan(c, p); }
 
 int gs360_color_apply_u8(gs360_ctx* c, const gs360_color_plan* p, const void* src, int H, int W, int C, size_t src_stride,
                          int red_index, void* dst, size_t dst_stride, int slot) {
-    if (int rc = check_ctx_slot(c, slot)) return rc;
-    if (!p || !src || !dst) return fail(GS360_ERR_ARG, "NULL argument");
-    if (p->device != c->device) return fail(GS360_ERR_ARG, "colour plan belongs to device %d, ctx is device %d", p->device, c->device);
-    if (C != 3 && C != 4) return fail(GS360_ERR_ARG, "the LUT stage needs 3 or 4 channels (got %d)", C);   // DF:693-697
-    if (red_index != 0 && red_index != 2) return fail(GS360_ERR_ARG, "red_index must be 0 (RGB) or 2 (BGR)");
-    if (H < 0 || W < 0) return fail(GS360_ERR_ARG, "bad size");
-    if (H == 0 || W == 0) return GS360_OK;
-    if (H > 65535) return fail(GS360_ERR_UNSUPPORTED, "image height %d above 65535", H);
-    if (src_stride == 0) src_stride = (size_t)W * C;
-    if (dst_stride == 0) dst_stride = (size_t)W * C;
-    if (src_stride < (size_t)W * C || dst_stride < (size_t)W * C) return fail(GS360_ERR_ARG, "stride smaller than a row");
-    HIP_TRY(hipSetDevice(c->device));
-    ColorLaunch L;
-    L.src = (const uint8_t*)src; L.dst = (uint8_t*)dst; L.rtab = p->d_rtab; L.tables = p->d_tables; L.cube = p->d_cube;
-    L.H = H; L.W = W; L.lut_size = p->lut_size; L.red_index = red_index; L.fixups = p->fixups;
-    L.src_stride = (int64_t)src_stride; L.dst_stride = (int64_t)dst_stride;
+    ColorLaunch L{};
+    if (int rc = check_apply(c, p ? &p->device : nullptr, src, H, W, C, src_stride, red_index, dst, dst_stride, slot, 1, L.img)) return rc;
+    if (!L.img.src) return GS360_OK;
+    L.rtab = p->d_rtab; L.tables = p->d_tables; L.cube = p->d_cube; L.lut_size = p->lut_size; L.fixups = p->fixups;
     HIP_TRY(launch_color(L, C, c->stream[slot]));
     return GS360_OK;
 }
 
-struct gs360_color_plan16 {
-    int device = 0;
-    gs360::Color16Launch L;
-    float* d_lut = nullptr;
-    float* d_thr = nullptr;
-    void* d_bins = nullptr;
-};
-
 int gs360_color_plan16_create(gs360_ctx* c, const float* lut, int lut_size, const float* domain_min, const float* domain_max,
                               int n_pieces, const float* piece_start, const int32_t* piece_base, const int32_t* piece_off,
                               const float* thresholds, gs360_color_plan16** out) {
-    if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
-    if (!lut || !domain_min || !domain_max || !out) return fail(GS360_ERR_ARG, "NULL argument");
-    if (lut_size < 2 || lut_size > 256) return fail(GS360_ERR_ARG, "LUT size %d outside [2,256]", lut_size);
+    if (int rc = check_create(c, lut && domain_min && domain_max && out, lut_size)) return rc;
     if (n_pieces < 0 || n_pieces > 4) return fail(GS360_ERR_ARG, "n_pieces must be in [0,4]");
     if (n_pieces && (!piece_start || !piece_base || !piece_off || !thresholds)) return fail(GS360_ERR_ARG, "NULL piece tables");
     gs360_color_plan16* p = new (std::nothrow) gs360_color_plan16();
@@ -161,10 +185,7 @@ int gs360_color_plan16_create(gs360_ctx* c, const float* lut, int lut_size, cons
         if (e == hipSuccess) e = hipMemcpy(p->d_bins, bins.data(), bins.size(), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
-        if (p->d_lut) (void)hipFree(p->d_lut);
-        if (p->d_thr) (void)hipFree(p->d_thr);
-        if (p->d_bins) (void)hipFree(p->d_bins);
-        delete p;
+        (void)release_plan(p);
         return fail(GS360_ERR_HIP, "colour plan setup failed: %s", hipGetErrorString(e));
     }
     p->L.lut = p->d_lut;
@@ -174,36 +195,15 @@ int gs360_color_plan16_create(gs360_ctx* c, const float* lut, int lut_size, cons
     return GS360_OK;
 }
 
-int gs360_color_plan16_destroy(gs360_ctx* c, gs360_color_plan16* p) {
-    if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
-    if (!p) return GS360_OK;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (p->d_lut) HIP_TRY(hipFree(p->d_lut));
-    if (p->d_thr) HIP_TRY(hipFree(p->d_thr));
-    if (p->d_bins) HIP_TRY(hipFree(p->d_bins));
-    delete p;
-    return GS360_OK;
-}
+int gs360_color_plan16_destroy(gs360_ctx* c, gs360_color_plan16* p) { return destroy_plan(c, p); }
 
 int gs360_color_apply_u16(gs360_ctx* c, const gs360_color_plan16* p, const void* src, int H, int W, int C, size_t src_stride,
                           int red_index, void* dst, size_t dst_stride, int slot) {
-    if (int rc = check_ctx_slot(c, slot)) return rc;
-    if (!p || !src || !dst) return fail(GS360_ERR_ARG, "NULL argument");
-    if (p->device != c->device) return fail(GS360_ERR_ARG, "colour plan belongs to device %d, ctx is device %d", p->device, c->device);
-    if (C != 3 && C != 4) return fail(GS360_ERR_ARG, "the LUT stage needs 3 or 4 channels (got %d)", C);
-    if (red_index != 0 && red_index != 2) return fail(GS360_ERR_ARG, "red_index must be 0 (RGB) or 2 (BGR)");
-    if (H < 0 || W < 0) return fail(GS360_ERR_ARG, "bad size");
-    if (H == 0 || W == 0) return GS360_OK;
-    if (H > 65535) return fail(GS360_ERR_UNSUPPORTED, "image height %d above 65535", H);
-    if (src_stride == 0) src_stride = (size_t)W * C * 2;
-    if (dst_stride == 0) dst_stride = (size_t)W * C * 2;
-    if (src_stride < (size_t)W * C * 2 || dst_stride < (size_t)W * C * 2 || ((src_stride | dst_stride) & 1))
-        return fail(GS360_ERR_ARG, "16-bit images need even strides of at least one row");
-    HIP_TRY(hipSetDevice(c->device));
+    ColorImage I{};
+    if (int rc = check_apply(c, p ? &p->device : nullptr, src, H, W, C, src_stride, red_index, dst, dst_stride, slot, 2, I)) return rc;
+    if (!I.src) return GS360_OK;
     gs360::Color16Launch L = p->L;
-    L.src = src; L.dst = dst; L.H = H; L.W = W; L.red_index = red_index;
-    L.src_stride = (int64_t)src_stride; L.dst_stride = (int64_t)dst_stride;
+    L.img = I;
     HIP_TRY(launch_color16(L, C, c->stream[slot]));
     return GS360_OK;
 }

@@ -24,8 +24,7 @@
 // 4400th of it), the part of it an image touches -- a natural image occupies a small fraction of the colour cube -- in the L2 / Infinity
 // Cache.  Results are those of the evaluating kernels by construction.  GS360_COLOR_CUBE=0 at plan creation keeps the per-pixel
 // evaluation (A/B, or to save the 64 MiB).
-#include <cstring>
-#include <vector>
+#include <type_traits>
 
 #include "gs360_kernels.h"
 
@@ -40,17 +39,6 @@ constexpr int kColorBlocks = 2048;   // persistent blocks of the dword-aligned p
 struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
 
 struct __attribute__((aligned(16))) CellEntry { float v[16]; };   // c00.xyz c10.xyz c01.xyz c11.xyz + 4 floats of padding
-
-struct ColorArgs {
-    const uint8_t* src;
-    uint8_t* dst;
-    const CellEntry* rtab;  // [blue cell][green cell][red level]
-    const float* tables;    // 768 level positions (R,G,B x 256), 256 thresholds, then kBins/4 dwords of packed bin levels
-    int32_t H, W;
-    int32_t n;              // LUT edge length
-    int32_t red;            // memory index of the red channel (0 or 2)
-    int64_t src_stride, dst_stride;
-};
 
 struct Cell {               // one channel's LUT cell: lower index, upper index, weight of the upper node
     int i0, i1;
@@ -94,7 +82,55 @@ __device__ __forceinline__ int level_of(const Lds& S, float x) {
     return lv;
 }
 
-struct Rgb8 { int r, g, b; };
+struct Rgb { int r, g, b; };
+
+// Pixel x of row y of an image side (strides are in bytes).
+template <int C, typename T>
+__device__ __forceinline__ T* pixel_at(const void* base, int64_t stride, int y, int x) {
+    return (T*)((const char*)base + (int64_t)y * stride) + (int64_t)x * C;
+}
+
+// One pixel of T samples: read R/G/B through the memory index of the red channel (0 or 2), apply f(r, g, b) -> Rgb, keep alpha
+// when C == 4, write back in memory order.
+template <int C, typename T, typename F>
+__device__ __forceinline__ void pixel_step(const ColorImage& I, int y, int x, F f) {
+    const T* sp = pixel_at<C, const T>(I.src, I.src_stride, y, x);
+    T* dp = pixel_at<C, T>(I.dst, I.dst_stride, y, x);
+    const int iR = I.red_index, iB = 2 - I.red_index;
+    const int alpha = (C == 4) ? sp[3] : 0;
+    const Rgb q = f((int)sp[iR], (int)sp[1], (int)sp[iB]);
+    dp[iR] = (T)q.r; dp[1] = (T)q.g; dp[iB] = (T)q.b;
+    if (C == 4) dp[3] = (T)alpha;
+}
+
+// A group of pixels held in C dwords -- four 8-bit or two 16-bit pixels, BITS per sample, sample i at bit i * BITS of the group.
+// The colour samples of pixel p as R, G, B ...
+template <int C, int BITS>
+__device__ __forceinline__ Rgb group_px(const uint32_t (&w)[C], int p, bool bgr) {
+    auto get = [&](int i) { return (int)((w[i * BITS / 32] >> (i * BITS % 32)) & ((1u << BITS) - 1u)); };
+    const int m0 = get(p * C), m2 = get(p * C + 2);
+    return {bgr ? m2 : m0, get(p * C + 1), bgr ? m0 : m2};
+}
+// ... its output levels or-ed into an output group in memory order ...
+template <int C, int BITS>
+__device__ __forceinline__ void group_put(uint32_t (&o)[C], int p, bool bgr, const Rgb& q) {
+    auto put = [&](int i, int v) { o[i * BITS / 32] |= (uint32_t)v << (i * BITS % 32); };
+    put(p * C, bgr ? q.b : q.r);
+    put(p * C + 1, q.g);
+    put(p * C + 2, bgr ? q.r : q.b);
+}
+// ... and the output group to start from: every fourth sample (alpha, C == 4) kept, the colour samples zero.
+template <int C, int BITS>
+__device__ __forceinline__ void group_keep_alpha(const uint32_t (&w)[C], uint32_t (&o)[C]) {
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        uint32_t mask = 0u;
+#pragma unroll
+        for (int j = 0; j < 32 / BITS; ++j)
+            if (C == 4 && (i * (32 / BITS) + j) % 4 == 3) mask |= ((1u << BITS) - 1u) << (j * BITS);
+        o[i] = w[i] & mask;
+    }
+}
 
 struct Taps {               // the four red-interpolated table entries around a pixel and its green/blue weights
     F3 c00, c10, c01, c11;
@@ -102,11 +138,11 @@ struct Taps {               // the four red-interpolated table entries around a 
 };
 
 // first half of the pipeline for one pixel: locate the cell and issue the table read (three aligned 16-byte loads of one entry)
-__device__ __forceinline__ Taps color_fetch(const ColorArgs& A, const Lds& S, int vr, int vg, int vb) {
-    const int n = A.n, nmax = n - 1;
+__device__ __forceinline__ Taps color_fetch(const ColorLaunch& A, const Lds& S, int vr, int vg, int vb) {
+    const int n = A.lut_size, nmax = n - 1;
     const Cell g = cell_of(S.pos[256 + vg], nmax);
     const Cell b = cell_of(S.pos[512 + vb], nmax);
-    const char* base = (const char*)A.rtab;        // the table is < 4 GiB: 32-bit byte offsets from a scalar base
+    const char* base = (const char*)A.rtab;        // [blue cell][green cell][red level]; < 4 GiB: 32-bit byte offsets from a scalar base
     const float4* e = (const float4*)(base + (size_t)(((((uint32_t)(b.i0 * n + g.i0)) << 8) + (uint32_t)vr) << 6));
     const float4 q0 = e[0], q1 = e[1], q2 = e[2];
     Taps t;
@@ -121,8 +157,8 @@ __device__ __forceinline__ Taps color_fetch(const ColorArgs& A, const Lds& S, in
 
 // second half: green stage, blue stage (DF:676-679), quantise
 template <int FIX>
-__device__ __forceinline__ Rgb8 color_finish(const Lds& S, const Taps& t) {
-    Rgb8 q;
+__device__ __forceinline__ Rgb color_finish(const Lds& S, const Taps& t) {
+    Rgb q;
     q.r = level_of<FIX>(S, lerp_ref(lerp_ref(t.c00.x, t.c10.x, t.gf), lerp_ref(t.c01.x, t.c11.x, t.gf), t.bf));
     q.g = level_of<FIX>(S, lerp_ref(lerp_ref(t.c00.y, t.c10.y, t.gf), lerp_ref(t.c01.y, t.c11.y, t.gf), t.bf));
     q.b = level_of<FIX>(S, lerp_ref(lerp_ref(t.c00.z, t.c10.z, t.gf), lerp_ref(t.c01.z, t.c11.z, t.gf), t.bf));
@@ -130,11 +166,12 @@ __device__ __forceinline__ Rgb8 color_finish(const Lds& S, const Taps& t) {
 }
 
 template <int FIX>
-__device__ __forceinline__ Rgb8 color_px(const ColorArgs& A, const Lds& S, int vr, int vg, int vb) {
+__device__ __forceinline__ Rgb color_px(const ColorLaunch& A, const Lds& S, int vr, int vg, int vb) {
     return color_finish<FIX>(S, color_fetch(A, S, vr, vg, vb));
 }
 
-__device__ __forceinline__ void load_tables(const ColorArgs& A, Lds& S) {
+// A.tables: 768 level positions (R,G,B x 256), 256 thresholds, then kBins/4 dwords of packed bin levels
+__device__ __forceinline__ void load_tables(const ColorLaunch& A, Lds& S) {
     constexpr int kPer = (1024 + kBins / 4) / kColorThreads;               // 5 dwords per thread, all in flight at once
     static_assert((1024 + kBins / 4) % kColorThreads == 0, "table size");
     float v[kPer];
@@ -153,18 +190,12 @@ __device__ __forceinline__ void load_tables(const ColorArgs& A, Lds& S) {
 
 // Any alignment: one thread per pixel, byte loads and stores.
 template <int C, int FIX>
-__global__ __launch_bounds__(kColorThreads) void color_lut_bytes_kernel(ColorArgs A) {
+__global__ __launch_bounds__(kColorThreads) void color_lut_bytes_kernel(ColorLaunch A) {
     __shared__ Lds S;
     load_tables(A, S);
     const int x = blockIdx.x * kColorThreads + threadIdx.x;
-    if (x >= A.W) return;
-    const uint8_t* sp = A.src + (int64_t)blockIdx.y * A.src_stride + (int64_t)x * C;
-    uint8_t* dp = A.dst + (int64_t)blockIdx.y * A.dst_stride + (int64_t)x * C;
-    const int iR = A.red, iB = 2 - A.red;
-    const int alpha = (C == 4) ? sp[3] : 0;
-    const Rgb8 q = color_px<FIX>(A, S, sp[iR], sp[1], sp[iB]);
-    dp[iR] = (uint8_t)q.r; dp[1] = (uint8_t)q.g; dp[iB] = (uint8_t)q.b;
-    if (C == 4) dp[3] = (uint8_t)alpha;
+    if (x >= A.img.W) return;
+    pixel_step<C, uint8_t>(A.img, blockIdx.y, x, [&](int r, int g, int b) { return color_px<FIX>(A, S, r, g, b); });
 }
 
 // Rows that start on a dword boundary: one thread per 4 pixels = C dwords in, C dwords out, so a wavefront moves
@@ -172,19 +203,19 @@ __global__ __launch_bounds__(kColorThreads) void color_lut_bytes_kernel(ColorArg
 // per block) and walk 1024-pixel row segments in row-major order.
 constexpr int kColorWaves = 5;
 template <int C, int FIX>
-__global__ __launch_bounds__(kColorThreads) __attribute__((amdgpu_waves_per_eu(kColorWaves, kColorWaves))) void color_lut_quad_kernel(ColorArgs A) {
+__global__ __launch_bounds__(kColorThreads) __attribute__((amdgpu_waves_per_eu(kColorWaves, kColorWaves))) void color_lut_quad_kernel(ColorLaunch A) {
     __shared__ Lds S;
     load_tables(A, S);
-    const int iR = A.red, iB = 2 - A.red;
-    const bool bgr = A.red != 0;
-    const int segs = (A.W + 4 * kColorThreads - 1) / (4 * kColorThreads);
-    const int total = segs * A.H;
+    const ColorImage& I = A.img;
+    const bool bgr = I.red_index != 0;
+    const int segs = (I.W + 4 * kColorThreads - 1) / (4 * kColorThreads);
+    const int total = segs * I.H;
     // the image dwords of a thread's NEXT row segment are requested before the current one is worked on: of the chain image read ->
     // level tables (LDS) -> entry read -> blend -> quantiser tables (LDS) -> store, the first link then costs nothing
     auto seg_src = [&](int t, int& y, int& x) {
         y = t / segs;
         x = ((t - y * segs) * kColorThreads + threadIdx.x) * 4;
-        return A.src + (int64_t)y * A.src_stride + (int64_t)x * C;
+        return pixel_at<C, const uint8_t>(I.src, I.src_stride, y, x);
     };
     uint32_t wn[C];
 #pragma unroll
@@ -192,14 +223,14 @@ __global__ __launch_bounds__(kColorThreads) __attribute__((amdgpu_waves_per_eu(k
     {
         int y0, x0;
         const uint8_t* p0 = seg_src(blockIdx.x, y0, x0);
-        if (blockIdx.x < (unsigned)total && x0 + 4 <= A.W) {
+        if (blockIdx.x < (unsigned)total && x0 + 4 <= I.W) {
 #pragma unroll
             for (int i = 0; i < C; ++i) wn[i] = ((const uint32_t*)p0)[i];
         }
     }
     for (int t = blockIdx.x; t < total; t += gridDim.x) {
         int y, x;
-        const uint8_t* sp = seg_src(t, y, x);
+        seg_src(t, y, x);
         uint32_t w[C];
 #pragma unroll
         for (int i = 0; i < C; ++i) w[i] = wn[i];
@@ -207,73 +238,52 @@ __global__ __launch_bounds__(kColorThreads) __attribute__((amdgpu_waves_per_eu(k
             int yn, xn;
             const int tn = t + (int)gridDim.x;
             const uint8_t* pn = seg_src(tn, yn, xn);
-            if (tn < total && xn + 4 <= A.W) {
+            if (tn < total && xn + 4 <= I.W) {
 #pragma unroll
                 for (int i = 0; i < C; ++i) wn[i] = ((const uint32_t*)pn)[i];
             }
         }
-        if (x >= A.W) continue;
-        uint8_t* dp = A.dst + (int64_t)y * A.dst_stride + (int64_t)x * C;
-        if (x + 4 <= A.W) {
+        if (x >= I.W) continue;
+        if (x + 4 <= I.W) {
             Taps taps[4];                          // all 16 table reads of the four pixels are in flight together
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-                int v[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int byte = p * C + c;
-                    v[c] = (w[byte >> 2] >> (8 * (byte & 3))) & 0xff;
-                }
-                taps[p] = color_fetch(A, S, bgr ? v[2] : v[0], v[1], bgr ? v[0] : v[2]);
+                const Rgb v = group_px<C, 8>(w, p, bgr);
+                taps[p] = color_fetch(A, S, v.r, v.g, v.b);
             }
             __builtin_amdgcn_sched_barrier(0);     // keep the scheduler from sinking reads below the first blend
             uint32_t o[C];
+            group_keep_alpha<C, 8>(w, o);
 #pragma unroll
-            for (int i = 0; i < C; ++i) o[i] = (C == 4) ? (w[i] & 0xff000000u) : 0u;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const Rgb8 q = color_finish<FIX>(S, taps[p]);
-                const int out3[3] = {bgr ? q.b : q.r, q.g, bgr ? q.r : q.b};
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int byte = p * C + c;
-                    o[byte >> 2] |= (uint32_t)out3[c] << (8 * (byte & 3));
-                }
-            }
-            uint32_t* d32 = (uint32_t*)dp;
+            for (int p = 0; p < 4; ++p) group_put<C, 8>(o, p, bgr, color_finish<FIX>(S, taps[p]));
+            uint32_t* d32 = (uint32_t*)pixel_at<C, uint8_t>(I.dst, I.dst_stride, y, x);
 #pragma unroll
             for (int i = 0; i < C; ++i) d32[i] = o[i];
         } else {
-            for (int p = 0; x + p < A.W; ++p) {
-                const uint8_t* s1 = sp + p * C;
-                uint8_t* d1 = dp + p * C;
-                const int alpha = (C == 4) ? s1[3] : 0;
-                const Rgb8 q = color_px<FIX>(A, S, s1[iR], s1[1], s1[iB]);
-                d1[iR] = (uint8_t)q.r; d1[1] = (uint8_t)q.g; d1[iB] = (uint8_t)q.b;
-                if (C == 4) d1[3] = (uint8_t)alpha;
-            }
+            for (int p = 0; x + p < I.W; ++p)
+                pixel_step<C, uint8_t>(I, y, x + p, [&](int r, int g, int b) { return color_px<FIX>(A, S, r, g, b); });
         }
     }
 }
 
 // ---- the cube: every possible 8-bit pixel through the pipeline once, then one read per pixel ---------------------------------------
-struct CubeArgs {
-    const uint8_t* src;
-    uint8_t* dst;
-    const uint32_t* cube;   // [blue][green][red] -> red | green << 8 | blue << 16
-    int32_t H, W;
-    int32_t red;            // memory index of the red channel (0 or 2)
-    int64_t src_stride, dst_stride;
-};
-
+// A.cube: [blue][green][red] -> red | green << 8 | blue << 16
 template <int FIX>
-__global__ __launch_bounds__(kColorThreads) void color_cube_kernel(ColorArgs A, uint32_t* cube) {
+__global__ __launch_bounds__(kColorThreads) void color_cube_kernel(ColorLaunch A, uint32_t* cube) {
     __shared__ Lds S;
     load_tables(A, S);
     for (uint32_t i = blockIdx.x * kColorThreads + threadIdx.x; i < (1u << 24); i += gridDim.x * kColorThreads) {
-        const Rgb8 q = color_px<FIX>(A, S, (int)(i & 255u), (int)((i >> 8) & 255u), (int)(i >> 16));
+        const Rgb q = color_px<FIX>(A, S, (int)(i & 255u), (int)((i >> 8) & 255u), (int)(i >> 16));
         cube[i] = (uint32_t)q.r | ((uint32_t)q.g << 8) | ((uint32_t)q.b << 16);
     }
+}
+
+template <int C>
+__device__ __forceinline__ void cube_pixel_step(const ColorLaunch& A, int y, int x) {
+    pixel_step<C, uint8_t>(A.img, y, x, [&](int r, int g, int b) {
+        const uint32_t q = ((const uint32_t*)A.cube)[(uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16)];
+        return Rgb{(int)q, (int)(q >> 8), (int)(q >> 16)};     // the store keeps the low byte of each
+    });
 }
 
 // v_perm_b32 selectors (bytes 0-3 = the second operand, 0x0c = a zero byte): keep the three colour bytes of a pixel in memory order
@@ -282,41 +292,35 @@ __global__ __launch_bounds__(kColorThreads) void color_cube_kernel(ColorArgs A, 
 __device__ __forceinline__ uint32_t cube_selector(int red) { return red != 0 ? 0x0c000102u : 0x0c020100u; }
 
 template <int C>
-__global__ __launch_bounds__(kColorThreads) void color_cube_bytes_kernel(CubeArgs A) {
+__global__ __launch_bounds__(kColorThreads) void color_cube_bytes_kernel(ColorLaunch A) {
     const int x = blockIdx.x * kColorThreads + threadIdx.x;
-    if (x >= A.W) return;
-    const uint8_t* sp = A.src + (int64_t)blockIdx.y * A.src_stride + (int64_t)x * C;
-    uint8_t* dp = A.dst + (int64_t)blockIdx.y * A.dst_stride + (int64_t)x * C;
-    const int iR = A.red, iB = 2 - A.red;
-    const int alpha = (C == 4) ? sp[3] : 0;
-    const uint32_t q = A.cube[(uint32_t)sp[iR] | ((uint32_t)sp[1] << 8) | ((uint32_t)sp[iB] << 16)];
-    dp[iR] = (uint8_t)q; dp[1] = (uint8_t)(q >> 8); dp[iB] = (uint8_t)(q >> 16);
-    if (C == 4) dp[3] = (uint8_t)alpha;
+    if (x < A.img.W) cube_pixel_step<C>(A, blockIdx.y, x);
 }
 
 // Rows that start on a dword boundary: a thread takes kCubeQuads groups of four pixels (C dwords in, four table reads, C dwords out each),
 // the groups of a thread one wavefront-row (256 pixels x 4) apart so that every load and store instruction of a wavefront covers
-// contiguous bytes; all table reads of a thread are in flight together.
+// contiguous bytes; all table reads of a thread are in flight together.  (The unpacking is alignbit / perm by hand, not group_px.)
 constexpr int kCubeQuads = 2;
 template <int C>
-__global__ __launch_bounds__(kColorThreads) void color_cube_quad_kernel(CubeArgs A) {
-    const uint32_t sel = cube_selector(A.red);
+__global__ __launch_bounds__(kColorThreads) void color_cube_quad_kernel(ColorLaunch A) {
+    const ColorImage& I = A.img;
+    const uint32_t* cube = (const uint32_t*)A.cube;
+    const uint32_t sel = cube_selector(I.red_index);
     const int x0 = (blockIdx.x * kCubeQuads * kColorThreads + threadIdx.x) * 4;
-    const uint8_t* srow = A.src + (int64_t)blockIdx.y * A.src_stride;
-    uint8_t* drow = A.dst + (int64_t)blockIdx.y * A.dst_stride;
+    const int y = blockIdx.y;
     uint32_t w[kCubeQuads][C], q[kCubeQuads][4];
 #pragma unroll
     for (int k = 0; k < kCubeQuads; ++k) {
         const int x = x0 + k * 4 * kColorThreads;
-        if (x + 4 <= A.W) {
+        if (x + 4 <= I.W) {
 #pragma unroll
-            for (int i = 0; i < C; ++i) w[k][i] = ((const uint32_t*)(srow + (int64_t)x * C))[i];
+            for (int i = 0; i < C; ++i) w[k][i] = ((const uint32_t*)pixel_at<C, const uint8_t>(I.src, I.src_stride, y, x))[i];
         }
     }
 #pragma unroll
     for (int k = 0; k < kCubeQuads; ++k) {
         const int x = x0 + k * 4 * kColorThreads;
-        if (x + 4 <= A.W) {
+        if (x + 4 <= I.W) {
             uint32_t px[4];
             if (C == 4) {
 #pragma unroll
@@ -328,18 +332,18 @@ __global__ __launch_bounds__(kColorThreads) void color_cube_quad_kernel(CubeArgs
                 px[3] = w[k][2] >> 8;
             }
 #pragma unroll
-            for (int p = 0; p < 4; ++p) q[k][p] = A.cube[__builtin_amdgcn_perm(0u, px[p], sel)];
+            for (int p = 0; p < 4; ++p) q[k][p] = cube[__builtin_amdgcn_perm(0u, px[p], sel)];
         }
     }
 #pragma unroll
     for (int k = 0; k < kCubeQuads; ++k) {
         const int x = x0 + k * 4 * kColorThreads;
-        if (x >= A.W) continue;
-        if (x + 4 <= A.W) {
+        if (x >= I.W) continue;
+        if (x + 4 <= I.W) {
             uint32_t o[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) o[p] = __builtin_amdgcn_perm(0u, q[k][p], sel);
-            uint32_t* d32 = (uint32_t*)(drow + (int64_t)x * C);
+            uint32_t* d32 = (uint32_t*)pixel_at<C, uint8_t>(I.dst, I.dst_stride, y, x);
             if (C == 4) {
 #pragma unroll
                 for (int p = 0; p < 4; ++p) d32[p] = o[p] | (w[k][p] & 0xff000000u);
@@ -349,15 +353,7 @@ __global__ __launch_bounds__(kColorThreads) void color_cube_quad_kernel(CubeArgs
                 d32[2] = (o[2] >> 16) | (o[3] << 8);
             }
         } else {                                   // the last, partial group of a row
-            const int iR = A.red, iB = 2 - A.red;
-            for (int p = 0; x + p < A.W; ++p) {
-                const uint8_t* s1 = srow + (int64_t)(x + p) * C;
-                uint8_t* d1 = drow + (int64_t)(x + p) * C;
-                const int alpha = (C == 4) ? s1[3] : 0;
-                const uint32_t v = A.cube[(uint32_t)s1[iR] | ((uint32_t)s1[1] << 8) | ((uint32_t)s1[iB] << 16)];
-                d1[iR] = (uint8_t)v; d1[1] = (uint8_t)(v >> 8); d1[iB] = (uint8_t)(v >> 16);
-                if (C == 4) d1[3] = (uint8_t)alpha;
-            }
+            for (int p = 0; x + p < I.W; ++p) cube_pixel_step<C>(A, y, x + p);
         }
     }
 }
@@ -391,37 +387,35 @@ __global__ void color_rtab_kernel(const float* lut /* [b][g][r][3] */, const flo
 // in-kernel; the sRGB re-encode goes through NumPy's implementation-defined float32 power, so it arrives as sorted
 // thresholds like the 8-bit path -- but in PIECES (the composite is only piecewise monotone at 16-bit resolution: Rec.709
 // knee, sRGB toe): piece p covers clip(x) in [start[p], start[p+1]), level = base[p] + #(thresholds of p <= clip(x)).
-struct Color16Args {
-    const uint16_t* src;
-    uint16_t* dst;
-    const float* lut;        // [b][g][r][3]
-    const float* thr;        // concatenated per-piece thresholds (sorted within a piece)
-    const void* bins;        // kBins16 entries of Bin16 (color16_build_bins)
-    float dmin[3], span[3];
-    float start[4];          // piece lower bounds (start[0] unused)
-    int32_t base[4], off[5];
-    int32_t n_pieces;        // 0: passthrough
-    int32_t H, W, n, red;
-    int64_t src_stride, dst_stride;   // bytes
-};
-
 constexpr int kBins16 = 65536;
 struct __attribute__((aligned(16))) Bin16 {   // answers for x = b / 65536
     uint32_t kp;                               // piece that holds x << 28 | thresholds of that piece <= x (absolute index)
     float t[3];                                // the next three thresholds of the piece (+inf behind its end)
 };
+
+// how many of the sorted t[0..n) are <= x (upper bound)
+__host__ __device__ inline int count_le(const float* t, int n, float x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t[mid] <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // The three output levels of a pixel.  A value's bin entry (one 16-byte read) counts the thresholds up to the bin's lower edge (<= the
 // value: the scaling by 2^16 and the truncation are exact) and brings the next three along -- enough wherever the encode curve rises by
 // less than three levels per 2^-16; past them the thresholds are counted one by one.  A bin that straddles a piece boundary (at most
 // three do) takes the binary search instead.
-__device__ __forceinline__ void levels16_of(const Color16Args& A, const float (&x)[3], int (&q)[3]) {
+__device__ __forceinline__ Rgb levels16_of(const Color16Launch& A, const float (&x)[3]) {
     float xc[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) xc[c] = fminf(fmaxf(x[c], 0.0f), 1.0f);
+    int q[3];
     if (A.n_pieces == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) q[c] = (int)__builtin_rintf(xc[c] * 65535.0f);
-        return;
+        return {q[0], q[1], q[2]};
     }
     const Bin16* bins = reinterpret_cast<const Bin16*>(A.bins);
     Bin16 e[3];
@@ -442,21 +436,17 @@ __device__ __forceinline__ void levels16_of(const Color16Args& A, const float (&
             if (n3 == 3)
                 while (k < end && A.thr[k] <= xc[c]) ++k;
         } else {
-            const float* t = A.thr + first;
-            int lo = 0, hi = end - first;                  // count of thresholds <= xc (upper bound)
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (t[mid] <= xc[c]) lo = mid + 1; else hi = mid;
-            }
-            k = first + lo;
+            k = first + count_le(A.thr + first, end - first, xc[c]);
         }
         q[c] = A.base[p] + (k - first);
     }
+    return {q[0], q[1], q[2]};
 }
 
 // one pixel: float01 conversion, domain mapping, cell lookup, the three interpolation stages in the reference's order, output levels
-__device__ __forceinline__ void color16_px(const Color16Args& A, const int (&v)[3], int (&q)[3]) {
-    const int n = A.n, nmax = n - 1;
+__device__ __forceinline__ Rgb color16_px(const Color16Launch& A, int vr, int vg, int vb) {
+    const int n = A.lut_size, nmax = n - 1;
+    const int v[3] = {vr, vg, vb};
     Cell c[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -479,81 +469,59 @@ __device__ __forceinline__ void color16_px(const Color16Args& A, const int (&v)[
     const float xs[3] = {stage3(n000.x, n001.x, n010.x, n011.x, n100.x, n101.x, n110.x, n111.x),
                          stage3(n000.y, n001.y, n010.y, n011.y, n100.y, n101.y, n110.y, n111.y),
                          stage3(n000.z, n001.z, n010.z, n011.z, n100.z, n101.z, n110.z, n111.z)};
-    levels16_of(A, xs, q);
+    return levels16_of(A, xs);
+}
+
+template <int C>
+__device__ __forceinline__ void color16_pixel_step(const Color16Launch& A, int y, int x) {
+    pixel_step<C, uint16_t>(A.img, y, x, [&](int r, int g, int b) { return color16_px(A, r, g, b); });
 }
 
 // Any alignment: one thread per pixel, 16-bit loads and stores.
 template <int C>
-__global__ __launch_bounds__(kColorThreads) void color_lut_u16_kernel(Color16Args A) {
+__global__ __launch_bounds__(kColorThreads) void color_lut_u16_kernel(Color16Launch A) {
     const int x = blockIdx.x * kColorThreads + threadIdx.x;
-    if (x >= A.W) return;
-    const uint16_t* sp = reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(A.src) + (int64_t)blockIdx.y * A.src_stride) + (int64_t)x * C;
-    uint16_t* dp = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(A.dst) + (int64_t)blockIdx.y * A.dst_stride) + (int64_t)x * C;
-    const int iR = A.red, iB = 2 - A.red;
-    const int v[3] = {sp[iR], sp[1], sp[iB]};
-    const int alpha = (C == 4) ? sp[3] : 0;
-    int q[3];
-    color16_px(A, v, q);
-    dp[iR] = (uint16_t)q[0]; dp[1] = (uint16_t)q[1]; dp[iB] = (uint16_t)q[2];
-    if (C == 4) dp[3] = (uint16_t)alpha;
+    if (x < A.img.W) color16_pixel_step<C>(A, blockIdx.y, x);
 }
 
 // Rows that start on a dword boundary: one thread per two pixels = C dwords in, C dwords out (the texture path is what bounds this
 // kernel -- 16-bit accesses cost an instruction each, like dwords)
 template <int C>
-__global__ __launch_bounds__(kColorThreads) void color_lut_u16_pair_kernel(Color16Args A) {
-    const int x = (blockIdx.x * kColorThreads + threadIdx.x) * 2;
-    if (x >= A.W) return;
-    const uint8_t* srow = reinterpret_cast<const uint8_t*>(A.src) + (int64_t)blockIdx.y * A.src_stride;
-    uint8_t* drow = reinterpret_cast<uint8_t*>(A.dst) + (int64_t)blockIdx.y * A.dst_stride;
-    const int iR = A.red, iB = 2 - A.red;
-    if (x + 2 > A.W) {                                  // the last pixel of an odd-width row
-        const uint16_t* sp = reinterpret_cast<const uint16_t*>(srow) + (int64_t)x * C;
-        uint16_t* dp = reinterpret_cast<uint16_t*>(drow) + (int64_t)x * C;
-        const int v[3] = {sp[iR], sp[1], sp[iB]};
-        const int alpha = (C == 4) ? sp[3] : 0;
-        int q[3];
-        color16_px(A, v, q);
-        dp[iR] = (uint16_t)q[0]; dp[1] = (uint16_t)q[1]; dp[iB] = (uint16_t)q[2];
-        if (C == 4) dp[3] = (uint16_t)alpha;
+__global__ __launch_bounds__(kColorThreads) void color_lut_u16_pair_kernel(Color16Launch A) {
+    const ColorImage& I = A.img;
+    const int x = (blockIdx.x * kColorThreads + threadIdx.x) * 2, y = blockIdx.y;
+    if (x >= I.W) return;
+    if (x + 2 > I.W) {                                  // the last pixel of an odd-width row
+        color16_pixel_step<C>(A, y, x);
         return;
     }
-    uint32_t w[C];
+    const bool bgr = I.red_index != 0;
+    uint32_t w[C], o[C];
 #pragma unroll
-    for (int i = 0; i < C; ++i) w[i] = reinterpret_cast<const uint32_t*>(srow + (int64_t)x * C * 2)[i];
-    auto sample = [&](int i) { return (int)((w[i >> 1] >> (16 * (i & 1))) & 0xffffu); };   // 16-bit sample i of the pair
-    uint32_t o[C];
+    for (int i = 0; i < C; ++i) w[i] = ((const uint32_t*)pixel_at<C, const uint16_t>(I.src, I.src_stride, y, x))[i];
+    group_keep_alpha<C, 16>(w, o);                      // alpha: the high half of dwords 1 and 3
 #pragma unroll
-    for (int i = 0; i < C; ++i) o[i] = 0u;
-#pragma unroll
-    for (int px = 0; px < 2; ++px) {
-        const int m[3] = {sample(px * C), sample(px * C + 1), sample(px * C + 2)};          // memory order
-        const int v[3] = {iR == 0 ? m[0] : m[2], m[1], iR == 0 ? m[2] : m[0]};
-        int q[3];
-        color16_px(A, v, q);
-        const int out3[3] = {iR == 0 ? q[0] : q[2], q[1], iR == 0 ? q[2] : q[0]};
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const int i = px * C + ch;
-            o[i >> 1] |= (uint32_t)out3[ch] << (16 * (i & 1));
-        }
-        if (C == 4) o[(px * C + 3) >> 1] |= w[(px * C + 3) >> 1] & 0xffff0000u;             // alpha: the high half of dwords 1 and 3
+    for (int p = 0; p < 2; ++p) {
+        const Rgb v = group_px<C, 16>(w, p, bgr);
+        group_put<C, 16>(o, p, bgr, color16_px(A, v.r, v.g, v.b));
     }
 #pragma unroll
-    for (int i = 0; i < C; ++i) reinterpret_cast<uint32_t*>(drow + (int64_t)x * C * 2)[i] = o[i];
+    for (int i = 0; i < C; ++i) ((uint32_t*)pixel_at<C, uint16_t>(I.dst, I.dst_stride, y, x))[i] = o[i];
 }
 
-template <int C, int FIX>
-void launch_variant(const ColorArgs& A, bool aligned, hipStream_t s) {
-    if (aligned) {
-        const long total = (long)((A.W + 4 * kColorThreads - 1) / (4 * kColorThreads)) * A.H;
-        dim3 grid((unsigned)(total < kColorBlocks ? total : kColorBlocks));
-        hipLaunchKernelGGL((color_lut_quad_kernel<C, FIX>), grid, dim3(kColorThreads), 0, s, A);
-    } else {
-        dim3 grid((unsigned)((A.W + kColorThreads - 1) / kColorThreads), (unsigned)A.H);
-        hipLaunchKernelGGL((color_lut_bytes_kernel<C, FIX>), grid, dim3(kColorThreads), 0, s, A);
-    }
+// ---- launches -----------------------------------------------------------------------------------------------------------------------
+// the dword kernels need every row of both sides to start on a dword boundary
+bool dword_aligned(const ColorImage& I) {
+    return (((uintptr_t)I.src | (uintptr_t)I.dst | (uint64_t)I.src_stride | (uint64_t)I.dst_stride) & 3u) == 0;
 }
+
+// one block row per image row, `per_block` pixels of it per block
+dim3 row_grid(const ColorImage& I, int per_block) { return dim3((unsigned)((I.W + per_block - 1) / per_block), (unsigned)I.H); }
+
+// f(std::integral_constant) for the channel count (3 or 4) / the quantiser variant (color_build_bins: 1, 2 or 0) as a template argument
+template <int N> using Int = std::integral_constant<int, N>;
+template <typename F> void with_channels(int C, F f) { if (C == 3) f(Int<3>{}); else f(Int<4>{}); }
+template <typename F> void with_fixups(int fixups, F f) { if (fixups == 1) f(Int<1>{}); else if (fixups == 2) f(Int<2>{}); else f(Int<0>{}); }
 
 }  // namespace
 
@@ -589,15 +557,9 @@ void color16_build_bins(int n_pieces, const float* start, const int32_t* off, co
         int p = 0;
         for (int q = 1; q < n_pieces; ++q)
             if (edge >= start[q]) p = q;
-        const float* lo = thr + off[p];
-        const float* const end = thr + off[p + 1];
-        const float* hi = end;
-        while (lo < hi) {                                                // upper bound: first threshold > edge
-            const float* mid = lo + (hi - lo) / 2;
-            if (*mid <= edge) lo = mid + 1; else hi = mid;
-        }
-        bins[b].kp = ((uint32_t)p << 28) | (uint32_t)(lo - thr);
-        for (int j = 0; j < 3; ++j) bins[b].t[j] = lo + j < end ? lo[j] : __builtin_inff();
+        const int k = off[p] + count_le(thr + off[p], off[p + 1] - off[p], edge);   // the first threshold > edge
+        bins[b].kp = ((uint32_t)p << 28) | (uint32_t)k;
+        for (int j = 0; j < 3; ++j) bins[b].t[j] = k + j < off[p + 1] ? thr[k + j] : __builtin_inff();
     }
 }
 
@@ -610,71 +572,43 @@ hipError_t build_color_rtab(const float* d_lut, const float* d_pos_r, void* d_rt
 size_t color_cube_bytes() { return ((size_t)1 << 24) * sizeof(uint32_t); }
 
 hipError_t build_color_cube(const ColorLaunch& L, void* d_cube, hipStream_t s) {
-    ColorArgs A;
-    A.src = nullptr; A.dst = nullptr; A.rtab = (const CellEntry*)L.rtab; A.tables = L.tables;
-    A.H = 0; A.W = 0; A.n = L.lut_size; A.red = 0; A.src_stride = 0; A.dst_stride = 0;
-    const dim3 grid(kColorBlocks), block(kColorThreads);
-    if (L.fixups == 1) hipLaunchKernelGGL((color_cube_kernel<1>), grid, block, 0, s, A, (uint32_t*)d_cube);
-    else if (L.fixups == 2) hipLaunchKernelGGL((color_cube_kernel<2>), grid, block, 0, s, A, (uint32_t*)d_cube);
-    else hipLaunchKernelGGL((color_cube_kernel<0>), grid, block, 0, s, A, (uint32_t*)d_cube);
-    return hipGetLastError();
-}
-
-static hipError_t launch_color_cube(const ColorLaunch& L, int C, hipStream_t s) {
-    CubeArgs A;
-    A.src = L.src; A.dst = L.dst; A.cube = (const uint32_t*)L.cube; A.H = L.H; A.W = L.W; A.red = L.red_index;
-    A.src_stride = L.src_stride; A.dst_stride = L.dst_stride;
-    const bool aligned = (((uintptr_t)L.src | (uintptr_t)L.dst | (uint64_t)L.src_stride | (uint64_t)L.dst_stride) & 3u) == 0;
-    if (aligned) {
-        const int per_block = 4 * kCubeQuads * kColorThreads;
-        const dim3 grid((unsigned)((L.W + per_block - 1) / per_block), (unsigned)L.H);
-        if (C == 3) hipLaunchKernelGGL((color_cube_quad_kernel<3>), grid, dim3(kColorThreads), 0, s, A);
-        else hipLaunchKernelGGL((color_cube_quad_kernel<4>), grid, dim3(kColorThreads), 0, s, A);
-    } else {
-        const dim3 grid((unsigned)((L.W + kColorThreads - 1) / kColorThreads), (unsigned)L.H);
-        if (C == 3) hipLaunchKernelGGL((color_cube_bytes_kernel<3>), grid, dim3(kColorThreads), 0, s, A);
-        else hipLaunchKernelGGL((color_cube_bytes_kernel<4>), grid, dim3(kColorThreads), 0, s, A);
-    }
+    with_fixups(L.fixups, [&](auto fix) {
+        hipLaunchKernelGGL((color_cube_kernel<decltype(fix)::value>), dim3(kColorBlocks), dim3(kColorThreads), 0, s, L, (uint32_t*)d_cube);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_color16(const Color16Launch& L, int C, hipStream_t s) {
-    Color16Args A;
-    A.src = (const uint16_t*)L.src; A.dst = (uint16_t*)L.dst; A.lut = L.lut; A.thr = L.thr; A.bins = L.bins;
-    for (int k = 0; k < 3; ++k) { A.dmin[k] = L.dmin[k]; A.span[k] = L.span[k]; }
-    for (int k = 0; k < 4; ++k) { A.start[k] = L.start[k]; A.base[k] = L.base[k]; }
-    for (int k = 0; k < 5; ++k) A.off[k] = L.off[k];
-    A.n_pieces = L.n_pieces; A.H = L.H; A.W = L.W; A.n = L.lut_size; A.red = L.red_index;
-    A.src_stride = L.src_stride; A.dst_stride = L.dst_stride;
-    const bool aligned = (((uintptr_t)L.src | (uintptr_t)L.dst | (uint64_t)L.src_stride | (uint64_t)L.dst_stride) & 3u) == 0;
-    if (aligned) {
-        dim3 grid((unsigned)(((L.W + 1) / 2 + kColorThreads - 1) / kColorThreads), (unsigned)L.H);
-        if (C == 3) hipLaunchKernelGGL((color_lut_u16_pair_kernel<3>), grid, dim3(kColorThreads), 0, s, A);
-        else hipLaunchKernelGGL((color_lut_u16_pair_kernel<4>), grid, dim3(kColorThreads), 0, s, A);
-    } else {
-        dim3 grid((unsigned)((L.W + kColorThreads - 1) / kColorThreads), (unsigned)L.H);
-        if (C == 3) hipLaunchKernelGGL((color_lut_u16_kernel<3>), grid, dim3(kColorThreads), 0, s, A);
-        else hipLaunchKernelGGL((color_lut_u16_kernel<4>), grid, dim3(kColorThreads), 0, s, A);
-    }
+    const bool aligned = dword_aligned(L.img);
+    with_channels(C, [&](auto c) {
+        constexpr int Cn = decltype(c)::value;
+        if (aligned) hipLaunchKernelGGL((color_lut_u16_pair_kernel<Cn>), row_grid(L.img, 2 * kColorThreads), dim3(kColorThreads), 0, s, L);
+        else hipLaunchKernelGGL((color_lut_u16_kernel<Cn>), row_grid(L.img, kColorThreads), dim3(kColorThreads), 0, s, L);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_color(const ColorLaunch& L, int C, hipStream_t s) {
-    if (L.cube) return launch_color_cube(L, C, s);
-    ColorArgs A;
-    A.src = L.src; A.dst = L.dst; A.rtab = (const CellEntry*)L.rtab; A.tables = L.tables;
-    A.H = L.H; A.W = L.W; A.n = L.lut_size; A.red = L.red_index;
-    A.src_stride = L.src_stride; A.dst_stride = L.dst_stride;
-    const bool aligned = (((uintptr_t)L.src | (uintptr_t)L.dst | (uint64_t)L.src_stride | (uint64_t)L.dst_stride) & 3u) == 0;
-    if (C == 3) {
-        if (L.fixups == 1) launch_variant<3, 1>(A, aligned, s);
-        else if (L.fixups == 2) launch_variant<3, 2>(A, aligned, s);
-        else launch_variant<3, 0>(A, aligned, s);
-    } else {
-        if (L.fixups == 1) launch_variant<4, 1>(A, aligned, s);
-        else if (L.fixups == 2) launch_variant<4, 2>(A, aligned, s);
-        else launch_variant<4, 0>(A, aligned, s);
-    }
+    const ColorImage& I = L.img;
+    const bool aligned = dword_aligned(I);
+    const dim3 block(kColorThreads);
+    with_channels(C, [&](auto c) {
+        constexpr int Cn = decltype(c)::value;
+        if (L.cube) {
+            if (aligned) hipLaunchKernelGGL((color_cube_quad_kernel<Cn>), row_grid(I, 4 * kCubeQuads * kColorThreads), block, 0, s, L);
+            else hipLaunchKernelGGL((color_cube_bytes_kernel<Cn>), row_grid(I, kColorThreads), block, 0, s, L);
+            return;
+        }
+        with_fixups(L.fixups, [&](auto fix) {
+            constexpr int FIX = decltype(fix)::value;
+            if (aligned) {                       // persistent blocks over the 1024-pixel row segments
+                const long total = (long)row_grid(I, 4 * kColorThreads).x * I.H;
+                hipLaunchKernelGGL((color_lut_quad_kernel<Cn, FIX>), dim3((unsigned)(total < kColorBlocks ? total : kColorBlocks)), block, 0, s, L);
+            } else {
+                hipLaunchKernelGGL((color_lut_bytes_kernel<Cn, FIX>), row_grid(I, kColorThreads), block, 0, s, L);
+            }
+        });
+    });
     return hipGetLastError();
 }
 

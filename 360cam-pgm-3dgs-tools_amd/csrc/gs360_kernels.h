@@ -140,27 +140,27 @@ struct FeBatch {           // kernel argument: all views of one launch + the com
 // ------------------------------------------------------------------------------------------------
 // input colour stage (gs360_color.hip): DF:684-725 for 8-bit images
 // ------------------------------------------------------------------------------------------------
+struct ColorImage {        // the image of one apply call, 8- or 16-bit samples; the launch records below are the kernels' arguments
+    const void* src; void* dst;
+    int32_t H, W, red_index;           // red_index: memory index of the red channel (0 or 2)
+    int64_t src_stride, dst_stride;     // bytes
+};
 struct ColorLaunch {
-    const uint8_t* src;
-    uint8_t* dst;
+    ColorImage img;
     const void* rtab;       // device float3[n*n*256]: LUT pre-interpolated along red for every red level
     const float* tables;    // device: level positions R,G,B x 256, 256 output thresholds, packed bin levels
     const void* cube;       // device uint32[2^24]: the stage evaluated for every 8-bit pixel (NULL: evaluate per pixel from rtab / tables)
-    int32_t H, W, lut_size, red_index;
-    int32_t fixups;         // 1 or 2 in-bin threshold compares, 0 = binary search (color_build_bins)
-    int64_t src_stride, dst_stride;
+    int32_t lut_size, fixups;           // fixups: 1 or 2 in-bin threshold compares, 0 = binary search (color_build_bins)
 };
 struct Color16Launch {     // 16-bit images: everything per pixel, output thresholds in monotone pieces (gs360_color.hip)
-    const void* src;
-    void* dst;
+    ColorImage img;
     const float* lut;       // device [b][g][r][3]
-    const float* thr;       // device, concatenated pieces
+    const float* thr;       // device, concatenated pieces (sorted within a piece)
     const void* bins;       // device, color16_bins_bytes() (color16_build_bins); unused when n_pieces == 0
     float dmin[3], span[3];
-    float start[4];
+    float start[4];         // piece lower bounds (start[0] unused)
     int32_t base[4], off[5];
-    int32_t n_pieces, H, W, lut_size, red_index;
-    int64_t src_stride, dst_stride;
+    int32_t n_pieces, lut_size;         // n_pieces 0: passthrough
 };
 hipError_t launch_color16(const Color16Launch& L, int C, hipStream_t s);
 size_t color16_bins_bytes();

@@ -570,12 +570,17 @@ class Context:
                                              1 if mask_outside else 0, int(mask_value), dp, 0, vo, slot), self.L)
 
     # -- input colour stage ------------------------------------------------------------------
-    def color_plan(self, lut_table, level_pos, out_thresholds):
-        """lut_table: float32 [n][n][n][3] ([b][g][r], .cube order); level_pos: float32 [3][256]; out_thresholds:
-        float32 [256] (entry 0 unused).  Returns an opaque plan handle (free with color_plan_free)."""
+    @staticmethod
+    def _color_lut(lut_table):
         lut = np.ascontiguousarray(lut_table, dtype=np.float32)
         if lut.ndim != 4 or lut.shape[3] != 3 or not (lut.shape[0] == lut.shape[1] == lut.shape[2]):
             raise ValueError("lut_table must be [n][n][n][3]")
+        return lut
+
+    def color_plan(self, lut_table, level_pos, out_thresholds):
+        """lut_table: float32 [n][n][n][3] ([b][g][r], .cube order); level_pos: float32 [3][256]; out_thresholds:
+        float32 [256] (entry 0 unused).  Returns an opaque plan handle (free with color_plan_free)."""
+        lut = self._color_lut(lut_table)
         pos = np.ascontiguousarray(level_pos, dtype=np.float32)
         thr = np.ascontiguousarray(out_thresholds, dtype=np.float32)
         if pos.shape != (3, 256) or thr.shape != (256,):
@@ -591,9 +596,7 @@ class Context:
 
     def color_plan16(self, lut_table, domain_min, domain_max, n_pieces, start, base, off, thresholds):
         """16-bit colour plan (include/gs360.h): LUT + domain + the piecewise output thresholds of gs360.color.output_pieces16."""
-        lut = np.ascontiguousarray(lut_table, dtype=np.float32)
-        if lut.ndim != 4 or lut.shape[3] != 3 or not (lut.shape[0] == lut.shape[1] == lut.shape[2]):
-            raise ValueError("lut_table must be [n][n][n][3]")
+        lut = self._color_lut(lut_table)
         dmin = np.ascontiguousarray(domain_min, dtype=np.float32)
         dmax = np.ascontiguousarray(domain_max, dtype=np.float32)
         st = np.ascontiguousarray(start, dtype=np.float32)
@@ -612,14 +615,15 @@ class Context:
         if plan:
             _check(self.L.gs360_color_plan16_destroy(self.handle, plan), self.L)
 
+    def _color_apply(self, fn, plan, src, H, W, Cn, dst, red_index, src_stride, dst_stride, slot):
+        _check(fn(self.handle, plan, src.ptr, H, W, Cn, src_stride, red_index, (dst or src).ptr, dst_stride, slot), self.L)
+
     def color_apply16_dev(self, plan, src, H, W, Cn, dst=None, red_index=0, src_stride=0, dst_stride=0, slot=0):
-        _check(self.L.gs360_color_apply_u16(self.handle, plan, src.ptr, H, W, Cn, src_stride, red_index,
-                                            (dst or src).ptr, dst_stride, slot), self.L)
+        self._color_apply(self.L.gs360_color_apply_u16, plan, src, H, W, Cn, dst, red_index, src_stride, dst_stride, slot)
 
     def color_apply_dev(self, plan, src, H, W, Cn, dst=None, red_index=0, src_stride=0, dst_stride=0, slot=0):
         """Apply a colour plan to a device-resident H x W x C image (in place when dst is None)."""
-        _check(self.L.gs360_color_apply_u8(self.handle, plan, src.ptr, H, W, Cn, src_stride, red_index,
-                                           (dst or src).ptr, dst_stride, slot), self.L)
+        self._color_apply(self.L.gs360_color_apply_u8, plan, src, H, W, Cn, dst, red_index, src_stride, dst_stride, slot)
 
     # -- frame sharpness statistics (gs360/framescore.py) -------------------------------------
     def frame_stats_dev(self, frames, H, W, Cn, band, stats, flags=0, smalls=None, small_w=0, small_h=0, red_index=0, stride=0, slot=0):

@@ -233,26 +233,26 @@ class ColorStage:
         self.space = normalize_lut_output_color_space(output_space)
         self.level_pos = level_positions(lut)
         self.thresholds = output_thresholds(self.space)
-        self._plans: Dict[object, object] = {}      # Context -> plan handle (the key keeps the context object alive)
-        self._plans16: Dict[object, object] = {}    # the 16-bit plans (built on first use: their table takes a second)
-        self._pieces16 = None
+        self._plans: Dict[object, object] = {}      # (Context, 16-bit?) -> plan handle (the key keeps the context object alive)
+        self._pieces16 = None                       # the 16-bit quantiser, built on first use: its table takes a second
         self._lock = threading.Lock()
 
-    def _plan(self, ctx):
+    def _cached_plan(self, ctx, wide, create):
         with self._lock:
-            plan = self._plans.get(ctx)
+            plan = self._plans.get((ctx, wide))
             if plan is None:
-                plan = self._plans[ctx] = ctx.color_plan(self.lut.table, self.level_pos, self.thresholds)
+                plan = self._plans[ctx, wide] = create()
             return plan
 
+    def _plan(self, ctx):
+        return self._cached_plan(ctx, False, lambda: ctx.color_plan(self.lut.table, self.level_pos, self.thresholds))
+
     def _plan16(self, ctx):
-        with self._lock:
-            plan = self._plans16.get(ctx)
-            if plan is None:
-                if self._pieces16 is None:
-                    self._pieces16 = output_pieces16(self.space)
-                plan = self._plans16[ctx] = ctx.color_plan16(self.lut.table, self.lut.domain_min, self.lut.domain_max, *self._pieces16)
-            return plan
+        def create():
+            if self._pieces16 is None:
+                self._pieces16 = output_pieces16(self.space)
+            return ctx.color_plan16(self.lut.table, self.lut.domain_min, self.lut.domain_max, *self._pieces16)
+        return self._cached_plan(ctx, True, create)
 
     @staticmethod
     def check_image(shape, dtype) -> None:
@@ -285,14 +285,10 @@ class ColorStage:
 
     def close(self) -> None:
         with self._lock:
-            for ctx, plan in self._plans.items():
+            for (ctx, wide), plan in self._plans.items():
                 if ctx.handle:
-                    ctx.color_plan_free(plan)
+                    (ctx.color_plan16_free if wide else ctx.color_plan_free)(plan)
             self._plans.clear()
-            for ctx, plan in self._plans16.items():
-                if ctx.handle:
-                    ctx.color_plan16_free(plan)
-            self._plans16.clear()
 
 
 def make_stage(lut_path, output_space: str = "srgb") -> Optional[ColorStage]:
