@@ -108,9 +108,41 @@ int gs360_tiff_lzw_decode(const uint8_t* in, size_t in_len, uint8_t* out, size_t
 // ---- baseline JPEG scans on the device (JPG-SPEC v1; kernels in gs360_jpeg.hip) ------------------------------------------
 namespace {
 
+// the sides every codec here takes; what: "JPEG sides are" or "the PNG encoder's sides are"
+int check_sides(const char* what, int H, int W) {
+    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(GS360_ERR_ARG, "%s 1..65535 (got %d x %d)", what, W, H);
+    return 0;
+}
+
+// what an encoder's call and each of its jobs have in common (gs360_jpeg_job and gs360_png_job name these fields alike)
+int check_encoder_call(gs360_ctx* c, const void* jobs, int n_jobs, bool outputs, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
+    if (n_jobs > 0 && (!jobs || !outputs)) return fail(GS360_ERR_ARG, "NULL argument");
+    return 0;
+}
+template <class Job>
+int check_encoder_job(const Job& j, int k, size_t row_bytes) {
+    if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
+    if (j.src_stride && j.src_stride < row_bytes) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
+    return 0;
+}
+
+inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// an offset cursor over a slot's scratch: take() -> where the next piece starts, aligned
+struct Carve {
+    size_t at = 0;
+    size_t take(size_t bytes, size_t align = 1) {
+        const size_t start = round_up(at, align);
+        at = start + bytes;
+        return start;
+    }
+};
+
 // the sides and components either codec ("encoder", "decoder") takes
 int check_jpeg_image(const char* codec, int H, int W, int C) {
-    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(GS360_ERR_ARG, "JPEG sides are 1..65535 (got %d x %d)", W, H);
+    if (int rc = check_sides("JPEG sides are", H, W)) return rc;
     if (C != 1 && C != 3) return fail(GS360_ERR_UNSUPPORTED, "the JPEG %s takes C = 1 or 3 (got %d)", codec, C);
     return 0;
 }
@@ -120,8 +152,6 @@ int check_jpeg_geometry(int H, int W, int C, int restart_interval) {
     if (restart_interval < 1 || restart_interval > 65535) return fail(GS360_ERR_ARG, "restart interval %d outside 1..65535", restart_interval);
     return 0;
 }
-
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 int check_jpeg_subsampling(int subsampling) {
     if (subsampling != GS360_JPEG_444 && subsampling != GS360_JPEG_420)
@@ -150,22 +180,35 @@ int gs360_jpeg_scan_bound_sub(int H, int W, int C, int restart_interval, int sub
 
 namespace {
 
+// scratch of a launch batch: coefficients (at 0), the quantiser table, the intervals' lengths and offsets and, with optimal tables, the
+// images' symbol counts and coder tables
+constexpr size_t kJpTableWords = 2 * 272;
+struct JpScratch { size_t quant, int_len, int_off, hist, total; };
+JpScratch jpeg_scratch(int64_t blocks, int64_t intervals, int images, bool optimal) {
+    Carve v;
+    JpScratch a{};
+    v.take((size_t)blocks * 128);
+    a.quant = v.take(128 * sizeof(JpQuant), 256);
+    a.int_len = v.take(round_up((size_t)intervals * 4, 256));
+    a.int_off = v.take((size_t)intervals * 8);
+    if (optimal) a.hist = v.take(2 * (size_t)images * kJpTableWords * sizeof(uint32_t), 256);
+    a.total = v.at;
+    return a;
+}
+
 // gs360_jpeg_scan_sub_u8; gs360_jpeg_scan_u8 (the Annex K tables) and gs360_jpeg_scan_opt_u8 (per-image optimal tables) with
 // GS360_JPEG_444
 int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality, int restart_interval, int subsampling,
               uint64_t* lengths_dev, uint8_t* tables_dev, bool optimal, int slot) {
-    if (int rc = check_ctx_slot(c, slot)) return rc;
-    if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
+    if (int rc = check_encoder_call(c, jobs, n_jobs, lengths_dev && (!optimal || tables_dev), slot)) return rc;
     if (n_jobs == 0) return GS360_OK;
-    if (!jobs || !lengths_dev || (optimal && !tables_dev)) return fail(GS360_ERR_ARG, "NULL argument");
     if (quality < 1 || quality > 100) return fail(GS360_ERR_ARG, "quality %d outside 1..100", quality);
     if (int rc = check_jpeg_subsampling(subsampling)) return rc;
     std::vector<JpGrid> grid(n_jobs);            // each job's MCU grid: checked here, then read by the sizing and the fill
     for (int k = 0; k < n_jobs; ++k) {
         const gs360_jpeg_job& j = jobs[k];
         if (int rc = check_jpeg_geometry(j.H, j.W, j.C, restart_interval)) return rc;
-        if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
-        if (j.src_stride && j.src_stride < (size_t)j.W * j.C) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
+        if (int rc = check_encoder_job(j, k, (size_t)j.W * j.C)) return rc;
         // the table construction's range: counts in uint32 below libjpeg's 10^9 sentinel, code lengths below 64 before limiting
         const JpGrid& g = grid[k] = jpeg_grid(j.H, j.W, j.C, subsampling);
         if (optimal && g.mcus() * g.bpm * 64 >= 1000000000ll)
@@ -174,17 +217,8 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream[slot];
     Staging& st = c->stage[slot];
-    // scratch of a launch batch: coefficients, the quantiser table, the intervals' lengths and offsets and, with optimal tables, the
-    // images' symbol counts and coder tables.  Sized for the call's largest batch before the first launch (growing it later would free
-    // memory that queued kernels still use)
-    constexpr size_t kTableWords = 2 * 272;
-    auto layout = [optimal](int64_t blocks, int64_t intervals, int images, size_t* quant_at, size_t* len_at, size_t* off_at, size_t* hist_at) {
-        *quant_at = round_up((size_t)blocks * 128, 256);
-        *len_at = *quant_at + 128 * sizeof(JpQuant);
-        *off_at = *len_at + round_up((size_t)intervals * 4, 256);
-        *hist_at = round_up(*off_at + (size_t)intervals * 8, 256);
-        return optimal ? *hist_at + 2 * (size_t)images * kTableWords * sizeof(uint32_t) : *off_at + (size_t)intervals * 8;
-    };
+    // the scratch is sized for the call's largest batch before the first launch (growing it later would free memory that queued
+    // kernels still use)
     size_t need = 0;
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
         int64_t blocks = 0, intervals = 0;
@@ -193,8 +227,7 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
             blocks += mcus * grid[k].bpm;
             intervals += (mcus + restart_interval - 1) / restart_interval;
         }
-        size_t a, b, d, e;
-        need = std::max(need, layout(blocks, intervals, std::min(GS360_MAX_VIEWS, n_jobs - k0), &a, &b, &d, &e));
+        need = std::max(need, jpeg_scratch(blocks, intervals, std::min(GS360_MAX_VIEWS, n_jobs - k0), optimal).total);
     }
     if (int rc = ensure(&st.d_jpeg, &st.jpeg_cap, need)) return rc;
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
@@ -227,17 +260,17 @@ int jpeg_scan(gs360_ctx* c, const gs360_jpeg_job* jobs, int n_jobs, int quality,
         if (tiles > INT32_MAX || intervals > INT32_MAX) return fail(GS360_ERR_ARG, "JPEG batch too large");
         L.total_tiles = (int32_t)tiles;
         L.total_int = (int32_t)intervals;
-        size_t quant_at, len_at, off_at, hist_at;
-        if (layout(blocks, intervals, L.n_jobs, &quant_at, &len_at, &off_at, &hist_at) > st.jpeg_cap) return fail(GS360_ERR_ARG, "JPEG scratch layout");
+        const JpScratch at = jpeg_scratch(blocks, intervals, L.n_jobs, optimal);
+        if (at.total > st.jpeg_cap) return fail(GS360_ERR_ARG, "JPEG scratch layout");
         uint8_t* base = (uint8_t*)st.d_jpeg;
         L.coef = (int16_t*)base;
-        L.quant = (JpQuant*)(base + quant_at);
-        L.int_len = (uint32_t*)(base + len_at);
-        L.int_off = (uint64_t*)(base + off_at);
+        L.quant = (JpQuant*)(base + at.quant);
+        L.int_len = (uint32_t*)(base + at.int_len);
+        L.int_off = (uint64_t*)(base + at.int_off);
         L.lengths = lengths_dev + k0;
         if (optimal) {
-            L.hist = (uint32_t*)(base + hist_at);
-            L.huff = L.hist + (size_t)L.n_jobs * kTableWords;
+            L.hist = (uint32_t*)(base + at.hist);
+            L.huff = L.hist + (size_t)L.n_jobs * kJpTableWords;
             L.tables = tables_dev + (size_t)k0 * 4 * GS360_JPEG_TABLE_BYTES;
             L.count_waves = opt(c, kOptJpegCountWaves);
         }
@@ -360,7 +393,7 @@ int gs360_jpeg_decode_gray_u8(gs360_ctx* c, const gs360_jpeg_dec_job* jobs, int 
 namespace {
 
 int check_png_geometry(int H, int W, int C, int bytes_per_sample) {
-    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(GS360_ERR_ARG, "the PNG encoder's sides are 1..65535 (got %d x %d)", W, H);
+    if (int rc = check_sides("the PNG encoder's sides are", H, W)) return rc;
     if (C != 1 && C != 3 && C != 4) return fail(GS360_ERR_UNSUPPORTED, "the PNG encoder takes C = 1, 3 or 4 (got %d)", C);
     if (bytes_per_sample != 1 && bytes_per_sample != 2)
         return fail(GS360_ERR_UNSUPPORTED, "the PNG encoder takes 1 or 2 bytes per sample (got %d)", bytes_per_sample);
@@ -369,6 +402,21 @@ int check_png_geometry(int H, int W, int C, int bytes_per_sample) {
 
 inline size_t png_filtered(int H, int W, int C, int bps) { return (size_t)H * (1 + (size_t)W * C * bps); }
 inline size_t png_chunks(size_t n) { return (n + kPnChunk - 1) / kPnChunk; }
+
+// scratch of a launch batch: the filtered streams (at 0; filt: their bytes, each image's rounded up), then per chunk its length,
+// offset, code tables and segment offsets
+struct PnScratch { size_t chunk_len, chunk_off, codes, seg_off, total; };
+PnScratch png_scratch(size_t filt, size_t chunks) {
+    Carve v;
+    PnScratch a{};
+    v.take(filt + 4);
+    a.chunk_len = v.take(chunks * 4, 256);
+    a.chunk_off = v.take(chunks * 8, 256);
+    a.codes = v.take(chunks * 320 * 4);
+    a.seg_off = v.take(chunks * kPnThreads * 4);
+    a.total = v.at;
+    return a;
+}
 
 }  // namespace
 
@@ -383,38 +431,27 @@ int gs360_png_bound(int H, int W, int C, int bytes_per_sample, size_t* bytes) {
 }
 
 int gs360_png_deflate(gs360_ctx* c, const gs360_png_job* jobs, int n_jobs, uint64_t* lengths_dev, uint32_t* adler_dev, int slot) {
-    if (int rc = check_ctx_slot(c, slot)) return rc;
-    if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
+    if (int rc = check_encoder_call(c, jobs, n_jobs, lengths_dev && adler_dev, slot)) return rc;
     if (n_jobs == 0) return GS360_OK;
-    if (!jobs || !lengths_dev || !adler_dev) return fail(GS360_ERR_ARG, "NULL argument");
     for (int k = 0; k < n_jobs; ++k) {
         const gs360_png_job& j = jobs[k];
         if (int rc = check_png_geometry(j.H, j.W, j.C, j.bytes_per_sample)) return rc;
-        if (!j.src || !j.out) return fail(GS360_ERR_ARG, "job %d: NULL image or output", k);
-        if (j.src_stride && j.src_stride < (size_t)j.W * j.C * j.bytes_per_sample) return fail(GS360_ERR_ARG, "job %d: src_stride below a row", k);
+        if (int rc = check_encoder_job(j, k, (size_t)j.W * j.C * j.bytes_per_sample)) return rc;
         if (j.bytes_per_sample == 2 && (((uintptr_t)j.src | j.src_stride) & 1)) return fail(GS360_ERR_ARG, "job %d: 16-bit rows are not 2-byte aligned", k);
     }
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream[slot];
     Staging& st = c->stage[slot];
-    // scratch of a launch batch, sized for the call's largest batch before the first launch: the filtered streams, then per chunk its
-    // length, offset, code tables and segment offsets
-    auto layout = [](size_t filt, size_t chunks, size_t* len_at, size_t* off_at, size_t* codes_at, size_t* seg_at) {
-        *len_at = round_up(filt + 4, 256);
-        *off_at = round_up(*len_at + chunks * 4, 256);
-        *codes_at = *off_at + chunks * 8;
-        *seg_at = *codes_at + chunks * 320 * 4;
-        return *seg_at + chunks * kPnThreads * 4;
-    };
+    // the scratch is sized for the call's largest batch before the first launch
     size_t need = 0;
     for (int k0 = 0; k0 < n_jobs; k0 += GS360_MAX_VIEWS) {
-        size_t filt = 0, chunks = 0, a, b, d, e;
+        size_t filt = 0, chunks = 0;
         for (int k = k0; k < std::min(n_jobs, k0 + GS360_MAX_VIEWS); ++k) {
             const size_t n = png_filtered(jobs[k].H, jobs[k].W, jobs[k].C, jobs[k].bytes_per_sample);
             filt += round_up(n + 4, 256);
             chunks += png_chunks(n);
         }
-        need = std::max(need, layout(filt, chunks, &a, &b, &d, &e));
+        need = std::max(need, png_scratch(filt, chunks).total);
     }
     if (int rc = ensure(&st.d_png, &st.png_cap, need)) return rc;
     size_t chunks_before = 0;                             // adler_dev: two words per chunk, the jobs' chunks in job order
@@ -457,14 +494,14 @@ int gs360_png_deflate(gs360_ctx* c, const gs360_png_job* jobs, int n_jobs, uint6
         if (rows > INT32_MAX || chunks > INT32_MAX) return fail(GS360_ERR_ARG, "PNG batch too large");
         L.total_rows = (int32_t)rows;
         L.total_chunks = (int32_t)chunks;
-        size_t len_at, off_at, codes_at, seg_at;
-        if (layout(filt, (size_t)chunks, &len_at, &off_at, &codes_at, &seg_at) > st.png_cap) return fail(GS360_ERR_ARG, "PNG scratch layout");
+        const PnScratch at = png_scratch(filt, (size_t)chunks);
+        if (at.total > st.png_cap) return fail(GS360_ERR_ARG, "PNG scratch layout");
         uint8_t* base = (uint8_t*)st.d_png;
         L.filt = base;
-        L.chunk_len = (uint32_t*)(base + len_at);
-        L.chunk_off = (uint64_t*)(base + off_at);
-        L.codes = (uint32_t*)(base + codes_at);
-        L.seg_off = (uint32_t*)(base + seg_at);
+        L.chunk_len = (uint32_t*)(base + at.chunk_len);
+        L.chunk_off = (uint64_t*)(base + at.chunk_off);
+        L.codes = (uint32_t*)(base + at.codes);
+        L.seg_off = (uint32_t*)(base + at.seg_off);
         L.lengths = lengths_dev + k0;
         L.adler = adler_dev + 2 * chunks_before;
         chunks_before += (size_t)chunks;

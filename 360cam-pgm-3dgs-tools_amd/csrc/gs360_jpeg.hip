@@ -23,7 +23,7 @@
 // jp_copy_out) and the entropy and count kernels from the same block walk (JpWalk).
 // No float atomics; the LDS bit buffer is filled with integer ORs and the histograms with integer adds, so nothing depends on the
 // order of the work.
-#include "gs360_kernels.h"
+#include "gs360_codecsteps.h"
 
 namespace gs360 {
 namespace {
@@ -358,17 +358,6 @@ struct JpWalk {
     }
 };
 
-// inclusive sum over the lanes of a wavefront
-template <class T>
-__device__ __forceinline__ T jp_wave_scan(T v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T up = __shfl_up(v, o, 64);
-        if (lane >= o) v += up;
-    }
-    return v;
-}
-
 // One wavefront, one restart interval.  kEmit = false counts the interval's bytes (stuffing and marker included) into int_len;
 // kEmit = true writes them at the image's out + int_off.
 template <bool kEmit>
@@ -422,7 +411,7 @@ __global__ void __launch_bounds__(64) jp_entropy_kernel(const JpLaunch L) {
             str = e >> 5;
             len = (int)(e & 31);
         }
-        const int incl = jp_wave_scan(len, lane);
+        const int incl = wave_scan(len, lane);
         const uint32_t total = carry + (uint32_t)__shfl(incl, 63, 64);            // <= 7 + 64 * 26 bits
         if (len) {
             const uint32_t at = carry + (uint32_t)(incl - len), w0 = at >> 5, sh = at & 31;
@@ -521,23 +510,12 @@ __global__ void __launch_bounds__(64) jp_count_kernel(const JpLaunch L) {
 
 // ---- optimal tables: construction ------------------------------------------------------------------------------------------------
 // T.81 K.2 as libjpeg's jpeg_gen_optimal_table runs it, one wavefront per table, entry e = lane + 64 * k (257 entries: the symbols and
-// the pseudo-symbol 256 with count 1, which reserves the all-ones code).  A merge step takes the two smallest non-zero counts, ties to
-// the LARGEST index (two wave minima of count << 9 | 511 - index), adds the second to the first and lengthens every symbol of both
-// trees: each entry carries its tree's id (the index that holds the tree's count), so the lanes lengthen and relabel their own
-// entries, the same set of symbols libjpeg reaches along its others[] chain.  Lane 0 then limits the lengths to 16 and drops the
+// the pseudo-symbol 256 with count 1, which reserves the all-ones code).  The merges, the fold of the lengths above 16 and the rank are
+// the shared steps of gs360_codecsteps.h (huff_merge, huff_fold_lengths, huff_rank).  Lane 0 limits the lengths to 16 and drops the
 // pseudo-symbol's code; HUFFVAL orders the symbols by unlimited length, then value (a rank every lane counts for its entries), and
 // the codes follow Annex C.
 // hist: per_image ? the count pass's [image][2][272] (block = image * 4 + {DC0, AC0, DC1, AC1}) : [block][256] counts.
 // huff (optional): the coder's (code << 5) | length entries, [image][2][272].  tables: [block][272] = 16 BITS + HUFFVAL, zero padded.
-__device__ __forceinline__ uint64_t jp_wave_min(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t u = __shfl_xor((unsigned long long)v, o, 64);
-        v = u < v ? u : v;
-    }
-    return v;
-}
-
 __global__ void __launch_bounds__(64) jp_tables_kernel(const uint32_t* hist, int per_image, uint32_t* huff, uint8_t* tables) {
     __shared__ uint8_t cs[257];                   // unlimited code lengths (< 64 for counts that sum below 10^9)
     __shared__ int bits[64];
@@ -548,46 +526,18 @@ __global__ void __launch_bounds__(64) jp_tables_kernel(const uint32_t* hist, int
     const uint32_t* src = per_image ? hist + (size_t)(b >> 1) * kJpHuffN + (ac ? 0 : 256) : hist + (size_t)b * 256;
     const int nsrc = per_image && !ac ? 16 : 256;
     uint32_t f[5];
-    int grp[5], len[5];
+    int len[5];
     bool used[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
         const int e = lane + 64 * k;
         f[k] = e < nsrc ? src[e] : (e == 256 ? 1u : 0u);
         used[k] = f[k] != 0;
-        grp[k] = e;
-        len[k] = 0;
     }
     for (int i = lane; i < kJpHuffN; i += 64) out[i] = 0;
     bits[lane] = 0;
     const bool any = __ballot(used[0] || used[1] || used[2] || used[3]) != 0;     // a real symbol with a count
-    for (;;) {
-        uint64_t best = UINT64_MAX;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const uint64_t key = ((uint64_t)f[k] << 9) | (uint64_t)(511 - (lane + 64 * k));
-            if (f[k] && key < best) best = key;
-        }
-        const uint64_t key1 = jp_wave_min(best);
-        const int c1 = 511 - (int)(key1 & 511);
-        best = UINT64_MAX;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int e = lane + 64 * k;
-            const uint64_t key = ((uint64_t)f[k] << 9) | (uint64_t)(511 - e);
-            if (f[k] && e != c1 && key < best) best = key;
-        }
-        const uint64_t key2 = jp_wave_min(best);
-        if (key2 == UINT64_MAX) break;
-        const int c2 = 511 - (int)(key2 & 511);
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int e = lane + 64 * k;
-            if (e == c1) f[k] += (uint32_t)(key2 >> 9);
-            if (e == c2) f[k] = 0;
-            if (used[k] && (grp[k] == c1 || grp[k] == c2)) { ++len[k]; grp[k] = c1; }
-        }
-    }
+    huff_merge(f, used, len, lane);
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
         const int e = lane + 64 * k;
@@ -597,14 +547,7 @@ __global__ void __launch_bounds__(64) jp_tables_kernel(const uint32_t* hist, int
     __syncthreads();
     if (lane == 0 && any) {
         // (the j > 0 and i > 0 guards never bind for counts that sum below 10^9; they keep other input from walking out of bits[])
-        for (int i = 63; i > 16; --i) {
-            while (bits[i] > 0) {
-                int jj = i - 2;
-                while (jj > 0 && bits[jj] == 0) --jj;
-                if (jj == 0) { bits[i] = 0; break; }
-                bits[i] -= 2; bits[i - 1] += 1; bits[jj + 1] += 2; bits[jj] -= 1;
-            }
-        }
+        huff_fold_lengths(bits, 16);
         int i = 16;
         while (i > 0 && bits[i] == 0) --i;
         if (i > 0) bits[i] -= 1;                                                  // the pseudo-symbol's code
@@ -623,11 +566,7 @@ __global__ void __launch_bounds__(64) jp_tables_kernel(const uint32_t* hist, int
         for (int k = 0; k < 4; ++k) {
             const int e = lane + 64 * k, le = len[k];
             if (!le) continue;
-            int rank = 0;
-            for (int s = 0; s < 256; ++s) {
-                const int ls = cs[s];
-                rank += (ls && (ls < le || (ls == le && s < e))) ? 1 : 0;
-            }
+            const int rank = huff_rank(cs, 256, le, e);
             out[16 + rank] = (uint8_t)e;
             mine[k] = word[rank];
         }
@@ -646,28 +585,10 @@ __global__ void __launch_bounds__(64) jp_tables_kernel(const uint32_t* hist, int
 }
 
 // ---- placement: one workgroup per image, exclusive scan of its intervals' lengths -------------------------------------------------
-__global__ void __launch_bounds__(kJpThreads) jp_offsets_kernel(const JpLaunch L) {
-    __shared__ unsigned long long wsum[kJpThreads / 64];
+__global__ void __launch_bounds__(kPlaceThreads) jp_offsets_kernel(const JpLaunch L) {
     const JpJob J = L.job[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long run = 0;
-    for (int i0 = 0; i0 < J.n_int; i0 += kJpThreads) {
-        const int i = i0 + tid;
-        const unsigned long long mine = i < J.n_int ? L.int_len[J.int_base + i] : 0ull;
-        const unsigned long long incl = jp_wave_scan(mine, lane);
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        unsigned long long before = run, all = run;
-#pragma unroll
-        for (int w = 0; w < kJpThreads / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
-        if (i < J.n_int) L.int_off[J.int_base + i] = before + incl - mine;
-        run = all;
-        __syncthreads();
-    }
-    if (tid == 0) L.lengths[blockIdx.x] = run <= J.cap ? run : UINT64_MAX;
+    const unsigned long long run = place_pieces(L.int_len + J.int_base, L.int_off + J.int_base, J.n_int);
+    if (threadIdx.x == 0) L.lengths[blockIdx.x] = run <= J.cap ? run : UINT64_MAX;
 }
 
 }  // namespace
@@ -683,7 +604,7 @@ hipError_t launch_jpeg_scan(const JpLaunch& L, hipStream_t s) {
         hipLaunchKernelGGL(jp_tables_kernel, dim3(L.n_jobs * 4), dim3(64), 0, s, (const uint32_t*)L.hist, 1, L.huff, L.tables);
     }
     hipLaunchKernelGGL(jp_entropy_kernel<false>, dim3(L.total_int), dim3(64), 0, s, L);
-    hipLaunchKernelGGL(jp_offsets_kernel, dim3(L.n_jobs), dim3(kJpThreads), 0, s, L);
+    hipLaunchKernelGGL(jp_offsets_kernel, dim3(L.n_jobs), dim3(kPlaceThreads), 0, s, L);
     hipLaunchKernelGGL(jp_entropy_kernel<true>, dim3(L.total_int), dim3(64), 0, s, L);
     return hipGetLastError();
 }

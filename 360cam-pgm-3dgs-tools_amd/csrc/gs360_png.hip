@@ -9,13 +9,13 @@
 //   parse      one workgroup per chunk of 64 KiB, the chunk in LDS (a pad dword per segment keeps the lanes on their own banks), one
 //              lane per segment of 512 bytes: a greedy walk over the three candidate distances (1, bpp, 1 + W * bpp) adds to the
 //              chunk's literal/length and distance histograms and to its Adler-32 partial sums; wavefront 0 and 1 build the two
-//              code tables (Huffman's merges as jp_tables_kernel runs them, lengths limited to 15); the walk runs again for the
+//              code tables (the Huffman steps jp_tables_kernel takes, gs360_codecsteps.h, lengths limited to 15); the walk runs again for the
 //              segments' bit counts, whose exclusive scan places them
 //   placement  one workgroup per image: exclusive scan of the chunks' byte lengths, the stream's length (UINT64_MAX past the capacity)
 //   emit       the parse kernel's walk a third time, writing: each lane owns the bytes that begin inside its segment's bits, stores them
 //              as bytes and completes its last one from the leading bits the lanes behind it publish in LDS
 // The walk is repeated instead of stored: a symbol list would take twice the filtered stream in device memory, the walk reads LDS only.
-#include "gs360_kernels.h"
+#include "gs360_codecsteps.h"
 
 namespace gs360 {
 namespace {
@@ -143,29 +143,12 @@ __device__ __forceinline__ void pn_len_code(int len, int& sym, int& eb, int& ev)
     sym = 257 + 4 * (eb + 1) + ((l >> eb) & 3);
     ev = l & ((1 << eb) - 1);
 }
-template <class T>
-__device__ __forceinline__ T pn_wave_scan(T v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T up = __shfl_up(v, o, 64);
-        if (lane >= o) v += up;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t pn_wave_min(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t u = __shfl_xor((unsigned long long)v, o, 64);
-        v = u < v ? u : v;
-    }
-    return v;
-}
 
 // ---- parse: histograms, code tables, bit counts ---------------------------------------------------------------------------------------
-// Code lengths of one alphabet by one wavefront, entry e = lane + 64 * k: Huffman's merges as jp_tables_kernel runs them (the two
-// smallest counts, ties to the LARGEST index, the sum staying at the smaller one's entry; every entry carries its tree's id and
-// lengthens itself), the counts of lengths above 15 folded down by T.81 K.3's procedure, the final lengths handed out in order of
-// (unlimited length, symbol).  An alphabet with no symbol used gives symbol 0 one bit, with one symbol used that symbol one bit.
+// Code lengths of one alphabet by one wavefront, entry e = lane + 64 * k, from the steps jp_tables_kernel takes as well
+// (gs360_codecsteps.h): Huffman's merges (huff_merge), the counts of lengths above 15 folded down by T.81 K.3's procedure
+// (huff_fold_lengths), the final lengths handed out in order of (unlimited length, symbol) (huff_rank).  An alphabet with no symbol
+// used gives symbol 0 one bit, with one symbol used that symbol one bit.
 // The codes are RFC 1951's canonical ones, kept bit-reversed (the stream is LSB-first) as (code << 5) | length.
 struct PnTableLds {
     uint8_t cs[2][320], lim[2][320];
@@ -175,7 +158,7 @@ __device__ __forceinline__ void pn_build_tables(PnTableLds& T, const uint32_t* h
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = wave ? kPnDist : kPnLitLen, at = wave ? kPnLitLen : 0;
     uint32_t f[5];
-    int grp[5], len[5];
+    int len[5];
     bool used[5];
     int nused = 0;
 #pragma unroll
@@ -184,37 +167,9 @@ __device__ __forceinline__ void pn_build_tables(PnTableLds& T, const uint32_t* h
         f[k] = e < n ? hist[at + e] : 0u;
         used[k] = f[k] != 0;
         nused += __popcll(__ballot(used[k]));
-        grp[k] = e;
-        len[k] = 0;
     }
     T.bits[wave][lane] = 0;
-    for (;;) {
-        uint64_t best = UINT64_MAX;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const uint64_t key = ((uint64_t)f[k] << 9) | (uint64_t)(511 - (lane + 64 * k));
-            if (f[k] && key < best) best = key;
-        }
-        const uint64_t key1 = pn_wave_min(best);
-        const int c1 = 511 - (int)(key1 & 511);
-        best = UINT64_MAX;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int e = lane + 64 * k;
-            const uint64_t key = ((uint64_t)f[k] << 9) | (uint64_t)(511 - e);
-            if (f[k] && e != c1 && key < best) best = key;
-        }
-        const uint64_t key2 = pn_wave_min(best);
-        if (key2 == UINT64_MAX) break;
-        const int c2 = 511 - (int)(key2 & 511);
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int e = lane + 64 * k;
-            if (e == c1) f[k] += (uint32_t)(key2 >> 9);
-            if (e == c2) f[k] = 0;
-            if (used[k] && (grp[k] == c1 || grp[k] == c2)) { ++len[k]; grp[k] = c1; }
-        }
-    }
+    huff_merge(f, used, len, lane);
     __syncthreads();                                                              // bits[] zeroed
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
@@ -223,16 +178,8 @@ __device__ __forceinline__ void pn_build_tables(PnTableLds& T, const uint32_t* h
     }
     __syncthreads();
     if (lane == 0) {
-        int* bits = T.bits[wave];
-        // (the j > 0 guard never binds for a complete code; it keeps other input from walking out of bits[])
-        for (int i = 63; i > 15; --i) {
-            while (bits[i] > 0) {
-                int j = i - 2;
-                while (j > 0 && bits[j] == 0) --j;
-                if (j == 0) { bits[i] = 0; break; }
-                bits[i] -= 2; bits[i - 1] += 1; bits[j + 1] += 2; bits[j] -= 1;
-            }
-        }
+        // (its j > 0 guard never binds for a complete code; it keeps other input from walking out of bits[])
+        huff_fold_lengths(T.bits[wave], 15);
     }
     __syncthreads();
 #pragma unroll
@@ -242,11 +189,7 @@ __device__ __forceinline__ void pn_build_tables(PnTableLds& T, const uint32_t* h
         if (nused < 2) {
             l = (nused ? used[k] : e == 0) ? 1 : 0;
         } else if (le) {
-            int rank = 0;
-            for (int s = 0; s < n; ++s) {
-                const int ls = T.cs[wave][s];
-                rank += (ls && (ls < le || (ls == le && s < e))) ? 1 : 0;
-            }
+            int rank = huff_rank(T.cs[wave], n, le, e);
             l = 1;
             while (l < 15 && rank >= T.bits[wave][l]) { rank -= T.bits[wave][l]; ++l; }
         }
@@ -327,7 +270,7 @@ __global__ void __launch_bounds__(kPnThreads) pn_parse_kernel(const PnLaunch L) 
             q += s.len;
         }
     }
-    const uint32_t incl = pn_wave_scan(nbits, lane);
+    const uint32_t incl = wave_scan(nbits, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     const size_t chunk = blockIdx.x;
@@ -343,28 +286,10 @@ __global__ void __launch_bounds__(kPnThreads) pn_parse_kernel(const PnLaunch L) 
 }
 
 // ---- placement: one workgroup per image, exclusive scan of its chunks' lengths ------------------------------------------------------
-__global__ void __launch_bounds__(256) pn_offsets_kernel(const PnLaunch L) {
-    __shared__ unsigned long long wsum[4];
+__global__ void __launch_bounds__(kPlaceThreads) pn_offsets_kernel(const PnLaunch L) {
     const PnJob J = L.job[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long run = 0;
-    for (int i0 = 0; i0 < J.n_chunks; i0 += 256) {
-        const int i = i0 + tid;
-        const unsigned long long mine = i < J.n_chunks ? L.chunk_len[J.chunk_base + i] : 0ull;
-        const unsigned long long incl = pn_wave_scan(mine, lane);
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        unsigned long long before = run, all = run;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
-        if (i < J.n_chunks) L.chunk_off[J.chunk_base + i] = before + incl - mine;
-        run = all;
-        __syncthreads();
-    }
-    if (tid == 0) L.lengths[blockIdx.x] = run <= J.cap ? run : UINT64_MAX;
+    const unsigned long long run = place_pieces(L.chunk_len + J.chunk_base, L.chunk_off + J.chunk_base, J.n_chunks);
+    if (threadIdx.x == 0) L.lengths[blockIdx.x] = run <= J.cap ? run : UINT64_MAX;
 }
 
 // ---- emit -----------------------------------------------------------------------------------------------------------------------
@@ -480,7 +405,7 @@ __global__ void __launch_bounds__(kPnThreads) pn_emit_kernel(const PnLaunch L) {
 hipError_t launch_png_deflate(const PnLaunch& L, hipStream_t s) {
     hipLaunchKernelGGL(pn_filter_kernel, dim3(L.total_rows), dim3(kPnFilterThreads), 0, s, L);
     hipLaunchKernelGGL(pn_parse_kernel, dim3(L.total_chunks), dim3(kPnThreads), 0, s, L);
-    hipLaunchKernelGGL(pn_offsets_kernel, dim3(L.n_jobs), dim3(256), 0, s, L);
+    hipLaunchKernelGGL(pn_offsets_kernel, dim3(L.n_jobs), dim3(kPlaceThreads), 0, s, L);
     hipLaunchKernelGGL(pn_emit_kernel, dim3(L.total_chunks), dim3(kPnThreads), 0, s, L);
     return hipGetLastError();
 }

@@ -665,17 +665,32 @@ class Context:
                                           len(pairs), out.ptr, points.ptr if points is not None else None, slot), self.L)
 
     # -- JPEG scans of device images (gs360/jpegenc.py) ---------------------------------------
+    @staticmethod
+    def _encoder_jobs(struct, jobs, fill):
+        """The job array of an encoder call: the out_capacity check (a job ends with its out buffer and out_capacity) and
+        fill(*job) -> the job's struct, per codec."""
+        arr = (struct * max(len(jobs), 1))()
+        for k, job in enumerate(jobs):
+            if job[-1] > job[-2].nbytes:
+                raise ValueError("out_capacity larger than the output buffer")
+            arr[k] = fill(*job)
+        return arr
+
+    @staticmethod
+    def _jpeg_job(src, H, W, Cn, stride, out, cap):
+        return JpegJob(src.ptr, int(H), int(W), int(Cn), int(stride), out.ptr, int(cap))
+
+    @staticmethod
+    def _png_job(src, H, W, Cn, bps, stride, out, cap):
+        return PngJob(src.ptr if isinstance(src, DeviceBuffer) else int(src), int(H), int(W), int(Cn), int(bps), int(stride), out.ptr, int(cap))
+
     def _jpeg_scan(self, fn, jobs, head, lengths, tables, slot):
         """What the three scan entry points share: the tables buffer's size check, the job array and the call.  head = (quality,
         restart[, subsampling]); tables = (DeviceBuffer or None,), or () for the entry point without the argument."""
         for t in tables:
             if t is not None and t.nbytes < 4 * JPEG_TABLE_BYTES * len(jobs):
                 raise ValueError("tables buffer below 4 x 272 bytes per job")
-        arr = (JpegJob * max(len(jobs), 1))()
-        for k, (src, H, W, Cn, stride, out, cap) in enumerate(jobs):
-            if cap > out.nbytes:
-                raise ValueError("out_capacity larger than the output buffer")
-            arr[k] = JpegJob(src.ptr, int(H), int(W), int(Cn), int(stride), out.ptr, int(cap))
+        arr = self._encoder_jobs(JpegJob, jobs, self._jpeg_job)
         _check(fn(self.handle, arr, len(jobs), *(int(v) for v in head), lengths.ptr,
                   *(t.ptr if t is not None else None for t in tables), slot), self.L)
 
@@ -708,13 +723,8 @@ class Context:
         adler = DeviceBuffer of two uint32 per chunk of PNG_CHUNK filtered bytes, the jobs' chunks in job order.  Asynchronous on
         `slot`."""
         jobs = list(jobs)
-        arr = (PngJob * max(len(jobs), 1))()
-        chunks = 0
-        for k, (src, H, W, Cn, bps, stride, out, cap) in enumerate(jobs):
-            if cap > out.nbytes:
-                raise ValueError("out_capacity larger than the output buffer")
-            chunks += -(-(int(H) * (1 + int(W) * int(Cn) * int(bps))) // PNG_CHUNK)
-            arr[k] = PngJob(src.ptr if isinstance(src, DeviceBuffer) else int(src), int(H), int(W), int(Cn), int(bps), int(stride), out.ptr, int(cap))
+        arr = self._encoder_jobs(PngJob, jobs, self._png_job)
+        chunks = sum(-(-(int(H) * (1 + int(W) * int(Cn) * int(bps))) // PNG_CHUNK) for _src, H, W, Cn, bps, *_rest in jobs)
         if lengths.nbytes < 8 * len(jobs) or adler.nbytes < 8 * chunks:
             raise ValueError("lengths or adler buffer too small")
         _check(self.L.gs360_png_deflate(self.handle, arr, len(jobs), lengths.ptr, adler.ptr, slot), self.L)

@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import capi, jpegenc, pngenc
+from . import capi, devcodec, jpegenc, pngenc
 from .fisheye import SensorCalibration, UndistortTables
 
 INTERPOLATIONS = {"nearest": 0, "linear": 1, "cubic": 2, "lanczos4": 4}   # cv2.INTER_* values (DF:59-64)
@@ -32,7 +32,6 @@ INTERPOLATIONS = {"nearest": 0, "linear": 1, "cubic": 2, "lanczos4": 4}   # cv2.
 
 jpeg_mode_from_env = jpegenc.mode_from_env      # the CLI's name for it: read once per run
 png_mode_from_env = pngenc.mode_from_env
-_PNG = "png"                                    # _collect's `jpeg` for views the device PNG encoder writes
 
 
 def engine_interpolation(flag: int) -> int:
@@ -61,8 +60,7 @@ class PairRenderer:
         self._scratch = None                # grow-only output buffer shared by the per-view launches of a pair
         self._plans = {}                    # (kind, id, nearest) -> map plan handle
         self.use_plans = os.environ.get("GS360_MAP_PLANS", "1") not in ("0", "off", "no")
-        self._stats = {"jpeg_device_images": 0, "jpeg_device_bytes": 0}
-        self._png_stats = {"png_device_images": 0, "png_device_bytes": 0}
+        self._stats = {"jpeg_device_images": 0, "jpeg_device_bytes": 0, "png_device_images": 0, "png_device_bytes": 0}
         self.dev_undistort = {}
         for sid, u in (undistort or {}).items():
             self.dev_undistort[sid] = (ctx.to_device(u.map_x), ctx.to_device(u.map_y),
@@ -84,33 +82,31 @@ class PairRenderer:
         """jpeg_device_images / jpeg_device_bytes: views the device encoder wrote (render_pair's jpeg_views / jpeg_masks) and their
         files' bytes, as Engine.stats() counts them"""
         with self.lock:
-            return dict(self._stats)
+            return {k: v for k, v in self._stats.items() if k.startswith("jpeg")}
 
     def png_stats(self):
         """png_device_images / png_device_bytes: the same counts for the device PNG encoder (render_pair's png_views / png_masks)"""
         with self.lock:
-            return dict(self._png_stats)
+            return {k: v for k, v in self._stats.items() if k.startswith("png")}
 
-    def _collect(self, keys, bufs, shapes, dtype, jpeg):
-        """(the views' launch queued on slot 0) -> {key: array}, or with `jpeg` = (quality, huffman) and 8-bit gray or RGB views
-        {key: bytes}: whole 4:2:0 JFIF files, encoded from the device buffers before they are freed.  A scan gets the view's raw size;
-        one that needs more is coded again, in the same mode, into a buffer of the bound.  `jpeg` = _PNG: whole PNG files in the same
-        way, for views of either depth and 1, 3 or 4 channels."""
-        if jpeg == _PNG:
-            esz = np.dtype(dtype).itemsize
-            with self.ctx.slot_locks[0]:
-                files = pngenc.encode_buffers(self.ctx, [(b, h, w, c, esz, 0) for b, (h, w, c) in zip(bufs, shapes)], slot=0, raw_capacity=True)
-            self._png_stats["png_device_images"] += len(files)
-            self._png_stats["png_device_bytes"] += sum(len(f) for f in files)
-            return dict(zip(keys, files))
-        if jpeg is None or np.dtype(dtype) != np.uint8 or any(c not in (1, 3) for _h, _w, c in shapes):
+    def _collect(self, keys, bufs, shapes, dtype, encoder):
+        """(the views' launch queued on slot 0) -> {key: array}, or with `encoder` = (quality, huffman) and 8-bit gray or
+        RGB views {key: bytes}: whole 4:2:0 JFIF files, encoded from the device buffers before they are freed.  A scan gets the view's
+        raw size; one that needs more is coded again, in the same mode, into a buffer of the bound.  `encoder` a devcodec.PngMode: whole
+        PNG files in the same way, for views of either depth and 1, 3 or 4 channels."""
+        png = isinstance(encoder, devcodec.PngMode)
+        if encoder is None or not (png or (np.dtype(dtype) == np.uint8 and all(c in (1, 3) for _h, _w, c in shapes))):
             return {k: self.ctx.download(b, shape, dtype=dtype, slot=0) for k, b, shape in zip(keys, bufs, shapes)}
-        quality, huffman = jpeg
         with self.ctx.slot_locks[0]:
-            files = jpegenc.encode_buffers(self.ctx, [(b, h, w, c) for b, (h, w, c) in zip(bufs, shapes)], quality=int(quality),
-                                           restart=jpegenc.RESTART, slot=0, huffman=huffman, subsampling="4:2:0", raw_capacity=True)
-        self._stats["jpeg_device_images"] += len(files)
-        self._stats["jpeg_device_bytes"] += sum(len(f) for f in files)
+            if png:
+                esz = np.dtype(dtype).itemsize
+                files = pngenc.encode_buffers(self.ctx, [(b, h, w, c, esz, 0) for b, (h, w, c) in zip(bufs, shapes)], slot=0, raw_capacity=True)
+            else:
+                quality, huffman = encoder
+                files = jpegenc.encode_buffers(self.ctx, [(b, h, w, c) for b, (h, w, c) in zip(bufs, shapes)], quality=int(quality),
+                                               restart=jpegenc.RESTART, slot=0, huffman=huffman, subsampling="4:2:0", raw_capacity=True)
+        self._stats["png_device_images" if png else "jpeg_device_images"] += len(files)
+        self._stats["png_device_bytes" if png else "jpeg_device_bytes"] += sum(len(f) for f in files)
         return dict(zip(keys, files))
 
     def close(self):
@@ -139,8 +135,8 @@ class PairRenderer:
                                      fill_value=valid_fill if valid_fill is not None else 0, slot=0, dtype=dtype)
         return self.ctx.download(self._scratch, (h, w, C), dtype=dtype, slot=0)
 
-    def _remap_views(self, dev, imgs, dmask, interp, border, valid_fill, jpeg=None):
-        """All views of the pair in ONE batched launch (no per-view launch tails), then the downloads (or, with `jpeg`, the device
+    def _remap_views(self, dev, imgs, dmask, interp, border, valid_fill, encoder=None):
+        """All views of the pair in ONE batched launch (no per-view launch tails), then the downloads (or, with `encoder`, the device
         encoder: _collect).  `dmask` set: the per-lens mask images are the sources (DF:2031-2043), else the lens images."""
         dtype = np.uint8
         if dmask is None and any(v.dtype == np.uint16 for v in imgs.values()):
@@ -176,7 +172,7 @@ class PairRenderer:
                 self.ctx.remap_plans_dev(planned, channels.pop(), interp=interp, border_value=border, slot=0, dtype=dtype)
             else:
                 self.ctx.remap_tables_dev(jobs, channels.pop(), interp=interp, border_value=border, slot=0, dtype=dtype)
-            return self._collect([vid for vid, _s in shapes], bufs, [shape for _v, shape in shapes], dtype, jpeg)
+            return self._collect([vid for vid, _s in shapes], bufs, [shape for _v, shape in shapes], dtype, encoder)
         finally:
             for b in bufs:
                 self.ctx.free(b)
@@ -201,8 +197,8 @@ class PairRenderer:
         before every resampling step, as load_prepared_input_image does on the host (DF:728-743); `want_color`
         returns the converted images (the --save-color-corrected-output files, DF:1953-1959)."""
         interp = engine_interpolation(interpolation)
-        jpeg_views = _PNG if png_views else jpeg_views
-        jpeg_masks = _PNG if png_masks else jpeg_masks
+        view_mode = devcodec.PngMode() if png_views else jpeg_views
+        mask_mode = devcodec.PngMode() if png_masks else jpeg_masks
         out = {"perspective": {}, "masks": {}, "fisheye": {}, "color": {}}
         with self.lock:
             imgs = {"X": _hwc(image_x), "Y": _hwc(image_y)}
@@ -247,14 +243,14 @@ class PairRenderer:
                     if self.fused and imgs["X"].dtype == np.uint16:
                         raise RuntimeError("16-bit lens images need table mode (the fused-map kernel is 8-bit)")
                     if self.fused:
-                        self._render_fused(out, imgs, dev, sensor_id_x, sensor_id_y, interp, mask_outside_model, mask_value, jpeg_views)
+                        self._render_fused(out, imgs, dev, sensor_id_x, sensor_id_y, interp, mask_outside_model, mask_value, view_mode)
                     else:
-                        out["perspective"] = self._remap_views(dev, imgs, None, interp, border, fill, jpeg_views)
+                        out["perspective"] = self._remap_views(dev, imgs, None, interp, border, fill, view_mode)
                     if dmask:
                         if self.fused:   # masks always go through the table path (nearest, border 0, invalid -> 0)
                             raise RuntimeError("mask rendering needs table mode")
                         out["masks"] = self._remap_views(None, None, dmask, capi.INTERP_NEAREST, (0.0, 0.0, 0.0, 0.0),
-                                                         0 if mask_outside_model else None, jpeg_masks)
+                                                         0 if mask_outside_model else None, mask_mode)
             finally:
                 for b in dev.values():
                     self.ctx.free(b)
@@ -262,7 +258,7 @@ class PairRenderer:
                     self.ctx.free(b)
         return out
 
-    def _render_fused(self, out, imgs, dev, sid_x, sid_y, interp, mask_outside, mask_value, jpeg=None):
+    def _render_fused(self, out, imgs, dev, sid_x, sid_y, interp, mask_outside, mask_value, encoder=None):
         views, calibs, srcs, dsts = [], [], [], []
         C = imgs["X"].shape[2]
         for key, sid in (("X", sid_x), ("Y", sid_y)):
@@ -284,7 +280,7 @@ class PairRenderer:
             self.ctx.fisheye_views_dev(srcs, calibs, C, views, self.lens_fov_deg, dsts, interp=interp,
                                        mask_outside=mask_outside, mask_value=mask_value, slot=0)
             out["perspective"] = self._collect([str(spec["view_id"]) for spec in self.specs], dsts,
-                                               [(int(spec["height"]), int(spec["width"]), C) for spec in self.specs], np.uint8, jpeg)
+                                               [(int(spec["height"]), int(spec["width"]), C) for spec in self.specs], np.uint8, encoder)
         finally:
             for d in dsts:
                 self.ctx.free(d)

@@ -28,6 +28,7 @@ on the launch's stream filters and deflates the batch's views where they are, on
 64 KiB cross PCIe, and a job writes the PNG framing around them.  The default, `host`, writes every file exactly as before.
 """
 import collections
+import functools
 import itertools
 import os
 import pathlib
@@ -36,7 +37,7 @@ import time
 
 import numpy as np
 
-from . import capi, hostmem, imageio, jpegdec, jpegenc, pngenc, video
+from . import capi, devcodec, hostmem, imageio, jpegdec, jpegenc, pngenc, video
 from .jobspec import JobSpec
 
 _FRAME_CACHE_BYTES = int(os.environ.get("GS360_FRAME_CACHE_MB", "4096")) << 20
@@ -48,13 +49,16 @@ _STALE_RUN_S = float(os.environ.get("GS360_STALE_RUN_S", "30"))            # an 
 _RECENT_SOURCES = 512                   # sources whose device is remembered after their record is gone (bounded)
 
 
-class _JpegScan:
-    """A view the device encoded (GS360_JPEG_ENCODER=device): the JFIF header and the scan, which aliases pinned host memory."""
-    __slots__ = ("header", "scan")
+class _CodedView:
+    """A view the device encoded (GS360_JPEG_ENCODER=device, GS360_PNG_ENCODER=device): the file's parts in order.  `scan`, the coded
+    bytes, aliases pinned host memory.  `tail` is bytes, or a callable that makes them from the coded bytes when the file is written:
+    a PNG's holds the CRC over the stream, which the writing thread computes, not a batch's leader under its slot lock."""
+    __slots__ = ("header", "scan", "tail")
 
-    def __init__(self, header, scan):
+    def __init__(self, header, scan, tail):
         self.header = header
         self.scan = scan
+        self.tail = tail
 
     def write(self, path):
         path = pathlib.Path(path)
@@ -62,23 +66,7 @@ class _JpegScan:
         with open(path, "wb") as f:
             f.write(self.header)
             f.write(self.scan)
-            f.write(jpegenc.EOI)
-
-
-class _PngStream:
-    """A view the device encoded (GS360_PNG_ENCODER=device): its geometry, the deflate stream, which aliases pinned host memory, and
-    the filtered scanlines' Adler-32."""
-    __slots__ = ("geometry", "stream", "adler")
-
-    def __init__(self, geometry, stream, adler):
-        self.geometry = geometry            # (H, W, C, bytes per sample)
-        self.stream = stream
-        self.adler = adler
-
-    def write(self, path):
-        path = pathlib.Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
-        path.write_bytes(pngenc.assemble(*self.geometry, self.stream, self.adler))
+            f.write(self.tail(self.scan) if callable(self.tail) else self.tail)
 
 
 def _fetch_coded(st, ctx, slot, coded, h_out):
@@ -95,7 +83,7 @@ def _fetch_coded(st, ctx, slot, coded, h_out):
 
 
 def _write_view(path, arr, jpeg_q):
-    if isinstance(arr, (_JpegScan, _PngStream)):
+    if isinstance(arr, _CodedView):
         arr.write(path)
     else:
         imageio.write_image(path, arr, jpeg_q=jpeg_q)
@@ -380,72 +368,61 @@ class Engine:
         return capi.View.make(job.fnum("yaw"), job.fnum("pitch"), job.fnum("h_fov"), job.fnum("v_fov"), job.width, job.height), 0
 
     @staticmethod
-    def _jpeg_mode(job: JobSpec, want_array=False):
-        """-> None (the host codecs write the view) or the device encoder's (quality, Huffman mode).  GS360_JPEG_ENCODER = host (default)
-        | device and GS360_JPEG_HUFFMAN = standard (default: the Annex K tables) | optimal (every view's own tables, the reference's
-        `-huffman optimal`; only meaningful with `device`), read once per job; the device encoder takes the .jpg / .jpeg views nobody
-        wants back as arrays."""
-        if want_array or pathlib.Path(str(job.dst)).suffix.lower() not in (".jpg", ".jpeg"):
-            return None
-        huffman = jpegenc.mode_from_env()
-        return None if huffman is None else (jpegenc.quality_for(job.jpeg_q), huffman)
+    def _encoder_mode(job: JobSpec, want_array=False):
+        """-> None (the host codecs write the view), a devcodec.JpegMode (quality, Huffman mode) or devcodec.PngMode(), read once per
+        job.  GS360_JPEG_ENCODER = host (default) | device and GS360_JPEG_HUFFMAN = standard (default: the Annex K tables) | optimal
+        (every view's own tables, the reference's `-huffman optimal`; only meaningful with `device`): the device encoder takes the .jpg /
+        .jpeg views nobody wants back as arrays.  GS360_PNG_ENCODER = host (default) | device: the same for the .png views, 8- and
+        16-bit."""
+        suffix = pathlib.Path(str(job.dst)).suffix.lower()
+        if not want_array and suffix in (".jpg", ".jpeg"):
+            huffman = jpegenc.mode_from_env()
+            return None if huffman is None else devcodec.JpegMode(jpegenc.quality_for(job.jpeg_q), huffman)
+        if not want_array and suffix == ".png" and pngenc.mode_from_env():
+            return devcodec.PngMode()
+        return None
 
-    def _encode_views(self, st, ctx, slot, d_out, h_out, shapes, C, mode):
-        """(slot lock held, the views' launch queued on `slot`) jpegenc.scan_items over the rendered views with the device pool as its
-        allocator: one scan call (mode = (quality, Huffman mode)), a scan is given the view's raw size and one that needs more (noise
-        at quality 100) is coded again into a buffer of the bound.  Only the scans' bytes come back, into the views' pinned blocks.
-        -> [_JpegScan]; h_out[i] is replaced where the scan is longer than the block."""
-        quality, huffman = mode
-        scans = jpegenc.scan_items(ctx, [(d, h, w, C) for d, (h, w) in zip(d_out, shapes)], lambda nb: st.take(st.dev_pool, nb, ctx.alloc),
-                                   lambda b: st.give(st.dev_pool, b), quality, jpegenc.RESTART, slot, huffman)
+    def _encode_views(self, st, ctx, slot, d_out, h_out, shapes, C, mode, esz=1):
+        """(slot lock held, the views' launch queued on `slot`) jpegenc.scan_items (mode = (quality, Huffman mode)) or
+        pngenc.deflate_items (mode a devcodec.PngMode; esz: bytes per sample) over the rendered views with the device pool as its
+        allocator: one call, a view's coded bytes are given about the view's raw size and those that need more (noise) are coded
+        again into a buffer of the bound.  Only the coded bytes come back, into the views' pinned blocks.  -> [_CodedView]; h_out[i]
+        is replaced where the coded bytes are longer than the block."""
+        def take(nbytes):
+            return st.take(st.dev_pool, nbytes, ctx.alloc)
+
+        def give(buf):
+            st.give(st.dev_pool, buf)
+        png = isinstance(mode, devcodec.PngMode)
+        if png:
+            coded = pngenc.deflate_items(ctx, [(d, h, w, C, esz, 0) for d, (h, w) in zip(d_out, shapes)], take, give, slot)
+        else:
+            quality, huffman = mode
+            coded = jpegenc.scan_items(ctx, [(d, h, w, C) for d, (h, w) in zip(d_out, shapes)], take, give, quality, jpegenc.RESTART, slot, huffman)
         try:
-            _fetch_coded(st, ctx, slot, [(d, length) for d, length, _tab in scans], h_out)
+            _fetch_coded(st, ctx, slot, [(d, length) for d, length, _extra in coded], h_out)
         finally:
-            for d, _length, _tab in scans:
-                st.give(st.dev_pool, d)
+            for d, _length, _extra in coded:
+                give(d)
         out = []
-        for hb, (_d, length, tab), (h, w) in zip(h_out, scans, shapes):
-            head = jpegenc.header(h, w, C, quality, jpegenc.RESTART, tab)
-            out.append(_JpegScan(head, np.frombuffer(hb.view, dtype=np.uint8, count=length)))
+        for hb, (_d, length, extra), (h, w) in zip(h_out, coded, shapes):
+            scan = np.frombuffer(hb.view, dtype=np.uint8, count=length)
+            if png:
+                view, tail_bytes = _CodedView(pngenc.head(h, w, C, esz, length), scan, functools.partial(pngenc.tail, adler=extra)), pngenc.TAIL_BYTES
+            else:
+                view, tail_bytes = _CodedView(jpegenc.header(h, w, C, quality, jpegenc.RESTART, extra), scan, jpegenc.EOI), len(jpegenc.EOI)
+            out.append(view)
             with st.pool_lock:
-                st.stats["jpeg_device_images"] += 1
-                st.stats["jpeg_device_bytes"] += len(head) + length + len(jpegenc.EOI)
+                st.stats["png_device_images" if png else "jpeg_device_images"] += 1
+                st.stats["png_device_bytes" if png else "jpeg_device_bytes"] += len(view.header) + length + tail_bytes
         return out
 
-    @staticmethod
-    def _png_mode(job: JobSpec, want_array=False):
-        """-> None (the host codecs write the view) or ("png",): GS360_PNG_ENCODER = host (default) | device, read once per job; the
-        device encoder takes the .png views, 8- and 16-bit, nobody wants back as arrays."""
-        if want_array or pathlib.Path(str(job.dst)).suffix.lower() != ".png":
-            return None
-        return ("png",) if pngenc.mode_from_env() else None
-
-    def _encode_png_views(self, st, ctx, slot, d_out, h_out, shapes, C, esz):
-        """(slot lock held, the views' launch queued on `slot`) pngenc.deflate_items over the rendered views with the device pool as its
-        allocator: one gs360_png_deflate call, a stream is given about the view's raw size and one that needs more (noise) is coded again
-        into a buffer of the bound.  Only the streams' bytes come back, into the views' pinned blocks.  -> [_PngStream]; h_out[i] is
-        replaced where the stream is longer than the block."""
-        streams = pngenc.deflate_items(ctx, [(d, h, w, C, esz, 0) for d, (h, w) in zip(d_out, shapes)],
-                                       lambda nb: st.take(st.dev_pool, nb, ctx.alloc), lambda b: st.give(st.dev_pool, b), slot)
-        try:
-            _fetch_coded(st, ctx, slot, [(d, length) for d, length, _adler in streams], h_out)
-        finally:
-            for d, _length, _adler in streams:
-                st.give(st.dev_pool, d)
-        out = []
-        for hb, (_d, length, adler), (h, w) in zip(h_out, streams, shapes):
-            out.append(_PngStream((h, w, C, esz), np.frombuffer(hb.view, dtype=np.uint8, count=length), adler))
-            with st.pool_lock:
-                st.stats["png_device_images"] += 1
-                st.stats["png_device_bytes"] += length + 6 + 57             # zlib header and Adler-32; signature, IHDR, IDAT framing, IEND
-        return out
-
-    def _launch_batch(self, st: _DeviceState, buf, H, W, C, views, interp, flags, dtype=np.uint8, jpeg=None):
+    def _launch_batch(self, st: _DeviceState, buf, H, W, C, views, interp, flags, dtype=np.uint8, encoder=None):
         """One batched launch for `views` of one resident frame -- or of a WINDOW of resident frames (`buf` a list: the frames of a video
         the view jobs walk together, PC:746-749, PC:1049-1078; ring families reach the source-major kernel from four frames per call).
-        Returns [(array aliasing pinned memory, PinnedBuffer)] per view; for a window a list of those, one per frame.  With `jpeg` (a
-        (quality, Huffman mode) pair) and an 8-bit gray or RGB frame the views are encoded where they are and the arrays are _JpegScan
-        objects; with `jpeg` = ("png",) (_png_mode) they are _PngStream objects, for any frame."""
+        Returns [(array aliasing pinned memory, PinnedBuffer)] per view; for a window a list of those, one per frame.  With `encoder`
+        (_encoder_mode's value) the views are encoded where they are and the arrays are _CodedView objects: JPEG for an 8-bit gray or
+        RGB frame, PNG for any frame."""
         with st.lock:
             slot = next(st.slot_cycle)
         ctx, L = st.ctx, st.ctx.L
@@ -456,17 +433,14 @@ class Engine:
         sizes = [v.height * v.width * C * esz for v in views] * len(bufs)           # frame-major, as gs360_equirect_views_u8 writes them
         d_out = [st.take(st.dev_pool, n, ctx.alloc) for n in sizes]
         h_out = [st.take(st.pin_pool, n, ctx.pinned) for n in sizes]
-        png = jpeg == ("png",)
-        encode = png or (jpeg is not None and np.dtype(dtype) == np.uint8 and C in (1, 3))
+        encode = encoder is not None and (isinstance(encoder, devcodec.PngMode) or (np.dtype(dtype) == np.uint8 and C in (1, 3)))
         scans = None
         t0 = time.perf_counter()
         try:
             with ctx.slot_locks[slot]:
                 ctx.equirect_views_dev(bufs, W, H, C, views, d_out, slot=slot, interp=interp, flags=flags, dtype=dtype)
-                if png:
-                    scans = self._encode_png_views(st, ctx, slot, d_out, h_out, [(v.height, v.width) for v in views] * len(bufs), C, esz)
-                elif encode:
-                    scans = self._encode_views(st, ctx, slot, d_out, h_out, [(v.height, v.width) for v in views] * len(bufs), C, jpeg)
+                if encode:
+                    scans = self._encode_views(st, ctx, slot, d_out, h_out, [(v.height, v.width) for v in views] * len(bufs), C, encoder, esz)
                 else:
                     for d, hb, n in zip(d_out, h_out, sizes):
                         capi._check(L.gs360_download(ctx.handle, hb.ptr, d.ptr, n, slot), L)
@@ -494,12 +468,12 @@ class Engine:
                     for hb, n, v in zip(h_out, sizes, views * len(bufs))]
         return [flat[f * n_views:(f + 1) * n_views] for f in range(len(bufs))] if window else flat
 
-    def _render(self, st: _DeviceState, fkey, get_frame, view, interp, flags=0, expected=1, stop_event=None, jpeg=None):
+    def _render(self, st: _DeviceState, fkey, get_frame, view, interp, flags=0, expected=1, stop_event=None, encoder=None):
         """Render `view` of the frame identified by `fkey`, coalesced with the other views of that frame that arrive
         within the linger window.  get_frame() -> (DeviceBuffer, H, W, C, dtype) is called by the batch leader only.
-        Returns (array, release): the array aliases pinned host memory until release() is called.  `jpeg`: the device encoder's
-        quality and Huffman mode for this view (_jpeg_mode), or ("png",) (_png_mode); views that differ in it do not share a batch."""
-        key = (fkey, interp, flags) if jpeg is None else (fkey, interp, flags, "jpeg") + tuple(jpeg)
+        Returns (array, release): the array aliases pinned host memory until release() is called.  `encoder`: the device encoder's
+        mode for this view (_encoder_mode); views that differ in it do not share a batch."""
+        key = (fkey, interp, flags) if encoder is None else (fkey, interp, flags, type(encoder).__name__) + encoder
         with st.batch_cond:
             b = st.open_batches.get(key)
             leader = b is None
@@ -524,7 +498,7 @@ class Engine:
                 if buf is None:                   # (a video's window past its last frame)
                     res = [None] * len(views)
                 else:
-                    res = self._launch_batch(st, buf, H, W, C, views, interp, flags, dtype, **({} if jpeg is None else {"jpeg": jpeg}))
+                    res = self._launch_batch(st, buf, H, W, C, views, interp, flags, dtype, **({} if encoder is None else {"encoder": encoder}))
                     if isinstance(buf, list):     # a window: per member the list of its view's frames
                         res = [[res[f][i] for f in range(len(buf))] for i in range(len(views))]
                 with st.batch_cond:
@@ -677,7 +651,7 @@ class Engine:
         of the view when want_array is set (the result itself lives in pooled pinned memory), else None."""
         view, flags = self._view_for(job)
         interp = self._interp_for(job)
-        jpeg = self._jpeg_mode(job, want_array) or self._png_mode(job, want_array)
+        encoder = self._encoder_mode(job, want_array)
         rec = self._job_touches(job.src)
         try:
             st = self.states[rec.dev]
@@ -689,7 +663,7 @@ class Engine:
                 return entry[0], entry[1], entry[2], entry[3], entry[5]
             try:
                 arr, release = self._render(st, self._frame_key(job.src), get_frame, view, interp, flags,
-                                            expected=rec.expected or capi.MAX_VIEWS, stop_event=stop_event, **({} if jpeg is None else {"jpeg": jpeg}))
+                                            expected=rec.expected or capi.MAX_VIEWS, stop_event=stop_event, **({} if encoder is None else {"encoder": encoder}))
             finally:
                 for entry in held:
                     self.release_frame(st, entry)
@@ -738,7 +712,7 @@ class Engine:
         """All frames of one view of a video; returns the number of frames written."""
         view, flags = self._view_for(job)
         interp = self._interp_for(job)
-        jpeg = self._jpeg_mode(job) or self._png_mode(job)
+        encoder = self._encoder_mode(job)
         sess, token = self._video_session(plan, stop_event, register_proc)
         written = 0
         try:
@@ -758,7 +732,7 @@ class Engine:
                     return bufs, H, W, 3, fdtype
                 outs, release = self._render(st, ("video", id(sess), k0), get_window, view, interp, flags,
                                              expected=min(sess.active_jobs, expected_jobs or sess.active_jobs), stop_event=stop_event,
-                                             **({} if jpeg is None else {"jpeg": jpeg}))
+                                             **({} if encoder is None else {"encoder": encoder}))
                 if outs is None:
                     break
                 try:

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from . import capi
+from . import capi, devcodec
 
 EOI = b"\xff\xd9"
 
@@ -134,55 +134,32 @@ def scan_items(ctx, items, take, give, quality=100, restart=RESTART, slot=0, huf
     if huffman not in HUFFMAN_MODES:
         raise ValueError("huffman must be 'standard' or 'optimal'")
     sub = _subsampling(subsampling)
-    n = len(items)
-    if not n:
-        return []
     optimal = huffman == "optimal"
-    taken, kept = [], []
 
-    def room(nbytes):
-        taken.append(take(nbytes))
-        return taken[-1]
+    def start(room):
+        d_len = room(8 * len(items))
+        d_tab = room(4 * TABLE_BYTES * len(items)) if optimal else None
 
-    def run(jobs):
-        ctx.jpeg_scan_sub_dev(jobs, d_len, d_tab, quality=quality, restart=restart, subsampling=sub, slot=slot)
-        tabs = ctx.download(d_tab, (len(jobs), 4 * TABLE_BYTES), np.uint8, slot) if optimal else [None] * len(jobs)
-        return [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)], [None if t is None else t.tobytes() for t in tabs]
-    try:
-        caps = [H * W * C if raw_capacity else scan_bound(H, W, C, restart, subsampling) for _b, H, W, C in items]
-        jobs = [(buf, H, W, C, 0, room(cap), cap) for (buf, H, W, C), cap in zip(items, caps)]
-        d_len = room(8 * n)
-        d_tab = room(4 * TABLE_BYTES * n) if optimal else None
-        lengths, tables = run(jobs)
-        for i, length in enumerate(lengths):
-            if length != capi.JPEG_OVERFLOW:
-                continue
-            buf, H, W, C = items[i]
-            bound = scan_bound(H, W, C, restart, subsampling)
-            if bound <= caps[i]:
-                raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
-            jobs[i] = (buf, H, W, C, 0, room(bound), bound)
-            (lengths[i],), (tables[i],) = run([jobs[i]])
-            if lengths[i] == capi.JPEG_OVERFLOW:
-                raise capi.Gs360Error(-2, "the JPEG scan did not fit its bound")
-        kept = [job[5] for job in jobs]
-        return list(zip(kept, lengths, tables))
-    finally:
-        for b in taken:
-            if not any(b is k for k in kept):
-                give(b)
+        def run(jobs):
+            ctx.jpeg_scan_sub_dev(jobs, d_len, d_tab, quality=quality, restart=restart, subsampling=sub, slot=slot)
+            tabs = ctx.download(d_tab, (len(jobs), 4 * TABLE_BYTES), np.uint8, slot) if optimal else [None] * len(jobs)
+            return [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)], [None if t is None else t.tobytes() for t in tabs]
+        return run
+
+    def bound(item):
+        return scan_bound(*item[1:], restart, subsampling)
+
+    def raw_size(item):
+        return item[1] * item[2] * item[3]
+    return devcodec.code_items(items, take, give, raw_size if raw_capacity else bound, bound, lambda item, out, cap: (*item, 0, out, cap), start,
+                               capi.JPEG_OVERFLOW, "JPEG scan")
 
 
 def encode_buffers(ctx, items, quality=100, restart=8, slot=0, huffman="standard", subsampling="4:4:4", raw_capacity=True):
     """(the caller holds `slot`) items: [(DeviceBuffer, H, W, C)] tight 8-bit device images -> [bytes], one whole JFIF file each:
     scan_items with the context's own allocator, then each scan's bytes come back and get their header and EOI."""
     scans = scan_items(ctx, items, ctx.alloc, ctx.free, quality, restart, slot, huffman, subsampling, raw_capacity)
-    try:
-        return [header(H, W, C, quality, restart, tab, subsampling) + ctx.download(d, (length,), np.uint8, slot).tobytes() + EOI
-                for (_b, H, W, C), (d, length, tab) in zip(items, scans)]
-    finally:
-        for d, _length, _tab in scans:
-            ctx.free(d)
+    return devcodec.files_of(ctx, items, scans, lambda it, scan, tab: header(*it[1:], quality, restart, tab, subsampling) + scan + EOI, slot)
 
 
 def encode_device(ctx, images, quality=100, restart=8, slot=0, huffman="standard", subsampling="4:4:4"):
@@ -193,20 +170,9 @@ def encode_device(ctx, images, quality=100, restart=8, slot=0, huffman="standard
     if huffman not in HUFFMAN_MODES:
         raise ValueError("huffman must be 'standard' or 'optimal'")
     _subsampling(subsampling)
-    items, owned = [], []
-    try:
-        for im in images:
-            if isinstance(im, tuple):
-                buf, H, W, Cn = im
-            else:
-                a = np.ascontiguousarray(im, dtype=np.uint8)
-                H, W = a.shape[:2]
-                Cn = 1 if a.ndim == 2 else a.shape[2]
-                buf = ctx.to_device(a, slot)
-                owned.append(buf)
-            items.append((buf, H, W, Cn))
-        with ctx.slot_locks[slot]:
-            return encode_buffers(ctx, items, quality, restart, slot, huffman, subsampling, raw_capacity=False)
-    finally:
-        for b in owned:
-            ctx.free(b)
+
+    def as_item(im):
+        a = np.ascontiguousarray(im, dtype=np.uint8)
+        return a, (a.shape[0], a.shape[1], 1 if a.ndim == 2 else a.shape[2])
+    return devcodec.encode_images(ctx, images, as_item,
+                                  lambda items: encode_buffers(ctx, items, quality, restart, slot, huffman, subsampling, raw_capacity=False), slot)

@@ -12,7 +12,7 @@ import zlib
 
 import numpy as np
 
-from . import capi
+from . import capi, devcodec
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 ZLIB_HEADER = b"\x78\x01"            # deflate, 32 KiB window, no preset dictionary, "fastest" level hint
@@ -61,11 +61,26 @@ def _png_chunk(tag, payload):
     return struct.pack(">I", len(payload)) + tag + payload + struct.pack(">I", zlib.crc32(tag + payload) & 0xFFFFFFFF)
 
 
-def assemble(H, W, C, bps, deflated, adler):
-    """the whole file around a deflate stream: signature, IHDR (non-interlaced, colour type 0 / 2 / 6), one IDAT, IEND"""
-    idat = ZLIB_HEADER + bytes(deflated) + struct.pack(">I", adler)
+def head(H, W, C, bps, length):
+    """the file's bytes in front of a deflate stream of `length` bytes: signature, IHDR (non-interlaced, colour type 0 / 2 / 6) and the
+    one IDAT chunk's length, tag and zlib header"""
     ihdr = struct.pack(">IIBBBBB", int(W), int(H), 8 * int(bps), _COLOUR_TYPE[int(C)], 0, 0, 0)
-    return SIGNATURE + _png_chunk(b"IHDR", ihdr) + _png_chunk(b"IDAT", idat) + _png_chunk(b"IEND", b"")
+    return SIGNATURE + _png_chunk(b"IHDR", ihdr) + struct.pack(">I", len(ZLIB_HEADER) + int(length) + 4) + b"IDAT" + ZLIB_HEADER
+
+
+def tail(deflated, adler):
+    """the file's bytes behind the deflate stream: its Adler-32, the IDAT chunk's CRC (which runs over the stream) and IEND"""
+    trailer = struct.pack(">I", adler)
+    crc = zlib.crc32(trailer, zlib.crc32(deflated, zlib.crc32(b"IDAT" + ZLIB_HEADER)))
+    return trailer + struct.pack(">I", crc & 0xFFFFFFFF) + _png_chunk(b"IEND", b"")
+
+
+TAIL_BYTES = len(tail(b"", 0))
+
+
+def assemble(H, W, C, bps, deflated, adler):
+    """the whole file around a deflate stream"""
+    return head(H, W, C, bps, len(deflated)) + bytes(deflated) + tail(deflated, adler)
 
 
 def deflate_items(ctx, items, take, give, slot=0, raw_capacity=True):
@@ -75,80 +90,39 @@ def deflate_items(ctx, items, take, give, slot=0, raw_capacity=True):
     chunk header's worth, and one that needs more (noise) is coded again, alone, into a buffer of the bound; otherwise every stream
     gets the bound at once.  Device memory comes from take(nbytes) and goes back through give(buffer): everything taken but the stream
     buffers returned is given back before this returns or raises; those are the caller's to give back."""
-    n = len(items)
-    if not n:
-        return []
-    taken, kept = [], []
+    def first(it):
+        _s, H, W, C, bps, _st = it
+        return min(bound(H, W, C, bps), H * W * C * bps + 4096) if raw_capacity else bound(H, W, C, bps)
 
-    def room(nbytes):
-        taken.append(take(nbytes))
-        return taken[-1]
+    def start(room):                                     # (the whole call's Adler buffer holds any single job's sums)
+        d_len, d_adler = room(8 * len(items)), room(8 * sum(n_chunks(*it[1:5]) for it in items))
 
-    def run(jobs):
-        counts = [n_chunks(H, W, C, bps) for _s, H, W, C, bps, _st, _o, _c in jobs]
-        d_len, d_adler = room(8 * len(jobs)), room(8 * sum(counts))
-        ctx.png_deflate_dev(jobs, d_len, d_adler, slot)
-        lengths = [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)]
-        sums = ctx.download(d_adler, (sum(counts), 2), np.uint32, slot)
-        adlers, at = [], 0
-        for (_s, H, W, C, bps, _st, _o, _c), cnt in zip(jobs, counts):
-            adlers.append(adler_combine(sums[at:at + cnt], filtered_bytes(H, W, C, bps)))
-            at += cnt
-        return lengths, adlers
-    try:
-        caps = [min(bound(H, W, C, bps), H * W * C * bps + 4096) if raw_capacity else bound(H, W, C, bps) for _s, H, W, C, bps, _st in items]
-        jobs = [(src, H, W, C, bps, stride, room(cap), cap) for (src, H, W, C, bps, stride), cap in zip(items, caps)]
-        lengths, adlers = run(jobs)
-        for i, length in enumerate(lengths):
-            if length != capi.PNG_OVERFLOW:
-                continue
-            src, H, W, C, bps, stride = items[i]
-            full = bound(H, W, C, bps)
-            if full <= caps[i]:
-                raise capi.Gs360Error(-2, "the PNG stream did not fit its bound")
-            jobs[i] = (src, H, W, C, bps, stride, room(full), full)
-            (lengths[i],), _ = run([jobs[i]])
-            if lengths[i] == capi.PNG_OVERFLOW:
-                raise capi.Gs360Error(-2, "the PNG stream did not fit its bound")
-        kept = [job[6] for job in jobs]
-        return list(zip(kept, lengths, adlers))
-    finally:
-        for b in taken:
-            if not any(b is k for k in kept):
-                give(b)
+        def run(jobs):
+            counts = [n_chunks(*job[1:5]) for job in jobs]
+            ctx.png_deflate_dev(jobs, d_len, d_adler, slot)
+            lengths = [int(v) for v in ctx.download(d_len, (len(jobs),), np.uint64, slot)]
+            sums = ctx.download(d_adler, (sum(counts), 2), np.uint32, slot)
+            ends = np.cumsum(counts)
+            return lengths, [adler_combine(sums[end - cnt:end], filtered_bytes(*job[1:5])) for job, cnt, end in zip(jobs, counts, ends)]
+        return run
+    return devcodec.code_items(items, take, give, first, lambda it: bound(*it[1:5]), lambda it, out, cap: (*it, out, cap), start,
+                               capi.PNG_OVERFLOW, "PNG stream")
 
 
 def encode_buffers(ctx, items, slot=0, raw_capacity=True):
     """(the caller holds `slot`) items: [(DeviceBuffer, H, W, C, bps, src_stride)] device images -> [bytes], one whole PNG file each:
     deflate_items with the context's own allocator, then each stream's bytes come back and get their zlib and PNG framing."""
     streams = deflate_items(ctx, items, ctx.alloc, ctx.free, slot, raw_capacity)
-    try:
-        return [assemble(H, W, C, bps, ctx.download(d, (length,), np.uint8, slot).tobytes(), adler)
-                for (_s, H, W, C, bps, _st), (d, length, adler) in zip(items, streams)]
-    finally:
-        for d, _length, _adler in streams:
-            ctx.free(d)
+    return devcodec.files_of(ctx, items, streams, lambda it, deflated, adler: assemble(*it[1:5], deflated, adler), slot)
 
 
 def encode_device(ctx, images, slot=0):
     """images: uint8 / uint16 ndarrays (H x W or H x W x C, C = 1, 3 or 4) or (DeviceBuffer, H, W, C, bps, src_stride) tuples of device
     images -> [bytes], one whole PNG file each.  One gs360_png_deflate call encodes them all; only the compressed bytes and 8 bytes of
     checksum per 64 KiB come back from the device."""
-    items, owned = [], []
-    try:
-        for im in images:
-            if isinstance(im, tuple):
-                items.append(im)
-                continue
-            a = np.ascontiguousarray(im)
-            if a.dtype not in (np.uint8, np.uint16):
-                raise ValueError("PNG images are uint8 or uint16")
-            H, W = a.shape[:2]
-            buf = ctx.to_device(a, slot)
-            owned.append(buf)
-            items.append((buf, H, W, 1 if a.ndim == 2 else a.shape[2], a.dtype.itemsize, 0))
-        with ctx.slot_locks[slot]:
-            return encode_buffers(ctx, items, slot, raw_capacity=False)
-    finally:
-        for b in owned:
-            ctx.free(b)
+    def as_item(im):
+        a = np.ascontiguousarray(im)
+        if a.dtype not in (np.uint8, np.uint16):
+            raise ValueError("PNG images are uint8 or uint16")
+        return a, (a.shape[0], a.shape[1], 1 if a.ndim == 2 else a.shape[2], a.dtype.itemsize, 0)
+    return devcodec.encode_images(ctx, images, as_item, lambda items: encode_buffers(ctx, items, slot, raw_capacity=False), slot)

@@ -1,6 +1,5 @@
 """The device JPEG scans (gs360_jpeg_scan_u8, csrc/gs360_jpeg.hip) against the NumPy restatement of JPG-SPEC v1 (tests/jpegenc_np.py):
 every scan and every length byte for byte."""
-import collections
 import io
 
 import numpy as np
@@ -11,6 +10,7 @@ from gs360 import jpegenc
 
 import jpegenc_np as ref
 import jpegopt_np as opt
+from util import CountingPool
 
 pytestmark = pytest.mark.gpu
 
@@ -158,26 +158,6 @@ def recode_reference(huffman, quality):
                 longer.add(i)
         _RECODE_REF[key] = (files, longer)
     return _RECODE_REF[key]
-
-
-class CountingPool:
-    """the engine's device pool in small: free buffers by size, every take and give counted"""
-
-    def __init__(self, ctx):
-        self.ctx, self.free, self.takes, self.gives = ctx, collections.defaultdict(list), 0, 0
-
-    def take(self, nbytes):
-        self.takes += 1
-        return self.free[nbytes].pop() if self.free[nbytes] else self.ctx.alloc(nbytes)
-
-    def give(self, buf):
-        self.gives += 1
-        self.free[buf.nbytes].append(buf)
-
-    def close(self):
-        for bufs in self.free.values():
-            for b in bufs:
-                self.ctx.free(b)
 
 
 @pytest.mark.parametrize("quality", [100, 95])

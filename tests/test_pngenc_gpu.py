@@ -8,6 +8,7 @@ from gs360 import capi, pngenc
 import pngenc_cases as cases
 import pngenc_np as ref
 from test_pngenc_cpu import check_size_conditions
+from util import CountingPool
 
 pytestmark = pytest.mark.gpu
 
@@ -112,3 +113,93 @@ def test_encode_device_writes_the_restatements_files(ctx):
 
 def test_size_conditions_on_the_device(ctx, tmp_path):
     check_size_conditions(lambda img: pngenc.encode_device(ctx, [img])[0], tmp_path)
+
+
+_RECODE = {}
+
+
+def recode_set():
+    """-> (images, their whole files, the indices coded again), computed once: a tall one-pixel noise image whose 32 000 filtered bytes
+    deflate past its first capacity H * W * C * bps + 4096, small photo-like cases of both depths, and a smooth image far below its"""
+    if not _RECODE:
+        noise = np.random.default_rng(20261020).integers(0, 256, size=(16000, 1, 1)).astype(np.uint8)
+        images = [noise, IMAGES["c3_u8"], IMAGES["c1_u16"], cases._photo(64, 64, 3, np.uint8, 21)]
+        files, longer = [], set()
+        for i, im in enumerate(images):
+            n = len(ref.deflate(im)[0])
+            print(f"image {i} {im.shape} {im.dtype}: restated stream {n} bytes, first capacity {im.nbytes + 4096}")
+            files.append(ref.encode(im))
+            if n > im.nbytes + 4096:
+                longer.add(i)
+        _RECODE.update(images=images, files=files, longer=longer)
+    return _RECODE["images"], _RECODE["files"], _RECODE["longer"]
+
+
+def test_streams_past_their_first_capacity_are_coded_again_under_pool_allocators(ctx):
+    """pngenc.deflate_items as the engine calls it (raw-size first capacities, taking and giving callables over a pool): the files
+    equal the restatement's, exactly the items whose restated stream exceeds the first capacity were coded again, and everything taken
+    but the returned stream buffers went back."""
+    images, wants, longer = recode_set()
+    assert 0 < len(longer) < len(images)                 # both branches run
+    pool = CountingPool(ctx)
+    srcs = [ctx.to_device(im) for im in images]
+    items = [(d, im.shape[0], im.shape[1], im.shape[2], im.dtype.itemsize, 0) for d, im in zip(srcs, images)]
+    try:
+        with ctx.slot_locks[0]:
+            streams = pngenc.deflate_items(ctx, items, pool.take, pool.give, 0)
+        assert pool.takes == pool.gives + len(streams)
+        recoded = {i for i, ((d, _n, _a), im) in enumerate(zip(streams, images)) if d.nbytes != im.nbytes + 4096}
+        assert recoded == longer
+        for i, ((d, n, adler), (_s, H, W, C, bps, _st)) in enumerate(zip(streams, items)):
+            assert d.nbytes == (pngenc.bound(H, W, C, bps) if i in longer else H * W * C * bps + 4096), i
+            assert pngenc.assemble(H, W, C, bps, ctx.download(d, (n,), np.uint8).tobytes(), adler) == wants[i], i
+        for d, _n, _a in streams:
+            pool.give(d)
+        assert pool.takes == pool.gives
+    finally:
+        pool.close()
+        for d in srcs:
+            ctx.free(d)
+
+
+def test_the_engine_replaces_the_pinned_block_of_exactly_the_png_views_coded_again(tmp_path):
+    """The engine's PNG step itself, without a render: a device state of its own, hand-made view outputs and pinned blocks.  Its views
+    share channel count and depth: gray 8-bit, the tall noise image (coded again) and a smooth one (not)."""
+    from gs360 import devcodec, engine
+    images = [recode_set()[0][0], cases._photo(64, 64, 1, np.uint8, 22)]
+    wants = [recode_set()[1][0], ref.encode(images[1])]
+    longer = {i for i, im in enumerate(images) if len(ref.deflate(im)[0]) > im.nbytes + 4096}
+    assert longer == {0}
+    st = engine._DeviceState(0)
+    try:
+        d_out = [st.ctx.to_device(im) for im in images]
+        blocks = [st.ctx.pinned(im.nbytes) for im in images]
+        h_out = list(blocks)
+        with st.ctx.slot_locks[0]:
+            out = engine.Engine._encode_views(None, st, st.ctx, 0, d_out, h_out, [im.shape[:2] for im in images], 1, devcodec.PngMode(), 1)
+        for i, view in enumerate(out):
+            engine._write_view(tmp_path / f"{i}.png", view, None)
+            assert (tmp_path / f"{i}.png").read_bytes() == wants[i], i
+            assert (h_out[i] is not blocks[i]) == (i in longer), i
+            assert (h_out[i].nbytes > blocks[i].nbytes) == (i in longer), i
+        assert st.stats["png_device_images"] == len(images) and st.stats["png_device_bytes"] == sum(len(w) for w in wants)
+    finally:
+        st.ctx.close()
+
+
+def test_chunks_past_one_round_of_the_placement_land_at_their_offsets(ctx):
+    """257 chunks, one more than the 256 the placement kernel scans per round, of different lengths (4097 x 4095 gray zeros, row y
+    opening with (37 * y) % 97 non-zero bytes: identical chunks would hide a misplaced one): length, bytes, guard and all 257 Adler
+    pairs of one call."""
+    rng = np.random.default_rng(20261021)
+    img = np.zeros((4097, 4095, 1), np.uint8)
+    for y in range(img.shape[0]):
+        img[y, :(37 * y) % 97, 0] = rng.integers(1, 256, (37 * y) % 97)
+    assert pngenc.n_chunks(4097, 4095, 1, 1) == 257
+    deflated, parts = ref.deflate(img)
+    (n, data, sums), = run_deflate(ctx, [img])
+    print(f"{n} bytes (restatement {len(deflated)}), {len(sums)} chunks")
+    assert n == len(deflated)
+    assert data[:n].tobytes() == deflated
+    assert (data[n:] == 0xA5).all()
+    assert len(sums) == 257 and sums == [p[:2] for p in parts]

@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests."""
+import collections
+
 import numpy as np
 
 SEED = 20260424
@@ -30,3 +32,23 @@ def ring_views(count, size, hfov, pitch=0.0):
 PRESET_FULL360 = [(0, 0), (45, 30), (45, -30), (90, 0), (135, 30), (135, -30), (180, 0), (-135, 30), (-135, -30),
                   (-90, 0), (-45, 30), (-45, -30)]
 PRESET_FISHEYELIKE = [(0, 0), (0, 30), (0, -30), (36, 0), (144, 0), (180, 0), (180, 30), (180, -30), (-144, 0), (-36, 0)]
+
+
+class CountingPool:
+    """the engine's device pool in small: free buffers by size, every take and give counted"""
+
+    def __init__(self, ctx):
+        self.ctx, self.free, self.takes, self.gives = ctx, collections.defaultdict(list), 0, 0
+
+    def take(self, nbytes):
+        self.takes += 1
+        return self.free[nbytes].pop() if self.free[nbytes] else self.ctx.alloc(nbytes)
+
+    def give(self, buf):
+        self.gives += 1
+        self.free[buf.nbytes].append(buf)
+
+    def close(self):
+        for bufs in self.free.values():
+            for b in bufs:
+                self.ctx.free(b)
