@@ -393,9 +393,10 @@ int gs360_remap_table_u16(gs360_ctx* c, const void* src, int H, int W, int C, si
 }
 
 // ---- fused fisheye -> views --------------------------------------------------------------------
-int gs360_fisheye_views_u8(gs360_ctx* c, const void* const* src_lens, const gs360_calib* calibs, int C, size_t src_stride,
-                           const gs360_view* views, int n_views, double lens_fov_deg, int interp, int mask_outside,
-                           int mask_value, void* const* dst, size_t dst_stride, uint8_t* const* valid_out, int slot) {
+int gs360_fisheye_views_border_u8(gs360_ctx* c, const void* const* src_lens, const gs360_calib* calibs, int C, size_t src_stride,
+                                  const gs360_view* views, int n_views, double lens_fov_deg, int interp, int mask_outside,
+                                  int mask_value, const double* border_value, void* const* dst, size_t dst_stride,
+                                  uint8_t* const* valid_out, int slot) {
     if (int rc = check_ctx_slot(c, slot)) return rc;
     if (!src_lens || !calibs || !views || !dst) return fail(GS360_ERR_ARG, "NULL argument");
     if (n_views < 0) return fail(GS360_ERR_ARG, "negative count");
@@ -411,11 +412,14 @@ int gs360_fisheye_views_u8(gs360_ctx* c, const void* const* src_lens, const gs36
         if (views[k].width < 1 || views[k].height < 1 || views[k].width > 32768 || views[k].height > 32768)
             return fail(GS360_ERR_ARG, "view %d has bad size", k);
     }
+    // (a launch keeps a single src_stride in its parameter block; refused before the first launch so that no view is written)
+    for (int k = 0; k < n_views; ++k)
+        if (calibs[k].width != calibs[k - k % GS360_MAX_VIEWS].width)
+            return fail(GS360_ERR_UNSUPPORTED, "views of one call must share the sensor width");
     HIP_TRY(hipSetDevice(c->device));
     mask_value = mask_value < 0 ? 0 : (mask_value > 255 ? 255 : mask_value);
     for (int v0 = 0; v0 < n_views; v0 += GS360_MAX_VIEWS) {
         int nv = n_views - v0 < GS360_MAX_VIEWS ? n_views - v0 : GS360_MAX_VIEWS;
-        // one launch per group of equal-width sensors keeps a single src_stride in the parameter block
         FeBatch B;
         std::memset(&B, 0, sizeof(B));
         FeCommon& L = B.common;
@@ -427,8 +431,6 @@ int gs360_fisheye_views_u8(gs360_ctx* c, const void* const* src_lens, const gs36
             B.view[k].valid_out = valid_out ? valid_out[v0 + k] : nullptr;
             B.view[k].tile_base = base;
             base += B.view[k].tiles_x * B.view[k].tiles_y;
-            if (calibs[v0 + k].width != calibs[v0].width)
-                return fail(GS360_ERR_UNSUPPORTED, "views of one call must share the sensor width");
         }
         L.n_views = nv;
         L.total_tiles = base;
@@ -436,17 +438,29 @@ int gs360_fisheye_views_u8(gs360_ctx* c, const void* const* src_lens, const gs36
         L.interp = interp; L.mask_outside = mask_outside ? 1 : 0; L.mask_value = mask_value;
         L.src_stride = (int64_t)(src_stride ? src_stride : (size_t)calibs[v0].width * C);
         L.dst_stride = (int64_t)dst_stride;
-        L.cval[0] = (uint8_t)mask_value;  // borderValue=float(mask_value) -> Scalar(v,0,0,0), DF:2007
+        for (int k = 0; k < 4; ++k) L.cval[k] = sat_u8(border_value ? border_value[k] : 0.0);
         L.cubic_tab = interp == GS360_INTERP_LANCZOS4 ? c->d_lanczos : c->d_cubic;
         L.pipelined = 1;
         for (int k = 0; k < nv; ++k)
             if (calibs[v0 + k].width < 8 || (uint64_t)L.src_stride * (uint64_t)calibs[v0 + k].height >= ((uint64_t)1 << 32)) L.pipelined = 0;
+        // (a 3-channel image off a dword boundary: the pipelined gathers read whole dwords from the base on; the straight-line samplers do not)
+        for (int k = 0; k < nv && C == 3; ++k)
+            if (reinterpret_cast<uintptr_t>(src_lens[v0 + k]) & 3) L.pipelined = 0;
         if ((uint64_t)L.src_stride >= ((uint64_t)1 << 24)) L.pipelined = 0;
         int persist_blocks = c->prop.multiProcessorCount * 8;
         if (const int v = opt(c, kOptTablePersist); v >= 0) persist_blocks = v;
         HIP_TRY(launch_fisheye(B, persist_blocks, C, c->stream[slot]));
     }
     return GS360_OK;
+}
+
+// borderValue=float(mask_value) -> Scalar(v,0,0,0), DF:2007: the value on channel 0 of the image as it lies in memory
+int gs360_fisheye_views_u8(gs360_ctx* c, const void* const* src_lens, const gs360_calib* calibs, int C, size_t src_stride,
+                           const gs360_view* views, int n_views, double lens_fov_deg, int interp, int mask_outside,
+                           int mask_value, void* const* dst, size_t dst_stride, uint8_t* const* valid_out, int slot) {
+    const double border[4] = {(double)mask_value, 0.0, 0.0, 0.0};      // (saturated to 0..255 like the mask value itself)
+    return gs360_fisheye_views_border_u8(c, src_lens, calibs, C, src_stride, views, n_views, lens_fov_deg, interp, mask_outside,
+                                         mask_value, border, dst, dst_stride, valid_out, slot);
 }
 
 // ---- host-buffer conveniences ------------------------------------------------------------------

@@ -26,7 +26,7 @@ EXPORTS = (
     "gs360_device_info", "gs360_device_pci_bus_id", "gs360_ctx_set_option", "gs360_ctx_get_option", "gs360_dev_alloc", "gs360_dev_free", "gs360_host_alloc", "gs360_host_free",
     "gs360_upload", "gs360_download", "gs360_dev_memset", "gs360_dev_bswap16", "gs360_sync", "gs360_event_record",
     "gs360_event_elapsed_ms", "gs360_equirect_views_u8", "gs360_equirect_views_masked_u8", "gs360_remap_table_u8",
-    "gs360_fisheye_views_u8", "gs360_remap_tables_u8", "gs360_map_plan_create", "gs360_map_plan_destroy", "gs360_remap_plans_u8", "gs360_remap_plans_u16",
+    "gs360_fisheye_views_u8", "gs360_fisheye_views_border_u8", "gs360_remap_tables_u8", "gs360_map_plan_create", "gs360_map_plan_destroy", "gs360_remap_plans_u8", "gs360_remap_plans_u16",
     "gs360_color_plan_create", "gs360_color_plan_destroy", "gs360_color_apply_u8",
     "gs360_equirect_views_u8_host", "gs360_remap_table_u8_host",
     "gs360_equirect_views_u16", "gs360_remap_table_u16", "gs360_remap_tables_u16", "gs360_equirect_views_u16_host", "gs360_remap_table_u16_host",
@@ -233,6 +233,8 @@ def load_library(path=None):
         L.gs360_remap_table_u8.argtypes = [vp, vp, i, i, i, sz, vp, vp, vp, i, i, i, C.POINTER(C.c_double), i, vp, sz, i]
         L.gs360_fisheye_views_u8.argtypes = [vp, pvp, C.POINTER(Calib), i, sz, C.POINTER(View), i, C.c_double, i, i, i,
                                              pvp, sz, pvp, i]
+        L.gs360_fisheye_views_border_u8.argtypes = [vp, pvp, C.POINTER(Calib), i, sz, C.POINTER(View), i, C.c_double, i, i, i,
+                                                    C.POINTER(C.c_double), pvp, sz, pvp, i]
         L.gs360_remap_tables_u8.argtypes = [vp, C.POINTER(RemapJob), i, i, i, C.POINTER(C.c_double), i]
         L.gs360_map_plan_create.argtypes = [vp, vp, vp, vp, i, i, i, i, pvp]
         L.gs360_map_plan_destroy.argtypes = [vp, vp]
@@ -559,15 +561,25 @@ class Context:
         _check(fn(self.handle, arr, pl, n, Cn, interp, bv, slot), self.L)
 
     def fisheye_views_dev(self, lens_bufs, calibs, Cn, views, lens_fov_deg, dsts, valid_outs=None,
-                          interp=INTERP_LINEAR, mask_outside=True, mask_value=0, slot=0):
+                          interp=INTERP_LINEAR, mask_outside=True, mask_value=0, slot=0, src_stride=0, dst_stride=0, border_value=None):
+        """lens_bufs / dsts / valid_outs: DeviceBuffer objects or raw device addresses (buf.ptr + offset), None = NULL; strides in
+        bytes, 0 = tight.  border_value: the border taps' colour per channel in memory order (gs360_fisheye_views_border_u8), None =
+        (mask_value, 0, 0, 0)."""
+        def addr(b):
+            return b if b is None or isinstance(b, int) else b.ptr
         nv = len(views)
-        sp = (C.c_void_p * nv)(*[b.ptr for b in lens_bufs])
-        dp = (C.c_void_p * nv)(*[b.ptr for b in dsts])
-        vo = (C.c_void_p * nv)(*[(b.ptr if b is not None else None) for b in valid_outs]) if valid_outs else None
+        sp = (C.c_void_p * nv)(*[addr(b) for b in lens_bufs])
+        dp = (C.c_void_p * nv)(*[addr(b) for b in dsts])
+        vo = (C.c_void_p * nv)(*[addr(b) for b in valid_outs]) if valid_outs else None
         ca = (Calib * nv)(*calibs)
         va = (View * nv)(*views)
-        _check(self.L.gs360_fisheye_views_u8(self.handle, sp, ca, Cn, 0, va, nv, float(lens_fov_deg), interp,
-                                             1 if mask_outside else 0, int(mask_value), dp, 0, vo, slot), self.L)
+        head = (self.handle, sp, ca, Cn, int(src_stride), va, nv, float(lens_fov_deg), interp, 1 if mask_outside else 0, int(mask_value))
+        tail = (dp, int(dst_stride), vo, slot)
+        if border_value is None:
+            _check(self.L.gs360_fisheye_views_u8(*head, *tail), self.L)
+        else:
+            bv = (C.c_double * 4)(*[float(x) for x in border_value])
+            _check(self.L.gs360_fisheye_views_border_u8(*head, bv, *tail), self.L)
 
     # -- input colour stage ------------------------------------------------------------------
     @staticmethod

@@ -243,7 +243,7 @@ class PairRenderer:
                     if self.fused and imgs["X"].dtype == np.uint16:
                         raise RuntimeError("16-bit lens images need table mode (the fused-map kernel is 8-bit)")
                     if self.fused:
-                        self._render_fused(out, imgs, dev, sensor_id_x, sensor_id_y, interp, mask_outside_model, mask_value, view_mode)
+                        self._render_fused(out, imgs, dev, sensor_id_x, sensor_id_y, interp, mask_outside_model, mask_value, border, view_mode)
                     else:
                         out["perspective"] = self._remap_views(dev, imgs, None, interp, border, fill, view_mode)
                     if dmask:
@@ -258,7 +258,7 @@ class PairRenderer:
                     self.ctx.free(b)
         return out
 
-    def _render_fused(self, out, imgs, dev, sid_x, sid_y, interp, mask_outside, mask_value, encoder=None):
+    def _render_fused(self, out, imgs, dev, sid_x, sid_y, interp, mask_outside, mask_value, border, encoder=None):
         views, calibs, srcs, dsts = [], [], [], []
         C = imgs["X"].shape[2]
         for key, sid in (("X", sid_x), ("Y", sid_y)):
@@ -278,7 +278,7 @@ class PairRenderer:
             dsts.append(self.ctx.alloc(int(spec["width"]) * int(spec["height"]) * C))
         try:
             self.ctx.fisheye_views_dev(srcs, calibs, C, views, self.lens_fov_deg, dsts, interp=interp,
-                                       mask_outside=mask_outside, mask_value=mask_value, slot=0)
+                                       mask_outside=mask_outside, mask_value=mask_value, slot=0, border_value=border)
             out["perspective"] = self._collect([str(spec["view_id"]) for spec in self.specs], dsts,
                                                [(int(spec["height"]), int(spec["width"]), C) for spec in self.specs], np.uint8, encoder)
         finally:

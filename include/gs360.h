@@ -251,13 +251,26 @@ int gs360_remap_plans_u16(gs360_ctx *ctx, const gs360_remap_job *jobs, const gs3
  * src_lens[k] (H x W x C of calibs[k]) with views[k].yaw_deg measured RELATIVE to that lens
  * (DF:1883).  Pixels outside the lens model / sensor get mask_value on all channels when
  * mask_outside != 0 (DF:2009-2014); border taps use {mask_value,0,0,0} as cv2 does.
- * valid_out[k] (h x w uint8, may be NULL / may contain NULLs) receives the validity mask.
+ * valid_out[k] (h x w uint8, tight rows, may be NULL / may contain NULLs) receives the validity mask.
+ * src_stride / dst_stride in bytes, 0 = tight; an explicit src_stride needs sensors of one width (GS360_ERR_ARG), and the views of
+ * each group of GS360_MAX_VIEWS share their sensor width in any case (GS360_ERR_UNSUPPORTED) -- both refused before anything is
+ * written.  A 3-channel lens image whose base is not 4-byte aligned is taken, by the byte-reading samplers (slower, same results).
  */
 int gs360_fisheye_views_u8(gs360_ctx *ctx, const void *const *src_lens, const gs360_calib *calibs,
                            int C, size_t src_stride,
                            const gs360_view *views, int n_views, double lens_fov_deg,
                            int interp, int mask_outside, int mask_value,
                            void *const *dst, size_t dst_stride, uint8_t *const *valid_out, int slot);
+/*
+ * The same with the border taps' colour given per channel of the image AS IT LIES IN MEMORY (border_value[4], saturated to 0..255,
+ * NULL = zeros), as gs360_remap_tables_u8 takes it: cv2's Scalar(mask_value,0,0,0) lands on blue of a BGR image, which is index 2
+ * of an RGB(A) array.  gs360_fisheye_views_u8 = this call with {mask_value,0,0,0}.  mask_value still fills the invalid pixels.
+ */
+int gs360_fisheye_views_border_u8(gs360_ctx *ctx, const void *const *src_lens, const gs360_calib *calibs,
+                                  int C, size_t src_stride,
+                                  const gs360_view *views, int n_views, double lens_fov_deg,
+                                  int interp, int mask_outside, int mask_value, const double *border_value,
+                                  void *const *dst, size_t dst_stride, uint8_t *const *valid_out, int slot);
 
 /* ---- input colour stage (dual-fisheye tool, before resampling) -------------------------------- */
 
