@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gs360_PlyOptimizer -- the reference's PointCloudOptimizer with its voxel downsampling on the GPU (VOX-SPEC v1).
+"""gs360_PlyOptimizer -- the reference's PointCloudOptimizer with its voxel downsampling on the GPU (VOX-SPEC v1, OCT-SPEC v1).
 
 Thins a photogrammetry point cloud before 3DGS training: loads a PLY file, keeps one point per voxel (a fixed voxel size, or a size
 searched for a target count), appends further PLY files and a synthetic sky dome, and writes a binary little-endian PLY.  It keeps
@@ -7,8 +7,10 @@ the reference's flags and defaults, parser complaints, log lines and exit codes 
 every probe of the target search is a key pass, a sort and a count on the device (gs360/pointcloud.py).  Without --out the run
 prints the statistics with NumPy and needs no GPU.
 
-Not built, and refused with one [ERR] line before anything is written: --downsample-method adaptive / --adaptive (the octree's
-split order is a serial priority queue) and a COLMAP text-model folder as input.
+--downsample-method adaptive / --adaptive (the octree sampling, PLY:1174-1407 and 1657-1703) runs when the environment says
+GS360_PLY_ADAPTIVE=device: path codes, sorts and picks on the device, the split queue over counts inside the library; --voxel-size
+is then the smallest voxel.  Without the variable the flag is refused with one [ERR] line before anything is written, as it was
+before the octree was built.  Not built, and refused the same way: a COLMAP text-model folder as input.
 """
 import argparse
 import os
@@ -29,11 +31,12 @@ def create_arg_parser():
     ap.add_argument("-o", "--out", dest="output", default=None, help="the PLY file to write; without it the run only prints the cloud's statistics")
     ap.add_argument("-t", "--target-points", type=int, default=None, help="about how many points to keep; goes before --voxel-size")
     ap.add_argument("-r", "--target-percent", type=float, default=None, help="the points to keep in percent of the input; becomes --target-points after loading")
-    ap.add_argument("-v", "--voxel-size", type=float, default=None, help="a fixed voxel edge in the cloud's units")
+    ap.add_argument("-v", "--voxel-size", type=float, default=None, help="a fixed voxel edge in the cloud's units; with the octree sampling the smallest voxel")
     ap.add_argument("--downsample-method", choices=("voxel", "spatial-hash", "adaptive"), default="voxel",
-                    help="voxel: fixed size or a search for the target; spatial-hash: one pass at an estimated size; adaptive is not built")
-    ap.add_argument("--adaptive", action="store_true", help="the octree sampling: not built")
-    ap.add_argument("--adaptive-weight", type=float, default=1.0, metavar="POWER", help="weight exponent of the octree sampling (not built)")
+                    help="voxel: fixed size or a search for the target; spatial-hash: one pass at an estimated size; adaptive: octree sampling "
+                         "that keeps detail where the cloud is dense (runs with GS360_PLY_ADAPTIVE=device in the environment, else ends with [ERR])")
+    ap.add_argument("--adaptive", action="store_true", help="deprecated: the same as --downsample-method adaptive")
+    ap.add_argument("--adaptive-weight", type=float, default=1.0, metavar="POWER", help="the octree sampling splits the node with the largest count ** POWER first (0: all alike)")
     ap.add_argument("-a", "--append-ply", action="append", default=[],
                     help="a PLY file to append after the downsampling, relative to the input's folder unless absolute; may be repeated")
     ap.add_argument("-k", "--keep-strategy", choices=("centroid", "center", "first", "random"), default="centroid",
@@ -76,7 +79,11 @@ def main(argv=None):
             ap.error(f"--sky-color {exc}")
 
     adaptive = args.adaptive or args.downsample_method == "adaptive"
-    if adaptive and args.output is not None:
+    try:
+        refused = adaptive and args.output is not None and not pointcloud.adaptive_mode_from_env()
+    except ValueError as exc:
+        return fail(str(exc))
+    if refused:
         return fail("--downsample-method adaptive is not built: the octree's split order is a serial priority queue")
     source_path = Path(os.path.expanduser(args.input)).resolve()
     if is_colmap_text_model_dir(source_path):
@@ -114,7 +121,17 @@ def main(argv=None):
 
     how = args.keep_strategy
     try:
-        if args.downsample_method == "spatial-hash":
+        if adaptive:
+            if args.downsample_method != "adaptive":
+                print("[warn] --adaptive is deprecated by --downsample-method; forcing method=adaptive.")
+            adaptive_target = target_points if has_target else stats.count
+            if adaptive_target == stats.count:
+                print("[adaptive] target not specified; defaulting to input count (no reduction).")
+            print("[adaptive] weight={:.3g} min_voxel={}".format(args.adaptive_weight, f"{args.voxel_size:.6g}" if has_voxel else "auto"))
+            xyz, rgb = pointcloud.adaptive_voxel_downsample(xyz, rgb, adaptive_target, weight_power=args.adaptive_weight, stats=stats,
+                                                            min_voxel_size=args.voxel_size if has_voxel else None, representative=how)
+            print(f"[adaptive] target~{adaptive_target:,} -> {xyz.shape[0]:,} points")
+        elif args.downsample_method == "spatial-hash":
             xyz, rgb = pointcloud.spatial_hash_downsample_one_pass(xyz, rgb, target_points=target_points,
                                                                    voxel_size=args.voxel_size if has_voxel else None, stats=stats,
                                                                    representative=how)

@@ -38,6 +38,7 @@ EXPORTS = (
     "gs360_jpeg_decode_gray_u8", "gs360_png_deflate", "gs360_png_bound", "gs360_mask_finish_u8", "gs360_mask_finish_scratch",
     "gs360_mask_shadow_scratch", "gs360_mask_shadow_candidates_u8", "gs360_mask_shadow_merge_u8",
     "gs360_voxel_scratch", "gs360_cloud_bounds_f32", "gs360_voxel_count_f32", "gs360_voxel_pick_f32",
+    "gs360_octree_scratch", "gs360_octree_pick_f32",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -284,6 +285,9 @@ def load_library(path=None):
         L.gs360_cloud_bounds_f32.argtypes = [vp, vp, i64, vp, sz, C.POINTER(C.c_float), i]
         L.gs360_voxel_count_f32.argtypes = [vp, vp, i64, C.POINTER(C.c_float), C.c_double, vp, sz, C.POINTER(i64), i]
         L.gs360_voxel_pick_f32.argtypes = [vp, vp, i64, C.POINTER(C.c_float), C.c_double, i, vp, sz, vp, vp, vp, C.POINTER(i64), i]
+        L.gs360_octree_scratch.argtypes = [vp, i64, C.POINTER(C.c_size_t)]
+        L.gs360_octree_pick_f32.argtypes = [vp, vp, i64, C.POINTER(C.c_float), C.c_double, i64, C.c_double, C.c_double, i, vp, sz, vp, vp, vp, vp,
+                                            C.POINTER(i64), C.POINTER(C.c_double), i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -817,6 +821,30 @@ class Context:
         _check(self.L.gs360_voxel_pick_f32(self.handle, xyz.ptr, int(n), mm, float(voxel), int(strategy), scratch.ptr, scratch.nbytes,
                                            ptr[0], ptr[1], ptr[2], C.byref(k), slot), self.L)
         return int(k.value)
+
+    # -- adaptive octree sampling of a resident point cloud (gs360/pointcloud.py) -----------------
+    def octree_scratch(self, n):
+        """gs360_octree_scratch: the bytes of scratch gs360_octree_pick_f32 needs for a cloud of n points"""
+        nbytes = C.c_size_t(0)
+        _check(self.L.gs360_octree_scratch(self.handle, int(n), C.byref(nbytes)), self.L)
+        return int(nbytes.value)
+
+    def octree_pick_dev(self, xyz, n, cube_min, cube_size, target, weight_power, min_voxel, strategy, scratch, order=None, slot=0, stages=False):
+        """gs360_octree_pick_f32 -> (picks, starts, counts, stage_ms): uint32 arrays of the k kept leaves in output order (picks is None
+        with VOXEL_SEGMENTS, starts and counts are None without it; they index `order`, a DeviceBuffer of n uint32), and the nine
+        stage times in milliseconds when `stages` is set"""
+        corner = (C.c_float * 3)(*[float(v) for v in cube_min])
+        k = C.c_int64(0)
+        segments = strategy == VOXEL_SEGMENTS
+        pick = None if segments else np.empty(int(target), dtype=np.uint32)
+        starts, counts = (np.empty(int(target), dtype=np.uint32), np.empty(int(target), dtype=np.uint32)) if segments else (None, None)
+        ms = (C.c_double * 9)() if stages else None
+        ptr = [a.ctypes.data if a is not None else None for a in (pick, starts, counts)]
+        _check(self.L.gs360_octree_pick_f32(self.handle, xyz.ptr, int(n), corner, float(cube_size), int(target), float(weight_power), float(min_voxel),
+                                            int(strategy), scratch.ptr, scratch.nbytes, ptr[0], order.ptr if order is not None else None, ptr[1],
+                                            ptr[2], C.byref(k), ms, slot), self.L)
+        k = int(k.value)
+        return tuple(a[:k] if a is not None else None for a in (pick, starts, counts)) + (list(ms) if stages else None,)
 
     def jpeg_decode_dev(self, jobs, status, slot=0):
         """gs360_jpeg_decode_u8: jobs = sequence of JpegDecJob (device pointers; gs360/jpegdec.py fills them), status = DeviceBuffer of

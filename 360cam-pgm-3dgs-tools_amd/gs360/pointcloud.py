@@ -1,4 +1,5 @@
-"""Point-cloud thinning for 3DGS training: the data-parallel part of gs360_PlyOptimizer.py on the GPU (VOX-SPEC v1).
+"""Point-cloud thinning for 3DGS training: the data-parallel part of gs360_PlyOptimizer.py on the GPU (VOX-SPEC v1 and OCT-SPEC v1,
+DESIGN.md 15 and 16).
 
 `Cloud` keeps the points resident on the device; a voxel-size probe of `voxel_downsample_to_target` then costs a key pass, a sort and
 a count, and only the count comes back.  The module functions carry the reference's names, signatures, return values and printed
@@ -8,10 +9,14 @@ Keys are float32: the reference's arrays are float32 and a Python-float voxel is
 float32 arithmetic under NumPy 2.  A voxel passed as a NumPy float64 is taken as float(voxel) and meets the same float32 grid.
 A grid too fine for 64-bit packed keys (the shrink loop's 1e-9 corner) is counted and picked on the host with NumPy.
 
+The adaptive octree sampling (PLY:1174-1407) sorts 36-bit path codes on the device, walks the split queue over counts inside the
+library and picks the kept leaves on the device (`Cloud.adaptive_downsample`, `adaptive_voxel_downsample`); only max_depth=12 is built.
+
 PLY files are read and written here (ASCII, binary little- and big-endian vertex elements; the writer's bytes are the reference's
 binary little-endian x/y/z + red/green/blue file).
 """
 import math
+import os
 import pathlib
 import sys
 from dataclasses import dataclass
@@ -24,6 +29,15 @@ from . import capi
 SKY_AXIS_CHOICES = ("+X", "-X", "+Y", "-Y", "+Z", "-Z")
 SH_C0 = 0.28209479177387814
 STRATEGIES = {"first": capi.VOXEL_FIRST, "center": capi.VOXEL_CENTER, "centroid": capi.VOXEL_CENTROID, "random": capi.VOXEL_SEGMENTS}
+
+
+def adaptive_mode_from_env():
+    """-> True when --downsample-method adaptive runs on the device.  GS360_PLY_ADAPTIVE = off (default: the flag is refused as it was
+    before the octree was built) | device."""
+    mode = os.environ.get("GS360_PLY_ADAPTIVE", "off")
+    if mode not in ("off", "device"):
+        raise ValueError(f"GS360_PLY_ADAPTIVE must be off or device (got {mode!r})")
+    return mode == "device"
 
 
 # ---- statistics -------------------------------------------------------------------------------------------------------------------
@@ -365,7 +379,7 @@ class Cloud:
             self.d_xyz = self._alloc(xyz.nbytes)
             ctx.upload(self.d_xyz, xyz, slot)
             self.scratch = self._alloc(ctx.voxel_scratch(self.n))
-            self._out = None
+            self._out = self._octree = None
             self.minmax = ctx.cloud_bounds_dev(self.d_xyz, self.n, self.scratch, slot)
         except Exception:
             self.close()
@@ -429,6 +443,34 @@ class Cloud:
             else:
                 idx = _host_pick(self.xyz, voxel, self.minmax[:3], representative)
         return idx if return_indices else self.xyz[idx]
+
+    def adaptive_downsample(self, target, weight_power=1.0, min_voxel_size=None, representative="centroid", stats=None):
+        """the pick index of every kept octree leaf, in the reference's output order, as int64 (PLY:1174-1407, max_depth 12); `stats`:
+        the statistics the cube is taken from, when they are not the cloud's own"""
+        n = self.n
+        target = n if target is None or target <= 0 else int(max(1, min(n, target)))
+        if target >= n:
+            return np.arange(n, dtype=np.int64)
+        if representative not in STRATEGIES:
+            raise ValueError(f"Unknown representative strategy: {representative}")
+        if stats is None or stats.count != n:
+            stats = self.stats()
+        extent = np.asarray(stats.extent, dtype=np.float32)
+        cube_size = float(np.max(extent))
+        pad = np.maximum((cube_size - extent) * 0.5, 0.0)
+        cube_min = np.asarray(stats.xyz_min - pad, dtype=np.float32)
+        min_voxel = float(min_voxel_size) if min_voxel_size else 0.0
+        power = float(weight_power) if weight_power is not None else 1.0
+        if self._octree is None:
+            self._octree = (self._alloc(self.ctx.octree_scratch(n)), self._alloc(4 * n))
+        scratch, order = self._octree
+        picks, starts, counts, _ms = self.ctx.octree_pick_dev(self.d_xyz, n, cube_min, cube_size, target, power, min_voxel, STRATEGIES[representative],
+                                                              scratch, order if representative == "random" else None, self.slot)
+        if representative != "random":
+            return picks.astype(np.int64)
+        members = self.ctx.download(order, (n,), np.uint32, self.slot).astype(np.int64)
+        return members[starts.astype(np.int64) + np.random.default_rng().integers(counts.astype(np.int64))]
+
 
 
 _default_ctx = None
@@ -618,3 +660,20 @@ def spatial_hash_downsample_one_pass(xyz, rgb, target_points=None, voxel_size=No
         return _passthrough(xyz, rgb, everything, return_indices)
     print(f"[spatial-hash] voxel={voxel:.6g}  out_points={result[0].shape[0]:,} (approx)")
     return result if return_indices else result[:2]
+
+
+def adaptive_voxel_downsample(xyz, rgb, target_points, weight_power=1.0, stats: Optional[PointCloudStats] = None, min_voxel_size=None,
+                              representative="centroid", max_depth=12, return_indices=False, *, cloud=None):
+    """the adaptive octree sampling that keeps detail where the cloud is dense (PLY:1174-1407): the reference's leaves and picks,
+    index for index; the tree is built to the reference's default depth of 12 only"""
+    n = int(xyz.shape[0])
+    if n == 0:
+        return _passthrough(xyz, rgb, np.zeros((0,), dtype=np.int64), return_indices)
+    target = n if target_points is None or target_points <= 0 else int(max(1, min(n, target_points)))
+    if target >= n:                                        # no tree, no device
+        return _passthrough(xyz, rgb, np.arange(n, dtype=np.int64), return_indices)
+    if max_depth != 12:
+        raise capi.Gs360Error(capi.ERR_UNSUPPORTED, f"an octree of max_depth={max_depth} is not built: path codes hold 12 levels")
+    with _Resident(xyz, cloud) as res:
+        pick_idx = res.adaptive_downsample(target, weight_power, min_voxel_size, representative, stats=stats)
+    return _passthrough(xyz[pick_idx], rgb[pick_idx], pick_idx, return_indices)

@@ -715,6 +715,32 @@ int gs360_voxel_pick_f32(gs360_ctx *ctx, const float *xyz_dev, int64_t n, const 
                          void *scratch_dev, size_t scratch_bytes, uint32_t *pick_dev, uint32_t *order_dev, uint32_t *starts_dev,
                          int64_t *k, int slot);
 
+/* ---- adaptive octree sampling of a resident point cloud (OCT-SPEC v1) ----------------------------------
+ * gs360_PlyOptimizer.py's adaptive_voxel_downsample (PLY:1174-1407) on the DEVICE array of n x 3 float32 (16-byte aligned) that the
+ * voxel calls take.  The caller computes the cube as the reference does (PLY:1231-1242): cube_size = the largest extent, cube_min
+ * (HOST, three floats) = the float32 minimum minus the float32 pad.  A point's path through the octree is a 36-bit code built by
+ * the reference's float32 add chain; (code, index) pairs are sorted stably, the split loop runs on the host over counts alone
+ * (weights are libm's pow((double) count, weight_power), a negative power counts as 0; min_voxel == 0: none), and the kept leaves
+ * are picked on the device over their points in ascending original index.
+ *   pick     *k = the number of leaves kept (<= target); pick[0 .. k) (HOST, room for `target`) = per kept leaf, in the reference's
+ *            output order (weight, then count, descending; then the smallest index ascending), the original index of its
+ *            representative: GS360_VOXEL_FIRST the smallest index, _CENTER / _CENTROID the point nearest the leaf's centre / the
+ *            float32 centroid summed in index order (ties: the smallest index).  GS360_VOXEL_SEGMENTS takes pick = NULL and returns
+ *            order_dev (DEVICE, n uint32: the indices grouped by leaf, ascending inside a leaf) with starts[0 .. k) and
+ *            counts[0 .. k) (HOST, room for `target` each): where each kept leaf lies in order_dev; the caller draws its own
+ *            representative.  With another strategy order_dev, starts and counts may be NULL.
+ *   stage_ms NULL, or a HOST array of nine doubles that receives the milliseconds of the stages (codes, sort, levels, download,
+ *            walk, ordinals, second sort, pick with its download, selection); asking for them drains the stream after every stage.
+ * scratch_dev: device memory of at least gs360_octree_scratch's bytes, 256-byte aligned.  The call returns when its result is there.
+ * Errors: GS360_ERR_ARG for n < 2, target outside [1, n), NULL or misaligned pointers, a scratch that is too small, a cube that is
+ * not finite and positive, a weight power that is not a number; GS360_ERR_UNSUPPORTED for n >= 2^31 and for a weight power at which
+ * pow(n, power) is not finite; GS360_ERR_INTERNAL when a leaf list left its bound (a defect, never data). */
+int gs360_octree_scratch(gs360_ctx *ctx, int64_t n, size_t *bytes);
+int gs360_octree_pick_f32(gs360_ctx *ctx, const float *xyz_dev, int64_t n, const float *cube_min, double cube_size, int64_t target,
+                          double weight_power, double min_voxel, int strategy, void *scratch_dev, size_t scratch_bytes,
+                          uint32_t *pick, uint32_t *order_dev, uint32_t *starts, uint32_t *counts, int64_t *k, double *stage_ms,
+                          int slot);
+
 /* ---- host-buffer conveniences (synchronous: H2D -> kernel -> D2H on `slot`) ----------------- */
 int gs360_equirect_views_u8_host(gs360_ctx *ctx, const uint8_t *src, int W, int H, int C, size_t src_stride,
                                  const gs360_view *views, int n_views,
