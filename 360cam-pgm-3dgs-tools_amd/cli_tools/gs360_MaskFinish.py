@@ -12,8 +12,11 @@ Outputs: `<stem>.png` (mask, alpha), `<stem>_cutout.png`, `<stem>_<mode>.png` (S
 GS360_PNG_ENCODER=device, else by gs360/imageio.py.  Every image is looked at before the first one is finished, so a run that ends
 with an [ERR] line has written nothing.  --include_shadow adds the reference's shadow estimate (SEG:499-558, MSK-SHADOW v1) between
 the close and the expansion when the environment says GS360_MASK_SHADOW=device; the estimate is not pinned against cv2 yet, so
-without that variable the flag is refused as before.  It reads the images in every mode.  Not built, and refused with one [ERR]
-line each: --mode inpaint (Telea inpainting), --include_shadow without GS360_MASK_SHADOW=device, 16-bit images in the compose modes
+without that variable the flag is refused as before.  It reads the images in every mode.  --mode inpaint (SEG:809-815) fills the
+finished mask's region of the image and writes `<stem>_inpaint.png` when the environment says GS360_MASK_INPAINT=device
+(MSK-INPAINT v1: Telea's weights in a level-ordered march; not pinned against cv2.inpaint, so without that variable the mode is
+refused as before).  Not built, and refused with one [ERR] line each: --mode inpaint without GS360_MASK_INPAINT=device,
+--include_shadow without GS360_MASK_SHADOW=device, 16-bit images in the compose modes, in the inpaint mode
 and with the shadow estimate, --edge-fuse-pixels above an image's shorter side or above 1024, an expansion above 512 pixels, an image
 side above 32768.
 """
@@ -26,9 +29,10 @@ if str(_PKG) not in sys.path:
     sys.path.insert(0, str(_PKG))
 
 IMAGE_SUFFIXES = (".jpg", ".jpeg", ".png", ".tif", ".tiff")
-# mode -> (output kind, invert, what follows the stem in the file name); inpaint has no entry: it is not built
+# mode -> (output kind, invert, what follows the stem in the file name); inpaint fills the image under the mask of kind "mask"
 OUTPUTS = {"mask": ("mask", True, ""), "alpha": ("rgba", True, ""), "cutout": ("rgba", False, "_cutout"),
-           "keep_person": ("keep", False, "_keep_person"), "remove_person": ("remove", False, "_remove_person")}
+           "keep_person": ("keep", False, "_keep_person"), "remove_person": ("remove", False, "_remove_person"),
+           "inpaint": ("mask", False, "_inpaint")}
 LAYER_THRESH = 127          # a raw mask or manual layer counts where it is brighter than this
 BATCH = 16                  # images per device call
 
@@ -40,9 +44,10 @@ def create_arg_parser():
     ap.add_argument("--raw-mask-dir", type=str, default=None,
                     help="folder of raw masks <stem>.png from any segmenter: target where brighter than 127, no file = nothing detected")
     ap.add_argument("-o", "--out", type=str, default=None, help="folder for the results (default: _mask beside the input folder)")
-    ap.add_argument("--mode", type=str, default="mask", choices=list(OUTPUTS) + ["inpaint"],
+    ap.add_argument("--mode", type=str, default="mask", choices=list(OUTPUTS),
                     help="what to write: the mask (target black), the image with the mask as alpha, the cutout, or the image with the "
-                         "target kept / blacked out; inpaint is not built")
+                         "target kept / blacked out; inpaint fills the target from its surroundings and runs with "
+                         "GS360_MASK_INPAINT=device in the environment, else ends the run with an [ERR] line")
     ap.add_argument("--close", type=int, default=5, help="side of the ellipse that closes small holes first (1 or less: no closing)")
     ap.add_argument("--include_shadow", action="store_true",
                     help="add the estimated cast shadow to the mask; runs with GS360_MASK_SHADOW=device in the environment, else ends "
@@ -86,15 +91,15 @@ def read_layer(path, size):
 
 
 def survey(images, params, kind, mode, shadow=False):
-    """every image's (W, H) and, for the compose modes and the shadow estimate, whether it is an 8-bit image -> (sizes, None) or
-    (None, the reason this build does not take the run)"""
+    """every image's (W, H) and, for the compose modes, the inpaint mode and the shadow estimate, whether it is an 8-bit image ->
+    (sizes, None) or (None, the reason this build does not take the run)"""
     from PIL import Image
     from gs360 import capi, maskfinish
     sizes = []
     for path in images:
         with Image.open(path) as im:
             sizes.append(im.size)                         # the header alone: the mask mode never reads pixels
-            if kind != "mask" and im.mode.startswith("I"):
+            if (kind != "mask" or mode == "inpaint") and im.mode.startswith("I"):
                 return None, f"{path.name}: 16-bit images are not built for --mode {mode}"
             if shadow and im.mode.startswith("I"):
                 return None, f"{path.name}: 16-bit images are not built for --include_shadow"
@@ -125,7 +130,13 @@ def main(argv=None):
         if value < 0:
             ap.error(f"{flag} must be 0 or greater")
     if args.mode == "inpaint":
-        return fail("--mode inpaint is not built: Telea inpainting is not part of this tool")
+        from gs360 import maskfinish
+        try:
+            on_device = maskfinish.inpaint_mode_from_env()
+        except ValueError as exc:
+            return fail(str(exc))
+        if not on_device:
+            return fail("--mode inpaint is not built: Telea inpainting is not part of this tool")
     if args.include_shadow:
         from gs360 import maskfinish
         try:
@@ -180,13 +191,15 @@ def main(argv=None):
                 adds = [read_layer(manual_dir / f"{maskfinish.manual_key(p)}__add.png", size) if manual_dir is not None else None
                         for p, size in batch]
                 pixels = None
-                if kind != "mask" or args.include_shadow:
+                if kind != "mask" or args.include_shadow or args.mode == "inpaint":
                     pixels = []
                     for p, _size in batch:
                         with Image.open(p) as im:
                             pixels.append(np.asarray(im.convert("RGB")))
                 with ctx.slot_locks[0]:
-                    if args.include_shadow:
+                    if args.mode == "inpaint":
+                        items, _counts = maskfinish.finish_with_inpaint_device(ctx, masks, params, adds, pixels, args.include_shadow)
+                    elif args.include_shadow:
                         items, _counts = maskfinish.finish_with_shadow_device(ctx, masks, params, None, adds, pixels, kind, invert)
                     else:
                         items, _counts = maskfinish.finish_device(ctx, masks, params, adds, pixels, kind, invert)

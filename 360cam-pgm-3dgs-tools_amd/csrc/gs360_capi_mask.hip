@@ -1,5 +1,6 @@
-// gs360_capi_mask.hip -- the mask-finishing entry points of libgs360hip.so (include/gs360.h; MSK-SPEC v1 and MSK-SHADOW v1, DESIGN.md
-// section 14): validation, the scratch layout and the launch sequence of the kernels in gs360_maskmorph.hip and gs360_maskshadow.hip.
+// gs360_capi_mask.hip -- the mask-finishing entry points of libgs360hip.so (include/gs360.h; MSK-SPEC v1, MSK-SHADOW v1 and MSK-INPAINT
+// v1): validation, the scratch layout and the launch sequence of the kernels in gs360_maskmorph.hip,
+// gs360_maskshadow.hip and gs360_maskinpaint.hip.
 // Every grid is sized by the function of gs360_maskplane.h that bounds its kernel.
 #include "gs360_capi_internal.h"
 #include "gs360_maskplane.h"
@@ -439,5 +440,156 @@ int gs360_mask_shadow_merge_u8(gs360_ctx* c, const gs360_shadow_job* jobs, int n
     HIP_TRY(hipMemcpyAsync(&err, scratch_dev, sizeof(err), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (err) return fail(GS360_ERR_INTERNAL, "a label walk ran past its bound");
+    return GS360_OK;
+}
+
+// ---- inpainting the masked region (MSK-INPAINT v1): gs360_maskinpaint.hip's kernels ----------------------------------------------
+namespace {
+
+constexpr size_t kMiHeadBytes = (sizeof(MiHead) + 255) / 256 * 256;
+constexpr size_t kMiTableBytes = (size_t)kMiMaxOffsets * 16 / 256 * 256 + 256;   // per job: (dy, dx) pairs, |r|, 1 / |r|^2
+// a job's area of the scratch behind the head: its offset table, then vert, lev and dist
+struct InpaintArea { size_t vert, lev, dist, total; };
+InpaintArea inpaint_area(int H, int W) {
+    InpaintArea a;
+    const size_t px = (size_t)H * W;
+    a.vert = kMiTableBytes;
+    a.lev = a.vert + round_up(px * 2, 256);
+    a.dist = a.lev + round_up(px * 2, 256);
+    a.total = a.dist + round_up(px * 4, 256);
+    return a;
+}
+
+int check_inpaint_job(int k, const gs360_inpaint_job& j) {
+    if (j.H < 1 || j.W < 1) return fail(GS360_ERR_ARG, "job %d: image of %d x %d", k, j.W, j.H);
+    if (j.H > GS360_MASK_MAX_SIDE || j.W > GS360_MASK_MAX_SIDE)
+        return fail(GS360_ERR_UNSUPPORTED, "job %d: image sides are 1..%d (got %d x %d)", k, GS360_MASK_MAX_SIDE, j.W, j.H);
+    if (!j.image || !j.fill) return fail(GS360_ERR_ARG, "job %d: NULL image or fill mask", k);
+    if ((j.image_stride && j.image_stride < (size_t)j.W * 3) || (j.fill_stride && j.fill_stride < (size_t)j.W))
+        return fail(GS360_ERR_ARG, "job %d: a stride below a row", k);
+    if (j.radius < 1) return fail(GS360_ERR_ARG, "job %d: inpaint radius %d", k, j.radius);
+    if (j.radius < 3 || j.radius > GS360_INPAINT_MAX_RADIUS)
+        return fail(GS360_ERR_UNSUPPORTED, "job %d: inpaint radius %d outside 3..%d", k, j.radius, GS360_INPAINT_MAX_RADIUS);
+    return 0;
+}
+
+// the jobs from k0 on that make one batch: at most GS360_MAX_VIEWS, their pixels numbered below 2^32 (a job has 2^30 at most)
+int inpaint_batch_len(const gs360_inpaint_job* jobs, int k0, int n_jobs, uint64_t* pixels) {
+    int n = 0;
+    *pixels = 0;
+    while (k0 + n < n_jobs && n < GS360_MAX_VIEWS && *pixels + (uint64_t)jobs[k0 + n].H * jobs[k0 + n].W <= UINT32_MAX) {
+        *pixels += (uint64_t)jobs[k0 + n].H * jobs[k0 + n].W;
+        ++n;
+    }
+    return n;
+}
+
+int check_inpaint_jobs(const gs360_inpaint_job* jobs, int n_jobs, size_t* need) {
+    if (n_jobs < 0) return fail(GS360_ERR_ARG, "n_jobs < 0");
+    if (n_jobs && !jobs) return fail(GS360_ERR_ARG, "NULL argument");
+    *need = 0;
+    for (int k = 0; k < n_jobs; ++k)
+        if (int rc = check_inpaint_job(k, jobs[k])) return rc;
+    uint64_t pixels;
+    for (int k0 = 0, n; k0 < n_jobs; k0 += n) {           // a batch's scratch: the head, the jobs' areas, the list
+        n = inpaint_batch_len(jobs, k0, n_jobs, &pixels);
+        size_t b = kMiHeadBytes + round_up((size_t)pixels * 4, 256);
+        for (int k = k0; k < k0 + n; ++k) b += inpaint_area(jobs[k].H, jobs[k].W).total;
+        *need = std::max(*need, b);
+    }
+    return 0;
+}
+
+// the offsets (dy, dx) with 0 < dy^2 + dx^2 <= radius^2 in row-major order, |r| and 1 / |r|^2 in double rounded to float32, laid
+// out as a job's table -> their number
+int inpaint_table(int radius, uint8_t* table) {
+    int32_t* off = (int32_t*)table;
+    float *rlen = (float*)(table + (size_t)kMiMaxOffsets * 8), *inv2 = rlen + kMiMaxOffsets;
+    int n = 0;
+    for (int dy = -radius; dy <= radius; ++dy)
+        for (int dx = -radius; dx <= radius; ++dx) {
+            const int d = dy * dy + dx * dx;
+            if (d == 0 || d > radius * radius) continue;
+            off[2 * n] = dy; off[2 * n + 1] = dx;
+            rlen[n] = (float)std::sqrt((double)d); inv2[n] = (float)(1.0 / (double)d);
+            ++n;
+        }
+    return n;
+}
+
+template <class Tiles>
+int inpaint_step(MiLaunch& L, hipStream_t s, MiStep step, Tiles tiles_of) {
+    return run_step(L, [step](const MiLaunch& l, hipStream_t st) { return launch_mask_inpaint(step, l, st); }, s, tiles_of);
+}
+
+}  // namespace
+
+int gs360_mask_inpaint_scratch(const gs360_inpaint_job* jobs, int n_jobs, size_t* bytes) {
+    if (!bytes) return fail(GS360_ERR_ARG, "NULL argument");
+    size_t need = 0;
+    if (int rc = check_inpaint_jobs(jobs, n_jobs, &need)) return rc;
+    *bytes = need;
+    return GS360_OK;
+}
+
+int gs360_mask_inpaint_u8(gs360_ctx* c, const gs360_inpaint_job* jobs, int n_jobs, void* scratch_dev, size_t scratch_bytes,
+                          uint32_t* levels_dev, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    size_t need = 0;
+    if (int rc = check_inpaint_jobs(jobs, n_jobs, &need)) return rc;
+    if (n_jobs == 0) return GS360_OK;
+    hipStream_t s;
+    if (int rc = begin_call(c, slot, n_jobs, scratch_dev, scratch_bytes, need, levels_dev, &s)) return rc;
+    MiHead* head = (MiHead*)scratch_dev;
+    HIP_TRY(hipMemsetAsync(head, 0, offsetof(MiHead, filled), s));                     // the error word: once per call
+    std::vector<uint8_t> tables((size_t)GS360_MAX_VIEWS * kMiTableBytes);
+    std::vector<uint32_t> seen(offsetof(MiHead, offs) / 4);                              // the head up to the histogram's end
+    uint64_t pixels;
+    for (int k0 = 0, n; k0 < n_jobs; k0 += n) {
+        n = inpaint_batch_len(jobs, k0, n_jobs, &pixels);
+        MiLaunch L;
+        std::memset(&L, 0, sizeof(L));
+        L.n_jobs = n; L.head = head; L.levels = levels_dev + k0; L.list_cap = (uint32_t)pixels;
+        HIP_TRY(hipMemsetAsync(head->filled, 0, sizeof(MiHead) - offsetof(MiHead, filled), s));
+        uint8_t* at = (uint8_t*)scratch_dev + kMiHeadBytes;
+        uint32_t base = 0;
+        for (int k = 0; k < n; ++k) {
+            const gs360_inpaint_job& j = jobs[k0 + k];
+            const InpaintArea a = inpaint_area(j.H, j.W);
+            MiJob& J = L.job[k];
+            J.img = (uint8_t*)j.image; J.fill = (const uint8_t*)j.fill;
+            J.img_stride = stride_or(j.image_stride, (size_t)j.W * 3);
+            J.fill_stride = stride_or(j.fill_stride, (size_t)j.W);
+            J.H = j.H; J.W = j.W; J.px_base = base;
+            base += (uint32_t)j.H * (uint32_t)j.W;
+            J.n_off = inpaint_table(j.radius, tables.data() + (size_t)k * kMiTableBytes);
+            J.off = (const int32_t*)at; J.rlen = (const float*)(at + (size_t)kMiMaxOffsets * 8); J.inv2 = J.rlen + kMiMaxOffsets;
+            J.vert = (uint16_t*)(at + a.vert); J.lev = (uint16_t*)(at + a.lev); J.dist = (float*)(at + a.dist);
+            HIP_TRY(hipMemcpyAsync(at, tables.data() + (size_t)k * kMiTableBytes, kMiTableBytes, hipMemcpyHostToDevice, s));
+            at += a.total;
+        }
+        L.list = (uint32_t*)at;
+        if (int rc = inpaint_step(L, s, kMiCols, [&](int, MiJob& J) { return mk_item_tiles(mi_cols_items(J)); })) return rc;
+        if (int rc = inpaint_step(L, s, kMiRows, [&](int, MiJob& J) { return row_tiles(J, kMiRowTile); })) return rc;
+        L.total_tiles = 1;
+        HIP_TRY(launch_mask_inpaint(kMiScan, L, s));
+        if (int rc = inpaint_step(L, s, kMiScatter, [&](int, MiJob& J) { return row_tiles(J, kMiRowTile); })) return rc;
+        // the one read of the batch: the error word so far, the pixels per level (the tables above are read by now as well)
+        HIP_TRY(hipMemcpyAsync(seen.data(), head, seen.size() * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (seen[0]) return fail(GS360_ERR_INTERNAL, "an inpaint lane left its bound");
+        const uint32_t* hist = seen.data() + offsetof(MiHead, hist) / 4;
+        if (hist[kMiFar]) return fail(GS360_ERR_UNSUPPORTED, "a masked region is deeper than %d levels", kMiMaxLevel);
+        for (int level = 1; level <= kMiMaxLevel; ++level) {
+            if (!hist[level]) continue;                  // (the levels of a batch have no gaps; an empty one has nothing to launch)
+            L.level = level; L.items = hist[level];
+            L.total_tiles = (int32_t)mk_item_tiles(hist[level]);
+            HIP_TRY(launch_mask_inpaint(kMiFill, L, s));
+        }
+    }
+    uint32_t err = 0;                                     // a fill lane that left its bound: the result is not to be used
+    HIP_TRY(hipMemcpyAsync(&err, head, sizeof(err), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err) return fail(GS360_ERR_INTERNAL, "an inpaint lane left its bound");
     return GS360_OK;
 }

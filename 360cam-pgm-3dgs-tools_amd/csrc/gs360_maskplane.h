@@ -1,6 +1,6 @@
-// gs360_maskplane.h -- what the mask kernels (gs360_maskmorph.hip, gs360_maskshadow.hip), their glue (gs360_capi_mask.hip) and the two
-// host checks (tests/tools/mask*_hostcheck.hip) share: the jobs and launches of both families, the steps on a bit plane and the launch
-// geometry of every step (MSK-SPEC v1 and MSK-SHADOW v1).  A mask lives as a bit plane: bit x & 31 of dword
+// gs360_maskplane.h -- what the mask kernels (gs360_maskmorph.hip, gs360_maskshadow.hip, gs360_maskinpaint.hip), their glue
+// (gs360_capi_mask.hip) and the host checks (tests/tools/mask*_hostcheck.hip) share: the jobs and launches of the families, the steps on a
+// bit plane and the launch geometry of every step (MSK-SPEC v1, MSK-SHADOW v1 and MSK-INPAINT v1).  A mask lives as a bit plane: bit x & 31 of dword
 // x >> 5, pw = ceil(W / 32) dwords per row, bits at columns >= W zero.  What is marked MK_HD is host-callable, so that the host
 // checks can step it under a sanitizer and the glue sizes a grid with the function that bounds the kernel.
 #pragma once
@@ -79,6 +79,45 @@ static_assert(sizeof(MsLaunch) <= 4096, "a launch travels by value as the kernel
 enum MsStep { kMsPixel, kMsBlurRows, kMsBlurCols, kMsLogic, kMsLabelInit, kMsLabelMerge, kMsLabelFlatten, kMsBorder, kMsFill, kMsArea, kMsSelect };
 hipError_t launch_mask_shadow(MsStep step, const MsLaunch& L, hipStream_t s);
 
+// Inpainting the masked region (gs360_maskinpaint.hip, MSK-INPAINT v1): one step over a batch of up to GS360_MAX_VIEWS images whose
+// pixels are numbered through the batch (px_base + y W + x, below 2^32).  A job's planes hold one entry per pixel: `vert` the
+// distance to the nearest pixel outside F in the pixel's column (kMiFar: none within kMiMaxLevel), `lev` L and `dist` T.
+constexpr int kMiThreads = kMkThreads;
+constexpr int kMiMaxLevel = 4095;                        // the largest K; a level of kMiFar marks a pixel beyond it
+constexpr int kMiFar = kMiMaxLevel + 1;
+constexpr int kMiMaxRadius = 8, kMiMaxOffsets = 196;     // the lattice points of a disc of radius 8 without its centre
+constexpr int kMiScanPer = (kMiFar + kMiThreads) / kMiThreads;   // levels a lane of the scan sums: 17, 256 x 17 >= 4097
+struct MiHead {                                          // the start of the call's scratch: err cleared per call, the rest per batch
+    uint32_t err, pad[15];                               // set when a lane left a bound (a defect)
+    uint32_t filled[GS360_MAX_VIEWS];                    // pixels of F per job
+    uint32_t hist[kMiFar + 1];                           // pixels per level over the batch; [0] stays 0
+    uint32_t offs[kMiFar + 1];                           // where a level's pixels begin in the list
+    uint32_t cursor[kMiFar + 1];                         // pixels of a level scattered so far
+};
+struct MiJob {
+    uint8_t* img;                        // H x W x 3, filled in place
+    const uint8_t* fill;                 // F: H x W bytes, set where > 0
+    int64_t img_stride, fill_stride;
+    uint16_t *vert, *lev;
+    float* dist;
+    const int32_t* off;                  // n_off x (dy, dx), row-major order (device memory)
+    const float *rlen, *inv2;            // |r| and 1 / |r|^2 per offset (device memory)
+    int32_t H, W, n_off;
+    uint32_t px_base;
+    int32_t tile_base, tiles_x, pad[2];
+};
+struct MiLaunch {
+    MiJob job[GS360_MAX_VIEWS];
+    int32_t n_jobs, total_tiles, level, pad;
+    uint32_t items, list_cap;            // fill: the level's pixels; the list's entries
+    MiHead* head;
+    uint32_t* list;                      // the batch's pixels of F grouped by level
+    uint32_t* levels;                    // n_jobs: K per job (the caller's buffer)
+};
+static_assert(sizeof(MiLaunch) <= 4096, "a launch travels by value as the kernels' argument");
+enum MiStep { kMiCols, kMiRows, kMiScan, kMiScatter, kMiFill };
+hipError_t launch_mask_inpaint(MiStep step, const MiLaunch& L, hipStream_t s);
+
 // ---- bits --------------------------------------------------------------------------------------------------------------------------
 MK_HD inline int mk_lo(int a, int b) { return a < b ? a : b; }
 MK_HD inline int mk_hi(int a, int b) { return a > b ? a : b; }
@@ -124,6 +163,8 @@ MK_HD inline int mk_element_halo(const int32_t* rows, int kw, int kh) {
 MK_HD inline void mk_atomic_or(uint32_t* p, uint32_t v) { __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 MK_HD inline void mk_atomic_add(uint32_t* p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 MK_HD inline int32_t mk_atomic_min(int32_t* p, int32_t v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+MK_HD inline uint32_t mk_atomic_fetch_add(uint32_t* p, uint32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+MK_HD inline void mk_atomic_max(uint32_t* p, uint32_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 MK_HD inline int32_t mk_atomic_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- launch geometry: the kernel's bound, the glue's grid and the host checks' loops all take a step's tiles or items from here ------
@@ -155,6 +196,10 @@ MK_HD inline int64_t mk_fuse_items(const MkJob& J) { return 2 * (int64_t)J.pw + 
 // border: the pixels of the four border lines; area: (band of kMsAreaRows cell rows, dword column), a plane of one row has no cells
 MK_HD inline int64_t ms_border_items(const MsJob& J) { return 2 * (int64_t)J.W + 2 * (int64_t)J.H; }
 MK_HD inline int64_t ms_area_items(const MsJob& J) { return J.H < 2 ? 0 : (int64_t)J.pw * ((J.H - 1 + kMsAreaRows - 1) / kMsAreaRows); }
+// inpaint: the column pass takes a column per item, the row pass and the scatter a pixel per lane along a row, the fill a listed pixel
+// per item; the scan is one workgroup
+constexpr MkTile kMiRowTile = {kMiThreads, 1};
+MK_HD inline int64_t mi_cols_items(const MiJob& J) { return J.W; }
 MK_HD inline int64_t mk_item_tiles(int64_t items) { return (items + kMkThreads - 1) / kMkThreads; }
 // one launch of a step's kernel over the batch's tiles; a batch without tiles launches nothing
 template <class Launch>

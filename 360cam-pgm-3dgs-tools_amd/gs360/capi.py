@@ -37,6 +37,7 @@ EXPORTS = (
     "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub", "gs360_jpeg_decode_u8", "gs360_jpeg_decode_scratch",
     "gs360_jpeg_decode_gray_u8", "gs360_png_deflate", "gs360_png_bound", "gs360_mask_finish_u8", "gs360_mask_finish_scratch",
     "gs360_mask_shadow_scratch", "gs360_mask_shadow_candidates_u8", "gs360_mask_shadow_merge_u8",
+    "gs360_mask_inpaint_scratch", "gs360_mask_inpaint_u8",
     "gs360_voxel_scratch", "gs360_cloud_bounds_f32", "gs360_voxel_count_f32", "gs360_voxel_pick_f32",
     "gs360_octree_scratch", "gs360_octree_pick_f32",
 )
@@ -57,6 +58,8 @@ MASK_MAX_ELEMENT = 1025
 MASK_MAX_FUSE = 1024                 # GS360_MASK_MAX_FUSE: the largest edge-fuse strip (and spread)
 SHADOW_MAX_PIXELS = 1 << 30          # GS360_SHADOW_MAX_PIXELS / GS360_SHADOW_MAX_RADIUS: the shadow estimate's largest image and filter radius
 SHADOW_MAX_RADIUS = 255
+INPAINT_MIN_RADIUS, INPAINT_MAX_RADIUS = 3, 8   # gs360_mask_inpaint_u8's radii (GS360_INPAINT_MAX_RADIUS) and its largest K
+INPAINT_MAX_LEVEL = 4095             # GS360_INPAINT_MAX_LEVEL
 VOXEL_FIRST, VOXEL_CENTER, VOXEL_CENTROID, VOXEL_SEGMENTS = 0, 1, 2, 3   # GS360_VOXEL_*: the `strategy` of gs360_voxel_pick_f32
 VOXEL_MAX_POINTS = (1 << 31) - 1     # GS360_VOXEL_MAX_POINTS: indices are 32-bit on the device
 ERR_ARG = -1                         # GS360_ERR_ARG / GS360_ERR_UNSUPPORTED
@@ -135,6 +138,12 @@ class ShadowJob(C.Structure):
                 ("open_kw", C.c_int32), ("open_kh", C.c_int32),
                 ("close_rows", C.c_void_p), ("weights", C.c_void_p), ("sdiv", C.c_void_p),
                 ("near_rows", C.c_void_p), ("sclose_rows", C.c_void_p), ("open_rows", C.c_void_p)]
+
+
+class InpaintJob(C.Structure):
+    """gs360_inpaint_job: one image of a batched inpaint call (device pointers)."""
+    _fields_ = [("image", C.c_void_p), ("image_stride", C.c_size_t), ("fill", C.c_void_p), ("fill_stride", C.c_size_t),
+                ("H", C.c_int32), ("W", C.c_int32), ("radius", C.c_int32), ("pad", C.c_int32)]
 
 
 class JpegDecJob(C.Structure):
@@ -280,6 +289,8 @@ def load_library(path=None):
         L.gs360_mask_shadow_scratch.argtypes = [C.POINTER(ShadowJob), i, C.POINTER(C.c_size_t)]
         L.gs360_mask_shadow_candidates_u8.argtypes = [vp, C.POINTER(ShadowJob), i, vp, sz, vp, i]
         L.gs360_mask_shadow_merge_u8.argtypes = [vp, C.POINTER(ShadowJob), i, vp, sz, vp, i]
+        L.gs360_mask_inpaint_scratch.argtypes = [C.POINTER(InpaintJob), i, C.POINTER(C.c_size_t)]
+        L.gs360_mask_inpaint_u8.argtypes = [vp, C.POINTER(InpaintJob), i, vp, sz, vp, i]
         i64 = C.c_int64
         L.gs360_voxel_scratch.argtypes = [vp, i64, C.POINTER(C.c_size_t)]
         L.gs360_cloud_bounds_f32.argtypes = [vp, vp, i64, vp, sz, C.POINTER(C.c_float), i]
@@ -789,6 +800,24 @@ class Context:
         """gs360_mask_shadow_merge_u8 on the scratch the candidates call left: M into every job's dst, count(M) into `counts`;
         returns when the kernels are done"""
         self._mask_shadow_call(self.L.gs360_mask_shadow_merge_u8, jobs, scratch, counts, slot, scratch_bytes)
+
+    def mask_inpaint_scratch(self, jobs):
+        """gs360_mask_inpaint_scratch: jobs = sequence of InpaintJob -> the bytes of scratch one gs360_mask_inpaint_u8 call on them needs"""
+        n = C.c_size_t(0)
+        arr = (InpaintJob * max(len(jobs), 1))(*jobs)
+        _check(self.L.gs360_mask_inpaint_scratch(arr, len(jobs), C.byref(n)), self.L)
+        return int(n.value)
+
+    def mask_inpaint_dev(self, jobs, scratch, levels, slot=0, scratch_bytes=None):
+        """gs360_mask_inpaint_u8: jobs = sequence of InpaintJob whose images are filled in place, scratch = DeviceBuffer of
+        mask_inpaint_scratch(jobs) bytes, levels = DeviceBuffer of len(jobs) uint32 (K per job).  Returns when the kernels are done."""
+        if levels.nbytes < 4 * len(jobs):
+            raise ValueError("levels buffer below 4 bytes per job")
+        nbytes = scratch.nbytes if scratch_bytes is None else int(scratch_bytes)
+        if nbytes > scratch.nbytes:
+            raise ValueError("scratch_bytes larger than the scratch buffer")
+        arr = (InpaintJob * max(len(jobs), 1))(*jobs)
+        _check(self.L.gs360_mask_inpaint_u8(self.handle, arr, len(jobs), scratch.ptr, nbytes, levels.ptr, slot), self.L)
 
     # -- JPEG files decoded into device images (gs360/jpegdec.py) ------------------------------
     # -- voxel downsampling of a resident point cloud (gs360/pointcloud.py) -----------------------

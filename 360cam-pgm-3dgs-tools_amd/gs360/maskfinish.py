@@ -9,6 +9,9 @@ With the shadow estimate (MSK-SHADOW v1, SEG:499-558 between the close and the e
 (csrc/gs360_maskshadow.hip): gs360_mask_shadow_candidates_u8 leaves the person plane, its count and the shadow candidates on the device,
 the host turns the count into element sizes (shadow_sizes), and gs360_mask_shadow_merge_u8 writes M = person | shadow, which the
 finishing call then reads from device memory.  The Gaussian's weights and the saturation divisors are data as well.
+
+Inpainting (MSK-INPAINT v1, the reference's --mode inpaint, SEG:809-815) comes after the chain: the finished mask, written with kind
+"mask" and invert off, is the fill mask F of gs360_mask_inpaint_u8 (csrc/gs360_maskinpaint.hip), which fills the image in place.
 """
 import dataclasses
 import math
@@ -131,6 +134,32 @@ def shadow_mode_from_env():
     if mode not in ("off", "device"):
         raise ValueError(f"GS360_MASK_SHADOW must be off or device (got {mode!r})")
     return mode == "device"
+
+
+INPAINT_RADIUS = 5                                       # cv2.inpaint's inpaintRadius in the reference (SEG:73)
+
+
+def inpaint_mode_from_env():
+    """-> True when --mode inpaint runs the device stage.  GS360_MASK_INPAINT = off (default: the mode is refused as before; the
+    stage's parity with cv2.inpaint is not pinned) | device."""
+    mode = os.environ.get("GS360_MASK_INPAINT", "off")
+    if mode not in ("off", "device"):
+        raise ValueError(f"GS360_MASK_INPAINT must be off or device (got {mode!r})")
+    return mode == "device"
+
+
+def inpaint_offsets(radius=INPAINT_RADIUS):
+    """-> (n x 2 int32 (dy, dx), |r| and 1 / |r|^2 as float32): MSK-INPAINT's neighbourhood, the offsets with
+    0 < dy^2 + dx^2 <= radius^2 in row-major order; both numbers are taken in double and rounded to float32, as the library does"""
+    radius = int(radius)
+    if not capi.INPAINT_MIN_RADIUS <= radius <= capi.INPAINT_MAX_RADIUS:
+        raise ValueError(f"inpaint radius must be {capi.INPAINT_MIN_RADIUS}..{capi.INPAINT_MAX_RADIUS} (got {radius})")
+    dy, dx = np.mgrid[-radius:radius + 1, -radius:radius + 1]
+    d = (dy * dy + dx * dx).reshape(-1)
+    use = (d > 0) & (d <= radius * radius)
+    pairs = np.stack([dy.reshape(-1)[use], dx.reshape(-1)[use]], axis=1).astype(np.int32)
+    d = d[use].astype(np.float64)
+    return pairs, np.sqrt(d).astype(np.float32), (1.0 / d).astype(np.float32)
 
 
 def gaussian_weights(sigma):
@@ -370,3 +399,65 @@ def finish_with_shadow(ctx, masks, params=None, shadow=None, adds=None, images=N
     with ctx.slot_locks[slot]:
         items, counts = finish_with_shadow_device(ctx, masks, params, shadow, adds, images, kind, invert, slot)
         return _download_and_free(ctx, items, slot), counts
+
+
+def inpaint_device(ctx, images, fills, radius=INPAINT_RADIUS, slot=0):
+    """(the caller holds `slot`) images: [(DeviceBuffer of H x W x 3 bytes, H, W)], filled in place; fills: per image a DeviceBuffer
+    of H x W bytes, set where > 0 (a finished mask of kind "mask" with invert off) -> K per image as a uint32 array: the levels
+    that were filled, 0 for a mask that is empty or covers the image (the image is left alone then).  Returns when the kernels are
+    done."""
+    n = len(images)
+    if len(fills) != n:
+        raise ValueError("one fill mask per image")
+    if not n:
+        return np.zeros(0, np.uint32)
+    jobs = []
+    for (buf, H, W), fill in zip(images, fills):
+        j = capi.InpaintJob()
+        j.image, j.fill, j.H, j.W, j.radius = buf.ptr, fill.ptr, int(H), int(W), int(radius)
+        jobs.append(j)
+    owned = []
+    try:
+        owned.append(ctx.alloc(ctx.mask_inpaint_scratch(jobs)))
+        owned.append(ctx.alloc(4 * n))
+        ctx.mask_inpaint_dev(jobs, owned[0], owned[1], slot)
+        return ctx.download(owned[1], (n,), np.uint32, slot)
+    finally:
+        for b in owned:
+            ctx.free(b)
+
+
+def finish_with_inpaint_device(ctx, masks, params=None, adds=None, images=None, shadow=None, radius=INPAINT_RADIUS, slot=0):
+    """(the caller holds `slot`) the finishing chain with kind "mask" and invert off -- after the shadow estimate when `shadow` is a
+    ShadowParams or True (the defaults) -- and the finished masks' regions of the images inpainted ->
+    ([(DeviceBuffer, H, W, 3, 1, 0)] the filled images left on the device, in pngenc's item form, K per image).  images: per mask
+    an H x W x 3 uint8 array; its copy on the device serves the shadow estimate, is filled in place and is the output.  The masks
+    never leave the device.  The output buffers are the caller's to free."""
+    params = params or Params()
+    if images is None or len(images) != len(masks):
+        raise ValueError("inpainting needs one image per mask")
+    shapes = _shapes(masks)
+    d_images, merged, finished = [], [], []
+    try:
+        for im, (H, W) in zip(images, shapes):
+            if isinstance(im, capi.DeviceBuffer):
+                raise ValueError("inpainting fills its own copy of an image: give arrays")
+            _device_plane(ctx, im, (H, W, 3), "image", d_images, slot)
+        if shadow:                                       # as finish_with_shadow_device, on the images that are resident already
+            merged, _counts = shadow_device(ctx, masks, d_images, params, shadow if isinstance(shadow, ShadowParams) else None, slot)
+            params = dataclasses.replace(params, close=1, thresh=0)
+            masks = [(H, W, m) for (H, W), m in zip(shapes, merged)]
+        finished, _counts = finish_device(ctx, masks, params, adds, None, "mask", False, slot)
+        levels = inpaint_device(ctx, [(b, H, W) for b, (H, W) in zip(d_images, shapes)], [it[0] for it in finished], radius, slot)
+        items, d_images = [(b, H, W, 3, 1, 0) for b, (H, W) in zip(d_images, shapes)], []
+        return items, levels
+    finally:
+        for b in d_images + merged + [it[0] for it in finished]:
+            ctx.free(b)
+
+
+def finish_with_inpaint(ctx, masks, params=None, adds=None, images=None, shadow=None, radius=INPAINT_RADIUS, slot=0):
+    """finish_with_inpaint_device with the outputs brought back: -> ([H x W x 3 uint8 arrays], K per image)"""
+    with ctx.slot_locks[slot]:
+        items, levels = finish_with_inpaint_device(ctx, masks, params, adds, images, shadow, radius, slot)
+        return _download_and_free(ctx, items, slot), levels

@@ -684,6 +684,37 @@ int gs360_mask_shadow_candidates_u8(gs360_ctx *ctx, const gs360_shadow_job *jobs
 int gs360_mask_shadow_merge_u8(gs360_ctx *ctx, const gs360_shadow_job *jobs, int n_jobs, void *scratch_dev, size_t scratch_bytes,
                                uint32_t *counts_dev, int slot);
 
+/* ---- inpainting the masked region (MSK-INPAINT v1) ------------------------------------------------------
+ * apply_mode's `inpaint` of gs360_SegmentationMaskTool.py (SEG:809-815: cv2.inpaint(image, mask, 5, INPAINT_TELEA)) on
+ * device-resident data: Telea's weights with a level-ordered march in place of the heap, so that the result depends on no order.
+ * `fill` is F, H x W bytes set where > 0 -- what gs360_mask_finish_u8 writes with GS360_MASK_OUT_MASK and invert = 0.  Per pixel of
+ * F: d2 = the exact squared distance to the nearest pixel outside F, L = the smallest k with k^2 >= d2, T = sqrtf(d2); the pixels of
+ * level k = 1 .. K = max L are computed from the pixels of lower levels within `radius` and written to `image` in place, one launch
+ * per level over the batch's list of pixels (DESIGN.md gives the arithmetic op by op; tests/maskinpaint_np.py restates it).  Pixels
+ * outside F are never written.  An image whose F is empty or covers it whole is left untouched, with levels_dev[k] = 0.
+ * levels_dev (device memory) receives each job's K.  scratch_dev: device memory of at least gs360_mask_inpaint_scratch's bytes for
+ * the same jobs, 256-byte aligned.  Per batch of up to GS360_MAX_VIEWS jobs (n_jobs may exceed that) the call reads the batch's
+ * level counts back ONCE, with one stream synchronisation, to size the launches of the levels; it reads its error word when the last
+ * launch is done and returns then.
+ * Errors: GS360_ERR_UNSUPPORTED for a side above 32768, a radius outside 3..8 (below 1 + sqrt 2 a pixel may have no lower level in
+ * reach) and for K > 4095 (d2 stays exact in float32, the launches stay bounded; no image is written then); GS360_ERR_ARG for NULL
+ * pointers, a stride below a row, a radius below 1, a scratch that is too small; GS360_ERR_INTERNAL when a lane left one of its
+ * bounds (a defect, never data). */
+#define GS360_INPAINT_MAX_RADIUS 8
+#define GS360_INPAINT_MAX_LEVEL 4095
+typedef struct gs360_inpaint_job {
+    void *image;                /* H x W x 3 uint8 RGB, filled in place */
+    size_t image_stride;
+    const void *fill;           /* H x W uint8 F */
+    size_t fill_stride;
+    int32_t H, W;
+    int32_t radius;             /* Telea's epsilon: 5 in the reference (SEG:73) */
+    int32_t pad;
+} gs360_inpaint_job;
+int gs360_mask_inpaint_scratch(const gs360_inpaint_job *jobs, int n_jobs, size_t *bytes);
+int gs360_mask_inpaint_u8(gs360_ctx *ctx, const gs360_inpaint_job *jobs, int n_jobs, void *scratch_dev, size_t scratch_bytes,
+                          uint32_t *levels_dev, int slot);
+
 /* ---- voxel downsampling of a resident point cloud (VOX-SPEC v1) ----------------------------------------
  * gs360_PlyOptimizer.py's compute_point_cloud_stats, _unique_voxel_count and voxel_downsample_by_size (PLY:110-128, 747-862) on a
  * DEVICE array of n x 3 float32 (16-byte aligned) that stays where it is from call to call:
