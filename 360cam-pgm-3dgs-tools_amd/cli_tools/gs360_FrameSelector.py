@@ -13,8 +13,11 @@ gs360_frame_stats_u8 (+ gs360_frame_fft_energy with `--fft device`); the optical
 on a thread pool (`--workers`, default: gs360.framescore's own, at most 16) that runs ahead of launches of 16 frames; with
 GS360_JPEG_DECODER=device baseline .jpg / .jpeg frames are decoded on the GPU instead, once for the scoring and the flow pass
 (gs360/framesource.py), and one more [INFO] line counts them.  The
-selection itself is gs360/frameselect.py.  8-bit sources only: a 16-bit or float image ends the run with one [ERR] line and exit
-code 1 before anything is moved.  The reference's memory-pressure limiter and its stdin listener are left out.
+selection itself is gs360/frameselect.py.  8-bit sources by default: a 16-bit or float image ends the run with one [ERR] line and
+exit code 1 before anything is moved.  With GS360_FS_DEPTH16=device (FS-DEPTH16 v1) 16-bit PNG / TIFF frames, those Video2Frames
+writes for sources of more than 8 bits per sample, are scored (gs360_frame_stats_u16 / gs360_frame_edge_u16), tracked
+(gs360_frame_flow_u16), selected and moved like any others, alone or mixed with 8-bit frames, and one more [INFO] line counts them;
+any other value of the variable is one [ERR] line.  The reference's memory-pressure limiter and its stdin listener are left out.
 
 main(argv, score_records=..., flow_magnitudes=...) replaces the two GPU seams, for tests that replay recorded scores.
 """
@@ -162,6 +165,8 @@ def main(argv=None, *, score_records=None, flow_magnitudes=None):
     scoring_needed = not args.apply_csv and not args.reselect_csv
     try:
         device_decoder = jpegdec.device_decoder_enabled()      # GS360_JPEG_DECODER
+        depth16 = framescore.depth16_mode_from_env()           # GS360_FS_DEPTH16
+        framescore.depth16_files.clear()
     except ValueError as exc:
         print(f"[ERR] {exc}")
         sys.exit(1)
@@ -277,6 +282,8 @@ def main(argv=None, *, score_records=None, flow_magnitudes=None):
         st = framesource.stats()
         print("[INFO] JPEG decoder: {} frames decoded on the device, {} fallbacks, {} reused".format(
             st["device_decoded"], st["fallbacks"], st["reused"]))
+    if depth16:
+        print("[INFO] 16-bit frames: {} scored and tracked at full depth on the device".format(len(framescore.depth16_files)))
 
     if not cancelled and args.metric == "hybrid" and tuples is not None:
         scores = framescore.hybrid_scores(tuples)

@@ -12,13 +12,25 @@ int check_frame_size(int H, int W) {
     return 0;
 }
 
-// An 8-bit source frame: channels, channel order and size, then the row stride (0 = packed rows, filled in here)
-int check_frame_layout(int H, int W, int C, int red_index, size_t* stride) {
+// A source frame of `depth` bits per sample (8 or 16): channels, channel order and size, then the row stride in bytes (0 = packed
+// rows, filled in here)
+int check_frame_layout(int H, int W, int C, int depth, int red_index, size_t* stride) {
     if (int rc = check_channels(C)) return rc;
     if (red_index != 0 && red_index != 2) return fail(GS360_ERR_ARG, "red_index must be 0 (RGB) or 2 (BGR)");
     if (int rc = check_frame_size(H, W)) return rc;
-    if (*stride == 0) *stride = (size_t)W * C;
-    if (*stride < (size_t)W * C) return fail(GS360_ERR_ARG, "stride smaller than a row");
+    const size_t row = (size_t)W * C * (depth / 8);
+    if (*stride == 0) *stride = row;
+    if (*stride < row) return fail(GS360_ERR_ARG, "stride smaller than a row");
+    return 0;
+}
+
+// FS-DEPTH16 v1's size bound: every pixel can add (8 * 65535)^2 to sum_lap2 (columns of 0 and 65535 in turn; sum_mag2's largest
+// term, 2 * (4 * 65535)^2, is smaller), and the sums are signed 64-bit.
+static_assert(GS360_FS16_MAX_PIXELS == INT64_MAX / ((int64_t)(8 * 65535) * (8 * 65535)), "GS360_FS16_MAX_PIXELS");
+int check_stats_pixels(int H, int W, int depth) {
+    if (depth == 16 && (int64_t)H * W > GS360_FS16_MAX_PIXELS)
+        return fail(GS360_ERR_UNSUPPORTED, "16-bit frame %d x %d above %lld pixels: its sums of squares could pass 64 bits", W, H,
+                    (long long)GS360_FS16_MAX_PIXELS);
     return 0;
 }
 
@@ -53,16 +65,16 @@ int flow_resize_mode(int cw, int ch, int sw, int sh, int* kx, int* ky) {
     return 2;
 }
 
-}  // namespace
-
-int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
-                         int band_y0, int band_y1, uint32_t flags, gs360_frame_stats* stats_dev, float* const* small_dev, int small_w,
-                         int small_h, int slot) {
+// gs360_frame_stats_u8 / _u16: one body, `depth` bits per sample
+int frame_stats(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, int depth, size_t stride, int red_index,
+                int band_y0, int band_y1, uint32_t flags, gs360_frame_stats* stats_dev, float* const* small_dev, int small_w,
+                int small_h, int slot) {
     if (int rc = check_ctx_slot(c, slot)) return rc;
     if (n_frames < 0) return fail(GS360_ERR_ARG, "n_frames < 0");
     if (n_frames == 0) return GS360_OK;
     if (!frames || !stats_dev) return fail(GS360_ERR_ARG, "NULL argument");
-    if (int rc = check_frame_layout(H, W, C, red_index, &stride)) return rc;
+    if (int rc = check_frame_layout(H, W, C, depth, red_index, &stride)) return rc;
+    if (int rc = check_stats_pixels(H, W, depth)) return rc;
     if (int rc = check_band(band_y0, band_y1, H)) return rc;
     if (flags & ~(GS360_FS_CIRCLE | GS360_FS_HIGHLIGHTS)) return fail(GS360_ERR_ARG, "unknown flags 0x%x", flags);
     if (int rc = check_frame_pointers(frames, n_frames)) return rc;
@@ -76,7 +88,7 @@ int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, 
     FsLaunch L;
     std::memset(&L, 0, sizeof(L));
     L.stride = (int64_t)stride;
-    L.H = H; L.W = W; L.C = C; L.red = red_index;
+    L.H = H; L.W = W; L.C = C; L.red = red_index; L.depth = depth;
     L.y0 = band_y0; L.y1 = band_y1;
     L.circle = (flags & GS360_FS_CIRCLE) ? 1 : 0;
     L.highlights = (flags & GS360_FS_HIGHLIGHTS) ? 1 : 0;
@@ -97,13 +109,14 @@ int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, 
     return GS360_OK;
 }
 
-int gs360_frame_edge_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
-                        int band_y0, int band_y1, gs360_frame_edge* out_dev, int slot) {
+// gs360_frame_edge_u8 / _u16
+int frame_edge(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, int depth, size_t stride, int red_index,
+               int band_y0, int band_y1, gs360_frame_edge* out_dev, int slot) {
     if (int rc = check_ctx_slot(c, slot)) return rc;
     if (n_frames < 0) return fail(GS360_ERR_ARG, "n_frames < 0");
     if (n_frames == 0) return GS360_OK;
     if (!frames || !out_dev) return fail(GS360_ERR_ARG, "NULL argument");
-    if (int rc = check_frame_layout(H, W, C, red_index, &stride)) return rc;
+    if (int rc = check_frame_layout(H, W, C, depth, red_index, &stride)) return rc;
     if (int rc = check_band(band_y0, band_y1, H)) return rc;
     if (int rc = check_frame_pointers(frames, n_frames)) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -112,7 +125,7 @@ int gs360_frame_edge_u8(gs360_ctx* c, const void* const* frames, int n_frames, i
     FsLaunch L;
     std::memset(&L, 0, sizeof(L));
     L.stride = (int64_t)stride;
-    L.H = H; L.W = W; L.C = C; L.red = red_index;
+    L.H = H; L.W = W; L.C = C; L.red = red_index; L.depth = depth;
     L.y0 = band_y0; L.y1 = band_y1;
     for (int f0 = 0; f0 < n_frames; f0 += GS360_MAX_FRAMES) {
         L.n_frames = std::min(GS360_MAX_FRAMES, n_frames - f0);
@@ -121,6 +134,32 @@ int gs360_frame_edge_u8(gs360_ctx* c, const void* const* frames, int n_frames, i
         HIP_TRY(launch_frame_edge(L, s));
     }
     return GS360_OK;
+}
+
+}  // namespace
+
+int gs360_frame_stats_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
+                         int band_y0, int band_y1, uint32_t flags, gs360_frame_stats* stats_dev, float* const* small_dev, int small_w,
+                         int small_h, int slot) {
+    return frame_stats(c, frames, n_frames, H, W, C, 8, stride, red_index, band_y0, band_y1, flags, stats_dev, small_dev, small_w,
+                       small_h, slot);
+}
+
+int gs360_frame_stats_u16(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
+                          int band_y0, int band_y1, uint32_t flags, gs360_frame_stats* stats_dev, float* const* small_dev, int small_w,
+                          int small_h, int slot) {
+    return frame_stats(c, frames, n_frames, H, W, C, 16, stride, red_index, band_y0, band_y1, flags, stats_dev, small_dev, small_w,
+                       small_h, slot);
+}
+
+int gs360_frame_edge_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
+                        int band_y0, int band_y1, gs360_frame_edge* out_dev, int slot) {
+    return frame_edge(c, frames, n_frames, H, W, C, 8, stride, red_index, band_y0, band_y1, out_dev, slot);
+}
+
+int gs360_frame_edge_u16(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
+                         int band_y0, int band_y1, gs360_frame_edge* out_dev, int slot) {
+    return frame_edge(c, frames, n_frames, H, W, C, 16, stride, red_index, band_y0, band_y1, out_dev, slot);
 }
 
 int gs360_frame_fft_energy(gs360_ctx* c, const float* const* small_dev, int n_frames, int small_w, int small_h, int H, int W,
@@ -165,14 +204,17 @@ int gs360_frame_fft_energy(gs360_ctx* c, const float* const* small_dev, int n_fr
     return GS360_OK;
 }
 
-int gs360_frame_flow_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
-                        int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags, const int* pairs,
-                        int n_pairs, gs360_frame_flow* out_dev, gs360_flow_point* points_dev, int slot) {
+namespace {
+
+// gs360_frame_flow_u8 / _u16
+int frame_flow(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, int depth, size_t stride, int red_index,
+               int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags, const int* pairs,
+               int n_pairs, gs360_frame_flow* out_dev, gs360_flow_point* points_dev, int slot) {
     if (int rc = check_ctx_slot(c, slot)) return rc;
     if (n_pairs < 0 || n_frames < 0) return fail(GS360_ERR_ARG, "n_frames or n_pairs < 0");
     if (n_pairs == 0) return GS360_OK;
     if (!frames || !pairs || !out_dev) return fail(GS360_ERR_ARG, "NULL argument");
-    if (int rc = check_frame_layout(H, W, C, red_index, &stride)) return rc;
+    if (int rc = check_frame_layout(H, W, C, depth, red_index, &stride)) return rc;
     if (crop_w < 1 || crop_h < 1 || crop_x0 < 0 || crop_y0 < 0 || crop_x0 + crop_w > W || crop_y0 + crop_h > H)
         return fail(GS360_ERR_ARG, "crop %d x %d at (%d, %d) outside the %d x %d frame", crop_w, crop_h, crop_x0, crop_y0, W, H);
     if (small_w < 1 || small_h < 1 || small_w > std::min(crop_w, GS360_FLOW_MAX_SIDE) || small_h > std::min(crop_h, GS360_FLOW_MAX_SIDE))
@@ -189,7 +231,7 @@ int gs360_frame_flow_u8(gs360_ctx* c, const void* const* frames, int n_frames, i
     FlLaunch L;
     std::memset(&L, 0, sizeof(L));
     L.stride = (int64_t)stride;
-    L.H = H; L.W = W; L.C = C; L.red = red_index;
+    L.H = H; L.W = W; L.C = C; L.red = red_index; L.depth = depth;
     L.circle = (flags & GS360_FS_CIRCLE) ? 1 : 0;
     L.cx0 = crop_x0; L.cy0 = crop_y0; L.cw = crop_w; L.ch = crop_h; L.sw = small_w; L.sh = small_h;
     L.mode = flow_resize_mode(crop_w, crop_h, small_w, small_h, &L.kx, &L.ky);
@@ -279,4 +321,20 @@ int gs360_frame_flow_u8(gs360_ctx* c, const void* const* frames, int n_frames, i
         p = q;
     }
     return GS360_OK;
+}
+
+}  // namespace
+
+int gs360_frame_flow_u8(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
+                        int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags, const int* pairs,
+                        int n_pairs, gs360_frame_flow* out_dev, gs360_flow_point* points_dev, int slot) {
+    return frame_flow(c, frames, n_frames, H, W, C, 8, stride, red_index, crop_x0, crop_y0, crop_w, crop_h, small_w, small_h, flags,
+                      pairs, n_pairs, out_dev, points_dev, slot);
+}
+
+int gs360_frame_flow_u16(gs360_ctx* c, const void* const* frames, int n_frames, int H, int W, int C, size_t stride, int red_index,
+                         int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags, const int* pairs,
+                         int n_pairs, gs360_frame_flow* out_dev, gs360_flow_point* points_dev, int slot) {
+    return frame_flow(c, frames, n_frames, H, W, C, 16, stride, red_index, crop_x0, crop_y0, crop_w, crop_h, small_w, small_h, flags,
+                      pairs, n_pairs, out_dev, points_dev, slot);
 }

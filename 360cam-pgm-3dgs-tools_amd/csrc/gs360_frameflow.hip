@@ -51,30 +51,32 @@ __device__ __forceinline__ unsigned ordered(float v) {   // float -> unsigned wi
 }
 __device__ __forceinline__ float unordered(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 
-// 1. crop, gray, INTER_AREA to sw x sh into level 0's plane; the circle at INTER_NEAREST's sample
-template <int C>
+// 1. crop, gray, INTER_AREA to sw x sh into level 0's plane; the circle at INTER_NEAREST's sample.  T: the sample type; a uint16_t
+// frame is read through its 8-bit view (FS-DEPTH16 v1), so everything after this kernel is FS-FLOW v1 unchanged.
+template <int C, typename T>
 __global__ void __launch_bounds__(kT) fl_small(const FlLaunch L) {
+    constexpr int kPx = C * (int)sizeof(T);                 // bytes per pixel
     const int dx = blockIdx.x * kT + threadIdx.x, dy = blockIdx.y, b = blockIdx.z;
     const bool in = dx < L.sw;
     int inmask = 0;
     if (in) {
-        const uint8_t* crop = L.src[b] + (int64_t)L.cy0 * L.stride + (int64_t)L.cx0 * C;
+        const uint8_t* crop = L.src[b] + (int64_t)L.cy0 * L.stride + (int64_t)L.cx0 * kPx;
         int v;
         if (L.mode == 0) {                 // no resize: the crop itself
-            v = gray_of<C>(crop + (int64_t)dy * L.stride + dx * C, L.red);
+            v = gray8_of<C, T>(crop + (int64_t)dy * L.stride + dx * kPx, L.red);
         } else if (L.mode == 1) {          // integer factors kx x ky: int block sum * float32(1 / area)
             int s = 0;
             for (int yy = 0; yy < L.ky; ++yy) {
-                const uint8_t* r = crop + (int64_t)(dy * L.ky + yy) * L.stride + (int64_t)dx * L.kx * C;
-                for (int xx = 0; xx < L.kx; ++xx) s += gray_of<C>(r + xx * C, L.red);
+                const uint8_t* r = crop + (int64_t)(dy * L.ky + yy) * L.stride + (int64_t)dx * L.kx * kPx;
+                for (int xx = 0; xx < L.kx; ++xx) s += gray8_of<C, T>(r + xx * kPx, L.red);
             }
             v = sat_u8((float)s * (1.0f / (float)(L.kx * L.ky)));
         } else {                           // general float32 tables, ResizeArea_Invoker's order
             const AreaSpan ax = area_span(dx, L.cw, L.scale_x), ay = area_span(dy, L.ch, L.scale_y);
             float sum = 0.0f;
-            if (ay.has_head) sum += ay.head * area_row<C>(crop + (int64_t)(ay.i1 - 1) * L.stride, ax, L.red);
-            for (int sy = ay.i1; sy < ay.i2; ++sy) sum += ay.mid * area_row<C>(crop + (int64_t)sy * L.stride, ax, L.red);
-            if (ay.has_tail) sum += ay.tail * area_row<C>(crop + (int64_t)ay.i2 * L.stride, ax, L.red);
+            if (ay.has_head) sum += ay.head * area_row<C, T, true>(crop + (int64_t)(ay.i1 - 1) * L.stride, ax, L.red);
+            for (int sy = ay.i1; sy < ay.i2; ++sy) sum += ay.mid * area_row<C, T, true>(crop + (int64_t)sy * L.stride, ax, L.red);
+            if (ay.has_tail) sum += ay.tail * area_row<C, T, true>(crop + (int64_t)ay.i2 * L.stride, ax, L.red);
             v = sat_u8(sum);
         }
         plane(L, L.slot[b], 0)[(int64_t)(dy + kPad) * L.pitch[0] + dx + kPad] = (uint8_t)v;
@@ -433,10 +435,10 @@ __global__ void __launch_bounds__(64) fl_pair(const FlLaunch L, const FlPairs Q)
 
 inline dim3 g2(int w, int h, int nf) { return dim3((unsigned)((w + kT - 1) / kT), (unsigned)h, (unsigned)nf); }
 
-template <int C>
+template <int C, typename T>
 hipError_t launch_frames_c(const FlLaunch& L, hipStream_t s) {
     const int nf = L.n_frames;
-    hipLaunchKernelGGL(fl_small<C>, g2(L.sw, L.sh, nf), dim3(kT), 0, s, L);
+    hipLaunchKernelGGL((fl_small<C, T>), g2(L.sw, L.sh, nf), dim3(kT), 0, s, L);
     for (int lev = 0; lev < L.levels; ++lev) {
         if (lev) hipLaunchKernelGGL(fl_pyr, g2(L.lw[lev], L.lh[lev], nf), dim3(kT), 0, s, L, lev);
         hipLaunchKernelGGL(fl_pad, g2(L.lw[lev] + 2 * kPad, L.lh[lev] + 2 * kPad, nf), dim3(kT), 0, s, L, lev);
@@ -456,15 +458,20 @@ hipError_t launch_frames_c(const FlLaunch& L, hipStream_t s) {
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t launch_frames_t(const FlLaunch& L, hipStream_t s) {
+    switch (L.C) {
+        case 1: return launch_frames_c<1, T>(L, s);
+        case 3: return launch_frames_c<3, T>(L, s);
+        case 4: return launch_frames_c<4, T>(L, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_frame_flow_frames(const FlLaunch& L, hipStream_t s) {
-    switch (L.C) {
-        case 1: return launch_frames_c<1>(L, s);
-        case 3: return launch_frames_c<3>(L, s);
-        case 4: return launch_frames_c<4>(L, s);
-        default: return hipErrorInvalidValue;
-    }
+    return L.depth == 16 ? launch_frames_t<uint16_t>(L, s) : launch_frames_t<uint8_t>(L, s);
 }
 
 hipError_t launch_frame_flow_pairs(const FlLaunch& L, const FlPairs& Q, hipStream_t s) {

@@ -5,14 +5,56 @@
 
 namespace gs360 {
 
-template <int C>
+// Sample k of the pixel at byte address p.  A uint16 sample is in host byte order; memcpy keeps a row that starts at an odd byte
+// address (a padded odd stride) legal.
+template <typename T>
+__host__ __device__ __forceinline__ int sample_of(const uint8_t* p, int k) {
+    if constexpr (sizeof(T) == 1) {
+        return p[k];
+    } else {
+        T v;
+        __builtin_memcpy(&v, p + k * (int)sizeof(T), sizeof(T));
+        return v;
+    }
+}
+
+// The gray at full depth: cv2 COLOR_BGR2GRAY has the same coefficients for 8U and 16U; 65535 * 16384 + 8192 < 2^31.
+template <int C, typename T = uint8_t>
 __host__ __device__ __forceinline__ int gray_of(const uint8_t* p, int red) {
     if constexpr (C == 1) {
-        return p[0];
+        return sample_of<T>(p, 0);
     } else {
-        const int r = p[red], g = p[1], b = p[2 - red];
-        return (r * 4899 + g * 9617 + b * 1868 + 8192) >> 14;    // cv2 COLOR_BGR2GRAY on 8U (yuv_shift 14)
+        const int r = sample_of<T>(p, red), g = sample_of<T>(p, 1), b = sample_of<T>(p, 2 - red);
+        return (r * 4899 + g * 9617 + b * 1868 + 8192) >> 14;    // cv2 COLOR_BGR2GRAY on 8U / 16U (yuv_shift 14)
     }
+}
+
+// The gray of the 8-bit view (FS-DEPTH16 v1, edge and flow passes): every sample >> 8 of a 16-bit pixel, then the 8-bit gray.
+template <int C, typename T>
+__host__ __device__ __forceinline__ int gray8_of(const uint8_t* p, int red) {
+    if constexpr (sizeof(T) == 1) {
+        return gray_of<C>(p, red);
+    } else if constexpr (C == 1) {
+        return sample_of<T>(p, 0) >> 8;
+    } else {
+        const int r = sample_of<T>(p, red) >> 8, g = sample_of<T>(p, 1) >> 8, b = sample_of<T>(p, 2 - red) >> 8;
+        return (r * 4899 + g * 9617 + b * 1868 + 8192) >> 14;
+    }
+}
+
+// FS-DEPTH16 v1's constants on the 16-bit gray g16, in units of 1/257 gray level (255 / 65535 = 1 / 257)
+constexpr int kFs16Highlight = 62259;       // the smallest g16 with g16 / 257 >= 0.95 * 255 = 242.25
+// The gray as the fft input's float32: the 8-bit gray itself, or the reference's float32 product g16 * float32(255 / 65535).
+template <int C, typename T>
+__host__ __device__ __forceinline__ float gray_f32(const uint8_t* p, int red) {
+    if constexpr (sizeof(T) == 1) return (float)gray_of<C>(p, red);
+    else return (float)gray_of<C, T>(p, red) * (float)(255.0 / 65535.0);
+}
+// The gray as plane 1 of the fft input holds it, an integer 8-bit level whose `>= 243` is the highlight test: floor(g16 / 257 + 0.75).
+template <int C, typename T>
+__host__ __device__ __forceinline__ float gray_level(const uint8_t* p, int red) {
+    if constexpr (sizeof(T) == 1) return (float)gray_of<C>(p, red);
+    else return (float)((gray_of<C, T>(p, red) + 192) / 257);
 }
 
 template <typename T>
@@ -46,13 +88,16 @@ __device__ __forceinline__ AreaSpan area_span(int d, int ssize, double scale) {
     return a;
 }
 
-// The gray of one row's output pixel along x: buf[dx] += S[sx] * alpha, in xtab order
-template <int C>
+// The gray of one row's output pixel along x: buf[dx] += S[sx] * alpha, in xtab order.  kView8: the 8-bit view of the samples (the
+// flow pass), else the gray at full depth scaled to [0, 255] (the fft input).
+template <int C, typename T = uint8_t, bool kView8 = false>
 __device__ __forceinline__ float area_row(const uint8_t* row, const AreaSpan& ax, int red) {
+    constexpr int kPx = C * (int)sizeof(T);
+    auto gray = [&](int sx) { return kView8 ? (float)gray8_of<C, T>(row + sx * kPx, red) : gray_f32<C, T>(row + sx * kPx, red); };
     float buf = 0.0f;
-    if (ax.has_head) buf += (float)gray_of<C>(row + (ax.i1 - 1) * C, red) * ax.head;
-    for (int sx = ax.i1; sx < ax.i2; ++sx) buf += (float)gray_of<C>(row + sx * C, red) * ax.mid;
-    if (ax.has_tail) buf += (float)gray_of<C>(row + ax.i2 * C, red) * ax.tail;
+    if (ax.has_head) buf += gray(ax.i1 - 1) * ax.head;
+    for (int sx = ax.i1; sx < ax.i2; ++sx) buf += gray(sx) * ax.mid;
+    if (ax.has_tail) buf += gray(ax.i2) * ax.tail;
     return buf;
 }
 

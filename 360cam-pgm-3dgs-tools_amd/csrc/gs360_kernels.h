@@ -286,6 +286,7 @@ struct FsLaunch {
     gs360_frame_stats* stats;            // n_frames records, cleared by the caller
     int64_t stride;
     int32_t H, W, C, red;
+    int32_t depth;                       // bits per sample: 16 = uint16 in host byte order (FS-DEPTH16 v1), else 8
     int32_t y0, y1;                      // band rows [y0, y1)
     int32_t circle, highlights;          // GS360_FS_CIRCLE / GS360_FS_HIGHLIGHTS
     int32_t n_frames, strips, total, chunk;   // strips per frame, strip workgroups in all, ceil(total / 8) (XCD order)
@@ -331,6 +332,7 @@ struct FlLaunch {
     int32_t n_frames;
     int64_t stride;
     int32_t H, W, C, red, circle;
+    int32_t depth;                       // bits per sample, as FsLaunch's; the pass runs on the 8-bit view (sample >> 8)
     int32_t cx0, cy0, cw, ch, sw, sh;    // crop and small (level-0) size
     int32_t mode, kx, ky;                // 0 no resize, 1 INTER_AREA integer factors kx x ky, 2 general INTER_AREA
     double scale_x, scale_y;             // cv2.resize's 1 / (sw / cw), 1 / (sh / ch)

@@ -33,6 +33,7 @@ EXPORTS = (
     "gs360_png_unfilter", "gs360_event_sync", "gs360_stream_wait_event",
     "gs360_color_plan16_create", "gs360_color_plan16_destroy", "gs360_color_apply_u16", "gs360_tiff_lzw_decode", "gs360_selftest_arith",
     "gs360_frame_stats_u8", "gs360_frame_fft_energy", "gs360_frame_flow_u8", "gs360_frame_edge_u8",
+    "gs360_frame_stats_u16", "gs360_frame_edge_u16", "gs360_frame_flow_u16",
     "gs360_jpeg_scan_u8", "gs360_jpeg_scan_bound", "gs360_jpeg_scan_opt_u8", "gs360_jpeg_huff_tables",
     "gs360_jpeg_scan_sub_u8", "gs360_jpeg_scan_bound_sub", "gs360_jpeg_decode_u8", "gs360_jpeg_decode_scratch",
     "gs360_jpeg_decode_gray_u8", "gs360_png_deflate", "gs360_png_bound", "gs360_mask_finish_u8", "gs360_mask_finish_scratch",
@@ -70,6 +71,7 @@ FS_HIGHLIGHTS = 0x2   # ignore_highlights
 FFT_MAX_SIDE = 512    # GS360_FFT_MAX_SIDE: gs360_frame_fft_energy's largest fft input side
 FLOW_MAX_SIDE = 320   # GS360_FLOW_MAX_SIDE: gs360_frame_flow_u8's largest small image side (FLOW_DOWNSCALE)
 FLOW_MAX_CORNERS = 1000   # GS360_FLOW_MAX_CORNERS: goodFeaturesToTrack's maxCorners
+FS16_MAX_PIXELS = (2 ** 63 - 1) // (8 * 65535) ** 2   # GS360_FS16_MAX_PIXELS: gs360_frame_stats_u16's largest H * W (FS-DEPTH16 v1)
 
 
 class Gs360Error(RuntimeError):
@@ -271,8 +273,11 @@ def load_library(path=None):
         L.gs360_stream_wait_event.argtypes = [vp, i, i, i]
         L.gs360_frame_stats_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, u32, vp, pvp, i, i, i]
         L.gs360_frame_edge_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, vp, i]
+        L.gs360_frame_stats_u16.argtypes = L.gs360_frame_stats_u8.argtypes
+        L.gs360_frame_edge_u16.argtypes = L.gs360_frame_edge_u8.argtypes
         L.gs360_frame_fft_energy.argtypes = [vp, pvp, i, i, i, i, i, i, i, u32, vp, i]
         L.gs360_frame_flow_u8.argtypes = [vp, pvp, i, i, i, i, sz, i, i, i, i, i, i, i, u32, C.POINTER(C.c_int), i, vp, vp, i]
+        L.gs360_frame_flow_u16.argtypes = L.gs360_frame_flow_u8.argtypes
         L.gs360_jpeg_scan_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, vp, i]
         L.gs360_jpeg_scan_bound.argtypes = [i, i, i, i, C.POINTER(C.c_size_t)]
         L.gs360_jpeg_scan_opt_u8.argtypes = [vp, C.POINTER(JpegJob), i, i, i, vp, vp, i]
@@ -653,23 +658,32 @@ class Context:
         self._color_apply(self.L.gs360_color_apply_u8, plan, src, H, W, Cn, dst, red_index, src_stride, dst_stride, slot)
 
     # -- frame sharpness statistics (gs360/framescore.py) -------------------------------------
-    def frame_stats_dev(self, frames, H, W, Cn, band, stats, flags=0, smalls=None, small_w=0, small_h=0, red_index=0, stride=0, slot=0):
-        """gs360_frame_stats_u8 on device frames (list of DeviceBuffer, H x W x C uint8): stats = DeviceBuffer of len(frames)
-        FrameStats records; smalls = None or one DeviceBuffer of 2 x small_h x small_w float32 per frame.  band = (y0, y1).
-        Asynchronous on `slot`."""
+    def _by_depth(self, name, depth):
+        """The _u8 or _u16 entry point of a FrameSelector pass (depth: bits per sample, 8 or 16)."""
+        if depth not in (8, 16):
+            raise ValueError(f"depth must be 8 or 16 (got {depth!r})")
+        return getattr(self.L, f"{name}_u{depth}")
+
+    def frame_stats_dev(self, frames, H, W, Cn, band, stats, flags=0, smalls=None, small_w=0, small_h=0, red_index=0, stride=0, slot=0,
+                        depth=8):
+        """gs360_frame_stats_u8 (depth 16: _u16) on device frames (list of DeviceBuffer, H x W x C uint8 / uint16): stats =
+        DeviceBuffer of len(frames) FrameStats records; smalls = None or one DeviceBuffer of 2 x small_h x small_w float32 per
+        frame.  band = (y0, y1).  Asynchronous on `slot`."""
         nf = len(frames)
         fp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in frames])
         sp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in smalls]) if smalls is not None else None
-        _check(self.L.gs360_frame_stats_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(band[0]),
-                                           int(band[1]), int(flags), stats.ptr, sp, int(small_w), int(small_h), slot), self.L)
+        fn = self._by_depth("gs360_frame_stats", depth)
+        _check(fn(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(band[0]),
+                  int(band[1]), int(flags), stats.ptr, sp, int(small_w), int(small_h), slot), self.L)
 
-    def frame_edge_dev(self, frames, H, W, Cn, band, out, red_index=0, stride=0, slot=0):
-        """gs360_frame_edge_u8 on device frames (list of DeviceBuffer, H x W x C uint8): out = DeviceBuffer of len(frames) FrameEdge
-        records.  band = (y0, y1).  Asynchronous on `slot`."""
+    def frame_edge_dev(self, frames, H, W, Cn, band, out, red_index=0, stride=0, slot=0, depth=8):
+        """gs360_frame_edge_u8 (depth 16: _u16) on device frames (list of DeviceBuffer, H x W x C uint8 / uint16): out =
+        DeviceBuffer of len(frames) FrameEdge records.  band = (y0, y1).  Asynchronous on `slot`."""
         nf = len(frames)
         fp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in frames])
-        _check(self.L.gs360_frame_edge_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(band[0]),
-                                          int(band[1]), out.ptr, slot), self.L)
+        fn = self._by_depth("gs360_frame_edge", depth)
+        _check(fn(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(band[0]),
+                  int(band[1]), out.ptr, slot), self.L)
 
     def frame_fft_energy_dev(self, smalls, small_w, small_h, H, W, band, out, flags=0, slot=0):
         """gs360_frame_fft_energy on the fft inputs frame_stats_dev wrote (one DeviceBuffer of 2 x small_h x small_w float32 per
@@ -679,17 +693,19 @@ class Context:
         _check(self.L.gs360_frame_fft_energy(self.handle, sp, nf, int(small_w), int(small_h), int(H), int(W), int(band[0]),
                                              int(band[1]), int(flags), out.ptr, slot), self.L)
 
-    def frame_flow_dev(self, frames, H, W, Cn, crop, small_w, small_h, pairs, out, flags=0, points=None, red_index=0, stride=0, slot=0):
-        """gs360_frame_flow_u8 on device frames (list of DeviceBuffer, H x W x C uint8): crop = (x0, y0, w, h), pairs = sequence of
-        (prev, curr) indices into frames; out = DeviceBuffer of len(pairs) FrameFlow records; points = None or a DeviceBuffer of
-        len(pairs) x FLOW_MAX_CORNERS FlowPoint records.  Asynchronous on `slot`."""
+    def frame_flow_dev(self, frames, H, W, Cn, crop, small_w, small_h, pairs, out, flags=0, points=None, red_index=0, stride=0, slot=0,
+                       depth=8):
+        """gs360_frame_flow_u8 (depth 16: _u16) on device frames (list of DeviceBuffer, H x W x C uint8 / uint16): crop = (x0, y0,
+        w, h), pairs = sequence of (prev, curr) indices into frames; out = DeviceBuffer of len(pairs) FrameFlow records; points =
+        None or a DeviceBuffer of len(pairs) x FLOW_MAX_CORNERS FlowPoint records.  Asynchronous on `slot`."""
         nf = len(frames)
         fp = (C.c_void_p * max(nf, 1))(*[b.ptr for b in frames])
         flat = [int(v) for pr in pairs for v in pr]
         pa = (C.c_int * max(len(flat), 1))(*flat)
-        _check(self.L.gs360_frame_flow_u8(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(crop[0]),
-                                          int(crop[1]), int(crop[2]), int(crop[3]), int(small_w), int(small_h), int(flags), pa,
-                                          len(pairs), out.ptr, points.ptr if points is not None else None, slot), self.L)
+        fn = self._by_depth("gs360_frame_flow", depth)
+        _check(fn(self.handle, fp, nf, int(H), int(W), int(Cn), int(stride), int(red_index), int(crop[0]),
+                  int(crop[1]), int(crop[2]), int(crop[3]), int(small_w), int(small_h), int(flags), pa,
+                  len(pairs), out.ptr, points.ptr if points is not None else None, slot), self.L)
 
     # -- JPEG scans of device images (gs360/jpegenc.py) ---------------------------------------
     @staticmethod

@@ -9,8 +9,9 @@ gs360_frame_flow_u8; what is left here is the reference's crop and size expressi
 logic over records.  flow_arrays is the batched entry on uint8 ndarrays or framescore.DeviceFrames: every frame is decoded and
 uploaded once, and the device computes each frame's corners and pyramid once, even when the frame is in two pairs.
 
-8-bit sources only: 16-bit and float images raise Gs360Error (GS360_ERR_UNSUPPORTED), as scoring does.  The Farneback method is
-not implemented.
+8-bit sources by default: 16-bit and float images raise Gs360Error (GS360_ERR_UNSUPPORTED), as scoring does.  With
+GS360_FS_DEPTH16=device (FS-DEPTH16 v1) uint16 frames go through gs360_frame_flow_u16, which reads every sample's high byte, as
+cv2.imread(IMREAD_GRAYSCALE) does of a 16-bit file, and is FS-FLOW v1 from there on.  The Farneback method is not implemented.
 """
 import concurrent.futures
 import math
@@ -74,6 +75,8 @@ def value_of(rec):
 
 def _host_gray(fr, red_index):
     a = np.asarray(fr)
+    if a.dtype == np.uint16:
+        a = (a >> 8).astype(np.uint8)     # FS-DEPTH16 v1: the flow pass reads a 16-bit frame's 8-bit view
     if a.ndim == 2 or a.shape[2] == 1:
         return a.reshape(a.shape[0], a.shape[1])
     a = a.astype(np.int32)
@@ -97,7 +100,8 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
     pts = np.zeros((len(pairs), capi.FLOW_MAX_CORNERS), POINT_DTYPE) if with_points else None
     ctx = ctx or framescore.default_context()
     flags = capi.FS_CIRCLE if mask_mode == "fisheye_circle" else 0
-    groups = {}                           # (H, W, C, on device, row stride, which frames) -> pair positions: one device call each
+    depths = [framescore.frame_depth(fr) for fr in frames]
+    groups = {}                           # (H, W, C, on device, row stride, which frames, depth) -> pair positions: one device call each
     gray = {}                             # frame index -> host gray, for pairs whose frames differ only in channels
     packed = {}                           # frame index -> packed host copy, for pairs of device frames of different row strides
     for k, (a, b) in enumerate(pairs):
@@ -106,24 +110,25 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
             continue
         dev = isinstance(frames[a], framescore.DeviceFrame), isinstance(frames[b], framescore.DeviceFrame)
         strides = framescore.row_stride(frames[a]), framescore.row_stride(frames[b])
-        if shapes[a] == shapes[b] and dev[0] == dev[1] and strides[0] == strides[1]:
-            groups.setdefault(shapes[a] + (dev[0], strides[0], "own"), []).append(k)
+        if shapes[a] == shapes[b] and dev[0] == dev[1] and strides[0] == strides[1] and depths[a] == depths[b]:
+            groups.setdefault(shapes[a] + (dev[0], strides[0], "own", depths[a]), []).append(k)
             continue
-        if shapes[a] == shapes[b] and dev[0] and dev[1]:
+        if shapes[a] == shapes[b] and dev[0] and dev[1] and depths[a] == depths[b]:
             # the entry point takes one stride per call: such a pair (no producer makes one today) runs on packed copies
             for f in (a, b):
                 if f not in packed:
                     packed[f] = framescore.host_copy(ctx, frames[f])
-            groups.setdefault(shapes[a] + (False, shapes[a][1] * shapes[a][2], "packed"), []).append(k)
+            groups.setdefault(shapes[a] + (False, shapes[a][1] * shapes[a][2] * (depths[a] // 8), "packed", depths[a]), []).append(k)
             continue
-        # a device frame beside a host frame (a file the device JPEG decoder left to the host): a packed gray plane pairs with the
-        # host frame's gray; any other device frame has no host twin to convert
-        if any(dv and (shapes[f][2] != 1 or frames[f].stride not in (0, shapes[f][1])) for f, dv in zip((a, b), dev)):
-            raise ValueError("a pair of device frames must share the channel count")
+        # a device frame beside a host frame (a file the device JPEG decoder left to the host), or an 8-bit host frame beside a
+        # 16-bit one: a packed 8-bit gray plane pairs with the host frame's gray (of its 8-bit view); any other device frame has no
+        # host twin to convert
+        if any(dv and (shapes[f][2] != 1 or depths[f] != 8 or frames[f].stride not in (0, shapes[f][1])) for f, dv in zip((a, b), dev)):
+            raise ValueError("a pair of device frames must share the channel count and the sample type")
         for f, dv in zip((a, b), dev):
             if not dv:
                 gray.setdefault(f, _host_gray(frames[f], red_index))
-        groups.setdefault(shapes[a][:2] + (1, False, shapes[a][1], "gray"), []).append(k)
+        groups.setdefault(shapes[a][:2] + (1, False, shapes[a][1], "gray", 8), []).append(k)
     for key, ks in groups.items():
         H, W, Cn = key[:3]
         use_gray = key[5] == "gray"
@@ -136,7 +141,8 @@ def flow_records(ctx, frames, pairs, crop_ratio, mask_mode="none", red_index=0, 
             pbuf = alloc(len(ks) * capi.FLOW_MAX_CORNERS * POINT_DTYPE.itemsize) if with_points else None
             with ctx.slot_locks[0]:
                 ctx.frame_flow_dev(bufs, H, W, Cn, (x0, y0, cw, ch), sw, sh, [(local[pairs[k][0]], local[pairs[k][1]]) for k in ks], out,
-                                   flags=flags, points=pbuf, red_index=0 if use_gray else red_index, stride=stride, slot=0)
+                                   flags=flags, points=pbuf, red_index=0 if use_gray else red_index, stride=stride, slot=0,
+                                   **framescore.depth_keyword(key[6]))
                 got = ctx.download(out, (len(ks),), RECORD_DTYPE)
                 if with_points:
                     gp = ctx.download(pbuf, (len(ks), capi.FLOW_MAX_CORNERS), POINT_DTYPE)

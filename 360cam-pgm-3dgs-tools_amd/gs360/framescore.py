@@ -17,7 +17,10 @@ flow's per-run normalisation of the hybrid features (FS:2363-2392).
 The path-based seams decode with imageio (Pillow) on the host; with GS360_JPEG_DECODER=device they read through
 gs360/framesource.py instead, which decodes baseline JPEG files on the GPU into gray planes (DeviceFrames with C = 1).
 
-8-bit sources only: 16-bit and float images raise Gs360Error (GS360_ERR_UNSUPPORTED), as does max_long > 0.
+8-bit sources by default: 16-bit and float images raise Gs360Error (GS360_ERR_UNSUPPORTED), as does max_long > 0.  With
+GS360_FS_DEPTH16=device (FS-DEPTH16 v1) uint16 frames, the 16-bit PNG / TIFF frames Video2Frames writes for
+sources of more than 8 bits per sample, go through gs360_frame_stats_u16 (exact sums on the 16-bit gray, in units of 1/257 gray
+level; finish(unit=257)) and gs360_frame_edge_u16 (the edge pass on the samples' high bytes).  Float images stay refused.
 """
 import collections
 import concurrent.futures
@@ -47,10 +50,23 @@ DEFAULT_FFT = "host"              # where score_* compute the fft term when thei
 FFT_DTYPE = capi.record_dtype(capi.FrameFft)
 EDGE_FIELDS = tuple(n for n, _ in capi.FrameEdge._fields_)
 
-# An H x W x C uint8 frame already in device memory.  stride: bytes from one row to the next, 0 = packed rows (W * C).  Every frame
-# keeps its own: frames of one shape and different strides never share a launch (the C entry points take one stride per call).
-DeviceFrame = collections.namedtuple("DeviceFrame", "buf H W C stride")
-DeviceFrame.__new__.__defaults__ = (0,)
+HIGHLIGHT_LEVEL16 = 62259        # FS-DEPTH16 v1: the smallest 16-bit gray g16 with g16 / 257 >= 242.25
+UNIT16 = 257                      # a 16-bit frame's sums are in units of 1 / 257 gray level (255 / 65535 = 1 / 257)
+
+# An H x W x C frame already in device memory, of uint8 samples or (depth 16) uint16 ones in host byte order.  stride: bytes from
+# one row to the next, 0 = packed rows (W * C samples).  Every frame keeps its own: frames of one shape and different strides never
+# share a launch (the C entry points take one stride per call).
+DeviceFrame = collections.namedtuple("DeviceFrame", "buf H W C stride depth")
+DeviceFrame.__new__.__defaults__ = (0, 8)
+
+
+def depth16_mode_from_env():
+    """-> True when 16-bit frames are scored and tracked on the GPU (FS-DEPTH16 v1).  GS360_FS_DEPTH16 = off (default: they are
+    refused as before) | device; any other value is a ValueError."""
+    mode = os.environ.get("GS360_FS_DEPTH16", "off")
+    if mode not in ("off", "device"):
+        raise ValueError(f"GS360_FS_DEPTH16 must be off or device (got {mode!r})")
+    return mode == "device"
 
 
 def band_rows(H, crop_ratio):
@@ -173,12 +189,27 @@ def mask_plan(st, H, W, ignore_highlights, mask_mode):
     return p255, masked
 
 
-def finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small=None, fft_rec=None):
+def in_gray_levels(st, unit):
+    """A record whose sums are in units of 1 / unit gray level (gs360_frame_stats_u16: unit 257) with those sums in gray levels:
+    sum_gray and sum_lap divided by unit, sum_lap2 and sum_mag2 by unit ** 2, each one correctly rounded integer division into a
+    double.  The counts stay integers."""
+    out = dict(st)
+    for sfx in ("", "_valid"):
+        for name, div in (("sum_gray", unit), ("sum_lap", unit), ("sum_lap2", unit * unit), ("sum_mag2", unit * unit)):
+            out[name + sfx] = int(st[name + sfx]) / div
+    return out
+
+
+def finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small=None, fft_rec=None, unit=1):
     """The 9-tuple of score_one_file from one frame's statistics.  st: mapping of the gs360_frame_stats fields; small: the two
     planes of the fft input (INTER_AREA image, gray at the nearest sample) for metric fft / hybrid; fft_rec: instead of small, the
-    frame's gs360_frame_fft record (mapping of its fields), computed with the flags of mask_mode and ignore_highlights."""
+    frame's gs360_frame_fft record (mapping of its fields), computed with the flags of mask_mode and ignore_highlights.  unit: 1
+    for an 8-bit frame's record, 257 for a 16-bit frame's (FS-DEPTH16 v1: the reference's float32 chain on g16 * 255 / 65535 with
+    the rounding removed)."""
     if metric not in METRICS:
         return FAILED                 # the reference's `sharp` is never bound: its except clause returns this
+    if unit != 1:
+        st = in_gray_levels(st, unit)
     p255, masked = mask_plan(st, H, W, ignore_highlights, mask_mode)
     use_valid = masked and st["n_valid"] > 0
     sfx = "_valid" if use_valid else ""
@@ -281,13 +312,18 @@ def default_context():
 
 
 def frame_shape(fr):
-    """(H, W, C) of a DeviceFrame or a uint8 ndarray; Gs360Error (GS360_ERR_UNSUPPORTED) for other dtypes, ValueError for other
-    shapes."""
+    """(H, W, C) of a DeviceFrame or a uint8 ndarray, with GS360_FS_DEPTH16=device also of a uint16 ndarray; Gs360Error
+    (GS360_ERR_UNSUPPORTED) for other dtypes, ValueError for other shapes or another value of the variable."""
     if isinstance(fr, DeviceFrame):
+        if fr.depth not in (8, 16):
+            raise ValueError(f"DeviceFrame of depth {fr.depth!r}: want 8 or 16")
+        if fr.depth == 16 and not depth16_mode_from_env():
+            raise capi.Gs360Error(-4, "frame scoring takes 8-bit images (got a 16-bit DeviceFrame; 16-bit ones with GS360_FS_DEPTH16=device)")
         return fr.H, fr.W, fr.C
     a = np.asarray(fr)
-    if a.dtype != np.uint8:
-        raise capi.Gs360Error(-4, f"frame scoring takes 8-bit images (got {a.dtype}); 16-bit and float sources are not implemented")
+    if a.dtype != np.uint8 and not (a.dtype == np.uint16 and depth16_mode_from_env()):
+        raise capi.Gs360Error(-4, f"frame scoring takes 8-bit images (got {a.dtype}); 16-bit and float sources are not implemented"
+                                  + (" (16-bit ones with GS360_FS_DEPTH16=device)" if a.dtype == np.uint16 else ""))
     if a.ndim == 2:
         return a.shape[0], a.shape[1], 1
     if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
@@ -295,21 +331,37 @@ def frame_shape(fr):
     return a.shape
 
 
+def frame_depth(fr):
+    """Bits per sample of a frame that frame_shape accepts: a DeviceFrame's depth, 16 for a uint16 ndarray, else 8."""
+    if isinstance(fr, DeviceFrame):
+        return fr.depth
+    return 16 if np.asarray(fr).dtype == np.uint16 else 8
+
+
+def depth_keyword(depth):
+    """The `depth` keyword of Context.frame_stats_dev / frame_edge_dev / frame_flow_dev: named only for 16-bit frames, so that
+    an 8-bit call is the call it was before the keyword existed."""
+    return {"depth": 16} if depth == 16 else {}
+
+
 def row_stride(fr):
-    """A frame's row stride in bytes, normalised: a DeviceFrame's own (its 0 = packed rows, W * C), a host frame's packed W * C
-    (host frames are uploaded contiguous)."""
+    """A frame's row stride in bytes, normalised: a DeviceFrame's own (its 0 = packed rows, W * C samples), a host frame's packed
+    row (host frames are uploaded contiguous)."""
     H, W, Cn = frame_shape(fr)
-    return (int(fr.stride) or W * Cn) if isinstance(fr, DeviceFrame) else W * Cn
+    packed = W * Cn * (frame_depth(fr) // 8)
+    return (int(fr.stride) or packed) if isinstance(fr, DeviceFrame) else packed
 
 
 def host_copy(ctx, fr):
-    """A DeviceFrame's pixels as a packed H x W x C host ndarray: one download of its rows, the padding dropped."""
+    """A DeviceFrame's pixels as a packed H x W x C host ndarray (uint8, or uint16 at depth 16): one download of its rows, the
+    padding dropped."""
     H, W, Cn = frame_shape(fr)
     stride = row_stride(fr)
+    row = W * Cn * (fr.depth // 8)
     with ctx.slot_locks[0]:
-        flat = ctx.download(fr.buf, ((H - 1) * stride + W * Cn,), np.uint8)
-    rows = np.lib.stride_tricks.as_strided(flat, (H, W * Cn), (stride, 1))
-    return np.ascontiguousarray(rows).reshape(H, W, Cn)
+        flat = ctx.download(fr.buf, ((H - 1) * stride + row,), np.uint8)
+    rows = np.ascontiguousarray(np.lib.stride_tricks.as_strided(flat, (H, row), (stride, 1)))
+    return rows.view(np.uint16 if fr.depth == 16 else np.uint8).reshape(H, W, Cn)
 
 
 @contextlib.contextmanager
@@ -327,11 +379,13 @@ def device_frames(ctx, frames):
         strides = {row_stride(fr) for fr in frames}
         if len(strides) > 1:
             raise ValueError(f"frames of row strides {sorted(strides)} in one launch: group them by stride")
+        if len({frame_depth(fr) for fr in frames}) > 1:
+            raise ValueError("8-bit and 16-bit frames in one launch: group them by sample type")
         bufs, stride = [], 0
         for fr in frames:
             if isinstance(fr, DeviceFrame):
                 bufs.append(fr.buf)
-                stride = 0 if row_stride(fr) == fr.W * fr.C else row_stride(fr)
+                stride = 0 if row_stride(fr) == fr.W * fr.C * (fr.depth // 8) else row_stride(fr)
             else:
                 owned.append(ctx.to_device(np.ascontiguousarray(fr)))
                 bufs.append(owned[-1])
@@ -342,9 +396,9 @@ def device_frames(ctx, frames):
 
 
 def _batches(frames, shapes):
-    """(i, j) index ranges of one launch each: consecutive frames of one size, one kind and one row stride, GS360_MAX_FRAMES at
-    most."""
-    kinds = [(shape, isinstance(fr, DeviceFrame), row_stride(fr)) for fr, shape in zip(frames, shapes)]
+    """(i, j) index ranges of one launch each: consecutive frames of one size, one kind, one sample type and one row stride,
+    GS360_MAX_FRAMES at most."""
+    kinds = [(shape, isinstance(fr, DeviceFrame), frame_depth(fr), row_stride(fr)) for fr, shape in zip(frames, shapes)]
     i = 0
     while i < len(frames):
         j = i + 1
@@ -358,6 +412,7 @@ def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_
     H, W, Cn = shape
     band = band_rows(H, crop_ratio)
     n = len(frames)
+    depth = frame_depth(frames[0])            # one per batch (_batches)
     want_small = metric in ("fft", "hybrid")
     on_device = want_small and fft == "device"
     sw, sh = fft_input_size(W, band[1] - band[0])
@@ -368,7 +423,7 @@ def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_
         ffts = alloc(n * FFT_DTYPE.itemsize) if on_device else None
         with ctx.slot_locks[0]:
             ctx.frame_stats_dev(bufs, H, W, Cn, band, stats, flags=flags, smalls=smalls, small_w=sw, small_h=sh, red_index=red_index,
-                                stride=stride, slot=0)
+                                stride=stride, slot=0, **depth_keyword(depth))
             if on_device:
                 ctx.frame_fft_energy_dev(smalls, sw, sh, H, W, band, ffts, flags=flags, slot=0)
             recs = ctx.download(stats, (n, len(FIELDS)), np.int64)
@@ -379,14 +434,15 @@ def _score_batch(ctx, frames, shape, metric, crop_ratio, augment_motion, ignore_
         st = {f: int(v) for f, v in zip(FIELDS, recs[k])}
         small = (planes[k][0], planes[k][1]) if want_small and not on_device else None
         fft_rec = {f: frecs[k][f].item() for f in FFT_DTYPE.names} if on_device else None
-        out.append(finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small, fft_rec=fft_rec))
+        out.append(finish(st, H, W, band, metric, augment_motion, ignore_highlights, mask_mode, small, fft_rec=fft_rec,
+                          unit=UNIT16 if depth == 16 else 1))
     return out
 
 
 def score_arrays(ctx, frames, metric, crop_ratio, augment_motion, ignore_highlights, mask_mode="none", red_index=0, fft=None):
-    """9-tuples for a sequence of frames: uint8 ndarrays (H x W or H x W x C, RGB(A) order unless red_index = 2) or DeviceFrames
-    already in device memory (decoded video frames, gs360/video.py).  Consecutive frames of one size, and for DeviceFrames one row
-    stride, share a launch of up to GS360_MAX_FRAMES frames.  ctx None = the process's default context.  fft: where the fft / hybrid metrics' FFT runs, "host" or
+    """9-tuples for a sequence of frames: uint8 ndarrays (H x W or H x W x C, RGB(A) order unless red_index = 2; uint16 ones too
+    with GS360_FS_DEPTH16=device) or DeviceFrames already in device memory (decoded video frames, gs360/video.py).  Consecutive
+    frames of one size and sample type, and for DeviceFrames one row stride, share a launch of up to GS360_MAX_FRAMES frames.  ctx None = the process's default context.  fft: where the fft / hybrid metrics' FFT runs, "host" or
     "device" (None = DEFAULT_FFT); with "device" no plane leaves the GPU."""
     fft = fft_mode(fft)
     frames = list(frames)
@@ -407,7 +463,8 @@ def _edge_batch(ctx, frames, shape, crop_ratio, red_index):
     with device_frames(ctx, frames) as (bufs, stride, alloc):
         recs = alloc(n * capi.C.sizeof(capi.FrameEdge))
         with ctx.slot_locks[0]:
-            ctx.frame_edge_dev(bufs, H, W, Cn, edge_band_rows(H, crop_ratio), recs, red_index=red_index, stride=stride, slot=0)
+            ctx.frame_edge_dev(bufs, H, W, Cn, edge_band_rows(H, crop_ratio), recs, red_index=red_index, stride=stride, slot=0,
+                               **depth_keyword(frame_depth(frames[0])))
             recs = ctx.download(recs, (n, len(EDGE_FIELDS)), np.int64)
     return [finish_edge({f: int(v) for f, v in zip(EDGE_FIELDS, r)}) for r in recs]
 
@@ -425,13 +482,20 @@ def edge_arrays(ctx, frames, crop_ratio, red_index=0):
 
 
 def decode(fp):
-    """The image at fp as a uint8 ndarray, None when it cannot be read; Gs360Error for a 16-bit image."""
+    """The image at fp as a uint8 ndarray, None when it cannot be read; a 16-bit image is a uint16 ndarray with
+    GS360_FS_DEPTH16=device, else Gs360Error."""
     try:
         a = imageio.read_image(fp)
     except (imageio.ImageIOError, OSError):
         return None
     frame_shape(a)
+    if a.dtype == np.uint16:
+        with _ctx_lock:
+            depth16_files.add(os.path.abspath(fp))
     return a
+
+
+depth16_files = set()             # the 16-bit files decode has read (absolute paths); the CLI clears and counts them
 
 
 def _source(decode_file, keep=False):

@@ -452,6 +452,31 @@ int gs360_frame_flow_u8(gs360_ctx *ctx, const void *const *frames, int n_frames,
                         int red_index, int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags,
                         const int *pairs, int n_pairs, gs360_frame_flow *out_dev, gs360_flow_point *points_dev, int slot);
 
+/* ---- the FrameSelector passes on 16-bit frames (FS-DEPTH16 v1) ----------
+ * The three passes above for frames of H x W x C uint16 samples in host byte order (what Video2Frames writes for sources of more
+ * than 8 bits per sample): the argument lists of their _u8 twins, `stride` in bytes (0 = tight, W * C * 2; odd strides are taken),
+ * base 4-byte aligned for the statistics and the edge pass.
+ *   gs360_frame_stats_u16  g16 = the sample (C = 1), else (R*4899 + G*9617 + B*1868 + 8192) >> 14 on the 16-bit samples (cv2
+ *       BGR2GRAY on 16U).  Counts, Laplacian, Sobel, band, circle and `valid` as gs360_frame_stats_u8 on the integer g16, with
+ *       highlight = g16 >= 62259 (the reference's g16 / 257 >= 242.25).  The sums are exact, in units of 1/257 gray level
+ *       (sum_gray, sum_lap) and of 1/257^2 (sum_lap2, sum_mag2); the host divides (gs360/framescore.py, finish(unit=257)).
+ *       small_dev: plane 0 = INTER_AREA of the float32 products (float)g16 * (float)(255.0 / 65535.0), in gs360_frame_stats_u8's
+ *       order; plane 1 = floor(g16 / 257 + 0.75) = (g16 + 192) / 257 at the nearest sample, the 8-bit level whose `>= 243` is the
+ *       highlight test above, so that gs360_frame_fft_energy and the host take the planes as they take the 8-bit ones.
+ *       H * W <= GS360_FS16_MAX_PIXELS, else GS360_ERR_UNSUPPORTED before any launch: a pixel adds up to (8 * 65535)^2 to sum_lap2
+ *       (columns of 0 and 65535 in turn; sum_mag2's terms stay below 2 * (4 * 65535)^2), and the sums are signed 64-bit.
+ *   gs360_frame_edge_u16, gs360_frame_flow_u16  run on the 8-bit view, every sample >> 8, and are FS-EDGE v1 / FS-FLOW v1 from
+ *       there: the records (and flow points) are those of the _u8 call on that view. */
+#define GS360_FS16_MAX_PIXELS (INT64_MAX / ((int64_t)(8 * 65535) * (8 * 65535)))   /* 33555456: 7680 x 3840 fits */
+int gs360_frame_stats_u16(gs360_ctx *ctx, const void *const *frames, int n_frames, int H, int W, int C, size_t stride,
+                          int red_index, int band_y0, int band_y1, uint32_t flags, gs360_frame_stats *stats_dev,
+                          float *const *small_dev, int small_w, int small_h, int slot);
+int gs360_frame_edge_u16(gs360_ctx *ctx, const void *const *frames, int n_frames, int H, int W, int C, size_t stride,
+                         int red_index, int band_y0, int band_y1, gs360_frame_edge *out_dev, int slot);
+int gs360_frame_flow_u16(gs360_ctx *ctx, const void *const *frames, int n_frames, int H, int W, int C, size_t stride,
+                         int red_index, int crop_x0, int crop_y0, int crop_w, int crop_h, int small_w, int small_h, uint32_t flags,
+                         const int *pairs, int n_pairs, gs360_frame_flow *out_dev, gs360_flow_point *points_dev, int slot);
+
 /* ---- baseline JPEG scans of device-resident images (JPG-SPEC v1) -------------------------
  * The image writer behind every view of cli_tools/gs360_360PerspCut.py: the `-q:v` / `-huffman optimal` arguments of PC:327-338 and the
  * mjpeg encoder ffmpeg runs for them (the host path hands the same pixels to Pillow, gs360/imageio.py).  For every job an H x W x C
