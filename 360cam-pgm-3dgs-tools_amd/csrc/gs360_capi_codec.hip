@@ -128,18 +128,6 @@ int check_encoder_job(const Job& j, int k, size_t row_bytes) {
     return 0;
 }
 
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// an offset cursor over a slot's scratch: take() -> where the next piece starts, aligned
-struct Carve {
-    size_t at = 0;
-    size_t take(size_t bytes, size_t align = 1) {
-        const size_t start = round_up(at, align);
-        at = start + bytes;
-        return start;
-    }
-};
-
 // the sides and components either codec ("encoder", "decoder") takes
 int check_jpeg_image(const char* codec, int H, int W, int C) {
     if (int rc = check_sides("JPEG sides are", H, W)) return rc;

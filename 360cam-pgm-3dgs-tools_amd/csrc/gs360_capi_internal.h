@@ -115,4 +115,16 @@ inline int ensure(void** p, size_t* cap, size_t need) {   // grows a slot's stag
 
 inline double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// an offset cursor over a slot's scratch: take() -> where the next piece starts, aligned
+struct Carve {
+    size_t at = 0;
+    size_t take(size_t bytes, size_t align = 1) {
+        const size_t start = round_up(at, align);
+        at = start + bytes;
+        return start;
+    }
+};
+
 }  // namespace gs360

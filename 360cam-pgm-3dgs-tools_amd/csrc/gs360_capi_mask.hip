@@ -9,7 +9,6 @@ using namespace gs360;
 
 namespace {
 
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline size_t plane_bytes(int H, int W) { return round_up((size_t)H * ((size_t)(W + 31) / 32) * 4, 256); }
 inline size_t plane_bytes(const gs360_mask_job& j) { return plane_bytes(j.H, j.W); }
 inline size_t rows_bytes(int kh) { return round_up((size_t)kh * 8, 256); }

@@ -526,33 +526,7 @@ hipError_t launch_jpeg_decode(const JdLaunch& L, bool gray, hipStream_t s);   //
 
 // The mask families (gs360_maskmorph.hip, gs360_maskshadow.hip) keep their jobs, launches and shared steps in gs360_maskplane.h.
 
-// Voxel downsampling of a resident point cloud (gs360_voxel.hip, VOX-SPEC v1 in DESIGN.md section 15).  The glue sorts the packed
-// keys between `keys` and `heads`; everything else of a count or a pick is one of these steps.
-constexpr int kVxThreads = 256;
-constexpr int kVxTile = 2048;                            // keys of a workgroup of the head passes: 4 rounds of 2 keys per lane
-constexpr int kVxBoundBlocks = 1024;                     // most workgroups (and partial records) of the bounds reduction
-constexpr int kVxScanThreads = 1024;                     // the one workgroup that scans the tiles' head counts
-constexpr int kVxLaneMax = 32;                           // a longer segment is picked by its wavefront, not by its lane
-constexpr uint32_t kVxErrKey = 1, kVxErrSegment = 2;     // bits of the error word: a key outside the bounds, a broken segment list
-struct VxLaunch {
-    const float* xyz;                    // n x 3
-    int64_t n;
-    float lo[3], v;                      // the cloud's minimum, (float) voxel
-    uint64_t kmax[3];                    // the largest key per axis (from the cloud's maximum)
-    int32_t shift[2];                    // packed = kx << shift[0] | ky << shift[1] | kz
-    int32_t strategy, pad;
-    float* partial;                      // bounds: kVxBoundBlocks x 8 (min xyz, max xyz, non-finite count, unused)
-    uint64_t* keys;                      // n packed keys (built, or sorted)
-    uint32_t* idx;                       // n indices (identity when built, the stable order when sorted); NULL: keys alone
-    uint32_t* tiles;                     // heads per tile, then their exclusive sums
-    int64_t n_tiles;
-    uint32_t* starts;                    // k segment starts
-    uint32_t* pick;                      // k picks
-    uint32_t* head;                      // the call's words: [0] error bits, [1] k
-};
-hipError_t launch_voxel_bounds(const VxLaunch& L, int phase, hipStream_t s);   // 0: partial records, 1: their reduction into record 0
-hipError_t launch_voxel_keys(const VxLaunch& L, hipStream_t s);
-hipError_t launch_voxel_heads(const VxLaunch& L, int phase, hipStream_t s);    // 0: count per tile, 1: scan, 2: compact the starts
-hipError_t launch_voxel_pick(const VxLaunch& L, int64_t k, hipStream_t s);
+// The point-cloud families (gs360_voxel.hip, gs360_octree.hip) keep their launches in gs360_voxel.h and gs360_octree.h and their
+// shared steps in gs360_cloudsteps.h.
 
 }  // namespace gs360

@@ -5,8 +5,8 @@
 // 36-bit path codes here: a node is a range of the sorted array, its children are the sub-ranges cut where the code first differs
 // at the next level.  The split order is a serial priority queue, but it looks at counts only (oc_walk, host); what touches points
 // is per point (oc_descend: the octant at every level by the reference's own float32 add chain), per sorted pair (oc_level) or per
-// leaf (oc_pick_lane: over the leaf's points in ascending original index, the float32 centroid sum point by point as
-// pts.mean(axis=0) adds).  Floating point is taken op by op.  Everything here is host-callable, so that
+// leaf (oc_pick_lane, gs360_cloudsteps.h's pick with OcTarget: over the leaf's points in ascending original index, the float32
+// centroid sum point by point as pts.mean(axis=0) adds).  Floating point is taken op by op.  Everything here is host-callable, so that
 // tests/tools/octree_hostcheck.hip can step it under a sanitizer.
 #pragma once
 #include <algorithm>
@@ -14,17 +14,14 @@
 #include <queue>
 #include <vector>
 
-#include "gs360_kernels.h"
+#include "gs360_cloudsteps.h"
 
 #pragma clang fp contract(off)
 
 namespace gs360 {
 
-#define OC_HD __host__ __device__
-
 constexpr int kOcDepth = 12;                             // the reference's max_depth; 3 bits per level: codes of 36 bits
 constexpr int kOcThreads = 256;
-constexpr int kOcLaneMax = 32;                           // a longer leaf is picked by its wavefront, not by its lane
 constexpr int kOcLeafSlack = 8;                          // a split adds at most 7 to leaves + heap: there are fewer than n + 8 leaves
 constexpr uint32_t kOcErrLeaf = 1, kOcErrIndex = 2;      // error words (plain stores, a word each): a broken leaf list, an index outside [0, n)
 constexpr double kOcEps = 1e-9;
@@ -55,7 +52,7 @@ hipError_t launch_octree_pick(const OcLaunch& L, hipStream_t s);
 
 // the add chain over the first `levels` (<= 12) levels of p's path: m = the corner reached, *next = the step of the level after
 // them (the half of that node); returns the child codes passed, the top level most significant
-OC_HD inline uint64_t oc_descend(const OcLaunch& L, const float* p, int levels, float* m, float* next) {
+CLOUD_HD inline uint64_t oc_descend(const OcLaunch& L, const float* p, int levels, float* m, float* next) {
     uint64_t code = 0;
     float h = L.half[0];
     for (int a = 0; a < 3; ++a) m[a] = L.lo[a];
@@ -76,51 +73,33 @@ OC_HD inline uint64_t oc_descend(const OcLaunch& L, const float* p, int levels, 
     *next = h;
     return code;
 }
-OC_HD inline uint64_t oc_point_code(const OcLaunch& L, float x, float y, float z) {
+CLOUD_HD inline uint64_t oc_point_code(const OcLaunch& L, float x, float y, float z) {
     const float p[3] = {x, y, z};
     float m[3], next;
     return oc_descend(L, p, kOcDepth, m, &next);
 }
 // the first level (1..12) at which two codes differ; 13 when they are equal
-OC_HD inline uint8_t oc_level(uint64_t prev, uint64_t cur) {
+CLOUD_HD inline uint8_t oc_level(uint64_t prev, uint64_t cur) {
     const uint64_t x = (prev ^ cur) & ((1ull << (3 * kOcDepth)) - 1);
     if (!x) return kOcDepth + 1;
     return (uint8_t)(kOcDepth - (63 - __builtin_clzll(x)) / 3);
 }
-OC_HD inline float oc_dist2(const float* p, const float* t) {
-    const float d0 = p[0] - t[0], d1 = p[1] - t[1], d2 = p[2] - t[2];
-    return (d0 * d0 + d1 * d1) + d2 * d2;
-}
 // the centre of the leaf of depth `depth` that holds point i
-OC_HD inline void oc_center(const OcLaunch& L, uint32_t i, int depth, float* t) {
+CLOUD_HD inline void oc_center(const OcLaunch& L, uint32_t i, int depth, float* t) {
     float h;
     oc_descend(L, L.xyz + 3 * (int64_t)i, depth, t, &h);
     for (int a = 0; a < 3; ++a) t[a] = t[a] + h;
 }
+// the octree family to gs360_cloudsteps.h: a float32 centroid sum, as pts.mean(axis=0) adds; the centre from the head point's add
+// chain to the leaf's depth
+struct OcTarget {
+    using Launch = OcLaunch;
+    using Sum = float;
+    using Tag = int;
+    CLOUD_HD static void center(const OcLaunch& L, int64_t s, int depth, float* t) { oc_center(L, L.idx[s], depth, t); }
+};
 // a lane's pick of the leaf [s, e) of the indices grouped by leaf
-OC_HD inline uint32_t oc_pick_lane(const OcLaunch& L, int64_t s, int64_t e, int depth) {
-    const uint32_t head = L.idx[s];
-    if (L.strategy == GS360_VOXEL_FIRST || e - s == 1) return head;
-    float t[3];
-    if (L.strategy == GS360_VOXEL_CENTER) oc_center(L, head, depth, t);
-    else {
-        float sum[3] = {0.0f, 0.0f, 0.0f};
-        for (int64_t p = s; p < e; ++p) {
-            const float* q = L.xyz + 3 * (int64_t)L.idx[p];
-            sum[0] += q[0]; sum[1] += q[1]; sum[2] += q[2];
-        }
-        const float cnt = (float)(e - s);
-        for (int a = 0; a < 3; ++a) t[a] = sum[a] / cnt;
-    }
-    uint32_t best_i = head;
-    float best = oc_dist2(L.xyz + 3 * (int64_t)best_i, t);
-    for (int64_t p = s + 1; p < e; ++p) {
-        const uint32_t i = L.idx[p];
-        const float d = oc_dist2(L.xyz + 3 * (int64_t)i, t);
-        if (d < best) { best = d; best_i = i; }
-    }
-    return best_i;
-}
+CLOUD_HD inline uint32_t oc_pick_lane(const OcLaunch& L, int64_t s, int64_t e, int depth) { return cloud_pick_lane<OcTarget>(L, s, e, depth); }
 
 // ---- the serial part: counts only (host) -------------------------------------------------------------------------------------------
 struct OcLeaf { uint32_t start, end; uint8_t depth; };

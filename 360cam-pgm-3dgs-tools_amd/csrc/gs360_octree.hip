@@ -1,7 +1,7 @@
 // gs360_octree.hip -- the kernels of the adaptive octree sampling (OCT-SPEC v1; gs360_PlyOptimizer.py's
 // adaptive_voxel_downsample, PLY:1174-1407).  The glue sorts (code, index) pairs after `codes` and (ordinal, index) pairs after
 // `ordinals` with rocPRIM's stable radix sort, and walks the tree over counts on the host between `levels` and `ordinals`; the
-// per-point, per-pair and per-leaf arithmetic is gs360_octree.h's.
+// per-point, per-pair and per-leaf arithmetic is gs360_octree.h's, the four-point pass and the pick gs360_cloudsteps.h's.
 //
 //   codes     four points per lane (three 16-byte loads): the 36-bit path code by the float32 add chain; two 16-byte code stores and
 //             one of indices.
@@ -9,8 +9,7 @@
 //   ordinals  a lane per sorted position: the leaf that holds it, by bisection of the leaf starts (32 rounds at the most), written at
 //             the point's original index; and the identity permutation that the second sort orders.
 //   pick      a lane owns a leaf and walks its points in ascending original index.  A leaf longer than 32 points is taken over by
-//             the lane's whole wavefront: 64 points are fetched at a time, the float32 sum still runs over them one by one (every lane
-//             adds the same shuffled values in the same order), the minimum is reduced as (dist2, position) pairs.
+//             the lane's whole wavefront (gs360_cloudsteps.h, with gs360_octree.h's target type: a float32 centroid sum).
 //
 // Every loop runs to a bound computed from n or a leaf's length; a leaf list that is not strictly increasing inside [0, n), or a
 // sorted index outside it, sets the error word instead of being followed.
@@ -20,23 +19,10 @@ namespace gs360 {
 namespace {
 
 __global__ __launch_bounds__(kOcThreads) void oc_codes_kernel(OcLaunch L) {
-    const int64_t g = (int64_t)blockIdx.x * kOcThreads + threadIdx.x, p0 = 4 * g;
-    if (p0 >= L.n) return;
-    if (p0 + 4 <= L.n) {
-        const float4* src = (const float4*)L.xyz + 3 * g;       // 48 bytes per lane: the cloud is 16-byte aligned
-        const float4 a = src[0], b = src[1], c = src[2];
-        const uint64_t c0 = oc_point_code(L, a.x, a.y, a.z), c1 = oc_point_code(L, a.w, b.x, b.y), c2 = oc_point_code(L, b.z, b.w, c.x),
-                       c3 = oc_point_code(L, c.y, c.z, c.w);
-        ((ulonglong2*)(L.codes + p0))[0] = make_ulonglong2(c0, c1);
-        ((ulonglong2*)(L.codes + p0))[1] = make_ulonglong2(c2, c3);
-        *(uint4*)(L.idx + p0) = make_uint4((uint32_t)p0, (uint32_t)p0 + 1, (uint32_t)p0 + 2, (uint32_t)p0 + 3);
-    } else {
-        for (int64_t p = p0; p < L.n; ++p) {
-            const float* q = L.xyz + 3 * p;
-            L.codes[p] = oc_point_code(L, q[0], q[1], q[2]);
-            L.idx[p] = (uint32_t)p;
-        }
-    }
+    cloud_codes4(L.xyz, L.n, (int64_t)blockIdx.x * kOcThreads + threadIdx.x, L.codes, L.idx, [&](float x, float y, float z, uint64_t* code) {
+        *code = oc_point_code(L, x, y, z);
+        return true;                                       // every point has a path
+    });
 }
 
 __global__ __launch_bounds__(kOcThreads) void oc_levels_kernel(OcLaunch L) {
@@ -73,43 +59,7 @@ __global__ __launch_bounds__(kOcThreads) void oc_ordinals_kernel(OcLaunch L) {
     L.ident[p] = (uint32_t)p;
 }
 
-// the wavefront's pick of the long leaf [s, e): every lane returns the same index
-__device__ inline uint32_t oc_pick_wave(const OcLaunch& L, int64_t s, int64_t e, int depth, int lane) {
-    float t[3];
-    if (L.strategy == GS360_VOXEL_CENTER) oc_center(L, L.idx[s], depth, t);
-    else {
-        float sum[3] = {0.0f, 0.0f, 0.0f};
-        for (int64_t base = s; base < e; base += 64) {
-            float p[3] = {0.0f, 0.0f, 0.0f};
-            if (base + lane < e) {
-                const float* q = L.xyz + 3 * (int64_t)L.idx[base + lane];
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-            }
-            const int cnt = e - base < 64 ? (int)(e - base) : 64;
-            for (int j = 0; j < cnt; ++j) {                // in index order, in every lane alike
-                sum[0] += __shfl(p[0], j); sum[1] += __shfl(p[1], j); sum[2] += __shfl(p[2], j);
-            }
-        }
-        const float cnt = (float)(e - s);
-        for (int a = 0; a < 3; ++a) t[a] = sum[a] / cnt;
-    }
-    float best = INFINITY;
-    uint32_t at = 0xFFFFFFFFu;                             // position in the leaf; none yet
-    for (int64_t base = s; base < e; base += 64) {
-        if (base + lane < e) {
-            const float d = oc_dist2(L.xyz + 3 * (int64_t)L.idx[base + lane], t);
-            if (at == 0xFFFFFFFFu || d < best) { best = d; at = (uint32_t)(base + lane - s); }
-        }
-    }
-    for (int off = 32; off; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const uint32_t oa = __shfl_xor(at, off);
-        if (oa != 0xFFFFFFFFu && (at == 0xFFFFFFFFu || ob < best || (ob == best && oa < at))) { best = ob; at = oa; }
-    }
-    return L.idx[s + at];
-}
 __global__ __launch_bounds__(kOcThreads) void oc_pick_kernel(OcLaunch L) {
-    const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * kOcThreads + threadIdx.x;
     int64_t s = 0, e = 0;
     int depth = 0;
@@ -120,17 +70,7 @@ __global__ __launch_bounds__(kOcThreads) void oc_pick_kernel(OcLaunch L) {
         depth = L.depth[g];
         if (!(s < e && e <= L.n && depth <= kOcDepth)) { L.head[0] = kOcErrLeaf; valid = false; }
     }
-    const bool wide = valid && e - s > kOcLaneMax && L.strategy != GS360_VOXEL_FIRST;
-    uint32_t pick = 0;
-    if (valid && !wide) pick = oc_pick_lane(L, s, e, depth);
-    uint64_t todo = __ballot(wide);                        // the same in every lane: the wavefront stays whole below
-    while (todo) {
-        const int l = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int64_t ws = __shfl(s, l), we = __shfl(e, l);
-        const uint32_t got = oc_pick_wave(L, ws, we, __shfl(depth, l), lane);
-        if (lane == l) pick = got;
-    }
+    const uint32_t pick = cloud_pick<OcTarget>(L, valid, s, e, depth, threadIdx.x & 63);
     if (valid) { L.pick[g] = pick; L.first[g] = L.idx[s]; }
 }
 

@@ -6,80 +6,26 @@
 //
 //   bounds    per-axis float32 minimum and maximum and a count of non-finite coordinates: a grid-stride pass into one record per
 //             workgroup, then one workgroup over the records.  No atomics.
-//   keys      four points per lane (three 16-byte loads): k_a = (uint64) floorf((x_a - min_a) / v), one float32 subtract and one
-//             correctly rounded float32 divide; packed with x most significant; stored as two 16-byte key stores and one of indices.
-//             A key outside [0, kmax_a] (bounds that do not bound the cloud, a NaN) sets the error word.
+//   keys      four points per lane (gs360_cloudsteps.h's pass): k_a = (uint64) floorf((x_a - min_a) / v), one float32 subtract and
+//             one correctly rounded float32 divide; packed with x most significant; stored as two 16-byte key stores and one of
+//             indices.  A key outside [0, kmax_a] (bounds that do not bound the cloud, a NaN) sets the error word.
 //   heads     a sorted key that differs from its predecessor opens a voxel.  Phase 0 counts the heads of every tile of 2048 keys
 //             (16-byte loads of two keys per lane, ballots), phase 1 is one workgroup's exclusive scan of the tile counts (the total is
 //             the number of voxels), phase 2 ranks the heads of a tile again from ballots and writes the segment starts in key order.
 //   pick      a lane owns a voxel: `first` is the segment head; `center` and `centroid` walk the segment in its (ascending original
 //             index) order -- the float64 centroid sum point by point, as np.add.at adds -- and keep the first minimum of
-//             dist2 = (d0 d0 + d1 d1) + d2 d2.  A segment longer than 32 points is taken over by the lane's whole wavefront: 64 points
-//             are fetched at a time, the float64 sum still runs over them one by one (every lane adds the same shuffled values in
-//             the same order), and the minimum is reduced as (dist2, position) pairs, so ties still go to the earliest point.
+//             dist2 = (d0 d0 + d1 d1) + d2 d2.  A segment longer than 32 points is taken over by the lane's whole wavefront.  The
+//             pick itself is gs360_cloudsteps.h's, with gs360_voxel.h's target type.
 //
 // Every loop runs to a bound computed from n (a segment's length, a tile count); a segment list that is not strictly increasing
 // inside [0, n) sets the error word instead of being walked.  Floating point is taken op by op (-ffp-contract=off; no fma here).
-// The per-lane arithmetic is host-callable (VX_HD) so that tests/tools/voxel_hostcheck.hip can step it under a sanitizer.
-#include "gs360_kernels.h"
+// The per-lane arithmetic (gs360_voxel.h) is host-callable so that tests/tools/voxel_hostcheck.hip can step it under a sanitizer.
+#include "gs360_voxel.h"
 
 #pragma clang fp contract(off)
 
 namespace gs360 {
 namespace {
-
-#define VX_HD __host__ __device__
-
-VX_HD inline uint64_t vx_mask(int bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1; }
-
-// one axis' key; false when it lies outside [0, kmax]
-VX_HD inline bool vx_axis_key(float x, float lo, float v, uint64_t kmax, uint64_t* k) {
-    const float q = floorf((x - lo) / v);
-    *k = 0;
-    if (!(q >= 0.0f && q < 9223372036854775808.0f)) return false;
-    *k = (uint64_t)q;
-    return *k <= kmax;
-}
-VX_HD inline bool vx_point_key(const VxLaunch& L, float x, float y, float z, uint64_t* key) {
-    uint64_t kx, ky, kz;
-    const bool okx = vx_axis_key(x, L.lo[0], L.v, L.kmax[0], &kx), oky = vx_axis_key(y, L.lo[1], L.v, L.kmax[1], &ky),
-               okz = vx_axis_key(z, L.lo[2], L.v, L.kmax[2], &kz), ok = okx && oky && okz;
-    *key = (L.shift[0] < 64 ? kx << L.shift[0] : 0) | (ky << L.shift[1]) | kz;
-    return ok;
-}
-// the centre of a packed key's voxel: t_a = min_a + ((float) k_a + 0.5f) * v
-VX_HD inline void vx_center(const VxLaunch& L, uint64_t key, float* t) {
-    const uint64_t k[3] = {L.shift[0] < 64 ? key >> L.shift[0] : 0, (key >> L.shift[1]) & vx_mask(L.shift[0] - L.shift[1]),
-                           key & vx_mask(L.shift[1])};
-    for (int a = 0; a < 3; ++a) t[a] = L.lo[a] + ((float)k[a] + 0.5f) * L.v;
-}
-VX_HD inline float vx_dist2(const float* p, const float* t) {
-    const float d0 = p[0] - t[0], d1 = p[1] - t[1], d2 = p[2] - t[2];
-    return (d0 * d0 + d1 * d1) + d2 * d2;
-}
-// a lane's pick of the segment [s, e) of the sorted indices
-VX_HD inline uint32_t vx_pick_lane(const VxLaunch& L, int64_t s, int64_t e, uint64_t key) {
-    if (L.strategy == GS360_VOXEL_FIRST) return L.idx[s];
-    float t[3];
-    if (L.strategy == GS360_VOXEL_CENTER) vx_center(L, key, t);
-    else {
-        double sum[3] = {0.0, 0.0, 0.0};
-        for (int64_t p = s; p < e; ++p) {
-            const float* q = L.xyz + 3 * (int64_t)L.idx[p];
-            sum[0] += (double)q[0]; sum[1] += (double)q[1]; sum[2] += (double)q[2];
-        }
-        const double cnt = (double)(e - s);
-        for (int a = 0; a < 3; ++a) t[a] = (float)(sum[a] / cnt);
-    }
-    uint32_t best_i = L.idx[s];
-    float best = vx_dist2(L.xyz + 3 * (int64_t)best_i, t);
-    for (int64_t p = s + 1; p < e; ++p) {
-        const uint32_t i = L.idx[p];
-        const float d = vx_dist2(L.xyz + 3 * (int64_t)i, t);
-        if (d < best) { best = d; best_i = i; }
-    }
-    return best_i;
-}
 
 // ---- bounds ----------------------------------------------------------------------------------------------------------------------
 struct VxBounds { float mn[3], mx[3], bad; };
@@ -133,28 +79,8 @@ __global__ __launch_bounds__(kVxThreads) void vx_bounds_kernel(VxLaunch L, int p
 
 // ---- keys ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kVxThreads) void vx_keys_kernel(VxLaunch L) {
-    const int64_t g = (int64_t)blockIdx.x * kVxThreads + threadIdx.x, p0 = 4 * g;
-    if (p0 >= L.n) return;
-    uint64_t key[4];
-    bool ok = true;
-    if (p0 + 4 <= L.n) {
-        const float4* src = (const float4*)L.xyz + 3 * g;       // 48 bytes per lane: the cloud is 16-byte aligned
-        const float4 a = src[0], b = src[1], c = src[2];
-        ok &= vx_point_key(L, a.x, a.y, a.z, &key[0]);
-        ok &= vx_point_key(L, a.w, b.x, b.y, &key[1]);
-        ok &= vx_point_key(L, b.z, b.w, c.x, &key[2]);
-        ok &= vx_point_key(L, c.y, c.z, c.w, &key[3]);
-        ((ulonglong2*)(L.keys + p0))[0] = make_ulonglong2(key[0], key[1]);
-        ((ulonglong2*)(L.keys + p0))[1] = make_ulonglong2(key[2], key[3]);
-        if (L.idx) *(uint4*)(L.idx + p0) = make_uint4((uint32_t)p0, (uint32_t)p0 + 1, (uint32_t)p0 + 2, (uint32_t)p0 + 3);
-    } else {
-        for (int64_t p = p0; p < L.n; ++p) {
-            const float* q = L.xyz + 3 * p;
-            ok &= vx_point_key(L, q[0], q[1], q[2], &key[0]);
-            L.keys[p] = key[0];
-            if (L.idx) L.idx[p] = (uint32_t)p;
-        }
-    }
+    const bool ok = cloud_codes4(L.xyz, L.n, (int64_t)blockIdx.x * kVxThreads + threadIdx.x, L.keys, L.idx,
+                                 [&](float x, float y, float z, uint64_t* key) { return vx_point_key(L, x, y, z, key); });
     if (!ok) atomicOr(L.head, kVxErrKey);
 }
 
@@ -225,43 +151,7 @@ __global__ __launch_bounds__(kVxScanThreads) void vx_scan_kernel(VxLaunch L) {
 }
 
 // ---- pick ------------------------------------------------------------------------------------------------------------------------
-// the wavefront's pick of the long segment [s, e): every lane returns the same index
-__device__ inline uint32_t vx_pick_wave(const VxLaunch& L, int64_t s, int64_t e, uint64_t key, int lane) {
-    float t[3];
-    if (L.strategy == GS360_VOXEL_CENTER) vx_center(L, key, t);
-    else {
-        double sum[3] = {0.0, 0.0, 0.0};
-        for (int64_t base = s; base < e; base += 64) {
-            float p[3] = {0.0f, 0.0f, 0.0f};
-            if (base + lane < e) {
-                const float* q = L.xyz + 3 * (int64_t)L.idx[base + lane];
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-            }
-            const int cnt = e - base < 64 ? (int)(e - base) : 64;
-            for (int j = 0; j < cnt; ++j) {                // in segment order, in every lane alike
-                sum[0] += (double)__shfl(p[0], j); sum[1] += (double)__shfl(p[1], j); sum[2] += (double)__shfl(p[2], j);
-            }
-        }
-        const double cnt = (double)(e - s);
-        for (int a = 0; a < 3; ++a) t[a] = (float)(sum[a] / cnt);
-    }
-    float best = INFINITY;
-    uint32_t at = 0xFFFFFFFFu;                             // position in the segment; none yet
-    for (int64_t base = s; base < e; base += 64) {
-        if (base + lane < e) {
-            const float d = vx_dist2(L.xyz + 3 * (int64_t)L.idx[base + lane], t);
-            if (at == 0xFFFFFFFFu || d < best) { best = d; at = (uint32_t)(base + lane - s); }
-        }
-    }
-    for (int off = 32; off; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const uint32_t oa = __shfl_xor(at, off);
-        if (oa != 0xFFFFFFFFu && (at == 0xFFFFFFFFu || ob < best || (ob == best && oa < at))) { best = ob; at = oa; }
-    }
-    return L.idx[s + at];
-}
 __global__ __launch_bounds__(kVxThreads) void vx_pick_kernel(VxLaunch L, int64_t k) {
-    const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * kVxThreads + threadIdx.x;
     int64_t s = 0, e = 0;
     bool valid = g < k;
@@ -270,19 +160,7 @@ __global__ __launch_bounds__(kVxThreads) void vx_pick_kernel(VxLaunch L, int64_t
         e = g + 1 < k ? (int64_t)L.starts[g + 1] : L.n;
         if (!(s < e && e <= L.n)) { atomicOr(L.head, kVxErrSegment); valid = false; }
     }
-    const uint64_t key = valid ? L.keys[s] : 0;
-    const bool wide = valid && e - s > kVxLaneMax && L.strategy != GS360_VOXEL_FIRST;
-    uint32_t pick = 0;
-    if (valid && !wide) pick = vx_pick_lane(L, s, e, key);
-    uint64_t todo = __ballot(wide);                        // the same in every lane: the wavefront stays whole below
-    while (todo) {
-        const int l = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int64_t ws = __shfl(s, l), we = __shfl(e, l);
-        const uint64_t wkey = __shfl(key, l);
-        const uint32_t got = vx_pick_wave(L, ws, we, wkey, lane);
-        if (lane == l) pick = got;
-    }
+    const uint32_t pick = cloud_pick<VxTarget>(L, valid, s, e, valid ? L.keys[s] : 0, threadIdx.x & 63);
     if (valid) L.pick[g] = pick;
 }
 

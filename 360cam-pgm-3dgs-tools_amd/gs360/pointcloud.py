@@ -357,10 +357,10 @@ def _host_pick(xyz, voxel, xyz_min, representative):
     return order[hits[first]]
 
 
-def _random_pick(order, starts, n):
-    """one point per segment at an offset drawn from an unseeded generator, as the reference draws"""
-    lens = np.diff(np.r_[starts, n])
-    return order[starts + np.random.default_rng().integers(np.maximum(lens, 1))]
+def _random_pick(order, starts, lens):
+    """one member of every segment (its start and length in `order`) at an offset drawn from an unseeded generator, as the reference
+    draws"""
+    return order[starts + np.random.default_rng().integers(lens)]
 
 
 # ---- the resident cloud -----------------------------------------------------------------------------------------------------------
@@ -429,8 +429,8 @@ class Cloud:
         try:
             if representative == "random":
                 k = self.ctx.voxel_pick_dev(self.d_xyz, self.n, self.minmax, voxel, capi.VOXEL_SEGMENTS, self.scratch, None, order, starts, self.slot)
-                idx = _random_pick(self.ctx.download(order, (self.n,), np.uint32, self.slot).astype(np.int64),
-                                   self.ctx.download(starts, (k,), np.uint32, self.slot).astype(np.int64), self.n)
+                starts_h = self.ctx.download(starts, (k,), np.uint32, self.slot).astype(np.int64)
+                idx = _random_pick(self.ctx.download(order, (self.n,), np.uint32, self.slot).astype(np.int64), starts_h, np.diff(np.r_[starts_h, self.n]))
             else:
                 k = self.ctx.voxel_pick_dev(self.d_xyz, self.n, self.minmax, voxel, STRATEGIES[representative], self.scratch, pick, None, None, self.slot)
                 idx = self.ctx.download(pick, (k,), np.uint32, self.slot).astype(np.int64)
@@ -439,7 +439,7 @@ class Cloud:
                 raise
             if representative == "random":
                 _uniq, order_h, starts_h = _host_segments(self.xyz, voxel, self.minmax[:3])
-                idx = _random_pick(order_h, starts_h, self.n)
+                idx = _random_pick(order_h, starts_h, np.diff(np.r_[starts_h, self.n]))
             else:
                 idx = _host_pick(self.xyz, voxel, self.minmax[:3], representative)
         return idx if return_indices else self.xyz[idx]
@@ -468,9 +468,7 @@ class Cloud:
                                                               scratch, order if representative == "random" else None, self.slot)
         if representative != "random":
             return picks.astype(np.int64)
-        members = self.ctx.download(order, (n,), np.uint32, self.slot).astype(np.int64)
-        return members[starts.astype(np.int64) + np.random.default_rng().integers(counts.astype(np.int64))]
-
+        return _random_pick(self.ctx.download(order, (n,), np.uint32, self.slot).astype(np.int64), starts.astype(np.int64), counts.astype(np.int64))
 
 
 _default_ctx = None

@@ -88,11 +88,12 @@ def test_key_layout_around_64_bits(bits, packed):
 
 
 def test_the_cases_know_the_kernels_constants():
-    """tests/voxel_cases.py sizes its clouds by the tile, scan and bounds constants of csrc/gs360_kernels.h"""
-    text = (PKG / "csrc" / "gs360_kernels.h").read_text()
+    """tests/voxel_cases.py sizes its clouds by the tile, scan and bounds constants of csrc/gs360_voxel.h and the lane threshold of
+    csrc/gs360_cloudsteps.h"""
+    text = (PKG / "csrc" / "gs360_voxel.h").read_text() + (PKG / "csrc" / "gs360_cloudsteps.h").read_text()
     value = lambda name: int(re.search(rf"constexpr int {name} = (\d+);", text).group(1))
     got = (voxel_cases.TILE, voxel_cases.SCAN_THREADS, voxel_cases.BOUND_BLOCKS, voxel_cases.BOUND_THREADS, voxel_cases.LANE_MAX)
-    assert got == tuple(value(n) for n in ("kVxTile", "kVxScanThreads", "kVxBoundBlocks", "kVxThreads", "kVxLaneMax"))
+    assert got == tuple(value(n) for n in ("kVxTile", "kVxScanThreads", "kVxBoundBlocks", "kVxThreads", "kCloudLaneMax"))
 
 
 def test_a_grid_of_1e9_per_unit_takes_the_host_path(gold):

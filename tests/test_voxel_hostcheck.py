@@ -1,5 +1,5 @@
 """The voxel kernels' per-lane arithmetic, checked on the CPU: tests/tools/voxel_hostcheck.hip calls the host-callable functions of
-csrc/gs360_voxel.hip (the key of a point, a voxel's centre, a lane's pick of a segment) on arrays of their exact size, built with
+csrc/gs360_voxel.h (the key of a point, a voxel's centre, a lane's pick of a segment) on arrays of their exact size, built with
 AddressSanitizer and UndefinedBehaviorSanitizer.  Every case must give the restatement's picks (tests/voxel_np.py) and no
 sanitizer report.  A stand-alone program: nothing is loaded into python."""
 import os

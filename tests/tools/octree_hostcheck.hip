@@ -1,7 +1,7 @@
 // octree_hostcheck.hip -- the adaptive octree sampling (csrc/gs360_octree.h, OCT-SPEC v1) stepped on the host.  A CPU-only stand-alone
 // program: it calls the header's host-callable functions -- the path code of every point (oc_point_code), over a stable sort of the
 // (code, index) pairs the divergence level of every sorted position (oc_level), the split loop over counts (oc_walk), the leaves'
-// ordinals and the stable sort by them, a lane's pick of every leaf (oc_pick_lane, with oc_center and oc_dist2) and the selection
+// ordinals and the stable sort by them, a lane's pick of every leaf (oc_pick_lane, with oc_center and cloud_dist2) and the selection
 // (oc_select) -- with every array allocated at its exact size, so that a build with -fsanitize=address,undefined
 // (tests/test_octree_hostcheck.py) turns any read or write outside a buffer, and any undefined shift or conversion, into a failure.
 // Usage: octree_hostcheck IN.bin OUT.bin; IN = n, target (int64), strategy, 0 (int32), weight power, smallest voxel (0: none), cube

@@ -1,12 +1,12 @@
-// voxel_hostcheck.hip -- the per-lane arithmetic of the voxel downsampling (csrc/gs360_voxel.hip, VOX-SPEC v1) stepped on the host.
-// A CPU-only stand-alone program: it includes the kernels' source and calls its host-callable functions -- the key of every point
+// voxel_hostcheck.hip -- the per-lane arithmetic of the voxel downsampling (csrc/gs360_voxel.h, VOX-SPEC v1) stepped on the host.
+// A CPU-only stand-alone program: it includes the kernels' header and calls its host-callable functions -- the key of every point
 // (vx_point_key), then, over a stable sort of the (key, index) pairs and the segment starts found here, a lane's pick of every
-// segment (vx_pick_lane, with vx_center and vx_dist2) -- with every array allocated at its exact size, so that a build with
+// segment (vx_pick_lane, with vx_center and cloud_dist2) -- with every array allocated at its exact size, so that a build with
 // -fsanitize=address,undefined (tests/test_voxel_hostcheck.py) turns any read or write outside a buffer, and any undefined shift or
 // conversion, into a failure.  Usage: voxel_hostcheck IN.bin OUT.bin; IN = n (int64), strategy, shift[0], shift[1], 0 (int32), the
 // cloud's minimum and (float) voxel (4 float32), kmax (3 uint64), the n x 3 float32 points; OUT = k picks (uint32).  Prints k and the
 // number of keys outside their bounds.
-#include "../../360cam-pgm-3dgs-tools_amd/csrc/gs360_voxel.hip"
+#include "../../360cam-pgm-3dgs-tools_amd/csrc/gs360_voxel.h"
 #include <algorithm>
 #include <cstdio>
 #include <numeric>

@@ -5,7 +5,7 @@ points on computed voxel faces, and voxels whose squared distances are subnormal
 import numpy as np
 
 TILE, SCAN_THREADS, BOUND_BLOCKS, BOUND_THREADS, LANE_MAX = 2048, 1024, 1024, 256, 32   # kVxTile, kVxScanThreads, kVxBoundBlocks,
-#                                                                                         kVxThreads, kVxLaneMax of csrc/gs360_kernels.h
+#                                                             kVxThreads of csrc/gs360_voxel.h, kCloudLaneMax of csrc/gs360_cloudsteps.h
 BIG_N = 2 * 1024 * 1024 + 2048 + 3         # 1026 tiles: a scan chunk of 2 with idle lanes, a capped bounds grid, a key tail of 3
 TWO_VOXEL_N = 2 * 1024 * 2048 + 1          # 2049 tiles: a scan chunk of 3
 PACKED_LAYOUTS = ((22, 21, 21), (0, 24, 24), (0, 32, 32), (32, 0, 32), (63, 1, 0), (1, 0, 63), (0, 1, 63))
