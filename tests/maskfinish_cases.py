@@ -76,6 +76,22 @@ def cases():
     return out
 
 
+def limit_cases():
+    """-> {name: Case}: masks past the kernels' own tiles (1024 pixels of a row per workgroup, 32 dwords per morph tile) at the largest
+    element the call takes and with side strips of several dwords.  Seeded on their own: cases() draws nothing from here."""
+    rng = np.random.default_rng(20261021)
+    out = {}
+    raw = np.zeros((140, 1700), np.uint8)                # two seeds: the 1025 x 1025 ellipse's rim lies in both morph tile columns
+    raw[70, 30], raw[10, 1650] = 255, 200
+    out["140x1700-p512"] = Case(raw, None, maskfinish.Params(close=1, expand_pixels=maskfinish.MAX_EXPAND, edge_fuse_pixels=0))
+    raw = content("corners", 33, 2100, rng)              # three pack / count / output tile columns, 65 dword seams
+    out["33x2100-corners"] = Case(raw, add_layer("overlap", raw, rng), maskfinish.Params(close=6, expand_pixels=15, edge_fuse_pixels=25, thresh=127))
+    raw = np.zeros((210, 1100), np.uint8)                # side strips of seven dwords, spread over 141 rows
+    raw[rng.random((210, 1100)) < 0.0005] = 255
+    out["210x1100-f200"] = Case(raw, None, maskfinish.Params(close=1, expand_pixels=0, edge_fuse_pixels=200))
+    return out
+
+
 def shape_of(case):
     return (case.raw if case.raw is not None else case.add).shape
 

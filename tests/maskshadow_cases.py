@@ -9,7 +9,10 @@ from gs360 import maskfinish
 
 BlurCase = namedtuple("BlurCase", "img raw sigma t delta_min sat_max")
 BLUR_SIZES = [((1, 1), 2), ((1, 37), 2), ((5, 3), 2), ((70, 131), 21), ((200, 333), 21)]   # ((H, W), sigma)
+BLUR_LIMIT_SIZES = [((40, 2100), 21), ((150, 70), 63.75), ((9, 2100), 63.75)]
 LABEL_SIZES = [(97, 130), (257, 513)]
+LABEL_WIDE = (97, 2100)                                  # past two tile columns of every shadow kernel; see wide_label_job
+LABEL_WIDE_NAMES = ("spiral", "seams", "rings", "checkerboard")
 LABEL_MIN_AREA = 20
 LABEL_NAMES = ("spiral", "checkerboard", "rings", "diagonals", "seams", "open-cs", "threshold", "empty", "full")
 ON, OFF = (128, 128, 128), (255, 0, 0)                   # S = 0 and S = 255: a pixel's saturation bit carries a plane
@@ -33,6 +36,24 @@ def blur_cases():
         dark = rng.random((H, W)) < 0.3
         img[dark] = (img[dark] * 0.4).astype(np.uint8)
         img[rng.random((H, W)) < 0.05] = (20, 20, 160)    # dark and saturated
+        raw = np.zeros((H, W), np.uint8)
+        raw[H // 3:H // 3 + max(1, H // 4), W // 3:W // 3 + max(1, W // 4)] = 255
+        out[f"{H}x{W}-s{sigma}"] = BlurCase(img, raw, sigma, 0.82, 12, 115)
+        out[f"{H}x{W}-s{sigma}-sign"] = BlurCase(textured(H, W, rng, 128, 3), raw, sigma, 1.0, 0, 255)
+    return out
+
+
+def blur_limit_cases():
+    """-> {name: BlurCase}, built as blur_cases() builds its own but seeded on their own: a second segment of the row pass (2048
+    outputs per workgroup) behind three pixel tile columns, and the largest radius the call takes (sigma 63.75: 511 taps, r = 255) on
+    a plane both of whose sides are below it and on a row of a full segment"""
+    rng = np.random.default_rng(20261022)
+    out = {}
+    for (H, W), sigma in BLUR_LIMIT_SIZES:
+        img = textured(H, W, rng)
+        dark = rng.random((H, W)) < 0.3
+        img[dark] = (img[dark] * 0.4).astype(np.uint8)
+        img[rng.random((H, W)) < 0.05] = (20, 20, 160)
         raw = np.zeros((H, W), np.uint8)
         raw[H // 3:H // 3 + max(1, H // 4), W // 3:W // 3 + max(1, W // 4)] = 255
         out[f"{H}x{W}-s{sigma}"] = BlurCase(img, raw, sigma, 0.82, 12, 115)
@@ -157,6 +178,29 @@ def blur_job(c):
     return Job(c.img, c.raw, 127, 5, w[len(w) // 2:], c.t, c.delta_min, c.sat_max, 25, 4, None, None, None)
 
 
+def ends_job(c):
+    """the image of a blur fixture under a filter of the same radius whose only weights are its two outermost taps, 0.5 each (the
+    weights are data to the call): after both passes illum is the mean of the four pixels r rows and r columns away, reflected, and
+    exact in float32.  With t = 1 and delta_min = 0 the bit compares a pixel with four others, so a staged value taken from one
+    place too far left or right, or the far end of a staged row or column read wrong, turns about half the bits it reaches; a
+    Gaussian of that radius moves illum by hundredths of a level there, which few bits show"""
+    r = len(maskfinish.gaussian_weights(c.sigma)) // 2
+    half = np.zeros(r + 1, np.float32)
+    half[r] = 0.5
+    return Job(c.img, c.raw, 127, 5, half, 1.0, 0.0, 255, 25, 4, None, None, None)
+
+
+def blur_limit_jobs():
+    """-> {name: Job}: blur_limit_cases() as blur_job makes them, and per size the -sign image under ends_job"""
+    out = {}
+    for name, c in blur_limit_cases().items():
+        out[name] = blur_job(c)
+        if name.endswith("-sign"):
+            j = ends_job(c)
+            out[name.split("-")[0] + f"-r{len(j.half) - 1}-ends"] = j
+    return out
+
+
 def label_job(name, X):
     """the plane as C2 of a job: a one-tap filter with t = 2 and delta_min = 0 leaves the saturation bit as C0, a rectangle that
     reaches the whole image from the one person pixel makes the near region everything, 1 x 1 elements leave close and open out
@@ -166,6 +210,30 @@ def label_job(name, X):
     one = rect_rows(1, 1)
     return Job(img, raw, 127, 1, np.ones(1, np.float32), 2.0, 0.0, 115, 25, LABEL_MIN_AREA, rect_rows(2 * W - 1, 2 * H - 1),
                (maskfinish.structuring_rows(3, 3)[0], 3, 3) if name == "full" else one, one)
+
+
+def wide_label_job(name, X):
+    """label_job for a plane wider than the largest element reaches from one pixel (maskfinish.MAX_EXPAND columns either way): the
+    person is one clear pixel of X near the middle of each of as many equal column ranges as it takes, so that the near rectangles
+    together still cover every column.  They reach 511 columns, not 512: with a reach of 31 more than a multiple of 32 the window's
+    last bit ends a dword and the morph kernel reads the last dword its halo stages (reach / 32 + 2 of them), and a rectangle, whose
+    last row is as wide as any, does so in the last row of the staged band, where the host check's sanitizer sees one dword less"""
+    H, W = X.shape
+    reach = maskfinish.MAX_EXPAND - 1
+    assert reach % 32 == 31
+    assert 2 * H - 1 <= 2 * reach + 1 and name != "full"
+    n = -(-W // (2 * reach + 1))
+    clear = np.argwhere(~X)
+    raw = np.zeros(X.shape, np.uint8)
+    covered = np.zeros(W, bool)
+    for k in range(n):
+        y, x = clear[np.abs(clear[:, 1] - (2 * k + 1) * W // (2 * n)).argmin()]
+        raw[y, x] = 255
+        covered[max(0, x - reach):x + reach + 1] = True
+    assert covered.all()
+    one = rect_rows(1, 1)
+    return Job(plane_image(X)[0], raw, 127, 1, np.ones(1, np.float32), 2.0, 0.0, 115, 25, LABEL_MIN_AREA,
+               rect_rows(min(2 * W - 1, 2 * reach + 1), 2 * H - 1), one, one)
 
 
 def photo_job(H, W, seed, person=True):

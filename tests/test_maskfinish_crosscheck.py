@@ -11,7 +11,7 @@ import maskfinish_np as ref
 
 cv2 = pytest.importorskip("cv2")
 
-CASES = cases.cases()
+CASES = {**cases.cases(), **cases.limit_cases()}        # the limit fixtures: a 1025 x 1025 ellipse, strips 200 wide
 
 
 def fixture_elements():

@@ -14,15 +14,20 @@ pytestmark = pytest.mark.gpu
 
 GUARD = 64
 CASES = cases.cases()
+LIMITS = cases.limit_cases()                             # run by tests/test_mask_limits_gpu.py alone: no test here names one
 CHANNELS = {"mask": 1, "rgba": 4, "keep": 3, "remove": 3}
 _REF = {}
+
+
+def case_of(name):
+    return CASES[name] if name in CASES else LIMITS[name]
 
 
 def want(name, kind="mask", invert=True, params=None, use_add=True):
     """-> (the restatement's output, its count), computed once per variant"""
     key = (name, kind, invert, params and dataclasses.astuple(params), use_add)
     if key not in _REF:
-        c = CASES[name]
+        c = case_of(name)
         shape = cases.shape_of(c)
         _REF[key] = ref.finish(c.raw, params or c.params, c.add if use_add else None, cases.image_for(shape) if kind != "mask" else None,
                                kind, invert, shape)
@@ -42,11 +47,11 @@ def run_finish(ctx, names, kind="mask", invert=True, pad=0, offset=0, params=Non
     """-> [(output array, count)] of ONE gs360_mask_finish_u8 call on the named fixtures; checks the guards behind every output and
     behind the scratch"""
     C = CHANNELS[kind]
-    shapes = [cases.shape_of(CASES[n]) for n in names]
+    shapes = [cases.shape_of(case_of(n)) for n in names]
     bufs, jobs, outs = [], [], []
     try:
         for n, (H, W) in zip(names, shapes):
-            c = CASES[n]
+            c = case_of(n)
             (j,), keep = maskfinish.build_jobs([(H, W)], params or c.params, kind, invert)
             bufs.append(keep)                             # (the element rows stay alive until the call has read them)
             if c.raw is not None:

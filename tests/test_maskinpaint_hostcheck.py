@@ -74,6 +74,11 @@ def test_sizes_past_a_tile_and_of_one(program, tmp_path):
     check(program, tmp_path, "30x37-frame", ref.photograph(30, 37, 5), frame)
 
 
+def test_one_region_with_levels_longer_than_a_workgroup(program, tmp_path):
+    """the device test's limit fixture (tests/test_mask_limits_gpu.py): a disc of radius 60 over the row tile seam at x = 256"""
+    check(program, tmp_path, "140x300-disc60", ref.photograph(140, 300, 5), ref.discs(140, 300, [(70, 230)], 60))
+
+
 def test_the_other_radii_and_noise(program, tmp_path):
     F = ref.fixture_mask()
     noise = np.random.default_rng(9).choice(np.array([0, 255], np.uint8), size=F.shape + (3,))

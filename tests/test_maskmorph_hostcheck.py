@@ -18,6 +18,7 @@ import maskfinish_np as ref
 
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 CASES = cases.cases()
+LIMITS = cases.limit_cases()
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +62,7 @@ def run(program, tmp_path, case, kind="mask", invert=True):
 
 
 def check(program, tmp_path, name, kind="mask", invert=True):
-    case = CASES[name]
+    case = CASES[name] if name in CASES else LIMITS[name]
     count, digest, got, img = run(program, tmp_path, case, kind, invert)
     want, n = ref.finish(case.raw, case.params, case.add, img, kind, invert, cases.shape_of(case))
     assert np.array_equal(got, want), (name, kind)
@@ -77,6 +78,15 @@ def test_every_small_fixture_equals_the_restatement_without_a_sanitizer_report(p
 def test_the_fixture_past_one_tile_and_one_band(program, tmp_path):
     """515 x 1030 with a 155 x 155 element: 17 x 2 tiles, three bands of element rows, the wide-window path"""
     check(program, tmp_path, "big-crowd-p77")
+
+
+def test_the_fixtures_past_the_tiles_at_the_largest_element_and_with_wide_strips(program, tmp_path):
+    """the device test's limit fixtures (tests/test_mask_limits_gpu.py): a 1025 x 1025 element (halo 18: the whole 68-dword staged
+    row, 16 bands) over two morph tile columns, three pack and output tile columns, side strips of seven dwords; one of them composed,
+    where a lane has one pixel"""
+    for name in LIMITS:
+        check(program, tmp_path, name)
+    check(program, tmp_path, "33x2100-corners", "rgba")
 
 
 @pytest.mark.parametrize("kind", ["rgba", "keep", "remove"])

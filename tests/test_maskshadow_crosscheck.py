@@ -13,9 +13,12 @@ import maskshadow_np as ref
 cv2 = pytest.importorskip("cv2")
 
 
-@pytest.mark.parametrize("name", list(cases.blur_cases()))
+BLUR = {**cases.blur_cases(), **cases.blur_limit_cases()}       # the limit fixtures: 511 taps, a row of 2100
+
+
+@pytest.mark.parametrize("name", list(BLUR))
 def test_gaussian_blur(name):
-    c = cases.blur_cases()[name]
+    c = BLUR[name]
     g = ref.gray_of(c.img).astype(np.float32)
     assert np.array_equal(ref.gray_of(c.img), cv2.cvtColor(c.img, cv2.COLOR_RGB2GRAY))
     w = maskfinish.gaussian_weights(c.sigma)
@@ -30,7 +33,7 @@ def test_hsv_saturation():
     assert np.array_equal(ref.saturation(img), cv2.cvtColor(img, cv2.COLOR_RGB2HSV)[:, :, 1])
 
 
-@pytest.mark.parametrize("size", cases.LABEL_SIZES)
+@pytest.mark.parametrize("size", cases.LABEL_SIZES + [cases.LABEL_WIDE])
 @pytest.mark.parametrize("name", cases.LABEL_NAMES)
 def test_the_contour_filter(size, name):
     X = cases.label_planes(*size)[name]

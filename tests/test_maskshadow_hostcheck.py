@@ -77,6 +77,18 @@ def test_two_label_fixtures_past_one_area_band_and_one_morph_tile(program, tmp_p
         check(program, tmp_path, f"{H}x{W}-{name}", cases.label_job(name, planes[name]))
 
 
+def test_the_fixtures_past_a_row_segment_at_the_largest_radius_and_past_two_tile_columns(program, tmp_path):
+    """the device test's limit fixtures (tests/test_mask_limits_gpu.py): the row pass's second segment, r = 255 on a full segment
+    (the last float of the staged row) and on a plane smaller than r both ways (the tallest staged column tile), each under the
+    Gaussian and under the two outermost taps alone, and two labelling planes 2100 wide"""
+    for name, job in cases.blur_limit_jobs().items():
+        check(program, tmp_path, name, job)
+    H, W = cases.LABEL_WIDE
+    planes = cases.label_planes(H, W)
+    for name in ("spiral", "seams"):
+        check(program, tmp_path, f"{H}x{W}-{name}", cases.wide_label_job(name, planes[name]))
+
+
 def test_the_photographs(program, tmp_path):
     check(program, tmp_path, "photo-97x130", cases.photo_job(97, 130, 12))
     check(program, tmp_path, "photo-97x130-nobody", cases.photo_job(97, 130, 12, person=False))
