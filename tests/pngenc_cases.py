@@ -1,5 +1,7 @@
 """The images the PNG-SPEC v1 tests encode (tests/test_pngenc_cpu.py with the NumPy restatement, tests/test_pngenc_gpu.py on the device):
-the smallest shapes that reach each hazard of the encoder, and the two seeded fixtures of the size conditions."""
+the smallest shapes that reach each hazard of the encoder, the two seeded fixtures of the size conditions, and (alphabet_cases(), for
+tests/test_pngenc_alphabet_gpu.py) the images that reach every match length, both ends of every distance symbol, both sides of the
+32 768 bound and the largest sides."""
 import numpy as np
 
 CHUNK, SEGMENT = 65536, 512          # PNG-SPEC v1's constants (tests/pngenc_np.py)
@@ -85,6 +87,102 @@ def shifted_rows_image():
     rng = np.random.default_rng(5)
     walk = (100 + np.cumsum(rng.choice([-2, -1, 1, 2], size=120))).astype(np.int64)
     return np.stack([(walk + 64 * y) % 256 for y in range(4)]).astype(np.uint8)[:, :, None]
+
+
+# ---- the length and distance alphabets, the 32 768 bound and the largest sides (tests/test_pngenc_alphabet_gpu.py) ---------------------
+# Each function below has its own seeded generators; cases() and the two size-condition fixtures above do not depend on them.
+def lengths_image():
+    """one gray row whose bytes are 0, 1 or 255 (filter None wins, as in runs_image): zero runs of every length 4..259 once, shuffled,
+    between alternating stretches of 2..5 bytes, none across the end of a 512-byte segment of the filtered stream.  Each run is a
+    literal and one distance-1 match, so the matches are every length 3..258 once.  A run that would cross a segment's end gives way
+    to the first one left that fits; where none fits the stretch runs on into the next segment.  One chunk."""
+    rng = np.random.default_rng(20261101)
+    left = [int(v) for v in rng.permutation(np.arange(4, 260))]
+    parts, pos = [_alternating(7)], 1 + 7                                              # pos: the filtered stream's (the type byte leads)
+    while left:
+        gap = int(rng.integers(2, 6))
+        room = SEGMENT - (pos + gap) % SEGMENT
+        fits = [n for n in left if n <= room]
+        if not fits:
+            gap += room
+        run = fits[0] if fits else left[0]
+        left.remove(run)
+        parts += [_alternating(gap), np.zeros(run, np.uint8)]
+        pos += gap + run
+    parts.append(_alternating(9))
+    row = np.concatenate(parts)
+    assert 1 + len(row) <= CHUNK
+    return row[None, :, None]
+
+
+def alphabet_distances():
+    """the first and last distance of each of RFC 1951's 30 distance symbols, without distance 1: 55 distances"""
+    firsts = [1, 2, 3, 4] + [(2 + h) * (1 << e) + 1 for e in range(1, 14) for h in (0, 1)]
+    lasts = firsts[1:] + [32769]
+    return sorted({d for f, l in zip(firsts, lasts) for d in (f, l - 1)} - {1})
+
+
+def walk_image(H, W, seed):
+    """gray 8-bit rows that are one random walk of steps +-1 and +-2, each 64 above the row before (shifted_rows_image's trick): every
+    row takes Sub and the residuals repeat at the row distance 1 + W"""
+    rng = np.random.default_rng(seed)
+    walk = (100 + np.cumsum(rng.choice([-2, -1, 1, 2], size=W))).astype(np.int64)
+    return np.stack([(walk + 64 * y) % 256 for y in range(H)]).astype(np.uint8)[:, :, None]
+
+
+def walk_image_rgba16(H, W, seed):
+    """the same for RGBA 16-bit: the four samples of a pixel are the walk's value, and every BYTE of a row is 64 above the row before's,
+    so no carry disturbs the repeat.  A pixel's Sub residuals are (0 or +-1, step) four times: nothing repeats at distance 1, equal
+    steps repeat at distance 8 = bpp, the rows at 1 + 8 W."""
+    rng = np.random.default_rng(seed)
+    walk = (1000 + np.cumsum(rng.choice([-2, -1, 1, 2], size=W))).astype(np.int64)
+    rows = []
+    for y in range(H):
+        hi, lo = ((walk >> 8) + 64 * y) % 256, (walk + 64 * y) % 256
+        rows.append(np.repeat(((hi << 8) | lo)[:, None], 4, axis=1))
+    return np.stack(rows).astype(np.uint16)
+
+
+def distance_cases():
+    """{name: 3 x (d - 1) x 1 walk image} for every distance d >= 5 of alphabet_distances(): the row distance is d.  (2, 3 and 4 are
+    cases()'s bpp candidates: rows that short hold no match.)  In call order: ascending, but the three images of more than one chunk
+    (d = 24 576, 24 577, 32 768) stand second in the first three launch batches of 16, so the chunks of later jobs and batches lie
+    behind theirs.  d = 32 768 is the last distance allowed; its third row is chunk 1 from position 0 to 32 767, every source of a
+    row-distance match in front of the chunk."""
+    ds = [d for d in alphabet_distances() if d >= 5]
+    order = ds[:-3]
+    for at, d in zip((1, 17, 33), ds[-3:]):
+        order.insert(at, d)
+    return {f"dist_{d}": walk_image(3, d - 1, 20261100 + d) for d in order}
+
+
+def bound_cases():
+    """the row candidate on both sides of 32 768, 3 rows each: 32 769 (dropped) and the last ones kept, for bpp = 1 and 8"""
+    return {
+        "bound_gray_32769": walk_image(3, 32768, 20261201),
+        "bound_rgba16_32769": walk_image_rgba16(3, 4096, 20261202),
+        "bound_rgba16_32761": walk_image_rgba16(3, 4095, 20261203),
+        "bound_gray_32768": walk_image(3, 32767, 20261100 + 32768),                    # distance_cases()'s dist_32768
+    }
+
+
+def side_cases():
+    """the largest sides: rows of 524 280 bytes (each across 8 chunks, 16 chunks in all; small values, nine pixels in ten zero) and
+    65 535 rows of one byte (a walk, so that Up takes most rows and None some)"""
+    rng = np.random.default_rng(20261301)
+    wide = (rng.integers(0, 4, size=(2, 65535, 4)) * (rng.random((2, 65535, 1)) < 0.1)).astype(np.uint16)
+    rng = np.random.default_rng(20261302)
+    tall = ((np.cumsum(rng.integers(-3, 4, size=65535)) + 5) % 256).astype(np.uint8)[:, None, None]
+    return {"side_wide_u16": wide, "side_tall_u8": tall}
+
+
+def alphabet_cases():
+    """{name: image} of all of the above"""
+    out = {"lengths": lengths_image()}
+    out.update(distance_cases())
+    out.update(bound_cases())
+    out.update(side_cases())
+    return out
 
 
 def cases():

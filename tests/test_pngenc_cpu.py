@@ -89,6 +89,120 @@ def test_the_cases_reach_their_hazards():
     assert sizes == {"chunk_exact": ref.CHUNK, "chunk_exact2": 2 * ref.CHUNK, "chunk_over1": ref.CHUNK + 256, "chunk_over2": 2 * ref.CHUNK + 256}
 
 
+# ---- the length and distance alphabets, the 32 768 bound, the largest sides -----------------------------------------------------------
+ALPHABET = cases.alphabet_cases()
+_RESTATED, _SYMBOLS = {}, {}
+
+
+def restated(name):
+    """-> (deflate bytes, [(adler a, adler b)] per chunk, the whole file) of an alphabet fixture by the restatement, computed once for
+    the CPU tests here and the device tests of tests/test_pngenc_alphabet_gpu.py"""
+    if name not in _RESTATED:
+        img = ALPHABET[name]
+        rows, _bpp, C, depth = ref.image_bytes(img)
+        deflated, parts = ref.deflate(img)
+        png = ref.assemble(img.shape[0], img.shape[1], C, depth, deflated, ref.adler_combine(parts))
+        _RESTATED[name] = (deflated, [p[:2] for p in parts], png)
+    return _RESTATED[name]
+
+
+def alphabet_symbols(name):
+    if name not in _SYMBOLS:
+        _SYMBOLS[name] = symbols_of(ALPHABET[name])
+    return _SYMBOLS[name]
+
+
+def matches_of(chunks):
+    return [s for chunk in chunks for s in chunk if len(s) == 2]
+
+
+def decode_png(png, img):
+    """a PNG file -> its pixels in img's shape: Pillow for 8 bits, the package's reader for 16"""
+    if img.dtype == np.uint8:
+        with Image.open(io.BytesIO(png)) as im:
+            assert im.mode == {1: "L", 3: "RGB", 4: "RGBA"}[img.shape[2]]
+            got = np.asarray(im)
+    else:
+        got = imageio._png_read(png)
+    assert got.dtype == img.dtype
+    return got.reshape(img.shape)
+
+
+@pytest.mark.parametrize("name", list(ALPHABET))
+def test_an_alphabet_fixtures_file_inflates_and_decodes_to_the_pixels(name):
+    """zlib and the decoders know RFC 1951's tables on their own: this is what proves the restatement's rows for the symbols that no
+    fixture reached before, independently of the kernels"""
+    img, png = ALPHABET[name], restated(name)[2]
+    assert zlib.decompress(ref.idat_payload(png)) == ref.filtered_stream(img).tobytes()
+    assert np.array_equal(decode_png(png, img), img)
+
+
+def test_the_length_fixture_reaches_every_length():
+    (chunk,) = alphabet_symbols("lengths")
+    found = matches_of([chunk])
+    assert sorted(s[0] for s in found) == list(range(3, 259)) and {s[1] for s in found} == {1}      # every length once, as runs
+    coded = {ref._length_symbol(s[0]) for s in found}
+    assert {c[0] for c in coded} == set(range(257, 286))
+    assert len(coded) == 256 and sum(1 << e for e in ref._LEN_EXTRA) == 257       # every extra value of each symbol but 284's 31st,
+    assert (284, 5, 31) not in coded and (285, 0, 0) in coded                      # which is length 258: symbol 285
+
+
+def test_the_distance_fixtures_reach_both_ends_of_every_distance_symbol():
+    listed = cases.alphabet_distances()
+    ends = {d for k in range(30) for d in (ref._DIST_BASE[k], (ref._DIST_BASE + [32769])[k + 1] - 1)}
+    assert len(listed) == 55 and set(listed) == ends - {1}
+    used = set()
+    for d in listed[3:]:
+        img = ALPHABET[f"dist_{d}"]
+        assert img.shape == (3, d - 1, 1) and d in {s[1] for s in matches_of(alphabet_symbols(f"dist_{d}"))}, d
+        used.add(d)
+    # 2, 3 and 4 (rows too short for a match): the bpp candidates of cases()
+    old = {s[1] for img in IMAGES.values() for s in matches_of(symbols_of(img))}
+    assert listed[:3] == [2, 3, 4] and old >= {1, 2, 3, 4}
+    used |= {1, 2, 3, 4}
+    assert {ref._distance_symbol(d)[0] for d in used} == set(range(30))
+    assert {ref._distance_symbol(d) for d in used} >= {(k, ref._DIST_EXTRA[k], v) for k in range(30) for v in (0, (1 << ref._DIST_EXTRA[k]) - 1)}
+    # the images of more than one chunk stand in front of later jobs and later launch batches of 16
+    names = list(cases.distance_cases())
+    multi = [i for i, n in enumerate(names) if pngenc.n_chunks(*ALPHABET[n].shape, 1) > 1]
+    assert len(names) == 52 and multi == [1, 17, 33] and [pngenc.n_chunks(*ALPHABET[names[i]].shape, 1) for i in multi] == [2, 2, 2]
+
+
+def test_the_widest_length_and_distance_fields_meet_in_one_match():
+    """5 length-extra bits with 13 distance-extra bits, both non-zero: the emit kernel's widest shifts; and the largest extra value a
+    distance has, 8191"""
+    wide = [(ref._length_symbol(s[0]), ref._distance_symbol(s[1])) for d in (24576, 24577, 32768) for s in matches_of(alphabet_symbols(f"dist_{d}"))]
+    assert any(l[1] == 5 and l[2] and e[1] == 13 and e[2] for l, e in wide)
+    assert any(l[1] == 5 and l[2] and e == (29, 13, 8191) for l, e in wide) and any(l[1] == 5 and l[2] and e == (28, 13, 8191) for l, e in wide)
+
+
+def test_the_row_candidate_on_both_sides_of_32768():
+    used = {name: [{s[1] for s in chunk if len(s) == 2} for chunk in alphabet_symbols(name)] for name in cases.bound_cases()}
+    assert all(len(chunks) == 2 for chunks in used.values())
+    assert ALPHABET["bound_gray_32769"].shape == (3, 32768, 1) and used["bound_gray_32769"] == [{1}, {1}]          # 32 769: dropped
+    assert ALPHABET["bound_rgba16_32769"].shape == (3, 4096, 4) and used["bound_rgba16_32769"] == [{8}, {8}]       # only bpp is used
+    assert ALPHABET["bound_rgba16_32761"].shape == (3, 4095, 4) and 32761 in used["bound_rgba16_32761"][0]         # kept and used
+    assert ALPHABET["bound_gray_32768"].shape == (3, 32767, 1) and 32768 in used["bound_gray_32768"][0]            # the last one allowed
+    assert np.array_equal(ALPHABET["bound_gray_32768"], ALPHABET["dist_32768"])
+    # the third row of the d = 32 768 image is chunk 1 from its first byte on, every position below the distance: a source in front
+    # of the chunk, so no row-distance match (the bytes do repeat there: chunk 0 holds such matches)
+    stream = ref.filtered_stream(ALPHABET["dist_32768"])
+    assert len(stream) == 3 * 32768 and np.array_equal(stream[65536 + 2:], stream[32768 + 2:65536])
+    assert 32768 not in used["bound_gray_32768"][1] and used["bound_gray_32768"][1] == {1}
+    assert 32761 not in used["bound_rgba16_32761"][1]
+
+
+def test_the_largest_sides():
+    wide, tall = ALPHABET["side_wide_u16"], ALPHABET["side_tall_u8"]
+    assert wide.shape == (2, 65535, 4) and wide.dtype == np.uint16 and tall.shape == (65535, 1, 1) and tall.dtype == np.uint8
+    assert pngenc.filtered_bytes(2, 65535, 4, 2) == 2 * 524281 and pngenc.n_chunks(2, 65535, 4, 2) == 16 == len(alphabet_symbols("side_wide_u16"))
+    assert 524281 > 7 * ref.CHUNK                                                  # a row lies across 8 chunks
+    assert pngenc.n_chunks(65535, 1, 1, 1) == 2 == len(alphabet_symbols("side_tall_u8"))
+    assert len(set(restated("side_wide_u16")[1])) == 16                            # no two chunks alike: a misplaced one shows
+    types = ref.filter_rows(*ref.image_bytes(tall)[:2])[1]
+    assert {0, 2} <= set(types.tolist())                                           # one-byte rows: None and Up both win rows
+
+
 def test_the_fibonacci_histogram_needs_the_length_limit():
     lit = np.zeros(ref.N_LITLEN, np.int64)
     lit[256] = 1

@@ -56,7 +56,9 @@ def run_deflate(ctx, images, pad=0, offset=0, caps=None, slot=0):
             ctx.free(b)
 
 
-def check(names, got):
+def check(names, got, want=want):
+    """want: name -> (deflate bytes, Adler pairs, ...) (tests/test_pngenc_alphabet_gpu.py brings its own fixtures')"""
+    assert len(names) == len(got)
     for name, (n, data, sums) in zip(names, got):
         deflated, parts, _png = want(name)
         print(f"{name}: {n} bytes (restatement {len(deflated)})")
