@@ -1,0 +1,119 @@
+// gs360_capi_video.hip -- C-ABI glue of the decoded-video colour conversion (include/gs360.h, VID-COLOR v1): the plan and the call.
+#include "gs360_capi_internal.h"
+#include "gs360_vidsteps.h"
+
+using namespace gs360;
+
+struct gs360_video_plan {
+    int device = 0;
+    int depth = 0;
+    VcCoef coef{};
+    float m[9] = {};
+    float* d_tables = nullptr;      // kVcLevels floats of linearised levels, then kVcEnc encode cells
+};
+
+// The integer coefficients of DESIGN.md 17.2 for a depth and range; tests/vidcolor_np.py derives the same numbers.
+static VcCoef video_coefficients(int depth, int full_range) {
+    const double Kr = 0.2126, Kb = 0.0722, Kg = 1.0 - Kr - Kb;
+    const double scale = 16383.0 * 16384.0;
+    const int s = 1 << (depth - 8), vmax = (1 << depth) - 1;
+    const double dy = full_range ? (double)vmax : 219.0 * s, dc = full_range ? (double)vmax : 224.0 * s;
+    VcCoef K;
+    K.cy = (int32_t)std::nearbyint(scale / dy);
+    K.crv = (int32_t)std::nearbyint((2.0 * (1.0 - Kr)) * scale / dc);
+    K.cgu = (int32_t)std::nearbyint((Kb * (2.0 * (1.0 - Kb)) / Kg) * scale / dc);
+    K.cgv = (int32_t)std::nearbyint((Kr * (2.0 * (1.0 - Kr)) / Kg) * scale / dc);
+    K.cbu = (int32_t)std::nearbyint((2.0 * (1.0 - Kb)) * scale / dc);
+    K.yoff = full_range ? 0 : 16 * s;
+    K.coff = 128 * s;
+    K.vmax = vmax;
+    return K;
+}
+
+int gs360_video_plan_create(gs360_ctx* c, int depth, int full_range, int keep_rec709, const float* primaries, const float* linear,
+                            const float* encode, gs360_video_plan** out) {
+    if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
+    if (!primaries || !linear || !encode || !out) return fail(GS360_ERR_ARG, "NULL argument");
+    if (depth != 8 && depth != 10) return fail(GS360_ERR_UNSUPPORTED, "video depth %d (8 and 10 bits are implemented)", depth);
+    if ((full_range | keep_rec709) & ~1) return fail(GS360_ERR_ARG, "full_range and keep_rec709 are 0 or 1");
+    // the tables index each other: a linear value outside [0,1] or a matrix entry that is no number would leave the encode table
+    const float outmax = depth == 8 ? 255.0f : 65535.0f;
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(primaries[i])) return fail(GS360_ERR_ARG, "primaries[%d] is not finite", i);
+    for (int i = 0; i < kVcLevels; ++i)
+        if (!(linear[i] >= 0.0f && linear[i] <= 1.0f)) return fail(GS360_ERR_ARG, "linear[%d] outside [0,1]", i);
+    for (int i = 0; i < kVcEnc; ++i) {
+        const float lo = encode[2 * i], hi = lo + encode[2 * i + 1];
+        if (!(lo >= 0.0f && lo <= outmax && hi >= 0.0f && hi <= outmax))
+            return fail(GS360_ERR_ARG, "encode cell %d leaves [0,%d]", i, (int)outmax);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    gs360_video_plan* p = new (std::nothrow) gs360_video_plan();
+    if (!p) return fail(GS360_ERR_NOMEM, "out of host memory");
+    p->device = c->device;
+    p->depth = depth;
+    p->coef = video_coefficients(depth, full_range);
+    std::memcpy(p->m, primaries, sizeof(p->m));
+    const size_t n_lin = kVcLevels * sizeof(float), n_enc = kVcEnc * 2 * sizeof(float);
+    hipError_t e = hipMalloc((void**)&p->d_tables, n_lin + n_enc);
+    if (e == hipSuccess) e = hipMemcpy(p->d_tables, linear, n_lin, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_tables + kVcLevels, encode, n_enc, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (p->d_tables) (void)hipFree(p->d_tables);
+        delete p;
+        return fail(e == hipErrorOutOfMemory ? GS360_ERR_NOMEM : GS360_ERR_HIP, "video plan setup failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return GS360_OK;
+}
+
+int gs360_video_plan_destroy(gs360_ctx* c, gs360_video_plan* p) {
+    if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
+    if (!p) return GS360_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const hipError_t e = hipFree(p->d_tables);
+    delete p;
+    HIP_TRY(e);
+    return GS360_OK;
+}
+
+int gs360_video_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360_video_job* jobs, int n_jobs, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (!p || (n_jobs > 0 && !jobs)) return fail(GS360_ERR_ARG, "NULL argument");
+    if (p->device != c->device) return fail(GS360_ERR_ARG, "video plan belongs to device %d, ctx is device %d", p->device, c->device);
+    if (n_jobs < 0 || n_jobs > GS360_MAX_FRAMES) return fail(GS360_ERR_ARG, "n_jobs %d outside [0,%d]", n_jobs, GS360_MAX_FRAMES);
+    if (n_jobs == 0) return GS360_OK;
+    const size_t bytes = p->depth == 8 ? 1 : 2;
+    VidLaunch L{};
+    for (int j = 0; j < n_jobs; ++j) {                       // every job is checked before anything is launched
+        const gs360_video_job& J = jobs[j];
+        if (!J.y || !J.cb || !J.cr || !J.dst) return fail(GS360_ERR_ARG, "job %d: NULL plane or destination", j);
+        if (J.W < 1 || J.H < 1 || J.W > 65535 || J.H > 65535) return fail(GS360_ERR_ARG, "job %d: size %d x %d outside 1..65535", j, J.W, J.H);
+        if (J.subsampling != GS360_VIDEO_444 && J.subsampling != GS360_VIDEO_422 && J.subsampling != GS360_VIDEO_420)
+            return fail(GS360_ERR_UNSUPPORTED, "job %d: subsampling %d (4:4:4, 4:2:2 and 4:2:0 are implemented)", j, J.subsampling);
+        VcImage& I = L.img[j];
+        I.sx = J.subsampling != GS360_VIDEO_444;
+        I.sy = J.subsampling == GS360_VIDEO_420;
+        const size_t y_row = (size_t)J.W * bytes, c_row = (size_t)((J.W + I.sx) >> I.sx) * bytes, d_row = 3 * y_row;
+        const size_t ys = J.y_stride ? J.y_stride : y_row, cbs = J.cb_stride ? J.cb_stride : c_row;
+        const size_t crs = J.cr_stride ? J.cr_stride : c_row, ds = J.dst_stride ? J.dst_stride : d_row;
+        if (ys < y_row || cbs < c_row || crs < c_row || ds < d_row) return fail(GS360_ERR_ARG, "job %d: stride smaller than a row", j);
+        const uintptr_t bits = (uintptr_t)J.y | (uintptr_t)J.cb | (uintptr_t)J.cr | (uintptr_t)J.dst | ys | cbs | crs | ds;
+        if (bytes == 2 && (bits & 1)) return fail(GS360_ERR_ARG, "job %d: 10-bit planes need even addresses and strides", j);
+        I.y = (const uint8_t*)J.y; I.cb = (const uint8_t*)J.cb; I.cr = (const uint8_t*)J.cr; I.dst = (uint8_t*)J.dst;
+        I.ys = (int64_t)ys; I.cbs = (int64_t)cbs; I.crs = (int64_t)crs; I.ds = (int64_t)ds;
+        I.W = J.W; I.H = J.H;
+        I.fast = (bits & 3) == 0;
+        I.gpr = (J.W + kVcGroup - 1) / kVcGroup;
+    }
+    L.lin = p->d_tables;
+    L.enc = reinterpret_cast<const float2*>(p->d_tables + kVcLevels);
+    std::memcpy(L.m, p->m, sizeof(L.m));
+    L.outmax = p->depth == 8 ? 255 : 65535;
+    L.coef = p->coef;
+    L.n_jobs = n_jobs;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_vidcolor(L, p->depth, c->stream[slot]));
+    return GS360_OK;
+}

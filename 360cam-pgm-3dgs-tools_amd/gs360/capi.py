@@ -41,6 +41,7 @@ EXPORTS = (
     "gs360_mask_inpaint_scratch", "gs360_mask_inpaint_u8",
     "gs360_voxel_scratch", "gs360_cloud_bounds_f32", "gs360_voxel_count_f32", "gs360_voxel_pick_f32",
     "gs360_octree_scratch", "gs360_octree_pick_f32",
+    "gs360_video_plan_create", "gs360_video_plan_destroy", "gs360_video_rgb",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -63,6 +64,7 @@ INPAINT_MIN_RADIUS, INPAINT_MAX_RADIUS = 3, 8   # gs360_mask_inpaint_u8's radii 
 INPAINT_MAX_LEVEL = 4095             # GS360_INPAINT_MAX_LEVEL
 VOXEL_FIRST, VOXEL_CENTER, VOXEL_CENTROID, VOXEL_SEGMENTS = 0, 1, 2, 3   # GS360_VOXEL_*: the `strategy` of gs360_voxel_pick_f32
 VOXEL_MAX_POINTS = (1 << 31) - 1     # GS360_VOXEL_MAX_POINTS: indices are 32-bit on the device
+VIDEO_444, VIDEO_422, VIDEO_420 = 0, 1, 2   # GS360_VIDEO_*: the `subsampling` of a gs360_video_job
 ERR_ARG = -1                         # GS360_ERR_ARG / GS360_ERR_UNSUPPORTED
 ERR_UNSUPPORTED = -4
 ERR_INTERNAL = -6                    # GS360_ERR_INTERNAL: a kernel's own bound was exceeded
@@ -118,6 +120,13 @@ class PngJob(C.Structure):
     """gs360_png_job: one image of a batched PNG deflate call (device pointers)."""
     _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("bytes_per_sample", C.c_int32),
                 ("src_stride", C.c_size_t), ("out", C.c_void_p), ("out_capacity", C.c_size_t)]
+
+
+class VideoJob(C.Structure):
+    """gs360_video_job: the planes of one decoded frame and its RGB destination (device pointers)."""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_size_t), ("cb_stride", C.c_size_t),
+                ("cr_stride", C.c_size_t), ("W", C.c_int32), ("H", C.c_int32), ("subsampling", C.c_int32), ("reserved", C.c_int32),
+                ("dst", C.c_void_p), ("dst_stride", C.c_size_t)]
 
 
 class MaskJob(C.Structure):
@@ -304,6 +313,9 @@ def load_library(path=None):
         L.gs360_octree_scratch.argtypes = [vp, i64, C.POINTER(C.c_size_t)]
         L.gs360_octree_pick_f32.argtypes = [vp, vp, i64, C.POINTER(C.c_float), C.c_double, i64, C.c_double, C.c_double, i, vp, sz, vp, vp, vp, vp,
                                             C.POINTER(i64), C.POINTER(C.c_double), i]
+        L.gs360_video_plan_create.argtypes = [vp, i, i, i, vp, vp, vp, pvp]
+        L.gs360_video_plan_destroy.argtypes = [vp, vp]
+        L.gs360_video_rgb.argtypes = [vp, vp, C.POINTER(VideoJob), i, i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -656,6 +668,35 @@ class Context:
     def color_apply_dev(self, plan, src, H, W, Cn, dst=None, red_index=0, src_stride=0, dst_stride=0, slot=0):
         """Apply a colour plan to a device-resident H x W x C image (in place when dst is None)."""
         self._color_apply(self.L.gs360_color_apply_u8, plan, src, H, W, Cn, dst, red_index, src_stride, dst_stride, slot)
+
+    # -- decoded video frames to RGB (gs360/vidcolor.py) ---------------------------------------
+    def video_plan(self, depth, full_range, keep_rec709, primaries, linear, encode):
+        """gs360_video_plan_create: primaries float32 [3][3], linear float32 [16384], encode float32 [1024][2] (gs360/vidcolor.py
+        builds them).  Returns an opaque plan handle (free with video_plan_free)."""
+        m = np.ascontiguousarray(primaries, dtype=np.float32)
+        lin = np.ascontiguousarray(linear, dtype=np.float32)
+        enc = np.ascontiguousarray(encode, dtype=np.float32)
+        if m.shape != (3, 3) or lin.shape != (16384,) or enc.shape != (1024, 2):
+            raise ValueError("primaries must be [3][3], linear [16384] and encode [1024][2]")
+        h = C.c_void_p()
+        _check(self.L.gs360_video_plan_create(self.handle, int(depth), int(full_range), int(keep_rec709), m.ctypes.data, lin.ctypes.data,
+                                              enc.ctypes.data, C.byref(h)), self.L)
+        return h
+
+    def video_plan_free(self, plan):
+        if plan:
+            _check(self.L.gs360_video_plan_destroy(self.handle, plan), self.L)
+
+    def video_rgb_dev(self, plan, jobs, slot=0):
+        """gs360_video_rgb: jobs = sequence of (y, cb, cr, W, H, subsampling, dst[, y_stride, cb_stride, cr_stride, dst_stride]),
+        the planes and dst DeviceBuffers or device addresses, strides in bytes (0 = tight).  Asynchronous on `slot`."""
+        def addr(b):
+            return b.ptr if isinstance(b, DeviceBuffer) else int(b)
+        arr = (VideoJob * max(len(jobs), 1))()
+        for k, (y, cb, cr, W, H, sub, dst, *strides) in enumerate(jobs):
+            ys, cbs, crs, ds = (list(strides) + [0, 0, 0, 0])[:4]
+            arr[k] = VideoJob(addr(y), addr(cb), addr(cr), int(ys), int(cbs), int(crs), int(W), int(H), int(sub), 0, addr(dst), int(ds))
+        _check(self.L.gs360_video_rgb(self.handle, plan, arr, len(jobs), slot), self.L)
 
     # -- frame sharpness statistics (gs360/framescore.py) -------------------------------------
     def _by_depth(self, name, depth):

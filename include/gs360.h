@@ -348,6 +348,42 @@ int gs360_color_plan16_destroy(gs360_ctx *ctx, gs360_color_plan16 *plan);
 int gs360_color_apply_u16(gs360_ctx *ctx, const gs360_color_plan16 *plan, const void *src, int H, int W, int C,
                           size_t src_stride, int red_index, void *dst, size_t dst_stride, int slot);
 
+/* ---- decoded video frames: Y'CbCr planes -> RGB (VID-COLOR v1) ----------------------------------------------
+ * The colour work of gs360_Video2Frames.py's filter `colorspace=iall=bt709:all=smpte170m[:trc=iec61966-2-1]` (V2F:464-466) on
+ * device-resident planes: BT.709 Y'CbCr of depth 8 (uint8) or 10 (uint16, value in the low 10 bits, larger samples clamped to 1023),
+ * limited or full range -> R'G'B' -> linear light -> SMPTE-C primaries -> sRGB (or, keep_rec709, the Rec.709 curve) -> interleaved
+ * RGB, uint8 for depth 8 and uint16 (levels 0..65535) for depth 10.  Chroma is replicated: pixel (x, y) takes the sample
+ * (x >> 1, y >> 1) of a 4:2:0 job and (x >> 1, y) of a 4:2:2 job; the chroma planes are ceil(W / 2) wide and, for 4:2:0,
+ * ceil(H / 2) high.  Every step is discrete and stated in DESIGN.md 17; tests/vidcolor_np.py restates it and gives the same bytes.
+ *   plan   the Y'CbCr -> R'G'B' step is integer arithmetic whose coefficients follow from depth and full_range; the float steps take
+ *          three HOST tables that gs360/vidcolor.py builds in float64: primaries = the 3 x 3 matrix (row-major), linear = 16384
+ *          floats in [0,1], the Rec.709 linearisation of R'G'B' level i / 16383; encode = 1024 pairs (a, b), the output level at
+ *          the lower edge of cell i of sqrt(linear value) * 1024 and its rise over the cell.  keep_rec709 names the curve `encode`
+ *          was built for.  A plan serves any number of calls; destroy waits for the device.
+ *   jobs   up to GS360_MAX_FRAMES per call; they may differ in size, subsampling and strides (bytes, 0 = tight).  Planes and
+ *          destination must not overlap.  Pointers and strides that are all multiples of 4 take the dword path.  Asynchronous on
+ *          `slot`.
+ * Errors, checked for every job before anything is written: GS360_ERR_UNSUPPORTED for a depth other than 8 or 10 and for another
+ * subsampling; GS360_ERR_ARG for NULL pointers, a side outside 1..65535, a stride below its row, an odd address or stride at depth
+ * 10, more than GS360_MAX_FRAMES jobs, tables with values that are no number or out of range. */
+#define GS360_VIDEO_444 0
+#define GS360_VIDEO_422 1
+#define GS360_VIDEO_420 2
+typedef struct gs360_video_job {
+    const void *y, *cb, *cr;                    /* H x W, and two chroma planes of the subsampled size */
+    size_t y_stride, cb_stride, cr_stride;      /* bytes; 0 = tight */
+    int32_t W, H;
+    int32_t subsampling;                        /* GS360_VIDEO_4xx */
+    int32_t reserved;
+    void *dst;                                  /* H x W x 3, uint8 or uint16 */
+    size_t dst_stride;                          /* bytes; 0 = tight */
+} gs360_video_job;
+typedef struct gs360_video_plan gs360_video_plan;
+int gs360_video_plan_create(gs360_ctx *ctx, int depth, int full_range, int keep_rec709, const float *primaries,
+                            const float *linear, const float *encode, gs360_video_plan **out);
+int gs360_video_plan_destroy(gs360_ctx *ctx, gs360_video_plan *plan);
+int gs360_video_rgb(gs360_ctx *ctx, const gs360_video_plan *plan, const gs360_video_job *jobs, int n_jobs, int slot);
+
 /* ---- frame sharpness statistics (the FrameSelector's scoring pass) ----------------------------
  * The per-pixel part of score_one_file in cli_tools/gs360_FrameSelector.py (FS:902-1044: gray conversion, fisheye-circle and
  * highlight masks, central crop band) with lapvar32 / tenengrad32 (FS:720-739: cv2.Laplacian ksize 3 + meanStdDev, cv2.Sobel x / y +
