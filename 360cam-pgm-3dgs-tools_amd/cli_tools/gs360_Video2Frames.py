@@ -8,8 +8,14 @@ reference's (V2F:247-716).  What differs is where the pixels are made: ONE ffmpe
 (gs360/vidcolor.py, VID-COLOR v1), and .jpg / .png frames are encoded from device memory when GS360_JPEG_ENCODER / GS360_PNG_ENCODER
 say `device` (default `host`: gs360/imageio.py writes them, as it always writes .tif).
 
-Refused with one `[ERR]` line and exit code 1: --fisheye-perspective (the v360 fisheye-input remap is not in the engine yet) and a
-stream the Y4M reader refuses (12 bits and above, monochrome, interlaced, truncated).
+--fisheye-perspective (V2F:467-493: `v360=<fisheye|equisolid>:rectilinear:...:interp=cubic` before the colour filter, `scale=S:S`
+after it) runs when GS360_V2F_FISHEYE=device: the decoder's command line stays as it is, and every frame leaves the GPU as the S x S
+pinhole view of VID-FISHEYE v1 (gs360/vidfisheye.py, DESIGN.md section 18: the planes interpolated with v360's cubic, then converted;
+rendered once at S x S, invisible pixels black; parity with a real ffmpeg's v360 is not pinned).  Without the variable the flag is
+refused as before; any other value of it is an error.
+
+Refused with one `[ERR]` line and exit code 1: --fisheye-perspective without GS360_V2F_FISHEYE=device, another value of that
+variable, and a stream the Y4M reader refuses (12 bits and above, monochrome, interlaced, truncated).
 """
 import argparse
 import pathlib
@@ -189,10 +195,11 @@ def _plane_jobs(header, buf, dst):
     return (y, cb, cr, w, h, header.subsampling, dst)
 
 
-def extract(args, ffmpeg_exec, in_path, out_dir, ext, prefix, suffix) -> int:
+def extract(args, ffmpeg_exec, in_path, out_dir, ext, prefix, suffix, fisheye=None) -> int:
+    """fisheye: None, or the vidfisheye.FisheyeView every frame is rendered through"""
     import numpy as np
     import gs360
-    from gs360 import imageio, jpegenc, pngenc, vidcolor, y4m
+    from gs360 import imageio, jpegenc, pngenc, vidcolor, vidfisheye, y4m
 
     cmd = decoder_argv(args, ffmpeg_exec, in_path)
     print("\n[exec] " + " ".join(shlex.quote(x) for x in cmd) + "\n")
@@ -231,12 +238,13 @@ def extract(args, ffmpeg_exec, in_path, out_dir, ext, prefix, suffix) -> int:
     jpeg_mode = jpegenc.mode_from_env() if ext in ("jpg", "jpeg") else None
     png_device = pngenc.mode_from_env() if ext == "png" else False
     out_dtype = np.uint8 if header.depth == 8 else np.uint16          # V2F:462: 8 bits stay 8, anything deeper is written as 16
-    H, W = header.height, header.width
+    H, W = (fisheye.size, fisheye.size) if fisheye else (header.height, header.width)       # of the frames written
     written = 0
     frames = None
     failure = None
     with gs360.Context(device=0, n_slots=2) as ctx:
-        stage = vidcolor.VideoColor(header.depth, header.full_range, args.keep_rec709)
+        color = vidcolor.VideoColor(header.depth, header.full_range, args.keep_rec709)
+        stage = vidfisheye.FisheyeStage(fisheye, header.depth, color=color) if fisheye else color
         dsts = []
         try:
             frames = _Frames(ctx, reader, slot=1)
@@ -271,7 +279,7 @@ def extract(args, ffmpeg_exec, in_path, out_dir, ext, prefix, suffix) -> int:
         finally:
             if frames is not None:
                 frames.close()
-            stage.close()
+            color.close()
     rc = finish_decoder(kill=failure is not None)
     if written:
         sys.stdout.write("\n")
@@ -291,6 +299,7 @@ def extract(args, ffmpeg_exec, in_path, out_dir, ext, prefix, suffix) -> int:
 def run(argv=None) -> int:
     args = build_parser().parse_args(argv)
     ffmpeg_exec = args.ffmpeg or "ffmpeg"
+    fisheye = None
     if not shutil.which(ffmpeg_exec):
         return _fail(f"ffmpeg executable not found: {ffmpeg_exec}")
     if args.fisheye_perspective:
@@ -300,7 +309,16 @@ def run(argv=None) -> int:
             return _fail("Output size must be greater than zero when using --fisheye-perspective.")
         if args.fisheye_input_fov <= 0.0:
             return _fail("Input fisheye FOV must be greater than zero when using --fisheye-perspective.")
-        return _fail("[ERR] --fisheye-perspective is not implemented by this drop-in: the engine has no fisheye-input v360 remap yet")
+        from gs360 import vidfisheye
+        try:
+            enabled = vidfisheye.mode_from_env()
+        except ValueError as exc:
+            return _fail(f"[ERR] {exc}")
+        if not enabled:
+            return _fail("[ERR] --fisheye-perspective is not implemented by this drop-in: the engine has no fisheye-input v360 remap yet")
+        if args.fisheye_size > vidfisheye.MAX_SIDE:
+            return _fail(f"[ERR] --fisheye-size {args.fisheye_size} is above the engine's {vidfisheye.MAX_SIDE}")
+        fisheye = vidfisheye.view_from_args(args.fisheye_focal_mm, args.fisheye_size, args.fisheye_projection, args.fisheye_input_fov)
     in_path = pathlib.Path(args.video).expanduser().resolve()
     if not in_path.exists():
         return _fail(f"Input file not found: {in_path}")
@@ -315,7 +333,7 @@ def run(argv=None) -> int:
         if existing is not None:
             print(f"Output exists and overwrite is disabled. First match: {existing.name}", file=sys.stderr)
             return _fail("Enable --overwrite to replace existing frames.")
-    return extract(args, ffmpeg_exec, in_path, out_dir, ext, prefix, suffix)
+    return extract(args, ffmpeg_exec, in_path, out_dir, ext, prefix, suffix, fisheye)
 
 
 def main() -> None:

@@ -1,6 +1,7 @@
-// gs360_capi_video.hip -- C-ABI glue of the decoded-video colour conversion (include/gs360.h, VID-COLOR v1): the plan and the call.
+// gs360_capi_video.hip -- C-ABI glue of the decoded-video colour conversion (include/gs360.h, VID-COLOR v1) and of the fisheye-to-pinhole
+// views of decoded frames (VID-FISHEYE v1): the plan and the two calls.
 #include "gs360_capi_internal.h"
-#include "gs360_vidsteps.h"
+#include "gs360_vidfishsteps.h"
 
 using namespace gs360;
 
@@ -78,6 +79,28 @@ int gs360_video_plan_destroy(gs360_ctx* c, gs360_video_plan* p) {
     return GS360_OK;
 }
 
+// One job's checks and its VcImage, for a destination of dst_w pixels a row: sides, subsampling, strides (0 = tight) and, at depth
+// 10, even addresses and strides.  src_bits / dst_bits: the planes' and the destination's pointers and strides OR'ed together.
+static int video_job_image(const gs360_video_job& J, int j, size_t bytes, int dst_w, VcImage& I, uintptr_t& src_bits, uintptr_t& dst_bits) {
+    if (!J.y || !J.cb || !J.cr || !J.dst) return fail(GS360_ERR_ARG, "job %d: NULL plane or destination", j);
+    if (J.W < 1 || J.H < 1 || J.W > 65535 || J.H > 65535) return fail(GS360_ERR_ARG, "job %d: size %d x %d outside 1..65535", j, J.W, J.H);
+    if (J.subsampling != GS360_VIDEO_444 && J.subsampling != GS360_VIDEO_422 && J.subsampling != GS360_VIDEO_420)
+        return fail(GS360_ERR_UNSUPPORTED, "job %d: subsampling %d (4:4:4, 4:2:2 and 4:2:0 are implemented)", j, J.subsampling);
+    I.sx = J.subsampling != GS360_VIDEO_444;
+    I.sy = J.subsampling == GS360_VIDEO_420;
+    const size_t y_row = (size_t)J.W * bytes, c_row = (size_t)((J.W + I.sx) >> I.sx) * bytes, d_row = 3 * (size_t)dst_w * bytes;
+    const size_t ys = J.y_stride ? J.y_stride : y_row, cbs = J.cb_stride ? J.cb_stride : c_row;
+    const size_t crs = J.cr_stride ? J.cr_stride : c_row, ds = J.dst_stride ? J.dst_stride : d_row;
+    if (ys < y_row || cbs < c_row || crs < c_row || ds < d_row) return fail(GS360_ERR_ARG, "job %d: stride smaller than a row", j);
+    src_bits = (uintptr_t)J.y | (uintptr_t)J.cb | (uintptr_t)J.cr | ys | cbs | crs;
+    dst_bits = (uintptr_t)J.dst | ds;
+    if (bytes == 2 && ((src_bits | dst_bits) & 1)) return fail(GS360_ERR_ARG, "job %d: 10-bit planes need even addresses and strides", j);
+    I.y = (const uint8_t*)J.y; I.cb = (const uint8_t*)J.cb; I.cr = (const uint8_t*)J.cr; I.dst = (uint8_t*)J.dst;
+    I.ys = (int64_t)ys; I.cbs = (int64_t)cbs; I.crs = (int64_t)crs; I.ds = (int64_t)ds;
+    I.W = J.W; I.H = J.H;
+    return GS360_OK;
+}
+
 int gs360_video_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360_video_job* jobs, int n_jobs, int slot) {
     if (int rc = check_ctx_slot(c, slot)) return rc;
     if (!p || (n_jobs > 0 && !jobs)) return fail(GS360_ERR_ARG, "NULL argument");
@@ -87,25 +110,10 @@ int gs360_video_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360_video_j
     const size_t bytes = p->depth == 8 ? 1 : 2;
     VidLaunch L{};
     for (int j = 0; j < n_jobs; ++j) {                       // every job is checked before anything is launched
-        const gs360_video_job& J = jobs[j];
-        if (!J.y || !J.cb || !J.cr || !J.dst) return fail(GS360_ERR_ARG, "job %d: NULL plane or destination", j);
-        if (J.W < 1 || J.H < 1 || J.W > 65535 || J.H > 65535) return fail(GS360_ERR_ARG, "job %d: size %d x %d outside 1..65535", j, J.W, J.H);
-        if (J.subsampling != GS360_VIDEO_444 && J.subsampling != GS360_VIDEO_422 && J.subsampling != GS360_VIDEO_420)
-            return fail(GS360_ERR_UNSUPPORTED, "job %d: subsampling %d (4:4:4, 4:2:2 and 4:2:0 are implemented)", j, J.subsampling);
-        VcImage& I = L.img[j];
-        I.sx = J.subsampling != GS360_VIDEO_444;
-        I.sy = J.subsampling == GS360_VIDEO_420;
-        const size_t y_row = (size_t)J.W * bytes, c_row = (size_t)((J.W + I.sx) >> I.sx) * bytes, d_row = 3 * y_row;
-        const size_t ys = J.y_stride ? J.y_stride : y_row, cbs = J.cb_stride ? J.cb_stride : c_row;
-        const size_t crs = J.cr_stride ? J.cr_stride : c_row, ds = J.dst_stride ? J.dst_stride : d_row;
-        if (ys < y_row || cbs < c_row || crs < c_row || ds < d_row) return fail(GS360_ERR_ARG, "job %d: stride smaller than a row", j);
-        const uintptr_t bits = (uintptr_t)J.y | (uintptr_t)J.cb | (uintptr_t)J.cr | (uintptr_t)J.dst | ys | cbs | crs | ds;
-        if (bytes == 2 && (bits & 1)) return fail(GS360_ERR_ARG, "job %d: 10-bit planes need even addresses and strides", j);
-        I.y = (const uint8_t*)J.y; I.cb = (const uint8_t*)J.cb; I.cr = (const uint8_t*)J.cr; I.dst = (uint8_t*)J.dst;
-        I.ys = (int64_t)ys; I.cbs = (int64_t)cbs; I.crs = (int64_t)crs; I.ds = (int64_t)ds;
-        I.W = J.W; I.H = J.H;
-        I.fast = (bits & 3) == 0;
-        I.gpr = (J.W + kVcGroup - 1) / kVcGroup;
+        uintptr_t src_bits = 0, dst_bits = 0;
+        if (int rc = video_job_image(jobs[j], j, bytes, jobs[j].W, L.img[j], src_bits, dst_bits)) return rc;
+        L.img[j].fast = ((src_bits | dst_bits) & 3) == 0;
+        L.img[j].gpr = (jobs[j].W + kVcGroup - 1) / kVcGroup;
     }
     L.lin = p->d_tables;
     L.enc = reinterpret_cast<const float2*>(p->d_tables + kVcLevels);
@@ -115,5 +123,66 @@ int gs360_video_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360_video_j
     L.n_jobs = n_jobs;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_vidcolor(L, p->depth, c->stream[slot]));
+    return GS360_OK;
+}
+
+// the float32 constants of a view, each a float64 expression rounded once; tests/vidfisheye_np.py derives the same.
+static VfView fisheye_constants(const gs360_video_fisheye_view& v) {
+    const double rad = M_PI / 180.0;
+    const double W = (double)v.W, H = (double)v.H;
+    double kx, ky;
+    if (v.projection == GS360_FISHEYE_EQUISOLID) {
+        const double s = std::sin(v.input_fov_deg * rad / 4.0);
+        kx = (W / 2.0) / s; ky = (H / 2.0) / s;
+    } else {
+        kx = W / (v.input_fov_deg * rad); ky = H / (v.input_fov_deg * rad);
+    }
+    VfView V;
+    V.proj = v.projection == GS360_FISHEYE_EQUISOLID ? kVfEquisolid : kVfEquidistant;
+    V.S = v.size;
+    V.tx = (float)(std::tan(v.h_fov_deg * rad / 2.0) / (double)v.size);
+    V.ty = (float)(std::tan(v.v_fov_deg * rad / 2.0) / (double)v.size);
+    V.kx32 = (float)(32.0 * kx); V.ky32 = (float)(32.0 * ky);
+    V.kx16 = (float)(16.0 * kx); V.ky16 = (float)(16.0 * ky);
+    V.ox32 = (float)(16 * v.W - 16); V.oy32 = (float)(16 * v.H - 16);
+    V.ox16 = (float)(8 * v.W - 16); V.oy16 = (float)(8 * v.H - 16);
+    return V;
+}
+
+int gs360_video_fisheye_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360_video_fisheye_view* view, const gs360_video_job* jobs,
+                            int n_jobs, int slot) {
+    if (int rc = check_ctx_slot(c, slot)) return rc;
+    if (!p || !view || (n_jobs > 0 && !jobs)) return fail(GS360_ERR_ARG, "NULL argument");
+    if (p->device != c->device) return fail(GS360_ERR_ARG, "video plan belongs to device %d, ctx is device %d", p->device, c->device);
+    if (n_jobs < 0 || n_jobs > GS360_MAX_FRAMES) return fail(GS360_ERR_ARG, "n_jobs %d outside [0,%d]", n_jobs, GS360_MAX_FRAMES);
+    const gs360_video_fisheye_view& v = *view;
+    if (v.projection != GS360_FISHEYE_EQUIDISTANT && v.projection != GS360_FISHEYE_EQUISOLID)
+        return fail(GS360_ERR_ARG, "fisheye projection %d (equidistant and equisolid are implemented)", v.projection);
+    // 16384: a 1/32-px coordinate stays below 2^19 + 2^4, far inside float32's integers
+    if (v.size < 1 || v.size > GS360_FISHEYE_MAX_SIDE) return fail(GS360_ERR_ARG, "view size %d outside 1..%d", v.size, GS360_FISHEYE_MAX_SIDE);
+    if (v.W < 1 || v.H < 1 || v.W > GS360_FISHEYE_MAX_SIDE || v.H > GS360_FISHEYE_MAX_SIDE)
+        return fail(GS360_ERR_ARG, "source %d x %d outside 1..%d", v.W, v.H, GS360_FISHEYE_MAX_SIDE);
+    if (!(v.input_fov_deg >= 1.0 && v.input_fov_deg <= 360.0)) return fail(GS360_ERR_ARG, "input fov %g outside [1,360]", v.input_fov_deg);
+    if (!(v.h_fov_deg >= 1.0 && v.h_fov_deg <= 179.0 && v.v_fov_deg >= 1.0 && v.v_fov_deg <= 179.0))
+        return fail(GS360_ERR_ARG, "view fov %g x %g outside [1,179]", v.h_fov_deg, v.v_fov_deg);
+    if (n_jobs == 0) return GS360_OK;
+    const size_t bytes = p->depth == 8 ? 1 : 2;
+    VfLaunch L{};
+    for (int j = 0; j < n_jobs; ++j) {                       // every job is checked before anything is launched
+        uintptr_t src_bits = 0, dst_bits = 0;
+        if (int rc = video_job_image(jobs[j], j, bytes, v.size, L.img[j], src_bits, dst_bits)) return rc;
+        if (jobs[j].W != v.W || jobs[j].H != v.H)
+            return fail(GS360_ERR_ARG, "job %d: %d x %d is not the view's source size %d x %d", j, jobs[j].W, jobs[j].H, v.W, v.H);
+        L.img[j].fast = (src_bits & 3) == 0;                 // the destination is written sample by sample
+    }
+    L.lin = p->d_tables;
+    L.enc = reinterpret_cast<const float2*>(p->d_tables + kVcLevels);
+    std::memcpy(L.m, p->m, sizeof(L.m));
+    L.outmax = p->depth == 8 ? 255 : 65535;
+    L.coef = p->coef;
+    L.view = fisheye_constants(v);
+    L.n_jobs = n_jobs;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_vidfisheye(L, p->depth, c->stream[slot]));
     return GS360_OK;
 }

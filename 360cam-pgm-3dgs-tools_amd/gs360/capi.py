@@ -41,7 +41,7 @@ EXPORTS = (
     "gs360_mask_inpaint_scratch", "gs360_mask_inpaint_u8",
     "gs360_voxel_scratch", "gs360_cloud_bounds_f32", "gs360_voxel_count_f32", "gs360_voxel_pick_f32",
     "gs360_octree_scratch", "gs360_octree_pick_f32",
-    "gs360_video_plan_create", "gs360_video_plan_destroy", "gs360_video_rgb",
+    "gs360_video_plan_create", "gs360_video_plan_destroy", "gs360_video_rgb", "gs360_video_fisheye_rgb",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -65,6 +65,8 @@ INPAINT_MAX_LEVEL = 4095             # GS360_INPAINT_MAX_LEVEL
 VOXEL_FIRST, VOXEL_CENTER, VOXEL_CENTROID, VOXEL_SEGMENTS = 0, 1, 2, 3   # GS360_VOXEL_*: the `strategy` of gs360_voxel_pick_f32
 VOXEL_MAX_POINTS = (1 << 31) - 1     # GS360_VOXEL_MAX_POINTS: indices are 32-bit on the device
 VIDEO_444, VIDEO_422, VIDEO_420 = 0, 1, 2   # GS360_VIDEO_*: the `subsampling` of a gs360_video_job
+FISHEYE_EQUIDISTANT, FISHEYE_EQUISOLID = 0, 1   # GS360_FISHEYE_*: the `projection` of a gs360_video_fisheye_view
+FISHEYE_MAX_SIDE = 16384             # GS360_FISHEYE_MAX_SIDE: the largest source side and view size of gs360_video_fisheye_rgb
 ERR_ARG = -1                         # GS360_ERR_ARG / GS360_ERR_UNSUPPORTED
 ERR_UNSUPPORTED = -4
 ERR_INTERNAL = -6                    # GS360_ERR_INTERNAL: a kernel's own bound was exceeded
@@ -127,6 +129,12 @@ class VideoJob(C.Structure):
     _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_size_t), ("cb_stride", C.c_size_t),
                 ("cr_stride", C.c_size_t), ("W", C.c_int32), ("H", C.c_int32), ("subsampling", C.c_int32), ("reserved", C.c_int32),
                 ("dst", C.c_void_p), ("dst_stride", C.c_size_t)]
+
+
+class VideoFisheyeView(C.Structure):
+    """gs360_video_fisheye_view: the geometry of a gs360_video_fisheye_rgb call."""
+    _fields_ = [("projection", C.c_int32), ("size", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
+                ("input_fov_deg", C.c_double), ("h_fov_deg", C.c_double), ("v_fov_deg", C.c_double)]
 
 
 class MaskJob(C.Structure):
@@ -316,6 +324,7 @@ def load_library(path=None):
         L.gs360_video_plan_create.argtypes = [vp, i, i, i, vp, vp, vp, pvp]
         L.gs360_video_plan_destroy.argtypes = [vp, vp]
         L.gs360_video_rgb.argtypes = [vp, vp, C.POINTER(VideoJob), i, i]
+        L.gs360_video_fisheye_rgb.argtypes = [vp, vp, C.POINTER(VideoFisheyeView), C.POINTER(VideoJob), i, i]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         if path is None:
@@ -687,16 +696,27 @@ class Context:
         if plan:
             _check(self.L.gs360_video_plan_destroy(self.handle, plan), self.L)
 
-    def video_rgb_dev(self, plan, jobs, slot=0):
-        """gs360_video_rgb: jobs = sequence of (y, cb, cr, W, H, subsampling, dst[, y_stride, cb_stride, cr_stride, dst_stride]),
-        the planes and dst DeviceBuffers or device addresses, strides in bytes (0 = tight).  Asynchronous on `slot`."""
+    @staticmethod
+    def _video_jobs(jobs):
         def addr(b):
             return b.ptr if isinstance(b, DeviceBuffer) else int(b)
         arr = (VideoJob * max(len(jobs), 1))()
         for k, (y, cb, cr, W, H, sub, dst, *strides) in enumerate(jobs):
             ys, cbs, crs, ds = (list(strides) + [0, 0, 0, 0])[:4]
             arr[k] = VideoJob(addr(y), addr(cb), addr(cr), int(ys), int(cbs), int(crs), int(W), int(H), int(sub), 0, addr(dst), int(ds))
-        _check(self.L.gs360_video_rgb(self.handle, plan, arr, len(jobs), slot), self.L)
+        return arr
+
+    def video_rgb_dev(self, plan, jobs, slot=0):
+        """gs360_video_rgb: jobs = sequence of (y, cb, cr, W, H, subsampling, dst[, y_stride, cb_stride, cr_stride, dst_stride]),
+        the planes and dst DeviceBuffers or device addresses, strides in bytes (0 = tight).  Asynchronous on `slot`."""
+        _check(self.L.gs360_video_rgb(self.handle, plan, self._video_jobs(jobs), len(jobs), slot), self.L)
+
+    def video_fisheye_rgb_dev(self, plan, view, jobs, slot=0):
+        """gs360_video_fisheye_rgb: view = (projection, size, W, H, input_fov_deg, h_fov_deg, v_fov_deg) or None (a NULL view); jobs
+        as for video_rgb_dev, every job's W x H the view's and its dst size x size x 3.  Asynchronous on `slot`."""
+        v = None if view is None else C.byref(VideoFisheyeView(int(view[0]), int(view[1]), int(view[2]), int(view[3]),
+                                                               float(view[4]), float(view[5]), float(view[6])))
+        _check(self.L.gs360_video_fisheye_rgb(self.handle, plan, v, self._video_jobs(jobs), len(jobs), slot), self.L)
 
     # -- frame sharpness statistics (gs360/framescore.py) -------------------------------------
     def _by_depth(self, name, depth):

@@ -384,6 +384,38 @@ int gs360_video_plan_create(gs360_ctx *ctx, int depth, int full_range, int keep_
 int gs360_video_plan_destroy(gs360_ctx *ctx, gs360_video_plan *plan);
 int gs360_video_rgb(gs360_ctx *ctx, const gs360_video_plan *plan, const gs360_video_job *jobs, int n_jobs, int slot);
 
+/* ---- decoded fisheye frames: Y'CbCr planes -> a pinhole view in RGB (VID-FISHEYE v1) ------------------------
+ * gs360_Video2Frames.py's --fisheye-perspective graph (V2F:467-493), `v360=<fisheye|equisolid>:rectilinear:ih_fov=F:iv_fov=F:
+ * h_fov=..:v_fov=..:interp=cubic` followed by the colorspace filter, on device-resident planes in one kernel: every pixel of the
+ * S x S view takes its place in the ideal fisheye image (yaw, pitch and roll zero, the lens circle spanning the W x H source), each of
+ * the three planes is interpolated there with v360's cubic (4 x 4 taps, 14-bit integer weights, 1/32-px phases, indices clamped to the
+ * plane, a subsampled plane at its own coordinate with chroma sample k at luma 2k + 1/2), and the three samples go through
+ * gs360_video_rgb's conversion unchanged: interpolate first, convert afterwards, the reference's order.  Pixels whose ray leaves the
+ * source are RGB (0, 0, 0).  Every step is discrete and stated in DESIGN.md 18; tests/vidfisheye_np.py restates it and gives the same
+ * bytes.  Deviations from the reference's chain: the view is rendered once at S x S in 4:4:4 (the reference renders at v360's default
+ * output size with subsampled chroma, then swscale's scale=S:S); 10-bit footage keeps its depth; invisible pixels are black; pixel
+ * centres sit at integers (the -1/2 convention of EQ-SPEC).  Parity with a real ffmpeg's v360 is NOT pinned: the definition is pinned
+ * against float64 mathematics and hand-derivable answers (tests/test_vidfisheye_cpu.py).
+ *   plan   a gs360_video_plan: depth, range, curve and tables as for gs360_video_rgb.
+ *   view   the geometry: gs360/vidfisheye.py's view_from_args derives the fields of view as the reference does; the library derives
+ *          the kernel's float32 constants from them.
+ *   jobs   up to GS360_MAX_FRAMES; every job's W x H is the view's; dst is S x S x 3 (dst_stride 0 = 3 S samples); subsampling and
+ *          strides may differ.  Plane pointers and strides that are all multiples of 4 take the dword path.  Asynchronous on `slot`.
+ * Errors, checked for the view and every job before anything is written: GS360_ERR_ARG for a NULL view, another projection, S or a
+ * source side outside 1..GS360_FISHEYE_MAX_SIDE, input_fov_deg outside [1,360], h_fov_deg or v_fov_deg outside [1,179], a job of
+ * another size than the view's, and whatever gs360_video_rgb refuses of a job (with its codes). */
+#define GS360_FISHEYE_EQUIDISTANT 0
+#define GS360_FISHEYE_EQUISOLID 1
+#define GS360_FISHEYE_MAX_SIDE 16384
+typedef struct gs360_video_fisheye_view {
+    int32_t projection;                         /* GS360_FISHEYE_EQUIDISTANT | GS360_FISHEYE_EQUISOLID */
+    int32_t size;                               /* S: the view is S x S */
+    int32_t W, H;                               /* every job's source size */
+    double input_fov_deg, h_fov_deg, v_fov_deg; /* the lens circle's field of view; the view's, both axes */
+} gs360_video_fisheye_view;
+int gs360_video_fisheye_rgb(gs360_ctx *ctx, const gs360_video_plan *plan, const gs360_video_fisheye_view *view,
+                            const gs360_video_job *jobs, int n_jobs, int slot);
+
 /* ---- frame sharpness statistics (the FrameSelector's scoring pass) ----------------------------
  * The per-pixel part of score_one_file in cli_tools/gs360_FrameSelector.py (FS:902-1044: gray conversion, fisheye-circle and
  * highlight masks, central crop band) with lapvar32 / tenengrad32 (FS:720-739: cv2.Laplacian ksize 3 + meanStdDev, cv2.Sobel x / y +
