@@ -232,6 +232,14 @@ def run_one(cmd: List[str]) -> Tuple[int, str]:
         plan = _video.build_decode_plan(job)
         if plan is None:
             return _run_subprocess(cmd)
+        try:
+            from gs360 import engine as _engine
+            if _engine.get_engine().video_feed == "planes":   # GS360_VIDEO_FEED as the engine read it (VID-FEED v1)
+                plan = _video.build_decode_plan(job, "planes")
+        except ValueError as exc:
+            return 1, f"[ERR] {exc}"
+        except Exception:  # noqa: BLE001  (no GPU / no library: reported below, exactly as before)
+            pass
     try:
         from gs360 import engine as _engine
         if plan is None:
@@ -306,6 +314,13 @@ def main():
     for attr in ("size", "hfov", "focal_mm"):
         setattr(args, f"{attr}_explicit", getattr(args, f"{attr}_explicit", False))
     _engine_choice = args.engine
+    if _selected_engine() != "ffmpeg":
+        try:
+            from gs360 import video as _video
+            _video.feed_from_env()                # GS360_VIDEO_FEED: a wrong value ends the run here, before anything is planned
+        except ValueError as exc:
+            print(f"[ERR] {exc}", file=sys.stderr)
+            sys.exit(1)
 
     input_path = pathlib.Path(args.input_dir).expanduser().resolve()
     if input_path.is_dir():

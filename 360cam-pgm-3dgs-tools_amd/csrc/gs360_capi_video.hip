@@ -8,6 +8,8 @@ using namespace gs360;
 struct gs360_video_plan {
     int device = 0;
     int depth = 0;
+    int out_bits = 0;               // 8 or 16: (8, 8), (10, 16) and, for VID-FEED v1, (10, 8)
+    int outmax = 0;                 // 255 or 65535, what the encode table was built for
     VcCoef coef{};
     float m[9] = {};
     float* d_tables = nullptr;      // kVcLevels floats of linearised levels, then kVcEnc encode cells
@@ -33,12 +35,19 @@ static VcCoef video_coefficients(int depth, int full_range) {
 
 int gs360_video_plan_create(gs360_ctx* c, int depth, int full_range, int keep_rec709, const float* primaries, const float* linear,
                             const float* encode, gs360_video_plan** out) {
+    return gs360_video_plan_create_out(c, depth, depth == 8 ? 8 : 16, full_range, keep_rec709, primaries, linear, encode, out);
+}
+
+int gs360_video_plan_create_out(gs360_ctx* c, int depth, int out_bits, int full_range, int keep_rec709, const float* primaries,
+                                const float* linear, const float* encode, gs360_video_plan** out) {
     if (!c) return fail(GS360_ERR_ARG, "ctx is NULL");
     if (!primaries || !linear || !encode || !out) return fail(GS360_ERR_ARG, "NULL argument");
     if (depth != 8 && depth != 10) return fail(GS360_ERR_UNSUPPORTED, "video depth %d (8 and 10 bits are implemented)", depth);
+    if (!((out_bits == 8) || (out_bits == 16 && depth == 10)))
+        return fail(GS360_ERR_UNSUPPORTED, "%d-bit RGB from %d-bit planes (8 from 8, 16 from 10 and 8 from 10 are implemented)", out_bits, depth);
     if ((full_range | keep_rec709) & ~1) return fail(GS360_ERR_ARG, "full_range and keep_rec709 are 0 or 1");
     // the tables index each other: a linear value outside [0,1] or a matrix entry that is no number would leave the encode table
-    const float outmax = depth == 8 ? 255.0f : 65535.0f;
+    const float outmax = out_bits == 8 ? 255.0f : 65535.0f;
     for (int i = 0; i < 9; ++i)
         if (!std::isfinite(primaries[i])) return fail(GS360_ERR_ARG, "primaries[%d] is not finite", i);
     for (int i = 0; i < kVcLevels; ++i)
@@ -53,6 +62,8 @@ int gs360_video_plan_create(gs360_ctx* c, int depth, int full_range, int keep_re
     if (!p) return fail(GS360_ERR_NOMEM, "out of host memory");
     p->device = c->device;
     p->depth = depth;
+    p->out_bits = out_bits;
+    p->outmax = (int)outmax;
     p->coef = video_coefficients(depth, full_range);
     std::memcpy(p->m, primaries, sizeof(p->m));
     const size_t n_lin = kVcLevels * sizeof(float), n_enc = kVcEnc * 2 * sizeof(float);
@@ -79,22 +90,26 @@ int gs360_video_plan_destroy(gs360_ctx* c, gs360_video_plan* p) {
     return GS360_OK;
 }
 
-// One job's checks and its VcImage, for a destination of dst_w pixels a row: sides, subsampling, strides (0 = tight) and, at depth
-// 10, even addresses and strides.  src_bits / dst_bits: the planes' and the destination's pointers and strides OR'ed together.
-static int video_job_image(const gs360_video_job& J, int j, size_t bytes, int dst_w, VcImage& I, uintptr_t& src_bits, uintptr_t& dst_bits) {
+// One job's checks and its VcImage, for a destination of dst_w pixels a row: sides, subsampling, strides (0 = tight) and, on whichever
+// side has 16-bit samples, even addresses and strides.  src_bits / dst_bits: the planes' and the destination's pointers and strides
+// OR'ed together.
+static int video_job_image(const gs360_video_job& J, int j, const gs360_video_plan& P, int dst_w, VcImage& I, uintptr_t& src_bits,
+                           uintptr_t& dst_bits) {
+    const size_t bytes = P.depth == 8 ? 1 : 2, dbytes = P.out_bits == 8 ? 1 : 2;
     if (!J.y || !J.cb || !J.cr || !J.dst) return fail(GS360_ERR_ARG, "job %d: NULL plane or destination", j);
     if (J.W < 1 || J.H < 1 || J.W > 65535 || J.H > 65535) return fail(GS360_ERR_ARG, "job %d: size %d x %d outside 1..65535", j, J.W, J.H);
     if (J.subsampling != GS360_VIDEO_444 && J.subsampling != GS360_VIDEO_422 && J.subsampling != GS360_VIDEO_420)
         return fail(GS360_ERR_UNSUPPORTED, "job %d: subsampling %d (4:4:4, 4:2:2 and 4:2:0 are implemented)", j, J.subsampling);
     I.sx = J.subsampling != GS360_VIDEO_444;
     I.sy = J.subsampling == GS360_VIDEO_420;
-    const size_t y_row = (size_t)J.W * bytes, c_row = (size_t)((J.W + I.sx) >> I.sx) * bytes, d_row = 3 * (size_t)dst_w * bytes;
+    const size_t y_row = (size_t)J.W * bytes, c_row = (size_t)((J.W + I.sx) >> I.sx) * bytes, d_row = 3 * (size_t)dst_w * dbytes;
     const size_t ys = J.y_stride ? J.y_stride : y_row, cbs = J.cb_stride ? J.cb_stride : c_row;
     const size_t crs = J.cr_stride ? J.cr_stride : c_row, ds = J.dst_stride ? J.dst_stride : d_row;
     if (ys < y_row || cbs < c_row || crs < c_row || ds < d_row) return fail(GS360_ERR_ARG, "job %d: stride smaller than a row", j);
     src_bits = (uintptr_t)J.y | (uintptr_t)J.cb | (uintptr_t)J.cr | ys | cbs | crs;
     dst_bits = (uintptr_t)J.dst | ds;
-    if (bytes == 2 && ((src_bits | dst_bits) & 1)) return fail(GS360_ERR_ARG, "job %d: 10-bit planes need even addresses and strides", j);
+    if (bytes == 2 && (src_bits & 1)) return fail(GS360_ERR_ARG, "job %d: 10-bit planes need even addresses and strides", j);
+    if (dbytes == 2 && (dst_bits & 1)) return fail(GS360_ERR_ARG, "job %d: a 16-bit destination needs an even address and stride", j);
     I.y = (const uint8_t*)J.y; I.cb = (const uint8_t*)J.cb; I.cr = (const uint8_t*)J.cr; I.dst = (uint8_t*)J.dst;
     I.ys = (int64_t)ys; I.cbs = (int64_t)cbs; I.crs = (int64_t)crs; I.ds = (int64_t)ds;
     I.W = J.W; I.H = J.H;
@@ -107,22 +122,21 @@ int gs360_video_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360_video_j
     if (p->device != c->device) return fail(GS360_ERR_ARG, "video plan belongs to device %d, ctx is device %d", p->device, c->device);
     if (n_jobs < 0 || n_jobs > GS360_MAX_FRAMES) return fail(GS360_ERR_ARG, "n_jobs %d outside [0,%d]", n_jobs, GS360_MAX_FRAMES);
     if (n_jobs == 0) return GS360_OK;
-    const size_t bytes = p->depth == 8 ? 1 : 2;
     VidLaunch L{};
     for (int j = 0; j < n_jobs; ++j) {                       // every job is checked before anything is launched
         uintptr_t src_bits = 0, dst_bits = 0;
-        if (int rc = video_job_image(jobs[j], j, bytes, jobs[j].W, L.img[j], src_bits, dst_bits)) return rc;
+        if (int rc = video_job_image(jobs[j], j, *p, jobs[j].W, L.img[j], src_bits, dst_bits)) return rc;
         L.img[j].fast = ((src_bits | dst_bits) & 3) == 0;
         L.img[j].gpr = (jobs[j].W + kVcGroup - 1) / kVcGroup;
     }
     L.lin = p->d_tables;
     L.enc = reinterpret_cast<const float2*>(p->d_tables + kVcLevels);
     std::memcpy(L.m, p->m, sizeof(L.m));
-    L.outmax = p->depth == 8 ? 255 : 65535;
+    L.outmax = p->outmax;
     L.coef = p->coef;
     L.n_jobs = n_jobs;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(launch_vidcolor(L, p->depth, c->stream[slot]));
+    HIP_TRY(launch_vidcolor(L, p->depth, p->out_bits, c->stream[slot]));
     return GS360_OK;
 }
 
@@ -155,6 +169,8 @@ int gs360_video_fisheye_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360
     if (!p || !view || (n_jobs > 0 && !jobs)) return fail(GS360_ERR_ARG, "NULL argument");
     if (p->device != c->device) return fail(GS360_ERR_ARG, "video plan belongs to device %d, ctx is device %d", p->device, c->device);
     if (n_jobs < 0 || n_jobs > GS360_MAX_FRAMES) return fail(GS360_ERR_ARG, "n_jobs %d outside [0,%d]", n_jobs, GS360_MAX_FRAMES);
+    if (p->out_bits != (p->depth == 8 ? 8 : 16))
+        return fail(GS360_ERR_UNSUPPORTED, "fisheye views of a %d-bit plan with %d-bit output are not implemented", p->depth, p->out_bits);
     const gs360_video_fisheye_view& v = *view;
     if (v.projection != GS360_FISHEYE_EQUIDISTANT && v.projection != GS360_FISHEYE_EQUISOLID)
         return fail(GS360_ERR_ARG, "fisheye projection %d (equidistant and equisolid are implemented)", v.projection);
@@ -166,11 +182,10 @@ int gs360_video_fisheye_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360
     if (!(v.h_fov_deg >= 1.0 && v.h_fov_deg <= 179.0 && v.v_fov_deg >= 1.0 && v.v_fov_deg <= 179.0))
         return fail(GS360_ERR_ARG, "view fov %g x %g outside [1,179]", v.h_fov_deg, v.v_fov_deg);
     if (n_jobs == 0) return GS360_OK;
-    const size_t bytes = p->depth == 8 ? 1 : 2;
     VfLaunch L{};
     for (int j = 0; j < n_jobs; ++j) {                       // every job is checked before anything is launched
         uintptr_t src_bits = 0, dst_bits = 0;
-        if (int rc = video_job_image(jobs[j], j, bytes, v.size, L.img[j], src_bits, dst_bits)) return rc;
+        if (int rc = video_job_image(jobs[j], j, *p, v.size, L.img[j], src_bits, dst_bits)) return rc;
         if (jobs[j].W != v.W || jobs[j].H != v.H)
             return fail(GS360_ERR_ARG, "job %d: %d x %d is not the view's source size %d x %d", j, jobs[j].W, jobs[j].H, v.W, v.H);
         L.img[j].fast = (src_bits & 3) == 0;                 // the destination is written sample by sample
@@ -178,7 +193,7 @@ int gs360_video_fisheye_rgb(gs360_ctx* c, const gs360_video_plan* p, const gs360
     L.lin = p->d_tables;
     L.enc = reinterpret_cast<const float2*>(p->d_tables + kVcLevels);
     std::memcpy(L.m, p->m, sizeof(L.m));
-    L.outmax = p->depth == 8 ? 255 : 65535;
+    L.outmax = p->outmax;
     L.coef = p->coef;
     L.view = fisheye_constants(v);
     L.n_jobs = n_jobs;

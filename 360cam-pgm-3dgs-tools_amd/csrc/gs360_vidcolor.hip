@@ -5,7 +5,8 @@
 // A streaming kernel: 1.5 to 6 bytes in, 3 to 6 bytes out per pixel.  A lane takes a group of 8 x 2 pixels (gs360_vidsteps.h): per row
 // 8 (uint8) or 16 (uint16) bytes of luma and 4 to 16 bytes of chroma come in as whole dwords and 24 or 48 bytes of RGB leave as whole
 // dwords; consecutive lanes take consecutive groups of a row, so a wavefront's loads and stores cover contiguous bytes.  The tail of a
-// row, and every pixel of a job whose pointers or strides are not multiples of 4, goes sample by sample.
+// row, and every pixel of a job whose pointers or strides are not multiples of 4, goes sample by sample.  The third instantiation,
+// uint16 planes -> uint8 RGB (VID-FEED v1), loads as the 10-bit one does and stores as the 8-bit one does.
 //
 // Both transfer curves are tables in LDS (64 KiB of linearised levels + 8 KiB of encode cells = 72 KiB: two workgroups per CU), read
 // with data-dependent addresses, so bank conflicts are the rule; the workgroups are persistent and load the tables once.
@@ -19,7 +20,7 @@ namespace {
 constexpr int kVcThreads = 512;
 constexpr int kVcBlocks = 512;       // persistent workgroups: 256 CUs x 2
 
-template <typename S>
+template <typename S, typename D>
 __global__ __launch_bounds__(kVcThreads) void vidcolor_kernel(VidLaunch A) {
     __shared__ float lin[kVcLevels];
     __shared__ float2 enc[kVcEnc];
@@ -38,13 +39,13 @@ __global__ __launch_bounds__(kVcThreads) void vidcolor_kernel(VidLaunch A) {
         while (t >= A.tile_end[j]) ++j;                       // tiles are numbered job by job
         const VcImage& I = A.img[j];
         const uint32_t g = (t - (j ? A.tile_end[j - 1] : 0u)) * kVcThreads + threadIdx.x;
-        if (g < (uint32_t)I.gpr * (uint32_t)((I.H + 1) >> 1)) vc_group<S>(I, A.coef, T, g);
+        if (g < (uint32_t)I.gpr * (uint32_t)((I.H + 1) >> 1)) vc_group<S, D>(I, A.coef, T, g);
     }
 }
 
 }  // namespace
 
-hipError_t launch_vidcolor(VidLaunch& L, int depth, hipStream_t s) {
+hipError_t launch_vidcolor(VidLaunch& L, int depth, int out_bits, hipStream_t s) {
     uint32_t total = 0;
     for (int j = 0; j < L.n_jobs; ++j) {
         total += (vc_groups(L.img[j]) + kVcThreads - 1) / kVcThreads;
@@ -52,8 +53,10 @@ hipError_t launch_vidcolor(VidLaunch& L, int depth, hipStream_t s) {
     }
     if (total == 0) return hipSuccess;
     const dim3 grid(total < (uint32_t)kVcBlocks ? total : (uint32_t)kVcBlocks), block(kVcThreads);
-    if (depth == 8) hipLaunchKernelGGL((vidcolor_kernel<uint8_t>), grid, block, 0, s, L);
-    else hipLaunchKernelGGL((vidcolor_kernel<uint16_t>), grid, block, 0, s, L);
+    if (depth == 8 && out_bits == 8) hipLaunchKernelGGL((vidcolor_kernel<uint8_t, uint8_t>), grid, block, 0, s, L);
+    else if (depth == 10 && out_bits == 16) hipLaunchKernelGGL((vidcolor_kernel<uint16_t, uint16_t>), grid, block, 0, s, L);
+    else if (depth == 10 && out_bits == 8) hipLaunchKernelGGL((vidcolor_kernel<uint16_t, uint8_t>), grid, block, 0, s, L);
+    else return hipErrorInvalidValue;            // plan_create_out makes no other pair
     return hipGetLastError();
 }
 

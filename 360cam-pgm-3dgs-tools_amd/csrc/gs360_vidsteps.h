@@ -24,7 +24,7 @@ struct VcTables {
     const float* lin;      // kVcLevels: Rec.709 R'G'B' level -> linear light
     const float2* enc;     // kVcEnc cells: (level at the cell's lower edge, rise over the cell), in output levels
     float m[9];            // BT.709 -> SMPTE-C primaries, row-major
-    int32_t outmax;        // 255 or 65535
+    int32_t outmax;        // 255 or 65535: the destination's largest level
 };
 
 struct VcImage {           // one job; strides in bytes
@@ -73,14 +73,15 @@ __host__ __device__ inline const S* vc_row(const uint8_t* base, int64_t stride, 
 }
 
 // One pixel through both steps with sample-sized loads and stores: the tail of a row, and every pixel of a job that is not `fast`.
-template <typename S>
+// D: the destination's sample type (uint8_t from uint16_t planes is the (10, 8) format of DESIGN.md section 19).
+template <typename S, typename D = S>
 __host__ __device__ inline void vc_pixel(const VcImage& I, const VcCoef& K, const VcTables& T, int x, int y) {
     const int cx = x >> I.sx, cy = y >> I.sy;
     int q[3], o[3];
     vc_rgb14(K, (int)vc_row<S>(I.y, I.ys, y)[x], (int)vc_row<S>(I.cb, I.cbs, cy)[cx], (int)vc_row<S>(I.cr, I.crs, cy)[cx], q);
     vc_levels(T, q, o);
-    S* d = reinterpret_cast<S*>(I.dst + (int64_t)y * I.ds) + 3 * (int64_t)x;
-    d[0] = (S)o[0]; d[1] = (S)o[1]; d[2] = (S)o[2];
+    D* d = reinterpret_cast<D*>(I.dst + (int64_t)y * I.ds) + 3 * (int64_t)x;
+    d[0] = (D)o[0]; d[1] = (D)o[1]; d[2] = (D)o[2];
 }
 
 // N samples of S as whole dwords from a dword-aligned address, and sample i of them
@@ -98,11 +99,11 @@ __host__ __device__ inline int vc_sample(const VcWords<S, N>& v, int i) {
     return (int)((v.w[i / kPer] >> ((i % kPer) * kBits)) & ((1u << kBits) - 1u));
 }
 
-// Eight pixels of row y from x0 (x0 + 8 <= W, `fast` job): whole-dword loads, 6 (uint8) or 12 (uint16) whole-dword stores.
+// Eight pixels of row y from x0 (x0 + 8 <= W, `fast` job): whole-dword loads, 6 (D = uint8) or 12 (D = uint16) whole-dword stores.
 // SX: the chroma planes are subsampled along the row (four samples serve the eight pixels).
-template <typename S, int SX>
+template <typename S, int SX, typename D = S>
 __host__ __device__ inline void vc_row8(const VcImage& I, const VcCoef& K, const VcTables& T, int x0, int y) {
-    constexpr int kBits = 8 * (int)sizeof(S), kPer = 32 / kBits, kC = kVcGroup >> SX, kOut = 3 * kVcGroup / kPer;
+    constexpr int kBits = 8 * (int)sizeof(D), kPer = 32 / kBits, kC = kVcGroup >> SX, kOut = 3 * kVcGroup / kPer;
     const int cy = y >> I.sy, cx0 = x0 >> SX;
     const VcWords<S, kVcGroup> Y = vc_load<S, kVcGroup>(vc_row<S>(I.y, I.ys, y) + x0);
     const VcWords<S, kC> U = vc_load<S, kC>(vc_row<S>(I.cb, I.cbs, cy) + cx0);
@@ -121,12 +122,12 @@ __host__ __device__ inline void vc_row8(const VcImage& I, const VcCoef& K, const
             out[s / kPer] |= (uint32_t)o[c] << ((s % kPer) * kBits);
         }
     }
-    S* d = reinterpret_cast<S*>(I.dst + (int64_t)y * I.ds) + 3 * (int64_t)x0;
+    D* d = reinterpret_cast<D*>(I.dst + (int64_t)y * I.ds) + 3 * (int64_t)x0;
     __builtin_memcpy(__builtin_assume_aligned(d, 4), out, sizeof(out));
 }
 
 // Group g of a job: pixels [8 gx, 8 gx + 8) of rows 2 gy and 2 gy + 1, clipped to the image.
-template <typename S>
+template <typename S, typename D = S>
 __host__ __device__ inline void vc_group(const VcImage& I, const VcCoef& K, const VcTables& T, uint32_t g) {
     const int gy = (int)(g / (uint32_t)I.gpr), gx = (int)(g - (uint32_t)gy * (uint32_t)I.gpr);
     const int x0 = gx * kVcGroup;
@@ -134,10 +135,10 @@ __host__ __device__ inline void vc_group(const VcImage& I, const VcCoef& K, cons
 #pragma unroll 1
     for (int y = 2 * gy; y < 2 * gy + 2 && y < I.H; ++y) {
         if (I.fast && n == kVcGroup) {
-            if (I.sx) vc_row8<S, 1>(I, K, T, x0, y);
-            else vc_row8<S, 0>(I, K, T, x0, y);
+            if (I.sx) vc_row8<S, 1, D>(I, K, T, x0, y);
+            else vc_row8<S, 0, D>(I, K, T, x0, y);
         } else {
-            for (int i = 0; i < n; ++i) vc_pixel<S>(I, K, T, x0 + i, y);
+            for (int i = 0; i < n; ++i) vc_pixel<S, D>(I, K, T, x0 + i, y);
         }
     }
 }
@@ -155,6 +156,6 @@ struct VidLaunch {         // the kernel's argument: a plan's tables (device mem
     uint32_t tile_end[kVcMaxJobs];               // tiles of 512 groups up to and including job j (filled by launch_vidcolor)
     VcImage img[kVcMaxJobs];
 };
-hipError_t launch_vidcolor(VidLaunch& L, int depth, hipStream_t s);   // gs360_vidcolor.hip; n_jobs >= 1
+hipError_t launch_vidcolor(VidLaunch& L, int depth, int out_bits, hipStream_t s);   // gs360_vidcolor.hip; n_jobs >= 1, (8, 8), (10, 16) or (10, 8)
 
 }  // namespace gs360

@@ -42,6 +42,7 @@ EXPORTS = (
     "gs360_voxel_scratch", "gs360_cloud_bounds_f32", "gs360_voxel_count_f32", "gs360_voxel_pick_f32",
     "gs360_octree_scratch", "gs360_octree_pick_f32",
     "gs360_video_plan_create", "gs360_video_plan_destroy", "gs360_video_rgb", "gs360_video_fisheye_rgb",
+    "gs360_video_plan_create_out",
 )
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF   # a scan length of gs360_jpeg_scan_u8: the scan did not fit its out_capacity
 JPEG_TABLE_BYTES = 272               # GS360_JPEG_TABLE_BYTES: one Huffman table of gs360_jpeg_scan_opt_u8 (16 BITS + HUFFVAL, zero padded)
@@ -322,6 +323,7 @@ def load_library(path=None):
         L.gs360_octree_pick_f32.argtypes = [vp, vp, i64, C.POINTER(C.c_float), C.c_double, i64, C.c_double, C.c_double, i, vp, sz, vp, vp, vp, vp,
                                             C.POINTER(i64), C.POINTER(C.c_double), i]
         L.gs360_video_plan_create.argtypes = [vp, i, i, i, vp, vp, vp, pvp]
+        L.gs360_video_plan_create_out.argtypes = [vp, i, i, i, i, vp, vp, vp, pvp]
         L.gs360_video_plan_destroy.argtypes = [vp, vp]
         L.gs360_video_rgb.argtypes = [vp, vp, C.POINTER(VideoJob), i, i]
         L.gs360_video_fisheye_rgb.argtypes = [vp, vp, C.POINTER(VideoFisheyeView), C.POINTER(VideoJob), i, i]
@@ -679,17 +681,20 @@ class Context:
         self._color_apply(self.L.gs360_color_apply_u8, plan, src, H, W, Cn, dst, red_index, src_stride, dst_stride, slot)
 
     # -- decoded video frames to RGB (gs360/vidcolor.py) ---------------------------------------
-    def video_plan(self, depth, full_range, keep_rec709, primaries, linear, encode):
-        """gs360_video_plan_create: primaries float32 [3][3], linear float32 [16384], encode float32 [1024][2] (gs360/vidcolor.py
-        builds them).  Returns an opaque plan handle (free with video_plan_free)."""
+    def video_plan(self, depth, full_range, keep_rec709, primaries, linear, encode, out_bits=None):
+        """gs360_video_plan_create_out: primaries float32 [3][3], linear float32 [16384], encode float32 [1024][2] (gs360/vidcolor.py
+        builds them); out_bits None = the depth's own pairing (8 -> 8, 10 -> 16), 8 with depth 10 = uint8 RGB from 10-bit planes.
+        Returns an opaque plan handle (free with video_plan_free)."""
+        if out_bits is None:
+            out_bits = 8 if int(depth) == 8 else 16
         m = np.ascontiguousarray(primaries, dtype=np.float32)
         lin = np.ascontiguousarray(linear, dtype=np.float32)
         enc = np.ascontiguousarray(encode, dtype=np.float32)
         if m.shape != (3, 3) or lin.shape != (16384,) or enc.shape != (1024, 2):
             raise ValueError("primaries must be [3][3], linear [16384] and encode [1024][2]")
         h = C.c_void_p()
-        _check(self.L.gs360_video_plan_create(self.handle, int(depth), int(full_range), int(keep_rec709), m.ctypes.data, lin.ctypes.data,
-                                              enc.ctypes.data, C.byref(h)), self.L)
+        _check(self.L.gs360_video_plan_create_out(self.handle, int(depth), int(out_bits), int(full_range), int(keep_rec709), m.ctypes.data,
+                                                  lin.ctypes.data, enc.ctypes.data, C.byref(h)), self.L)
         return h
 
     def video_plan_free(self, plan):

@@ -163,6 +163,7 @@ class Engine:
         if n <= 0:
             raise capi.Gs360Error(-3, "no MI355X visible: the gs360 engine has no CPU fallback "
                                       "(use --engine ffmpeg to run the reference's ffmpeg path)")
+        self.video_feed = video.feed_from_env()   # GS360_VIDEO_FEED, read (and checked) once per engine, before any context exists
         want = os.environ.get("GS360_DEVICES")
         if devices is None and want:
             devices = [int(t) for t in want.split(",") if t.strip()]
@@ -170,6 +171,7 @@ class Engine:
         self.states = [_DeviceState(d) for d in self.devices]
         self._warned_cubic = False
         self.device_decoder = jpegdec.device_decoder_enabled()    # GS360_JPEG_DECODER, read (and checked) once per engine
+        self._feed_stats = video.FeedStats()      # what the sessions did with `planes` decode plans (video_feed_stats)
         self.videos = {}                          # DecodePlan.key -> the video.VideoSession new view jobs join
         self._video_done = {}                     # DecodePlan.key -> view jobs finished so far (all sessions of that video)
         self.videos_lock = threading.Lock()
@@ -687,6 +689,12 @@ class Engine:
         return dict(total)
 
     # -- video: one decode, frames resident in HBM, every view job walks them (gs360/video.py) -------------------
+    def video_feed_stats(self):
+        """VID-FEED v1: frames this engine's sessions converted from decoded planes on the device, and `planes` plans that went back
+        to their PPM command at the stream header.  (stats() and its keys are the launch counters' alone.)"""
+        with self._feed_stats.lock:
+            return {"plane_fed_frames": self._feed_stats.plane_fed_frames, "feed_fallbacks": self._feed_stats.feed_fallbacks}
+
     def _video_session(self, plan, stop_event, register_proc):
         """-> (session, token).  A job joins the video's current session; when that one has already retired its first frames
         (a long video under a small budget and a job that starts late) a fresh session -- a second decode -- takes its place
@@ -704,7 +712,8 @@ class Engine:
                     self._video_done.pop(plan.key, None)  # no session of this video is alive: a count left by a cancelled or partly
                                                           # failed run must not make the new run's jobs look finished early
                 self._video_budget.total = video._BUDGET_BYTES * max(1, len(self.states))
-                sess = self.videos[plan.key] = video.VideoSession(self.states, plan, stop_event, register_proc, shared=self._video_budget)
+                sess = self.videos[plan.key] = video.VideoSession(self.states, plan, stop_event, register_proc, shared=self._video_budget,
+                                                                  feed_stats=self._feed_stats)
                 token = sess.join()
             return sess, token
 

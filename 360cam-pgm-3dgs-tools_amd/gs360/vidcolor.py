@@ -60,14 +60,21 @@ def encode_table(keep_rec709: bool, outmax: int) -> np.ndarray:
 
 
 class VideoColor:
-    """The tables of one (depth, range, curve) and, per Context, its plan."""
+    """The tables of one (depth, range, curve, output depth) and, per Context, its plan.  out_bits None is the depth's own pairing
+    (uint8 from 8-bit planes, uint16 from 10-bit ones); 8 with depth 10 is VID-FEED v1's uint8 RGB from 10-bit planes."""
 
-    def __init__(self, depth: int, full_range: bool = False, keep_rec709: bool = False):
+    def __init__(self, depth: int, full_range: bool = False, keep_rec709: bool = False, out_bits=None):
         if depth not in (8, 10):
             raise ValueError("VID-COLOR v1 takes 8- and 10-bit planes (got {})".format(depth))
+        if out_bits is None:
+            out_bits = 8 if depth == 8 else 16
+        if (int(depth), int(out_bits)) not in ((8, 8), (10, 16), (10, 8)):
+            raise ValueError("no {}-bit RGB from {}-bit planes: 8 from 8, 16 from 10 and 8 from 10 are converted".format(out_bits, depth))
         self.depth, self.full_range, self.keep_rec709 = int(depth), bool(full_range), bool(keep_rec709)
+        self.out_bits = int(out_bits)
         self.in_dtype = np.dtype(np.uint8 if depth == 8 else np.uint16)
-        self.outmax = 255 if depth == 8 else 65535
+        self.out_dtype = np.dtype(np.uint8 if self.out_bits == 8 else np.uint16)
+        self.outmax = 255 if self.out_bits == 8 else 65535
         self.matrix = primaries_matrix().astype(np.float32)
         self.linear = linear_table()
         self.encode = encode_table(self.keep_rec709, self.outmax)
@@ -78,7 +85,8 @@ class VideoColor:
         with self._lock:
             p = self._plans.get(ctx)
             if p is None:
-                p = self._plans[ctx] = ctx.video_plan(self.depth, self.full_range, self.keep_rec709, self.matrix, self.linear, self.encode)
+                p = self._plans[ctx] = ctx.video_plan(self.depth, self.full_range, self.keep_rec709, self.matrix, self.linear, self.encode,
+                                                           out_bits=self.out_bits)
             return p
 
     def convert_dev(self, ctx, jobs, slot: int = 0) -> None:
@@ -95,10 +103,10 @@ class VideoColor:
             raise ValueError("chroma planes {} / {} fit no subsampling of a {} x {} frame".format(u.shape, v.shape, W, H))
         with ctx.slot_locks[slot]:
             bufs = [ctx.to_device(p, slot=slot) for p in (y, u, v)]
-            dst = ctx.alloc(H * W * 3 * self.in_dtype.itemsize)
+            dst = ctx.alloc(H * W * 3 * self.out_dtype.itemsize)
             try:
                 self.convert_dev(ctx, [(bufs[0], bufs[1], bufs[2], W, H, sub, dst)], slot=slot)
-                return ctx.download(dst, (H, W, 3), dtype=self.in_dtype, slot=slot)
+                return ctx.download(dst, (H, W, 3), dtype=self.out_dtype, slot=slot)
             finally:
                 for b in bufs + [dst]:
                     ctx.free(b)

@@ -15,6 +15,10 @@ Two argv shapes are understood (anything else returns None and the caller falls 
   * the planner's:        -ss S -i V -to T -vf fps=F,colorspace=...,v360=... -vsync vfr -start_number 0 ... out_%07d_X.png
   * the GUI's selection:  -copyts -i V -ss S -to T -vf select='eq(n\\,i)+...',colorspace=...,v360=... -frame_pts 1 ...
     (gs360_GUI.py:19081-19148): output numbers are the selected source frame indices.
+With GS360_VIDEO_FEED=planes (VID-FEED v1) the decoder only decodes: the job's colorspace= filter, one of the
+reference's forms, leaves its command line, it pipes YUV4MPEG2 planes (half the bytes of the RGB frame), and gs360/vidcolor.py
+converts them into the resident RGB frame on the upload stream; a stream header the conversion does not take restarts the decoder
+once on the PPM command.
 Geometry/sampling are the engine's (EQ-SPEC v1 on RGB); ffmpeg's v360 interpolates the YUV planes, so outputs are not
 bit-comparable with the reference's -- parity at this seam is unpinned (no ffmpeg in the build or test images).
 """
@@ -29,8 +33,9 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import capi
+from . import capi, y4m
 from .jobspec import JobSpec
+from .vidcolor import VideoColor
 
 # options that belong to the encoder / muxer of the per-view process and have no meaning for the shared decoder
 _ENCODER_OPTIONS = {"-c:v", "-q:v", "-qmin", "-qmax", "-pix_fmt", "-huffman", "-colorspace", "-color_primaries",
@@ -46,6 +51,35 @@ class DecodePlan:
     key: Tuple                            # identical for every view job of the same video + decode settings
     numbers: Optional[Tuple[int, ...]]    # output number of the k-th decoded frame; None = start_number + k
     start_number: int
+    feed: str = "ppm"                     # "ppm": RGB frames from the decoder; "planes": Y4M planes, converted on the device
+    keep_rec709: bool = False             # planes: the removed colorspace filter had no trc option (the Rec.709 curve stays)
+    out_bits: int = 8                     # planes: depth of the resident RGB frames (16 for -pix_fmt rgb48le)
+    fallback_argv: Tuple[str, ...] = ()   # planes: the PPM command the reader restarts on when the stream's header is not convertible
+
+
+FEED_ENV = "GS360_VIDEO_FEED"
+_CS_REQUIRED = {"iall=bt709", "all=smpte170m", "format=yuv444p"}
+_CS_OPTIONAL = {"trc=iec61966-2-1", "range=jpeg"}
+
+
+def feed_from_env(environ=None) -> str:
+    """GS360_VIDEO_FEED: unset, empty or `ppm` -> "ppm", `planes` -> "planes" (VID-FEED v1), anything else is an error"""
+    value = (os.environ if environ is None else environ).get(FEED_ENV, "")
+    if value in ("", "ppm"):
+        return "ppm"
+    if value == "planes":
+        return "planes"
+    raise ValueError("{} must be `ppm`, `planes` or unset (got {!r})".format(FEED_ENV, value))
+
+
+def _reference_colorspace(flt: str) -> Optional[bool]:
+    """One of the reference's colorspace= forms (PC:299-314: iall=bt709, all=smpte170m, format=yuv444p, optionally trc=iec61966-2-1,
+    optionally range=jpeg, in any order) -> its keep_rec709 ("no trc option"); None for any other option set."""
+    opts = flt[len("colorspace="):].split(":")
+    have = set(opts)
+    if len(have) != len(opts) or not _CS_REQUIRED <= have or have - _CS_REQUIRED - _CS_OPTIONAL:
+        return None
+    return "trc=iec61966-2-1" not in have
 
 
 def _select_indices(flt: str) -> Optional[List[int]]:
@@ -62,8 +96,12 @@ def _select_indices(flt: str) -> Optional[List[int]]:
     return out
 
 
-def build_decode_plan(job: JobSpec) -> Optional[DecodePlan]:
-    """Decoder command for a video view job, or None when the argv is not one of the two understood shapes."""
+def build_decode_plan(job: JobSpec, feed: str = "ppm") -> Optional[DecodePlan]:
+    """Decoder command for a video view job, or None when the argv is not one of the two understood shapes.  feed "planes" (VID-FEED
+    v1): the chain's one colorspace= filter, when it is one of the reference's forms, is taken out of the
+    decoder's chain and the decoder writes Y4M planes; any other chain keeps the PPM plan."""
+    if feed not in ("ppm", "planes"):
+        raise ValueError("feed must be `ppm` or `planes` (got {!r})".format(feed))
     if job.is_still_image or job.filters_after:
         return None
     if "%" not in job.dst.name:
@@ -105,9 +143,20 @@ def build_decode_plan(job: JobSpec) -> Optional[DecodePlan]:
                 out += [k, v]
         return out
     argv += keep(job.input_options) + ["-i", str(job.src)] + keep(job.output_options)
+    head = list(argv)
     argv += ["-vf", ",".join(pre + ["format=rgb48be" if deep else "format=rgb24"]), "-an", "-f", "image2pipe", "-c:v", "ppm", "pipe:1"]
-    key = (str(job.src), tuple(argv[1:]))
     start = int(job.options.get("-start_number", "0")) if numbers is None else 0
+    if feed == "planes":
+        cs = [f for f in pre if f.startswith("colorspace=")]
+        keep_rec709 = _reference_colorspace(cs[0]) if len(cs) == 1 else None
+        if keep_rec709 is not None:
+            rest = [f for f in pre if f is not cs[0]]
+            y4m_argv = head + ["-vf", ",".join(rest) if rest else "null", "-an", "-f", "yuv4mpegpipe", "-strict", "-1", "pipe:1"]
+            out_bits = 16 if deep else 8
+            # the colour options left the command line: they are part of what view jobs must agree on to share a decode
+            key = (str(job.src), tuple(y4m_argv[1:]), keep_rec709, out_bits)
+            return DecodePlan(tuple(y4m_argv), key, numbers, start, "planes", keep_rec709, out_bits, tuple(argv))
+    key = (str(job.src), tuple(argv[1:]))
     return DecodePlan(tuple(argv), key, numbers, start)
 
 
@@ -179,6 +228,20 @@ class SharedBudget:
             self.used += n
 
 
+class FeedStats:
+    """what an engine's sessions did with `planes` plans, summed (Engine.video_feed_stats)"""
+
+    def __init__(self):
+        self.plane_fed_frames = 0
+        self.feed_fallbacks = 0
+        self.lock = threading.Lock()
+
+    def add(self, frames, fallbacks):
+        with self.lock:
+            self.plane_fed_frames += frames
+            self.feed_fallbacks += fallbacks
+
+
 # View jobs take the frames of a video in WINDOWS of this many (one batched launch per window and device: ring families -- the
 # `full360coverage` preset, PC:616-680 -- reach the source-major kernel from four frames per call, csrc/gs360_capi_equirect.hip); frames are dealt to
 # the devices in blocks of a window, so that a window's frames sit on one device.  GS360_VIDEO_WINDOW=1: one frame per launch (A/B).
@@ -194,7 +257,7 @@ class VideoSession:
     were retired cannot join (join() returns None): the engine starts a second session for it and its fellow late-comers.
     Thread-safe."""
 
-    def __init__(self, states, plan: DecodePlan, stop_event=None, register_proc=None, budget=None, shared=None):
+    def __init__(self, states, plan: DecodePlan, stop_event=None, register_proc=None, budget=None, shared=None, feed_stats=None):
         self.states = states
         self.plan = plan
         self.stop_event = stop_event
@@ -217,6 +280,10 @@ class VideoSession:
         self.done_jobs = 0
         self.closing = False
         self.proc = None
+        self.color = None                         # `planes` feed: the session's VideoColor (a plan per device context), closed with it
+        self.plane_fed_frames = 0                 # frames converted from planes on the device
+        self.feed_fallbacks = 0                   # 1 when a `planes` plan went back to its PPM command at the stream header
+        self.feed_stats = feed_stats              # the engine's FeedStats, or None
         self.thread = threading.Thread(target=self._reader, name="gs360-video-decode", daemon=True)
         self.thread.start()
 
@@ -271,8 +338,51 @@ class VideoSession:
             self.peak_bytes = max(self.peak_bytes, self.bytes)
             self.cond.notify_all()
 
+    def _start_decoder(self, argv, errlog):
+        try:
+            self.proc = subprocess.Popen(list(argv), stdout=subprocess.PIPE, stderr=errlog, bufsize=1 << 20)
+        except OSError as exc:
+            raise PpmError("{}: {}".format(argv[0], exc)) from exc
+        if self.register_proc:
+            self.register_proc(self.proc, True)
+        return self.proc.stdout
+
+    def _open_planes(self, out):
+        """The Y4M reader of a `planes` decoder, or None when the reader has to go back to the PPM feed: the header is not 8- or
+        10-bit progressive 4:2:0 / 4:2:2 / 4:4:4, or it is 8-bit where 16-bit frames were asked for (the PPM path widens those as
+        the reference's format filter does)."""
+        try:
+            reader = y4m.Y4MReader(out)
+        except y4m.Y4MError:
+            return None
+        if reader.header.depth == 8 and self.plan.out_bits == 16:
+            return None
+        return reader
+
+    def _fall_back(self, errlog):
+        """kill and reap the `planes` decoder, start the plan's PPM command: once, before any frame is published"""
+        proc = self.proc
+        try:
+            proc.kill()
+        except Exception:
+            pass
+        proc.wait()
+        proc.stdout.close()
+        if self.register_proc:
+            self.register_proc(proc, False)
+        errlog.seek(0)
+        errlog.truncate()
+        self.feed_fallbacks += 1
+        if self.feed_stats is not None:
+            self.feed_stats.add(0, 1)
+        out = self._start_decoder(self.plan.fallback_argv, errlog)
+        if self.closing:                          # close() may have killed the decoder this one replaces
+            raise PpmError("cancelled")
+        return out
+
     def _reader(self):
         pinned = {}                               # (device, nbytes) -> [two pinned blocks]
+        blocks = {}                               # (device, frame_bytes) -> (state, [two device plane blocks]), `planes` feed only
         turn = {}                                 # device -> which of its two blocks the next frame takes
         pending = None                            # (state, event index, publish args) of the upload still in flight
         errlog = None
@@ -280,35 +390,47 @@ class VideoSession:
             # stderr goes to an unnamed temporary file, not a pipe: a damaged stream can make ffmpeg print more than a pipe
             # buffer holds while this thread is blocked on stdout, which would stall decoder and view jobs alike
             errlog = tempfile.TemporaryFile()
-            try:
-                self.proc = subprocess.Popen(list(self.plan.argv), stdout=subprocess.PIPE, stderr=errlog, bufsize=1 << 20)
-            except OSError as exc:
-                raise PpmError("{}: {}".format(self.plan.argv[0], exc)) from exc
-            if self.register_proc:
-                self.register_proc(self.proc, True)
-            out = self.proc.stdout
+            out = self._start_decoder(self.plan.argv, errlog)
+            reader = None                         # `planes` feed: the Y4M stream; None = PPM frames
+            if self.plan.feed == "planes":
+                reader = self._open_planes(out)
+                if reader is None:
+                    out = self._fall_back(errlog)
+                else:
+                    hd = reader.header
+                    self.color = VideoColor(hd.depth, hd.full_range, self.plan.keep_rec709, out_bits=8 if hd.depth == 8 else self.plan.out_bits)
             k = 0
             while True:
                 if self.stop_event is not None and self.stop_event.is_set():
                     raise PpmError("cancelled")
-                head = read_ppm_header(out)
-                if head is None:
-                    break
-                w, h, maxval = head
-                if maxval not in (255, 65535):
-                    raise PpmError("decoder delivered {}-level samples; the engine takes 8- or 16-bit frames".format(maxval + 1))
-                fdtype = np.uint16 if maxval == 65535 else np.uint8
+                if reader is not None:
+                    w, h = hd.width, hd.height
+                    fdtype = np.uint16 if self.color.out_bits == 16 else np.uint8
+                    nstage = hd.frame_bytes       # what crosses the pipe and PCIe; the budget counts the RGB frame, as for PPM
+                else:
+                    head = read_ppm_header(out)
+                    if head is None:
+                        break
+                    w, h, maxval = head
+                    if maxval not in (255, 65535):
+                        raise PpmError("decoder delivered {}-level samples; the engine takes 8- or 16-bit frames".format(maxval + 1))
+                    fdtype = np.uint16 if maxval == 65535 else np.uint8
                 nbytes = w * h * 3 * np.dtype(fdtype).itemsize
+                if reader is None:
+                    nstage = nbytes
                 st = self.state_for(k)
                 # two pinned staging blocks per device: the pipe read of frame k overlaps the H2D copy of frame k-1
-                pair = pinned.get((id(st), nbytes))
+                pair = pinned.get((id(st), nstage))
                 if pair is None:
-                    pair = pinned[(id(st), nbytes)] = [st.ctx.pinned(nbytes), st.ctx.pinned(nbytes)]
+                    pair = pinned[(id(st), nstage)] = [st.ctx.pinned(nstage), st.ctx.pinned(nstage)]
                 which = turn.get(id(st), 0)        # the device's two staging blocks in turn
-                turn[id(st)] = which ^ 1
                 stage = pair[which]
-                host = np.frombuffer(stage.view, dtype=np.uint8, count=nbytes)      # the pinned block as an array
-                read_exact_into(out, memoryview(host))
+                host = np.frombuffer(stage.view, dtype=np.uint8, count=nstage)      # the pinned block as an array
+                if reader is None:
+                    read_exact_into(out, memoryview(host))
+                elif not reader.read_into(host):
+                    break
+                turn[id(st)] = which ^ 1
                 if pending is not None:           # frame k-1 has had this whole pipe read to land
                     pst, pev, pargs = pending
                     pst.ctx.event_sync(pst.upload_slot, pev)
@@ -316,17 +438,34 @@ class VideoSession:
                     pending = None
                 with self.cond:
                     self._make_room(nbytes)
+                if reader is not None and (id(st), nstage) not in blocks:
+                    # two device plane blocks per device, outside the budget like the pinned blocks.  Stream order alone makes their
+                    # reuse safe: a block's previous conversion precedes the next upload into it on the same (upload) stream.
+                    mine = blocks[(id(st), nstage)] = (st, [])
+                    for _ in range(2):
+                        mine[1].append(self._alloc(st, nstage))
                 buf = self._alloc(st, nbytes)
                 ev = _EVENT_BASE + which
                 try:
                     with st.upload_lock:          # the engine's still-image uploads share this stream (engine.resident_frame)
-                        st.ctx.upload(buf, host, slot=st.upload_slot, sync=False)
-                        if fdtype == np.uint16:           # PPM samples are big-endian: swapped on the device, behind the copy
-                            st.ctx.bswap16(buf, nbytes // 2, slot=st.upload_slot)
+                        if reader is not None:
+                            block = blocks[(id(st), nstage)][1][which]
+                            st.ctx.upload(block, host, slot=st.upload_slot, sync=False)
+                            n_y, n_c = (ph * pw * hd.dtype.itemsize for ph, pw in hd.plane_shapes[:2])
+                            self.color.convert_dev(st.ctx, [(block.ptr, block.ptr + n_y, block.ptr + n_y + n_c, w, h, hd.subsampling, buf)],
+                                                   slot=st.upload_slot)
+                        else:
+                            st.ctx.upload(buf, host, slot=st.upload_slot, sync=False)
+                            if fdtype == np.uint16:           # PPM samples are big-endian: swapped on the device, behind the copy
+                                st.ctx.bswap16(buf, nbytes // 2, slot=st.upload_slot)
                         st.ctx.event_record(st.upload_slot, ev)
                 except Exception:
                     st.ctx.free(buf)              # not published, not pending: nobody else would release it
                     raise
+                if reader is not None:
+                    self.plane_fed_frames += 1
+                    if self.feed_stats is not None:
+                        self.feed_stats.add(1, 0)
                 pending = (st, ev, (st, buf, h, w, fdtype, nbytes))
                 k += 1
             if pending is not None:
@@ -358,6 +497,13 @@ class VideoSession:
             for pair in pinned.values():
                 for stage in pair:
                     stage.free()
+            for bst, pair in blocks.values():     # (freeing device memory waits for the stream's work on it)
+                for block in pair:
+                    try:
+                        if bst.ctx.handle:
+                            bst.ctx.free(block)
+                    except Exception:
+                        pass
             if errlog is not None:
                 errlog.close()
             if self.proc is not None and self.register_proc:
@@ -453,6 +599,9 @@ class VideoSession:
             self.cursors.clear()
             self.cond.notify_all()
         self.thread.join(timeout=5.0)
+        if self.color is not None and not self.thread.is_alive():
+            self.color.close()
+            self.color = None
         with self.cond:
             for st, buf, _h, _w, _dt in self.frames.values():
                 if st.ctx.handle:

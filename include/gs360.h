@@ -363,9 +363,17 @@ int gs360_color_apply_u16(gs360_ctx *ctx, const gs360_color_plan16 *plan, const 
  *   jobs   up to GS360_MAX_FRAMES per call; they may differ in size, subsampling and strides (bytes, 0 = tight).  Planes and
  *          destination must not overlap.  Pointers and strides that are all multiples of 4 take the dword path.  Asynchronous on
  *          `slot`.
- * Errors, checked for every job before anything is written: GS360_ERR_UNSUPPORTED for a depth other than 8 or 10 and for another
- * subsampling; GS360_ERR_ARG for NULL pointers, a side outside 1..65535, a stride below its row, an odd address or stride at depth
- * 10, more than GS360_MAX_FRAMES jobs, tables with values that are no number or out of range. */
+ *   out    gs360_video_plan_create_out names the destination's depth as well (VID-FEED v1): (depth, out_bits) =
+ *          (8, 8) and (10, 16) are what gs360_video_plan_create makes; (10, 8) writes uint8 RGB from 10-bit planes, what the
+ *          reference's `format=yuv444p` does inside its filter: the depth-10 integer step and the same `linear` table, an `encode`
+ *          table built for levels 0..255.  The destination's row is 3 W samples of out_bits; the encode cells are checked against
+ *          the plan's own largest level.
+ * Errors, checked for every job before anything is written: GS360_ERR_UNSUPPORTED for a depth other than 8 or 10, for (8, 16) and any
+ * out_bits other than 8 or 16, and for another subsampling; GS360_ERR_ARG for NULL pointers, a side outside 1..65535, a stride below
+ * its row, an odd address or stride on a side with 16-bit samples (the planes at depth 10, the destination at out_bits 16), more than
+ * GS360_MAX_FRAMES jobs, tables with values that are no number or out of range.  Parity with a real ffmpeg's filter is not pinned
+ * (no build or test image carries one): the definition is pinned against float64 mathematics (tests/test_vidcolor_cpu.py,
+ * tests/test_vidfeed_cpu.py). */
 #define GS360_VIDEO_444 0
 #define GS360_VIDEO_422 1
 #define GS360_VIDEO_420 2
@@ -381,6 +389,8 @@ typedef struct gs360_video_job {
 typedef struct gs360_video_plan gs360_video_plan;
 int gs360_video_plan_create(gs360_ctx *ctx, int depth, int full_range, int keep_rec709, const float *primaries,
                             const float *linear, const float *encode, gs360_video_plan **out);
+int gs360_video_plan_create_out(gs360_ctx *ctx, int depth, int out_bits, int full_range, int keep_rec709, const float *primaries,
+                                const float *linear, const float *encode, gs360_video_plan **out);
 int gs360_video_plan_destroy(gs360_ctx *ctx, gs360_video_plan *plan);
 int gs360_video_rgb(gs360_ctx *ctx, const gs360_video_plan *plan, const gs360_video_job *jobs, int n_jobs, int slot);
 
@@ -403,7 +413,8 @@ int gs360_video_rgb(gs360_ctx *ctx, const gs360_video_plan *plan, const gs360_vi
  *          strides may differ.  Plane pointers and strides that are all multiples of 4 take the dword path.  Asynchronous on `slot`.
  * Errors, checked for the view and every job before anything is written: GS360_ERR_ARG for a NULL view, another projection, S or a
  * source side outside 1..GS360_FISHEYE_MAX_SIDE, input_fov_deg outside [1,360], h_fov_deg or v_fov_deg outside [1,179], a job of
- * another size than the view's, and whatever gs360_video_rgb refuses of a job (with its codes). */
+ * another size than the view's, and whatever gs360_video_rgb refuses of a job (with its codes); GS360_ERR_UNSUPPORTED for a plan
+ * whose out_bits is not its depth's own (the (10, 8) plans of gs360_video_plan_create_out). */
 #define GS360_FISHEYE_EQUIDISTANT 0
 #define GS360_FISHEYE_EQUISOLID 1
 #define GS360_FISHEYE_MAX_SIDE 16384
